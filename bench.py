@@ -14,7 +14,11 @@ For N>1 (weak scaling) every rank aligns its own reads against its own replica o
 --strong divides one read set over the ranks instead (BASELINE config 4's shape) with the product's work queue
 (graphchainer_amd/workqueue.py): length-sorted batches handed out dynamically.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|5] [--sv-fraction F]
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step and the figures
+derived from the timed steps). --full adds everything else this file measures or checks: the CPU baseline and the parity check against the oracle,
+the end-to-end, SV and repeats legs, the same-read-set leg and the index cache round trip. --dump-outputs DIR writes what the last timed step returned.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|5] [--sv-fraction F] [--full] [--dump-outputs DIR]
        --gpus N > 1 run plainly (no WORLD_SIZE in the environment) starts the N ranks itself: a fresh child process
        `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py <same arguments>`, before this process has
        touched the GPU; rank 0's JSON line comes through and the exit code is the child's. Fewer than N visible devices: a loud refusal, not an N=1 number.
@@ -85,7 +89,17 @@ def parse_args():
                     help="batches in flight per GPU, each on its own gc_stream and host thread (like the reference's -t worker threads): one batch's seeding, fragment "
                          "pipeline, distances and assembly run beside another's whole-read pass (r5, ms per 10 k x 10 kb batch: " + ", ".join(f"{k} -> {v:.0f}" for k, v in sorted(BATCH_MS_BY_INFLIGHT.items())) + "; "
                          "a batch in flight holds 19 GB of device memory, the whole-read scratch of 27 GB is shared per device)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline leg and the parity check against the oracle, the end-to-end, SV and repeats legs, "
+                         "the same-read-set leg and (one rank) the index cache round trip. Without it the run sets up, warms up, times the steps and prints the result line; "
+                         "--no-cpu-baseline, --e2e-steps, --e2e-formats, --sv-leg-steps and --repeats-leg-steps act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what this rank's last timed step returned as DIR/<name>.npy (float64): the per-read arrays of every read of the step, "
+                         "and the per-read lists of a fixed, seeded sample of its reads; at most 64 MB in all")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = True
+        args.e2e_steps = args.sv_leg_steps = args.repeats_leg_steps = 0
     # config 5 on one GPU (BASELINE configs[4] is the whole genome over eight): 24 chromosome graphs, 2 000 CLR-like 50 kb reads, --colinear-gap 50000
     if args.reads is None:
         args.reads = 100_000 if args.config == 3 else 2_000 if args.config == 5 else 10_000
@@ -255,6 +269,94 @@ def start_host_memory_watchdog(cap_gb):
     return state
 
 
+# --dump-outputs: what gc_align_batch returned for the reads of the last timed step. One value per read (read order), the list lengths behind the result's
+# offset arrays, and for a seeded sample of the reads that have a list the lists themselves. Timings and counters stay out: they are not results.
+DUMP_PER_READ = ["chain_score", "long_edit_distance", "chain_edit_distance", "chained_better", "failed_assertion", "capacity_exceeded", "seeds_extended", "seeds_extended_long",
+                 "flatten_ties", "flatten_ties_long", "path_first_offset", "path_last_offset", "path_cells", "chain_aln_start", "chain_aln_end"]
+DUMP_LISTS = {"read_seed_off": ["seed_node", "seed_offset", "seed_seqpos", "seed_goodness"],
+              "read_anchor_off": ["anchor_x", "anchor_y", "anchor_first_node", "anchor_first_offset", "anchor_first_seqpos", "anchor_last_node", "anchor_last_offset", "anchor_last_seqpos", "anchor_score"],
+              "read_chain_off": ["chain"], "read_longall_off": ["longall_start", "longall_end", "longall_score"], "read_long_off": ["long_index"], "read_path_off": ["path_node"],
+              "read_chain_trace_off": ["chain_trace_node", "chain_trace_offset", "chain_trace_seqpos", "chain_trace_switch"]}
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20240611
+
+
+def dump_outputs(directory, results, chunk_list, per_step, steps):
+    """Writes the last timed step's results (run_queue's [(item, (batch index, out))]) as directory/<name>.npy, float64 (every value is an integer below 2^53).
+    read_index: the reads' indices in their read set, ascending; the other per-read arrays follow it. Per list: sample_<list>_read_index, the seeded sample of the
+    reads that have one, and sample_<field> their lists one after the other (lengths: n_<list> of those reads); sample_anchor_path with sample_anchor_path_len,
+    one length per sampled anchor. Every file holds at least one value."""
+    last = [(int(item), b, out) for item, (b, out) in results if int(item) // per_step == steps - 1]
+    if not last:
+        raise SystemExit("--dump-outputs: no timed step to dump (--steps 0)")
+    last.sort(key=lambda x: x[0])
+    i64 = lambda a: np.asarray(a).astype(np.int64)
+    read_index = np.concatenate([i64(chunk_list[b]) for _i, b, _o in last])
+    src = np.concatenate([np.full(len(chunk_list[b]), k) for k, (_i, b, _o) in enumerate(last)])
+    row = np.concatenate([np.arange(len(chunk_list[b])) for _i, b, _o in last])
+    order = np.argsort(read_index, kind="stable")
+    read_index, src, row = read_index[order], src[order], row[order]
+    rng = np.random.default_rng(DUMP_SEED)
+    per_read_fields = len(DUMP_PER_READ) + len(DUMP_LISTS) + 1
+    cap = (DUMP_MAX_BYTES // 2) // (8 * per_read_fields)
+    if len(read_index) > cap:                                  # (a step of more reads than half the budget holds: a seeded sample of them)
+        keep = np.sort(rng.choice(len(read_index), size=cap, replace=False))
+        read_index, src, row = read_index[keep], src[keep], row[keep]
+    outs = [o for _i, _b, o in last]
+    at = np.concatenate([[0], np.cumsum([len(chunk_list[b]) for _i, b, _o in last])])[src] + row     # (position in the step's batches, one after the other)
+    arrays = {"read_index": read_index}
+    for name in DUMP_PER_READ:
+        arrays[name] = np.concatenate([i64(o[name]) for o in outs])[at]
+    for off_name in DUMP_LISTS:
+        arrays["n_" + off_name[len("read_"):-len("_off")]] = np.concatenate([np.diff(i64(o[off_name])) for o in outs])[at]
+    base = sum(8 * len(a) for a in arrays.values())
+
+    offsets = [{k: i64(o[k]) for k in list(DUMP_LISTS) + ["anchor_path_off"]} for o in outs]
+    # one seeded sample per list: drawn from the reads whose list is not empty (chained alignments' traces exist for the reads the chained alignment wins,
+    # seeds only when the caller keeps them), so that no file is empty; a list empty for every read of the step is not written (its n_<list> says so)
+    drawn = {}
+    for off_name in DUMP_LISTS:
+        group = off_name[len("read_"):-len("_off")]
+        holders = np.nonzero(arrays["n_" + group] > 0)[0]
+        if len(holders):
+            drawn[off_name] = rng.permutation(holders)[:256]
+
+    def lists(k):
+        got = {}
+        for off_name, order_drawn in drawn.items():
+            sample = np.sort(order_drawn[:k])
+            got[f"sample_{off_name[len('read_'):-len('_off')]}_read_index"] = read_index[sample]
+            fields = DUMP_LISTS[off_name]
+            for name in fields + (["anchor_path"] if off_name == "read_anchor_off" else []):
+                parts, lens = [], []
+                for j in sample:
+                    o, off, r = outs[src[j]], offsets[src[j]], row[j]
+                    lo, hi = int(off[off_name][r]), int(off[off_name][r + 1])
+                    if name == "anchor_path":
+                        path_off = off["anchor_path_off"]
+                        parts.append(i64(o[name][int(path_off[lo]):int(path_off[hi])]))
+                        lens.append(np.diff(path_off[lo:hi + 1]))
+                    else:
+                        parts.append(i64(o[name][lo:hi]))
+                got["sample_" + name] = np.concatenate(parts)
+                if name == "anchor_path":
+                    got["sample_anchor_path_len"] = np.concatenate(lens)
+        return {name: a for name, a in got.items() if len(a)}
+
+    k = 256
+    while True:
+        sampled = lists(k)
+        if base + sum(8 * len(a) for a in sampled.values()) <= DUMP_MAX_BYTES or k <= 1:
+            break
+        k //= 2
+    arrays.update(sampled)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return {"dir": directory, "files": len(arrays), "bytes": int(sum(8 * len(a) for a in arrays.values())), "reads": int(len(read_index)), "sampled_reads_per_list": k,
+            "batches": len(last), "what": "the last timed step's results: per-read values of its reads and, per list, the lists of a seeded sample of the reads that have one"}
+
+
 def main():
     args = parse_args()
     rc = launch_ranks(args, sys.argv[1:])
@@ -315,8 +417,11 @@ def main():
         args.distinct_batches = 4 if (args.config == 2 and sg is not None) else 1
     if sg is None or args.config != 2:
         args.distinct_batches = 1
-    extra_sets = [sg.sample_reads(args.reads, args.read_len, seed=11 + 1000 * d + (0 if strong else rank), sv_fraction=args.sv_fraction) for d in range(1, args.distinct_batches)]
-    args.extra_cpu_reads = {f"set{d + 1}": rs[:1000] for d, rs in enumerate(extra_sets)} if (rank == 0 and world == 1) else {}
+    # (drawn on a thread of their own: the graph and index builds below run in the library, outside the GIL; the CPU leg of --full needs them at once)
+    from concurrent.futures import ThreadPoolExecutor
+    extra_sets_drawn = ThreadPoolExecutor(max_workers=1).submit(
+        lambda: [sg.sample_reads(args.reads, args.read_len, seed=11 + 1000 * d + (0 if strong else rank), sv_fraction=args.sv_fraction) for d in range(1, args.distinct_batches)])
+    args.extra_cpu_reads = {f"set{d + 1}": rs[:1000] for d, rs in enumerate(extra_sets_drawn.result())} if (rank == 0 and world == 1 and args.full) else {}
     if legs and args.sv_leg_steps > 0:
         sv_reads = sg.sample_reads(args.reads, args.read_len, seed=13, sv_fraction=0.2)
         args.extra_cpu_reads["sv"] = sv_reads[:1000]
@@ -373,7 +478,8 @@ def main():
         cache = os.path.join(args.setup_dir, "index.gcidx")
     t_graph = t_index = t_save = t_load = 0.0
     cache_bytes = 0
-    use_cache = not (args.no_index_cache and world == 1 and not setup_reused)
+    # (one rank: the save / load round trip only reports its own times and checks the file - --full, or --setup-dir, which keeps the file for a later run)
+    use_cache = not ((args.no_index_cache or not (args.full or args.setup_dir)) and world == 1 and not setup_reused)
     built = None
     if rank == 0 and not setup_reused:
         t0 = time.time()
@@ -447,6 +553,7 @@ def main():
     per_step = len(batches)
     extra_summaries = getattr(args, "extra_cpu_summaries", None) or {}
     flat_chunks, flat_batches, flat_summaries = list(chunks), list(batches), [cpu_summary] * per_step
+    extra_sets = extra_sets_drawn.result()
     for d, rs in enumerate(extra_sets):
         set_chunks = length_sorted_batches(rs, args.batch)
         flat_chunks += set_chunks
@@ -536,8 +643,9 @@ def main():
               + f"; all threads {sum(d for d, _ in used) / args.steps:.3f}, process {rank_cpu_s / args.steps:.3f}, container {host_cpu_s / args.steps:.3f}", file=sys.stderr)
     mem_free_end, _ = gca.device_memory()
     # what re-aligning ONE read set step after step (the bench up to r5) is worth: a few steps of it, timed the same way, outside `value`
+    dumped = dump_outputs(args.dump_outputs, outs, flat_chunks, per_step, args.steps) if args.dump_outputs and rank == 0 else None
     same_batch = None
-    if n_sets > 1 and dist is None:
+    if n_sets > 1 and dist is None and args.full:
         k = max(1, args.steps)                             # (as many steps as the timed region: a short run would be mostly pipeline fill)
         sync()
         t_same = time.perf_counter()
@@ -867,6 +975,7 @@ def main():
             "sv_leg": sv_leg,
             "repeats_leg": repeats_leg,
             "inflight_choice": inflight_choice,
+            "outputs_dump": dumped,
             "per_rank": per_rank,
             # inputs are resident before the timed region; what putting them there costs (host-side packing + PCIe), and the rate with it included
             "distinct_read_sets": n_sets, "same_read_set_every_step": same_batch,

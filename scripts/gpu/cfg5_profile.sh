@@ -1,4 +1,5 @@
 #!/bin/bash
+repo=$(cd "$(dirname "$0")/../.." && pwd)
 # config 5 at one or more sizes: the bench line with the CPU leg and the parity sample (GC_DEBUG_TIMES: stage times and "[gc mem]" lines), then a rocprofv3 kernel trace of the same
 # workload from the kept set-up (bench.py --setup-dir: the second process loads the index cache instead of building again).
 # usage: bash scripts/gpu/cfg5_profile.sh <tag> [backbone bp per chromosome ...]      (8000000 = 192 Mbp, 40000000 = 960 Mbp); CFG5_ARGS adds bench flags; CFG5_ALONE=1 adds the trace with one batch in flight, CFG5_PMC=1 a counter pass
@@ -9,7 +10,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for b in $sizes; do
   setup=/tmp/gcsetup_$b
-  GC_DEBUG_TIMES=1 timeout ${CFG5_TIMEOUT:-2400} python3 $GRAFT_REPO_ROOT/bench.py --config 5 --backbone $b --setup-dir $setup --steps ${CFG5_STEPS:-15} --warmup ${CFG5_WARMUP:-5} --e2e-steps ${CFG5_E2E:-0} $CFG5_ARGS > $out/cfg5_$b.json 2> $out/cfg5_$b.err
+  GC_DEBUG_TIMES=1 timeout ${CFG5_TIMEOUT:-2400} python3 $repo/bench.py --full --config 5 --backbone $b --setup-dir $setup --steps ${CFG5_STEPS:-15} --warmup ${CFG5_WARMUP:-5} --e2e-steps ${CFG5_E2E:-0} $CFG5_ARGS > $out/cfg5_$b.json 2> $out/cfg5_$b.err
   echo "size $b rc $?"
   grep "gc mem" $out/cfg5_$b.err | tail -4
   python3 - $out/cfg5_$b.json <<'PY'

@@ -1,4 +1,5 @@
 #!/bin/bash
+repo=$(cd "$(dirname "$0")/../.." && pwd)
 # usage: bash scripts/gpu/check.sh <tag> [bench args...]   - all GPU tests (whole log kept), then one default bench.py line (with the CPU leg unless told otherwise)
 tag=${1:-check}; shift
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
@@ -8,7 +9,7 @@ timeout 1800 python -X faulthandler -m pytest tests -q -m gpu -x $PYTEST_ARGS > 
 echo "pytest rc $?"
 tail -15 $out/pytest.txt
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 5 "$@" > $out/bench.json 2> $out/bench.err
+timeout 900 python3 $repo/bench.py --full --steps 10 --warmup 5 "$@" > $out/bench.json 2> $out/bench.err
 echo "bench rc $?"
 tail -3 $out/bench.err
 python3 - $out/bench.json <<'PY'

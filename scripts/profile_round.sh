@@ -1,4 +1,5 @@
 #!/bin/bash
+repo=$(cd "$(dirname "$0")/.." && pwd)
 # Round profile on the GPU box: bench line (with CPU baseline), rocprofv3 kernel stats, PMC passes, section stamps.
 # Usage (from the repo root, through gpurun): bash scripts/profile_round.sh r01
 set -u
@@ -6,7 +7,7 @@ tag=${1:-r01}
 out=$GRAFT_REPO_ROOT/gpurun_out/profile_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout 400 python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+timeout 400 python3 $repo/bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 # (r6: a steady state - ten timed steps behind five warm-up steps; the r05 trace was --steps 3 --warmup 1, five of whose eight passes were the streams' lock-stepped first batches)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --e2e-steps 0 --sv-leg-steps 0 --repeats-leg-steps 0 --steps 10 --warmup 5 > $out/stats.log 2>&1
 timeout 400 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_LDS --kernel-trace --output-format csv -d $out/pmc_a -o p -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --e2e-steps 0 --distinct-batches 1 --steps 1 --warmup 0 > $out/pmc_a.log 2>&1

@@ -1,6 +1,11 @@
 """Pins the oracle's leaf functions against the reference's own sources compiled unmodified
-(oracle/_ref/libref_units.so = WordSlice.h, AlignmentCorrectnessEstimation.cpp, edlib)."""
+(oracle/_ref/libref_units.so = WordSlice.h, AlignmentCorrectnessEstimation.cpp, edlib).
+
+Where oracle/_ref is not built (its sources are not part of this repository), the reference's outputs for the same seeded
+inputs come from tests/golden/ref_units.expected.npz, which tests/golden/make_ref_units_golden.py recorded from oracle/_ref;
+where it is built, the live outputs are compared with the oracle and with that recording."""
 import ctypes as C
+import hashlib
 import os
 import random
 
@@ -10,9 +15,35 @@ import pytest
 from oracle import RefUnits, load_oracle_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-pytestmark = pytest.mark.skipif(
-    not (os.path.exists(os.path.join(HERE, "..", "oracle", "_ref", "libref_units.so")) or os.path.isdir("/root/reference/src")),
-    reason="reference units not built and no reference tree")
+REF_GOLDEN = os.path.join(HERE, "golden", "ref_units.expected.npz")
+
+
+def live_ref():
+    """RefUnits when oracle/_ref/libref_units.so is built (or can be), else None."""
+    try:
+        return RefUnits()
+    except (FileNotFoundError, OSError):
+        return None
+
+
+def reference(name):
+    """The reference units' outputs for one test's inputs (RECORDED[name]): live when the units are built - and then they must equal the
+    recording - else the recording."""
+    recorded = np.load(REF_GOLDEN)[name]
+    ref = live_ref()
+    if ref is None:
+        return recorded
+    got = RECORDED[name](ref)
+    assert np.array_equal(got, recorded), f"{name}: the reference units' outputs differ from {os.path.basename(REF_GOLDEN)}"
+    return got
+
+
+def digest(*arrays):
+    """16 bytes that stand for the exact bytes of `arrays` (a case's output where it is a whole series)."""
+    h = hashlib.blake2b(digest_size=16)
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8)
 
 
 def random_column(rng, flat=False):
@@ -61,43 +92,72 @@ def values(col):
 
 
 @pytest.fixture(scope="module")
-def libs():
-    return load_oracle_lib(), RefUnits().lib
+def ora():
+    return load_oracle_lib()
 
 
-def test_merge_matches_reference_and_pointwise_min(libs):
-    ora, ref = libs
+def merge_cases():
     rng = random.Random(1)
-    u64, i32 = C.c_uint64, C.c_int32
+    cases = []
     for it in range(20000):
         a = random_column(rng)
         b = perturb(rng, a) if it % 2 else random_column(rng)
         # the reference requires |score difference| small enough for its loop; keep columns within 64 of each other
-        ovp, ovn, os_ = u64(), u64(), i32()
-        rvp, rvn, rs = u64(), u64(), i32()
-        ora.gco_merge(*a, *b, C.byref(ovp), C.byref(ovn), C.byref(os_))
-        ref.ref_merge(*a, *b, C.byref(rvp), C.byref(rvn), C.byref(rs))
-        assert (ovp.value, ovn.value, os_.value) == (rvp.value, rvn.value, rs.value), (a, b)
+        cases.append((a, b))
+    return cases
+
+
+def merge_outputs(fn, cases):
+    """fn = gco_merge / ref_merge: [(VP, VN, scoreEnd)] of every case."""
+    u64, i32 = C.c_uint64, C.c_int32
+    out = np.zeros((len(cases), 3), dtype=np.int64)
+    for k, (a, b) in enumerate(cases):
+        vp, vn, s = u64(), u64(), i32()
+        fn(*a, *b, C.byref(vp), C.byref(vn), C.byref(s))
+        out[k] = (np.uint64(vp.value).view(np.int64), np.uint64(vn.value).view(np.int64), s.value)
+    return out
+
+
+def test_merge_matches_reference_and_pointwise_min(ora):
+    cases = merge_cases()
+    got = merge_outputs(ora.gco_merge, cases)
+    want = reference("merge")
+    for k, (a, b) in enumerate(cases):
+        assert np.array_equal(got[k], want[k]), (a, b)
+        vp, vn = (int(x) & ((1 << 64) - 1) for x in got[k][:2])
         mins = [min(x, y) for x, y in zip(values(a), values(b))]
-        assert values((ovp.value, ovn.value, os_.value)) == mins
+        assert values((vp, vn, int(got[k][2]))) == mins
 
 
-def test_changed_min_score_get_value_before_start(libs):
-    ora, ref = libs
+def score_cases():
     rng = random.Random(2)
+    cases = []
     for it in range(20000):
         a = random_column(rng)
         b = perturb(rng, a) if it % 2 else random_column(rng)
-        assert ora.gco_changed_min_score(*a, *b) == ref.ref_changed_min_score(*a, *b), (a, b)
-        assert ora.gco_score_before_start(*a) == ref.ref_score_before_start(*a)
-        row = rng.randrange(64)
-        assert ora.gco_get_value(*a, row) == ref.ref_get_value(*a, row) == values(a)[row + 1]
+        cases.append((a, b, rng.randrange(64)))
+    return cases
 
 
-def test_myers_step_is_the_cell_recurrence(libs):
+def score_outputs(lib, prefix, cases):
+    """[(changedMinScore(a, b), scoreBeforeStart(a), getValue(a, row))] of every case."""
+    changed, before, value = (getattr(lib, prefix + n) for n in ("changed_min_score", "score_before_start", "get_value"))
+    return np.array([(changed(*a, *b), before(*a), value(*a, row)) for a, b, row in cases], dtype=np.int64)
+
+
+def test_changed_min_score_get_value_before_start(ora):
+    cases = score_cases()
+    got = score_outputs(ora, "gco_", cases)
+    want = reference("scores")
+    for k, (a, b, row) in enumerate(cases):
+        assert got[k][0] == want[k][0], (a, b)
+        assert got[k][1] == want[k][1]
+        assert got[k][2] == want[k][2] == values(a)[row + 1]
+
+
+def test_myers_step_is_the_cell_recurrence(ora):
     """getNextSlice against the plain DP recurrence (the reference's assertSliceCorrectness twin,
     src/GraphAlignerBitvectorCommon.h:812-826)."""
-    ora, _ = libs
     rng = random.Random(3)
     u64, i32 = C.c_uint64, C.c_int32
     for _ in range(5000):
@@ -115,25 +175,34 @@ def test_myers_step_is_the_cell_recurrence(libs):
         assert hp.value - hn.value == n[64] - o[64]
 
 
-def test_correctness_hmm_matches_reference(libs):
-    ora, ref = libs
+def correctness_cases():
     rng = random.Random(4)
+    cases = []
     for _ in range(200):
         n = rng.randint(1, 200)
         lo, hi = rng.choice([(0, 8), (5, 20), (20, 40), (0, 70)])
-        mm = np.array([rng.randint(lo, hi) for _ in range(n)], dtype=np.int32)
-        oc, ow, of = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
-        rc, rw, rf = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
-        ora.gco_correctness_series(mm.ctypes.data, n, oc.ctypes.data, ow.ctypes.data, of.ctypes.data)
-        ref.ref_correctness_series(mm.ctypes.data, n, rc.ctypes.data, rw.ctypes.data, rf.ctypes.data)
-        assert np.array_equal(oc.view(np.uint64), rc.view(np.uint64))   # bit-exact doubles
-        assert np.array_equal(ow.view(np.uint64), rw.view(np.uint64))
-        assert np.array_equal(of, rf)
+        cases.append(np.array([rng.randint(lo, hi) for _ in range(n)], dtype=np.int32))
+    return cases
 
 
-def test_edit_distance_matches_edlib(libs):
-    ora, ref = libs
+def correctness_series(fn, mm):
+    n = len(mm)
+    c, w, f = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+    fn(mm.ctypes.data, n, c.ctypes.data, w.ctypes.data, f.ctypes.data)
+    return c, w, f
+
+
+def test_correctness_hmm_matches_reference(ora):
+    cases = correctness_cases()
+    # bit-exact doubles: a case's three series enter its digest as bytes
+    want = reference("correctness")
+    for k, mm in enumerate(cases):
+        assert np.array_equal(digest(*correctness_series(ora.gco_correctness_series, mm)), want[k]), mm.tolist()
+
+
+def edit_distance_cases():
     rng = random.Random(5)
+    cases = []
     for _ in range(300):
         la = rng.choice([1, 5, 63, 64, 65, 130, 500])
         a = "".join(rng.choice("ACGT") for _ in range(la))
@@ -148,7 +217,15 @@ def test_edit_distance_matches_edlib(libs):
             else:
                 b.insert(i, rng.choice("ACGT"))
         b = "".join(b) or "A"
-        assert ora.gco_edit_distance(a.encode(), len(a), b.encode(), len(b)) == ref.ref_edit_distance(a.encode(), len(a), b.encode(), len(b))
+        cases.append((a.encode(), b.encode()))
+    return cases
+
+
+def test_edit_distance_matches_edlib(ora):
+    cases = edit_distance_cases()
+    want = reference("edit_distance")
+    for (a, b), w in zip(cases, want):
+        assert ora.gco_edit_distance(a, len(a), b, len(b)) == w, (a, b)
 
 
 # ---- edlib PATH mode (src/Aligner.cpp:845) and the E-value (src/EValue.cpp) ----------------------------------------
@@ -203,34 +280,57 @@ def _path_cases(rng):
         yield (b"ACG" * 2000)[:qn], _mut(rng, (b"ACG" * 2000)[:qn], 0.05)
 
 
+def edit_path_record(d, ops):
+    """One case of edlib's PATH output as recorded: distance, op count, digest of the op string."""
+    return np.concatenate([np.array([d, len(ops)], dtype=np.int64).view(np.uint8), digest(np.asarray(ops, dtype=np.uint8))])
+
+
 def test_edit_path_matches_edlib_op_for_op():
     """oracle/edlib_path.hpp against the real edlib (oracle/_ref): same distance, same op string, same "no alignment" cases."""
     from oracle.binding import oracle_edit_path
-    ref = RefUnits()
-    rng = random.Random(2024)
+    cases = list(_path_cases(random.Random(2024)))
+    want = reference("edit_path")
     n = hirschberg = 0
-    for q, t in _path_cases(rng):
-        want_d, want_ops = ref.edit_path(q, t)
+    for (q, t), w in zip(cases, want):
         got_d, got_ops = oracle_edit_path(q, t)
+        want_d, want_len = w[:16].view(np.int64)
         assert got_d == want_d, (len(q), len(t))
-        assert np.array_equal(got_ops, want_ops), (len(q), len(t), want_d)
-        if len(want_ops):
+        assert np.array_equal(edit_path_record(got_d, got_ops), w), (len(q), len(t), want_d)
+        if want_len:
             # an op string is an alignment: it consumes both strings and costs the distance
-            assert np.sum(want_ops != 2) == len(q) and np.sum(want_ops != 1) == len(t) and np.sum(want_ops != 0) == want_d
+            assert np.sum(got_ops != 2) == len(q) and np.sum(got_ops != 1) == len(t) and np.sum(got_ops != 0) == want_d
         n += 1
         hirschberg += (20 * ((len(q) + 63) // 64) + 8) * len(t) >= 1 << 20
     assert n > 200 and hirschberg >= 15
 
 
-def test_evalue_matches_reference_bitwise():
-    from oracle.binding import oracle_evalue
-    ref = RefUnits()
+def evalue_cases():
     rng = random.Random(7)
+    cases = []
     for _ in range(300):
         ident = rng.choice([0.7, 0.5, 0.66, 0.9, rng.uniform(0.05, 0.95)])
         db, q = rng.randint(1, 10**10), rng.randint(1, 10**5)
         length = rng.randint(0, 60000)
         edits = rng.randint(0, max(1, length))
-        want = ref.evalue(ident, db, q, length, edits)
-        got = oracle_evalue(ident, db, q, length, edits)
-        assert want.tobytes() == got.tobytes(), (ident, db, q, length, edits, want, got)
+        cases.append((ident, db, q, length, edits))
+    return cases
+
+
+def test_evalue_matches_reference_bitwise():
+    from oracle.binding import oracle_evalue
+    cases = evalue_cases()
+    want = reference("evalue")
+    for c, w in zip(cases, want):
+        got = oracle_evalue(*c)
+        assert w.tobytes() == got.tobytes(), (c, w.view(np.float64), got)
+
+
+# seeded inputs -> the reference units' outputs, as tests/golden/make_ref_units_golden.py records them
+RECORDED = {
+    "merge": lambda ref: merge_outputs(ref.lib.ref_merge, merge_cases()),
+    "scores": lambda ref: score_outputs(ref.lib, "ref_", score_cases()),
+    "correctness": lambda ref: np.array([digest(*correctness_series(ref.lib.ref_correctness_series, mm)) for mm in correctness_cases()]),
+    "edit_distance": lambda ref: np.array([ref.lib.ref_edit_distance(a, len(a), b, len(b)) for a, b in edit_distance_cases()], dtype=np.int64),
+    "edit_path": lambda ref: np.array([edit_path_record(*ref.edit_path(q, t)) for q, t in _path_cases(random.Random(2024))]),
+    "evalue": lambda ref: np.array([ref.evalue(*c) for c in evalue_cases()]).view(np.uint64),
+}
