@@ -96,6 +96,11 @@
 		launchZeroWords(stream, dCounters, 8);
 		ExtendConfig cfg;
 		cfg.bandwidth = P->bandwidth;
+		// --ramp-bandwidth: a fragment extension is ONE slice (split_len <= 64 rows), and slice 0 always runs with the ramp bandwidth; the rewind needs an earlier
+		// slice to return to, so it never fires. An extension with the ramp on is exactly an extension at the ramp bandwidth, the slice's stored bandwidth
+		// (which the backtrace reads) included (src/GraphAlignerBitvectorBanded.h:544,572-576,608). --tangle-effort goes to the cores as it is.
+		if (P->ramp_bandwidth > P->bandwidth) cfg.bandwidth = P->ramp_bandwidth;
+		cfg.maxCells = P->max_cells_per_slice < 0 || P->max_cells_per_slice >= 0xffffffffll ? ~0u : (uint32_t)P->max_cells_per_slice;   // (no slice reaches 2^32 - 1 cells)
 		cfg.maxSlices = 3;
 		cfg.maxItems = 72;
 		cfg.maxPending = 48;
@@ -179,7 +184,7 @@
 			if (fragKernel) {
 				unsigned long long* claims = dFragClaims + 2 * (nExtendRounds++ & 3u);
 				if (nExtendRounds > 4) launchZeroWords(stream, claims, 2);
-				launchExtendFrag(stream, G->dev, G->devTables, cfg.bandwidth, dWork, nWork, fragReads, dResults, dFragItems, fragWaves, dTrace, dCursors + 1, traceBudget, dCounters, sel, claims, dFragRetry, claims + 1, dFragClaims + 8);
+				launchExtendFrag(stream, G->dev, G->devTables, cfg.bandwidth, dWork, nWork, fragReads, dResults, dFragItems, fragWaves, dTrace, dCursors + 1, traceBudget, dCounters, sel, claims, dFragRetry, claims + 1, dFragClaims + 8, cfg.maxCells);
 				ExtSelection declined;
 				declined.mode = 2; declined.list = dFragRetry; declined.listCount = claims + 1;
 				// What the kernel declined (233 of cfg2's 4.4 M extensions) goes to the plain-layout kernel on the large slabs - when there is anything: its count comes to the host

@@ -45,6 +45,8 @@
 				j.alnBegin = (uint32_t)(r * maxAlignments);
 			});
 			lcfg.bandwidth = P->bandwidth;
+			lcfg.rampBandwidth = P->ramp_bandwidth;
+			lcfg.maxCells = P->max_cells_per_slice < 0 || P->max_cells_per_slice >= 0xffffffffll ? ~0u : (uint32_t)P->max_cells_per_slice;   // (no slice reaches 2^32 - 1 cells)
 			lcfg.maxSlices = (uint32_t)(maxReadLen / 64 + 3);
 			lcfg.maxItems = (uint32_t)std::max<uint64_t>(8192, (maxReadLen / 64 + 3) * 24);   // (slice, node) tiles of one extension: ~8 per slice on cfg2, room for 24
 			lcfg.maxPending = 96;

@@ -443,6 +443,8 @@ void gc_params_default(gc_params* p)
 	p->device_output = 0;
 	p->e_cutoff = -1;
 	memset(&p->capacity, 0, sizeof(p->capacity));   // automatic
+	p->ramp_bandwidth = 0;          // off (src/AlignerMain.cpp:147)
+	p->max_cells_per_slice = -1;    // unlimited (src/AlignerMain.cpp:149: SIZE_MAX)
 }
 
 int gc_graph_create_from_gfa(const char* gfa_path, gc_graph** out)

@@ -164,7 +164,7 @@ struct SliceInfo {  // reference: DPSlice, src/GraphAlignerBitvectorCommon.h:138
 	uint32_t first, count;      // this slice's NodeItems are items[first .. first+count)
 	int32_t bandwidth;
 	int32_t j;                  // first read row of the slice (-64 for the initial slice)
-	uint32_t flags;             // bit0 currentlyCorrect, bit1 correctFromCorrect, bit2 falseFromCorrect
+	uint32_t flags;             // bit0 currentlyCorrect, bit1 correctFromCorrect, bit2 falseFromCorrect, bit3 flatten tie, bit4 scoresNotValid (SLICE_NOT_VALID)
 	double correctLogOdds, falseLogOdds;
 };
 
@@ -205,7 +205,13 @@ struct ExtendConfig {
 	uint32_t maxTrace;
 	uint32_t maxCols = 0;   // whole-read pass, one extension per wave: columns of the DP kept for the backtrace (0: the backtrace recomputes its tiles)
 	uint32_t regCap = 64;   // whole-read pass, register tables: nodes per slice before the extension is retried with the LDS/HBM tables (test hook, <= 64)
+	// band controls (gc_params::ramp_bandwidth / max_cells_per_slice). Only the BAND instantiation of extendSeedT reads them; the host launches it when either is on.
+	// (32-bit: an 8-byte member would realign the struct every whole-read kernel takes by value. No slice holds 2^32 cells, so ~0u means unlimited)
+	int32_t rampBandwidth = 0;   // rampBandwidth: 0 off, else > bandwidth
+	uint32_t maxCells = ~0u;     // maxCellsPerSlice: ~0u unlimited
+	__host__ __device__ bool bandControls() const { return rampBandwidth != 0 || maxCells != ~0u; }
 };
+enum : uint32_t { SLICE_NOT_VALID = 16u };   // SliceInfo::flags: the slice reached maxCellsPerSlice (DPSlice::scoresNotValid, ...Banded.h:581-584)
 
 // status codes of one extension
 enum : uint32_t { EXT_OK = 0, EXT_FAILED = 1, EXT_ASSERT = 2, EXT_OVERFLOW = 3 };
@@ -475,7 +481,8 @@ __device__ inline bool pushTrace(const LaneScratch& sc, const ExtendConfig& cfg,
 	return true;
 }
 
-// reference: pickBacktraceCorner, ...Common.h:710-804 (scoresNotValid is never set: unlimited cells per slice)
+// reference: pickBacktraceCorner, ...Common.h:710-804. scoresNotValid is set only with a cell limit (BAND): the default instantiation folds its tests away.
+template <bool BAND = false>
 __device__ inline bool backtraceCorner(const DGraph& g, const LaneScratch& sc, uint32_t s, uint32_t node, int itemIdx, const Eq4& eq, Cell& out, bool& nodeSwitch)
 {
 	const SliceInfo& cur = sc.slices[s];
@@ -486,7 +493,7 @@ __device__ inline bool backtraceCorner(const DGraph& g, const LaneScratch& sc, u
 	int32_t scoreHere = wsValue(itemStart(sc.items[itemIdx]), 0);
 	int prevSelf = findItem(sc.itemNodes, prev, node);
 	uint32_t inBegin = g.inOff[node], inEnd = g.inOff[node + 1];
-	if (scoreHere > quitScore) {
+	if ((BAND && (cur.flags & SLICE_NOT_VALID)) || scoreHere > quitScore) {
 		int32_t smallest = scoreHere + 1;
 		out = Cell { 0, 0, 0 };
 		nodeSwitch = false;
@@ -515,7 +522,7 @@ __device__ inline bool backtraceCorner(const DGraph& g, const LaneScratch& sc, u
 		int p = findItem(sc.itemNodes, prev, nb);
 		if (p >= 0) {
 			int32_t corner = sc.items[p].eScore;
-			if (corner > previousQuitScore) {
+			if ((BAND && (prev.flags & SLICE_NOT_VALID)) || corner > previousQuitScore) {
 				if (corner < bestInvalidScore) { bestInvalidScore = corner; bestInvalid = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, j - 1 }; }
 			} else if (corner == scoreHere - (eqBit ? 0 : 1)) {
 				out = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, j - 1 }; nodeSwitch = true; return true;
@@ -534,7 +541,8 @@ struct EqFromBases {
 	const char* seq; const uint8_t* iupac;
 	__device__ __forceinline__ void rows(int len, int j, Eq4& eq) const { eqVector(seq, len, j, iupac, eq); }
 };
-template <class EQS>
+// BAND: the band controls of cfg (ramp, cell limit); the default instantiation is the plain band.
+template <class EQS, bool BAND = false>
 __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables& ct, const EQS& eqs, const ExtendConfig& cfg, const LaneScratch& sc,
 	int len, uint32_t startNode, uint32_t startOffset, uint32_t& nTrace, int32_t& score, ExtCounters& cnt)
 {
@@ -568,6 +576,10 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 	uint32_t nItems = 1;
 	uint32_t nSlices = 1;
 	Eq4 eq;
+	// the ramp (getViterbiSlices, ...Banded.h:540-644): slices up to rampUntil run with the ramp bandwidth - slice 0 always. The snapshot a rewind returns to is
+	// the kept slice rampRedoIndex (sc.slices[rampRedoIndex + 1]): kept slices and their items are a stack, so rewinding is truncating it.
+	int rampUntil = 0, rampRedoIndex = -1;
+	const bool rampOn = BAND && cfg.rampBandwidth > cfg.bandwidth;
 	for (int slice = 0; slice < numSlices; slice++) {
 		const SliceInfo prev = sc.slices[nSlices - 1];
 		int j = prev.j + 64;
@@ -575,6 +587,8 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 		int32_t previousQuitScore = prev.minScore + prev.bandwidth;
 		int32_t previousMinScore = prev.minScore;
 		int bandwidth = cfg.bandwidth;
+		if (BAND && rampOn && rampUntil >= slice) bandwidth = cfg.rampBandwidth;
+		uint32_t cells = 0;   // (BAND) the slice's cellsProcessed: a node computed once (a DAG has no revisits, so no early leave) counts its length (...Common.h:1162)
 		int flatRows = (j + 64 > len) ? (len - j) : 0;   // last partial slice (...Banded.h:414)
 		// seed the queue from the previous slice's in-band nodes (...Banded.h:235-277; linearizable is all-false)
 		uint32_t nPending = 0;
@@ -626,6 +640,10 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 					if (status != EXT_OK) return status;
 				}
 			}
+			if (BAND) {   // ...Banded.h:400-405: past the limit the rest of the queue is dropped
+				cells += (uint32_t)g.nodeLength[p.node];
+				if (cells > cfg.maxCells) break;
+			}
 		}
 		if (cur.count == 0) return EXT_ASSERT;
 		const uint32_t flatTie = flatRows > 0 ? (flatOffset >> 31) << 3 : 0u;   // kept in the slice's flags (bit 3)
@@ -643,7 +661,21 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			cur.falseLogOdds = (c > d ? c : d) + ct.wrongOdds[idx];
 			cur.flags = (cur.correctLogOdds > cur.falseLogOdds ? 1u : 0u) | (cfc ? 2u : 0u) | (ffc ? 4u : 0u) | flatTie;
 		}
+		if (BAND) {
+			// ...Banded.h:572-576: the snapshot; then the cell flag (:581-584, note >= where the break above has >)
+			if (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u))) rampRedoIndex = slice - 1;
+			if (cells >= cfg.maxCells) cur.flags |= SLICE_NOT_VALID;
+		}
 		if (!(cur.flags & 2u)) break;   // !CorrectFromCorrect: stop, slice not kept (...Banded.h:589-607)
+		if (BAND && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
+			// ...Banded.h:608-644: not currently correct - redo from the snapshot with the ramp bandwidth up to this slice. (rampRedoIndex >= 0 here: the
+			// snapshot is taken at slice rampUntil + 1 at the latest, before this test)
+			rampUntil = slice;
+			slice = rampRedoIndex;
+			nSlices = (uint32_t)rampRedoIndex + 2;
+			nItems = sc.slices[nSlices - 1].first + sc.slices[nSlices - 1].count;
+			continue;
+		}
 		sc.slices[nSlices++] = cur;
 	}
 	// removeWronglyAlignedEnd, ...Common.h:1231-1241
@@ -696,7 +728,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 		int row = here.seqPos & 63;
 		if (row == 0 && here.offset == 0) {
 			Cell nxt; bool sw;
-			if (!backtraceCorner(g, sc, s, curNode, curItem, eq, nxt, sw)) return EXT_ASSERT;
+			if (!backtraceCorner<BAND>(g, sc, s, curNode, curItem, eq, nxt, sw)) return EXT_ASSERT;
 			if (!pushTrace(sc, cfg, nTrace, nxt, sw, status)) return status;
 			here = nxt;
 			continue;
@@ -720,7 +752,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			if (refillTo != NO_REFILL) continue;
 			if (off == 0) {
 				Cell nxt; bool sw;
-				if (!backtraceCorner(g, sc, s, curNode, curItem, eq, nxt, sw)) return EXT_ASSERT;
+				if (!backtraceCorner<BAND>(g, sc, s, curNode, curItem, eq, nxt, sw)) return EXT_ASSERT;
 				if (!pushTrace(sc, cfg, nTrace, nxt, sw, status)) return status;
 				here = nxt;
 				continue;
@@ -733,7 +765,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			int32_t scoreUp = scoreDiagonal + (int32_t)((pn.HP >> off) & 1) - (int32_t)((pn.HN >> off) & 1);
 			int32_t quitScore = cs.minScore + cs.bandwidth, previousQuitScore = ps.minScore + ps.bandwidth;
 			Cell nxt;
-			if (scoreHere > quitScore || scoreDiagonal > previousQuitScore || scoreUp > previousQuitScore) {
+			if ((BAND && ((cs.flags | ps.flags) & SLICE_NOT_VALID)) || scoreHere > quitScore || scoreDiagonal > previousQuitScore || scoreUp > previousQuitScore) {
 				nxt = scoreDiagonal < scoreUp ? Cell { curNode, off - 1, here.seqPos - 1 } : Cell { curNode, off, here.seqPos - 1 };
 			} else {
 				NodeSeq nseq = loadNodeSeq(g, curNode);
@@ -758,7 +790,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			int offset = sp & 63;
 			if (offset == 0) {
 				Cell nxt; bool sw;
-				if (!backtraceCorner(g, sc, s, curNode, curItem, eq, nxt, sw)) return EXT_ASSERT;
+				if (!backtraceCorner<BAND>(g, sc, s, curNode, curItem, eq, nxt, sw)) return EXT_ASSERT;
 				if (!pushTrace(sc, cfg, nTrace, nxt, sw, status)) return status;
 				here = nxt;
 				continue;
@@ -769,7 +801,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			int32_t quitScore = cs.minScore + cs.bandwidth;
 			Cell nxt { 0, 0, 0 };
 			bool sw = false, found = false;
-			if (scoreHere > quitScore) {
+			if ((BAND && (cs.flags & SLICE_NOT_VALID)) || scoreHere > quitScore) {
 				int32_t smallest = wsValue(start, offset - 1);
 				nxt = Cell { curNode, 0, sp - 1 };
 				for (uint32_t e = g.inOff[curNode]; e < g.inOff[curNode + 1]; e++) {
@@ -841,10 +873,11 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 	return status;
 }
 
+template <bool BAND = false>
 __device__ inline uint32_t extendSeed(const DGraph& g, const CorrectnessTables& ct, const uint8_t* iupac, const ExtendConfig& cfg, const LaneScratch& sc,
 	const char* seq, int len, uint32_t startNode, uint32_t startOffset, uint32_t& nTrace, int32_t& score, ExtCounters& cnt)
 {
-	return extendSeedT(g, ct, EqFromBases { seq, iupac }, cfg, sc, len, startNode, startOffset, nTrace, score, cnt);
+	return extendSeedT<EqFromBases, BAND>(g, ct, EqFromBases { seq, iupac }, cfg, sc, len, startNode, startOffset, nTrace, score, cnt);
 }
 
 } // namespace gcdev

@@ -580,9 +580,11 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 
 
 // Full seed extension, wave layout. Trace goes to trace region `which` of the wave scratch (start cell first).
-template <bool REGCOLS>
+// BAND: the band controls (gc_params::ramp_bandwidth / max_cells_per_slice) as extendSeedT<.., true> has them. The ramp's rewind and the cell limit's break run here; an
+// extension that keeps a slice flagged scoresNotValid answers EXT_OVERFLOW (its read goes to the plain-layout fallback, whose backtrace has the flagged rules).
+template <bool REGCOLS, bool BAND = false>
 __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const CorrectnessTables& ct, const EqSource& eqSrc, int bandwidthCfg, lds_u32* lds, const WaveScratch& wsx,
-	int len, uint32_t startNode, uint32_t startOffset, uint32_t which, uint32_t& nTrace, int32_t& score, ExtCounters& cnt)
+	int len, uint32_t startNode, uint32_t startOffset, uint32_t which, uint32_t& nTrace, int32_t& score, ExtCounters& cnt, int rampBandwidth = 0, uint32_t maxCells = ~0u)
 {
 	const LaneLdsT<REGCOLS> L { lds, wsx.lane, wsx.lanes, wsx.spillBase(), {}, wsx.regCap < 64 ? wsx.regCap : 64u, { 0, 0, 0, 0, 0 }, 0, 0 };
 	uint32_t status = EXT_OK;
@@ -619,12 +621,22 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 	GC_MARK_START();
 	int32_t prevMinScore = 0, prevBandwidth = 1, prevJ = -64;
 	double prevCorrect = ct.initCorrect, prevFalse = ct.initFalse;
+	// (BAND) the ramp, ...Banded.h:540-644: the snapshot is the kept slice rampRedoIndex - its record and items are on the stack already; what a rewind needs besides them is
+	// kept here: its correctness state, the column-store cursor behind its items, and the minima of its band entries (the item records hold column-store offsets instead),
+	// which go to the trace region - unused until the backtrace
+	int rampUntil = 0, rampRedoIndex = -1;
+	const bool rampOn = BAND && rampBandwidth > bandwidthCfg;
+	double snapCorrect = 0, snapFalse = 0;
+	uint32_t snapCols = 0;
 	Eq4 eq;
 	for (int slice = 0; slice < numSlices; slice++) {
 		int j = prevJ + 64;
 		eqVectorBits(eqSrc, len, j, eq);
 		int32_t previousQuitScore = prevMinScore + prevBandwidth;
 		int bandwidth = bandwidthCfg;
+		if (BAND && rampOn && rampUntil >= slice) bandwidth = rampBandwidth;
+		const uint32_t sliceCols = nCols;   // (BAND) the column-store cursor behind the previous slice's items
+		uint32_t cells = 0;                 // (BAND) cellsProcessed: on a DAG a node is computed once per slice and counts its length (...Common.h:1162)
 		int flatRows = (j + 64 > len) ? (len - j) : 0;
 		const int cb = REGCOLS ? 1 : (buf ^ 1);   // table buffer `cb` = current slice
 		auto prevFind = [&](uint32_t node) __attribute__((always_inline)) -> int { return L.find((uint32_t)(REGCOLS ? 0 : buf), nPrev, node); };
@@ -763,6 +775,10 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				}
 				GC_MARK(4);   // out-edge pushes
 			} else GC_MARK(3);
+			if (BAND) {   // ...Banded.h:400-405: past the limit the rest of the queue is dropped
+				cells += tileLength;
+				if (cells > maxCells) break;
+			}
 		}
 		GC_MARK(1);
 		if (cur.count == 0) return EXT_ASSERT;
@@ -781,7 +797,33 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			curFalse = (c > d ? c : d) + ct.wrongOdds[idx];
 			cur.flags = (curCorrect > curFalse ? 1u : 0u) | (cfc ? 2u : 0u) | (ffc ? 4u : 0u) | flatTie;
 		}
+		if (BAND) {
+			if (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u))) {   // ...Banded.h:572-576: the previous slice is the snapshot
+				if (nPrev > wsx.maxTrace) return EXT_OVERFLOW;
+				rampRedoIndex = slice - 1;
+				snapCorrect = prevCorrect; snapFalse = prevFalse; snapCols = sliceCols;
+				for (uint32_t i = 0; i < nPrev; i++) { const int32_t mn = L.pMin(buf, i); if (wsx.storer()) wsx.word(wsx.traceBase(i, which)) = (unsigned long long)(uint32_t)mn; }
+			}
+			if (cells >= maxCells) cur.flags |= SLICE_NOT_VALID;   // ...Banded.h:581-584 (>=)
+		}
 		if (!(cur.flags & 2u)) break;
+		if (BAND && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
+			// ...Banded.h:608-644: redo from the snapshot with the ramp bandwidth up to this slice - truncate the slice and item stacks and the column store to it, and reload
+			// the previous-slice table (entry e = item first + e) and the correctness state (rampRedoIndex >= 0: the snapshot is taken at slice rampUntil + 1 at the latest)
+			rampUntil = slice;
+			slice = rampRedoIndex;
+			nSlices = (uint32_t)rampRedoIndex + 2;
+			const WSlice snap = loadSlice(wsx, nSlices - 1);
+			nItems = snap.first + snap.count;
+			nCols = snapCols;
+			prevMinScore = snap.minScore; prevBandwidth = snap.bandwidth; prevJ = snap.j; prevCorrect = snapCorrect; prevFalse = snapFalse;
+			nPrev = snap.count;
+			for (uint32_t i = 0; i < snap.count; i++) {
+				const NodeItem it = loadItem(wsx, snap.first + i);
+				L.pSet(buf, i, it.node, it.sScore, (int32_t)(uint32_t)wsx.word(wsx.traceBase(i, which)), it.HP, it.HN);
+			}
+			continue;
+		}
 		storeSlice(wsx, nSlices++, cur);
 		prevMinScore = cur.minScore; prevBandwidth = cur.bandwidth; prevJ = cur.j; prevCorrect = curCorrect; prevFalse = curFalse;
 		nPrev = cur.count;
@@ -799,6 +841,8 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		}
 	}
 	if (nSlices <= 1) return EXT_FAILED;
+	if (BAND && maxCells != ~0u)   // a kept slice that reached the cell limit: its backtrace takes the scoresNotValid rules, which this core does not have
+		for (uint32_t k = 1; k < nSlices; k++) if (loadSlice(wsx, k).flags & SLICE_NOT_VALID) return EXT_OVERFLOW;
 	WSlice last = loadSlice(wsx, nSlices - 1);
 	if (last.minScore < 0 || last.minScore > len + 128) return EXT_ASSERT;
 	score = last.minScore;

@@ -62,11 +62,13 @@ struct FragDevStore {
 
 uint64_t extendFragScratchBytes(uint32_t waves) { return (uint64_t)waves * FRAG_I * 3 * 64 * sizeof(uint4); }
 
-// 127 VGPRs or fewer: four waves per SIMD, which is also what the LDS words of four waves per SIMD leave room for
+// 127 VGPRs or fewer: four waves per SIMD, which is also what the LDS words of four waves per SIMD leave room for.
+// CELLS (gc_params::max_cells_per_slice): a lane whose slice reached the limit declines its extension - the break and the scoresNotValid walk are k_extend_slab_band's.
+template <bool CELLS>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_extend(DGraph g, const CorrectnessTables* __restrict__ ct, int32_t bandwidth,
 	const ExtItem* __restrict__ work, uint32_t nWork, const FragReads reads, ExtResult* __restrict__ results, uint4* __restrict__ itemScratch,
 	PoolCell* __restrict__ tracePool, unsigned long long* __restrict__ traceCursor, uint64_t traceCapacity, unsigned long long* __restrict__ counters, ExtSelection sel,
-	unsigned long long* __restrict__ claim, uint32_t* __restrict__ retryList, unsigned long long* __restrict__ retryCount, unsigned long long* __restrict__ stamps)
+	unsigned long long* __restrict__ claim, uint32_t* __restrict__ retryList, unsigned long long* __restrict__ retryCount, unsigned long long* __restrict__ stamps, uint32_t maxCells)
 {
 	__shared__ uint32_t ldsWords[FRAG_WORDS * 64];
 	__shared__ uint32_t waveCounters[8];
@@ -75,6 +77,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
 	FragParams P;
 	P.bandwidth = bandwidth;
 	P.keepMask = __ballot(fragSliceKept(*ct, (int)lane));
+	if (CELLS) P.maxCells = maxCells;
 	FragMem<FragDevStore> m;
 	m.lds = ldsWords + lane;
 	m.items = itemScratch + (uint64_t)blockIdx.x * (FRAG_I * 3 * 64) + lane;
@@ -116,14 +119,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
 					// (a full trace pool answers EXT_OVERFLOW like anything else that did not fit, but is not handed to the plain-layout kernel: that would find the same pool full - a stream's
 					// first batch on a 960 Mbp graph sent 7.5 M of 42 M extensions through its 2 048 lanes for 2.4 s before the host sized the pool again)
 					const bool poolFull = L.status == EXT_POOL_FULL;
-					res.status = poolFull ? (uint32_t)EXT_OVERFLOW : L.status;
+					const uint32_t status = CELLS && fragCellLimitReached(P, L) ? (uint32_t)EXT_OVERFLOW : L.status;
+					res.status = poolFull ? (uint32_t)EXT_OVERFLOW : status;
 					res.score = L.resultScore;
-					res.traceOff = L.status == EXT_OK ? L.traceBase : 0;
-					res.traceLen = L.status == EXT_OK ? L.nTrace : 0;
-					res.pad = L.status == EXT_OK ? L.tie : 0;
+					res.traceOff = status == EXT_OK ? L.traceBase : 0;
+					res.traceLen = status == EXT_OK ? L.nTrace : 0;
+					res.pad = status == EXT_OK ? L.tie : 0;
 					results[L.work] = res;
 					if (poolFull) {}
-					else if (L.status == EXT_OVERFLOW) { retryList[atomicAdd(retryCount, 1ull)] = L.work; atomicAdd(&waveCounters[6], 1u); }   // declined: the plain-layout kernel runs it (and counts its work)
+					else if (status == EXT_OVERFLOW) { retryList[atomicAdd(retryCount, 1ull)] = L.work; atomicAdd(&waveCounters[6], 1u); }   // declined: the plain-layout kernel runs it (and counts its work)
 					else {
 						const bool flat = L.len < 64;
 						const uint32_t dpTiles = L.cntTiles & 0xffffu, btTiles = L.cntTiles >> 16, dpCols = L.cntCols & 0xffffu, btCols = L.cntCols >> 16;
@@ -232,7 +236,7 @@ uint32_t extendFragWaves()
 {
 	static const uint32_t waves = []() {
 		int perCu = 0, dev = 0, cus = 256;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_extend, 64, 0) != hipSuccess || perCu <= 0) perCu = 12;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_extend<false>, 64, 0) != hipSuccess || perCu <= 0) perCu = 12;
 		hipDeviceProp_t prop;
 		if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
 		return (uint32_t)(perCu * cus);
@@ -242,14 +246,18 @@ uint32_t extendFragWaves()
 
 void launchExtendFrag(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, int32_t bandwidth, const ExtItem* work, uint32_t nWork, const FragReads& reads, ExtResult* results,
 	uint4* itemScratch, uint32_t scratchWaves, PoolCell* tracePool, unsigned long long* traceCursor, uint64_t traceCapacity, unsigned long long* counters, ExtSelection sel, unsigned long long* claim,
-	uint32_t* retryList, unsigned long long* retryCount, unsigned long long* stamps)
+	uint32_t* retryList, unsigned long long* retryCount, unsigned long long* stamps, uint64_t maxCells)
 {
 	if (nWork == 0) return;
 	const uint32_t upper = sel.mode == 1 ? 2 * sel.nFrags : nWork;
 	uint32_t waves = (upper + 63) / 64;
 	if (waves > scratchWaves) waves = scratchWaves;
 	if (waves == 0) return;
-	hipLaunchKernelGGL(k_extend, dim3(waves), dim3(64), 0, stream, g, ct, bandwidth, work, nWork, reads, results, itemScratch, tracePool, traceCursor, traceCapacity, counters, sel, claim, retryList, retryCount, stamps);
+	// (a fragment's slice has at most GC_FRAG_ITEMS tiles of 64 columns: a larger limit is never reached here)
+	if (maxCells < 0xffffull)
+		hipLaunchKernelGGL(k_extend<true>, dim3(waves), dim3(64), 0, stream, g, ct, bandwidth, work, nWork, reads, results, itemScratch, tracePool, traceCursor, traceCapacity, counters, sel, claim, retryList, retryCount, stamps, (uint32_t)maxCells);
+	else
+		hipLaunchKernelGGL(k_extend<false>, dim3(waves), dim3(64), 0, stream, g, ct, bandwidth, work, nWork, reads, results, itemScratch, tracePool, traceCursor, traceCapacity, counters, sel, claim, retryList, retryCount, stamps, 0u);
 }
 
 } // namespace gcdev

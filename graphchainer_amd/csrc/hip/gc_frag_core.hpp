@@ -45,6 +45,7 @@ enum : uint32_t { TF_START = 1u, TF_WALK = 2u };   // Lane::tileFlags: the tile 
 struct FragParams {
 	int32_t bandwidth;
 	uint64_t keepMask;       // bit i: a slice whose minimum is min(i, 63) above the initial slice's is kept and currently correct (the HMM's one step)
+	uint32_t maxCells = 0xffffffffu;   // maxCellsPerSlice (0xffffffff: unlimited). The ramp needs nothing here: a fragment extension is one slice, run at the ramp bandwidth
 };
 
 // The HMM's single step laid open: the slice is kept when CorrectFromCorrect holds for the initial state (src/GraphAlignerBitvectorBanded.h:589-607) and survives
@@ -141,6 +142,9 @@ __device__ inline uint64_t eqOfColumn2(const Eq4& eq, uint64_t w0, uint64_t w1, 
 	return (code & 2) ? hi : lo;
 }
 
+// The cell limit (...Banded.h:400-405,581-584) changes a slice only when its cell count - the DP's columns, a DAG node being computed once - reaches the limit (>=: the
+// scoresNotValid flag; the break needs more). This core then declines (EXT_OVERFLOW) and the plain-layout core runs the extension with the limit. (Counted in the low half of cntCols.)
+__host__ __device__ inline bool fragCellLimitReached(const FragParams& P, const Lane& L) { return (L.cntCols & 0xffffu) >= P.maxCells; }
 __device__ inline void fragRetire(Lane& L, uint32_t status) { L.status = status; L.phase = PH_FETCH; }
 
 __device__ inline uint64_t fragFlatMask(uint32_t len) { return len >= 64 ? ~0ull : ((1ull << len) - 1); }

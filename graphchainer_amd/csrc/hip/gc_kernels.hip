@@ -158,6 +158,7 @@ __device__ __forceinline__ LaneScratch laneScratch(uint8_t* slab, const ExtendCo
 // 4 waves per SIMD (<= 128 VGPRs; the kernel wanted 131 and ran 3): it waits on memory 56 % of the time, so the extra wave
 // pays for the 4 spilled registers: 34.2 -> 29.0 ms alone on cfg2 (5 or 6 waves spill 57 / 196 registers and lose).
 #define GC_EXTEND_SLAB_PARAMS DGraph g, const CorrectnessTables* __restrict__ ct, const uint8_t* __restrict__ iupac, ExtendConfig cfg, 	const ExtItem* __restrict__ work, uint32_t nWork, const char* __restrict__ bases, ExtResult* __restrict__ results, 	uint8_t* __restrict__ scratch, uint64_t slabBytes, PoolCell* __restrict__ tracePool, unsigned long long* __restrict__ traceCursor, uint64_t traceCapacity, 	unsigned long long* __restrict__ counters, uint32_t retryStatus, ExtSelection sel
+template <bool BAND>
 __device__ __forceinline__ void extendSlabBody(GC_EXTEND_SLAB_PARAMS)
 {
 #if defined(GC_EXTEND_PRIO) && GC_EXTEND_PRIO
@@ -181,7 +182,7 @@ __device__ __forceinline__ void extendSlabBody(GC_EXTEND_SLAB_PARAMS)
 		ExtItem it = work[w];
 		uint32_t nTrace = 0;
 		int32_t score = 0;
-		uint32_t status = extendSeed(g, *ct, iupac, cfg, sc, bases + it.seqOff, (int)it.seqLen, it.node, it.offset, nTrace, score, cnt);
+		uint32_t status = extendSeed<BAND>(g, *ct, iupac, cfg, sc, bases + it.seqOff, (int)it.seqLen, it.node, it.offset, nTrace, score, cnt);
 		ExtResult res;
 		res.status = status;
 		res.score = score;
@@ -214,7 +215,12 @@ __device__ __forceinline__ void extendSlabBody(GC_EXTEND_SLAB_PARAMS)
 // 4 waves per SIMD (<= 128 VGPRs): everything, when the lockstep kernel is switched off (GC_EXTEND_SLAB=1)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_extend_slab(GC_EXTEND_SLAB_PARAMS)
 {
-	extendSlabBody(g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
+	extendSlabBody<false>(g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
+}
+// the same with the band controls (gc_params::ramp_bandwidth / max_cells_per_slice): the fragments whose slice reaches the cell limit, which k_extend declines
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_extend_slab_band(GC_EXTEND_SLAB_PARAMS)
+{
+	extendSlabBody<true>(g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
 }
 // =====================================================================================================
 // K3b - fragment post-pass: merges the two one-way traces of every seed, replays the reference's serial
@@ -875,6 +881,7 @@ __device__ inline uint32_t endToEndScore(LongAln* mine, uint32_t nAln, uint32_t 
 	return contiguousEnd == readLen ? minGoodness : current;
 }
 
+template <bool BAND>   // BAND: the band controls of cfg (extendSeedT<.., true>)
 __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTables* __restrict__ ct, const uint8_t* __restrict__ iupac, ExtendConfig cfg,
 	const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, const char* __restrict__ bases, uint64_t rcBase,
 	uint32_t minClusterSize, uint32_t maxAlignments, uint8_t* __restrict__ scratch, uint64_t slabBytes,
@@ -927,11 +934,11 @@ __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTab
 			if (p > 0) {
 				uint32_t twinNode, twinOffset;
 				twinOf(g, sd.node, sd.offset, twinNode, twinOffset);
-				stB = extendSeed(g, *ct, iupac, cfg, ls.sc, bases + rcBase + job.readOff + (uint64_t)(L - p), p, twinNode, twinOffset, nB, scoreB, cnt);
+				stB = extendSeed<BAND>(g, *ct, iupac, cfg, ls.sc, bases + rcBase + job.readOff + (uint64_t)(L - p), p, twinNode, twinOffset, nB, scoreB, cnt);
 				ties += cnt.flattenTie;
 				if (stB == EXT_OK) for (uint32_t i = 0; i < nB; i++) ls.traceB[i] = ls.sc.trace[i];
 			}
-			if (p < L - 1 && stB != EXT_ASSERT) { stF = extendSeed(g, *ct, iupac, cfg, ls.sc, bases + job.readOff + (uint64_t)(p + 1), L - 1 - p, sd.node, sd.offset, nF, scoreF, cnt); ties += cnt.flattenTie; }   // (a throwing backward extension ends getAlignmentFromSeed before the forward one runs)
+			if (p < L - 1 && stB != EXT_ASSERT) { stF = extendSeed<BAND>(g, *ct, iupac, cfg, ls.sc, bases + job.readOff + (uint64_t)(p + 1), L - 1 - p, sd.node, sd.offset, nF, scoreF, cnt); ties += cnt.flattenTie; }   // (a throwing backward extension ends getAlignmentFromSeed before the forward one runs)
 			if (stB == EXT_ASSERT || stF == EXT_ASSERT) { status = 1; break; }
 			if (stB == EXT_OVERFLOW || stF == EXT_OVERFLOW) { status = 2; break; }
 			bool hasB = stB == EXT_OK, hasF = stF == EXT_OK;
@@ -1112,7 +1119,7 @@ __global__ void __launch_bounds__(64) k_long_select(DGraph g, const LongJob* __r
 #ifndef GC_LONG_MIN_WAVES
 #define GC_LONG_MIN_WAVES 1
 #endif
-template <int LANES, bool PERSISTENT>
+template <int LANES, bool PERSISTENT, bool BAND = false>   // BAND: the band controls of cfg (extendSeedWave<.., true>)
 #ifndef GC_LONG_WAVES_ONE
 #define GC_LONG_WAVES_ONE 5   // waves per SIMD the one-extension-per-wave instantiation is compiled for. 8: 64 VGPRs, 35 of them spilled to 112 B of scratch per lane; 7: 72 / 80 B; 6: 80 / 48 B;
                               // 5 (and 4): 87 VGPRs, no scratch. The kernel is bound by the CU's scalar unit, not by latency: all five measure the same, so the build without scratch is kept
@@ -1162,7 +1169,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES =
 			uint32_t nTrace = 0;
 			int32_t score = 0;
 			EqSource eqSrc { masks + it.maskOff, it.maskWords, it.startBit };
-			res.status = extendSeedWave<LANES == 1>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt);
+			if (BAND) res.status = extendSeedWave<LANES == 1, true>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt,
+				cfg.rampBandwidth, cfg.maxCells);
+			else res.status = extendSeedWave<LANES == 1>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt);
 			res.score = score;
 			res.pad = cnt.flattenTie;   // (k_long_merge adds the flags of the extensions the reference would have run to the read's count)
 			if (res.status == EXT_OK) {
@@ -1510,7 +1519,8 @@ void launchExtend(hipStream_t stream, const DGraph& g, const CorrectnessTables* 
 	if (nWork == 0) return;
 	const uint32_t upper = sel.mode == 1 ? 2 * sel.nFrags : nWork;   // (a device-side list holds at most nWork items; waves beyond its count leave at once)
 	uint32_t lanes = retryStatus ? retryLanes : extendGridLanes(upper);
-	hipLaunchKernelGGL(k_extend_slab, dim3(lanes / 64), dim3(64), 0, stream, g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
+	if (cfg.bandControls()) hipLaunchKernelGGL(k_extend_slab_band, dim3(lanes / 64), dim3(64), 0, stream, g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
+	else hipLaunchKernelGGL(k_extend_slab, dim3(lanes / 64), dim3(64), 0, stream, g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
 }
 
 void launchBuildAnchors(hipStream_t stream, const DGraph& g, const Fragment* frags, uint32_t nFrags, const FragSeed* seeds, const ExtResult* ext,
@@ -1596,8 +1606,11 @@ void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 #else
 	const uint32_t pad = 0;
 #endif
-#define GC_LAUNCH_TEAM(N) do { if (persistent) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_extend<N, true>), dim3(blocks), dim3(64), pad, stream, g, ct, masks, cfg, work, order, nWork, scratch, words, tracePool, traceCursor, traceCapacity, results, counters, nextSlot, retryStatus, nWorkOnDevice, capListOut, capCountOut); \
-	else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_extend<N, false>), dim3(blocks), dim3(64), pad, stream, g, ct, masks, cfg, work, order, nWork, scratch, words, tracePool, traceCursor, traceCapacity, results, counters, nextSlot, retryStatus, nWorkOnDevice, capListOut, capCountOut); } while (0)
+	// the band controls (gc_params::ramp_bandwidth / max_cells_per_slice) run in their own instantiation: the default one is compiled as before
+	const bool band = cfg.bandControls();
+#define GC_LAUNCH_ONE(N, P, B) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_extend<N, P, B>), dim3(blocks), dim3(64), pad, stream, g, ct, masks, cfg, work, order, nWork, scratch, words, tracePool, traceCursor, traceCapacity, results, counters, nextSlot, retryStatus, nWorkOnDevice, capListOut, capCountOut)
+#define GC_LAUNCH_TEAM(N) do { if (band) { if (persistent) GC_LAUNCH_ONE(N, true, true); else GC_LAUNCH_ONE(N, false, true); } \
+	else if (persistent) GC_LAUNCH_ONE(N, true, false); else GC_LAUNCH_ONE(N, false, false); } while (0)
 	switch (lanes) {
 		case 1: GC_LAUNCH_TEAM(1); break;
 		case 2: GC_LAUNCH_TEAM(2); break;
@@ -1608,6 +1621,7 @@ void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 		default: GC_LAUNCH_TEAM(64); break;
 	}
 #undef GC_LAUNCH_TEAM
+#undef GC_LAUNCH_ONE
 }
 #ifdef GC_EXPERIMENTS
 void launchLongExtendLane(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint64_t* masks, const ExtendConfig& cfg, const LongWork* work, const uint32_t* order, uint32_t nWork,
@@ -1723,8 +1737,12 @@ void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables
 {
 	if (nReads == 0) return;
 	uint32_t blocks = (nReads + 63) / 64;
-	hipLaunchKernelGGL(k_long_pass, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, maxAlignments, scratch, slabBytes,
-		cellPool, cellCursor, cellCapacity, alns, results, counters);
+	if (cfg.bandControls())
+		hipLaunchKernelGGL(k_long_pass<true>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, maxAlignments, scratch, slabBytes,
+			cellPool, cellCursor, cellCapacity, alns, results, counters);
+	else
+		hipLaunchKernelGGL(k_long_pass<false>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, maxAlignments, scratch, slabBytes,
+			cellPool, cellCursor, cellCapacity, alns, results, counters);
 }
 
 } // namespace gcdev

@@ -86,6 +86,13 @@ typedef struct gc_params {
 	double  e_cutoff;           /* --E-cutoff (src/AlignerMain.cpp:159,271-274; SelectECutoff src/AlignmentSelection.cpp:57-61,91-99):
 	                             *    alignments with a larger E-value are dropped before selection; -1 (default) keeps all */
 	gc_capacities capacity;     /* sizes of the device-side tables (all 0 = automatic: sized from the batch) */
+	int32_t ramp_bandwidth;     /* -B, --ramp-bandwidth, rampBandwidth (src/AlignerMain.cpp:95,147,248): 0 (default) off; else > bandwidth
+	                             *    (src/AlignerMain.cpp:380-383; GC_ERR_INVALID otherwise). An extension's first slice, and the slices redone after
+	                             *    a slice turns "not currently correct", run with this band (getViterbiSlices, src/GraphAlignerBitvectorBanded.h:530-644).
+	                             *    A fragment extension is one slice, so the fragment pass runs at this bandwidth outright. */
+	int64_t max_cells_per_slice; /* -C, --tangle-effort, maxCellsPerSlice (src/AlignerMain.cpp:96,149,249): -1 (default) unlimited; 0 and up literal
+	                             *    (< -1: GC_ERR_INVALID). A slice stops taking nodes once its DP cells pass this count, and a slice that reaches it
+	                             *    is backtraced with the "scores not valid" rules (src/GraphAlignerBitvectorBanded.h:400-405,579-584, ...Common.h:599-804). */
 } gc_params;
 
 void gc_params_default(gc_params* p);
