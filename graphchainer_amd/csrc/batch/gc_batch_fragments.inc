@@ -255,9 +255,6 @@
 			HIP_CHECK(hipMemsetAsync(dCursor, 0, sizeof(unsigned long long), stream));
 			int stitchClass = maxReadLen > 16384 ? 3 : 0;
 			if (const char* env = getenv("GC_STITCH_CLASS")) stitchClass = atoi(env) == 3 ? 3 : 0;
-#ifdef GC_EXPERIMENTS
-			if (getenv("GC_STITCH_SMALL") && atoi(getenv("GC_STITCH_SMALL")) && maxReadLen <= 16384) stitchClass = 1;   // (r4: the half-size search tables, measured and not kept)
-#endif
 			launchStitch(stream, G->dev, dJobs, (uint32_t)n, dAnchors, dFrags, dFragStatus, dChainOut, dChainLen, dChainStatus, dPathPool, pathCapacity, (long long)P->colinear_gap, dSlotOf,
 				dRegions, dStitchNodes, stitchDenseCap, dCursor, dStitchInfo,
 				(uint32_t)capacityOr("GC_TEST_STITCH_SET_MAX", P->capacity.stitch_set_max, 0), (uint32_t)capacityOr("GC_TEST_STITCH_BFS_CAP", P->capacity.stitch_bfs_cap, 0),

@@ -1,6 +1,6 @@
 // gc_batch.hip, stage by stage (r6: one file of 2 000 lines before): the whole-read pass: set-up, the round loop, fallback reruns, selection and NW distance, its own host thread.
 // Member functions of struct BatchRun - this file is included INSIDE the struct's body (gc_batch.hip), which holds the members, the constructor and run().
-	// ---------------- K3-long set-up: buffers, the round loop (runLongGroup), the rerun rules; nothing runs yet
+	// ---------------- K3-long set-up: buffers, the round loop (runLongRounds), the rerun rules; nothing runs yet
 	void prepareWholeReadPass()
 	{
 		// ---------------- K3-long: whole-read pass on its own stream (src/Aligner.cpp:630-654)
@@ -63,20 +63,12 @@
 			dLongAlns = st->longAlns.reserve<LongAln>(n * maxAlignments);
 			LongReadResult* dLongResults = st->longResults.reserve<LongReadResult>(n);
 			dLongCells = st->longCells.reserve<LongCell>(cellBudget, true);
-			// Read groups: the rounds of one group are serial (select -> extend -> merge, host decides when to stop). Groups can
-			// run their round loops concurrently, each on its own stream and host thread (GC_LONG_GROUPS). Measured on cfg2
-			// (10k reads): 1 group 367 ms/step, 2 groups 517, 4 groups 477, 8 groups 607 - the groups' big rounds coincide and
-			// their tails too, so nothing overlaps usefully and the kernels slow each other down. Default: one group.
-			nGroups = 1;
-			if (const char* env = expEnv("GC_LONG_GROUPS")) nGroups = (uint32_t)std::max(1, std::min(16, atoi(env)));   // (experiments build only)
-			if (n < 64ull * nGroups) nGroups = 1;
-			while (st->groupStreams.size() < nGroups) {
-				hipStream_t q = nullptr;
-				createStream(&q, 1);
-				st->groupStreams.push_back(q);
-				for (int k = 0; k < 2 * LONG_EVENT_RING; k++) { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreate(&e)); st->groupEvents.push_back(e); }   // a ring of (begin, end) pairs around the rounds' extension launches
+			// the rounds are serial (select -> extend -> merge, the host decides when to stop) and have a stream of their own beside the pass's stream
+			if (!st->roundStream) {
+				createStream(&st->roundStream);
+				for (auto& e : st->roundEvents) HIP_CHECK(hipEventCreate(&e));
 			}
-			// cursors: [0] cell pool, [8..15] counters (+ [16..31] profiling stamps), per group g at 32+8g: [+0] work count, [+1] round trace cursor
+			// cursors: [0] cell pool, [8..15] counters (+ [16..31] profiling stamps), the round loop's at [32..35]: work count, round trace cursor, next work slot, length of the retry list
 			cursorWords = 32 + 8 * 16;
 			dLongCursor = st->longCursor.reserve<unsigned long long>(cursorWords);
 			hLongAlns = st->hLongAlns.reserve<LongAln>(n * maxAlignments);
@@ -86,45 +78,32 @@
 			HIP_CHECK(hipMemsetAsync(dLongCursor, 0, cursorWords * sizeof(unsigned long long), ls));
 			if (nLongSeeds && !deviceGlue) HIP_CHECK(hipMemcpyAsync(dLongSeeds, hSeeds, nLongSeeds * sizeof(LongSeed), hipMemcpyHostToDevice, ls));
 			if (n) HIP_CHECK(hipMemcpyAsync(dLongJobs, hJobs, n * sizeof(LongJob), hipMemcpyHostToDevice, ls));
-			syncStream(ls);   // the group streams start from uploaded inputs
+			syncStream(ls);   // the round stream starts from uploaded inputs
 			// rounds: select -> extend -> merge until no read has a seed left to extend (see gc_kernels.hip, "K3-long in rounds")
 			dLongState = st->longState.reserve<LongState>(n);
-			const uint64_t workCapacity = 8 * n + 64ull * nGroups;   // all groups together; group g owns the slice for its reads
+			workCapacity = 8 * n + 64;
 			dLongWork = st->longWork.reserve<LongWork>(workCapacity);
 			dLongWorkResults = st->longWorkResults.reserve<LongWorkResult>(workCapacity);
-			dCandSeed = st->longCandSeed.reserve<uint32_t>(2 * workCapacity);   // (two halves: k_long_round alternates them by the round's parity)
+			dCandSeed = st->longCandSeed.reserve<uint32_t>(2 * workCapacity);   // (the rounds use the first half; the size is as it has been)
 			dWorkLen = st->longWorkLen.reserve<uint32_t>(workCapacity);   // written by k_long_select, sorted into dOrder by k_long_order: the host only
 			dRetryList = st->longRetryList.reserve<uint32_t>(workCapacity);   // work items whose band outgrew the register tables (per round)
 			dOrder = st->longOrder.reserve<uint32_t>(workCapacity);       // learns the round's work count (k_publish: no copy-engine transfer in the round loop)
-			groupBegin.assign(nGroups + 1, 0); groupTraceBegin.assign(nGroups + 1, 0);
-			for (uint32_t g = 0; g <= nGroups; g++) groupBegin[g] = n * g / nGroups;
-			for (uint32_t g = 0; g < nGroups; g++) {
-				uint64_t budget = 0;
-				for (uint64_t r = groupBegin[g]; r < groupBegin[g + 1]; r++) { uint64_t len = R->offsets[r + 1] - R->offsets[r]; budget += 4 * (len + len / 2 + 1024); }   // up to four candidate seeds' worth per read (the speculation rule below keeps rounds within it)
-				groupTraceBegin[g + 1] = groupTraceBegin[g] + budget;
-			}
-			dRoundTrace = st->longRoundTrace.reserve<unsigned long long>(groupTraceBegin[nGroups]);
-			// extension scratch: one region per lane of a resident wave (persistent waves fetch work items), per read group
+			roundTraceBudget = 0;
+			for (uint64_t r = 0; r < n; r++) { uint64_t len = R->offsets[r + 1] - R->offsets[r]; roundTraceBudget += 4 * (len + len / 2 + 1024); }   // up to four candidate seeds' worth per read (the speculation rule of the round loop keeps rounds within it)
+			dRoundTrace = st->longRoundTrace.reserve<unsigned long long>(roundTraceBudget);
+			// extension scratch: one region per lane of a resident wave (persistent waves fetch work items)
 			// (bounded by a memory budget: 0.8 MB per lane for 10 kb reads, 2.4 MB for 50 kb reads; GC_TEST_LONG_SCRATCH_GB overrides the 48 GB)
 			uint64_t scratchBudget = P->capacity.long_scratch_bytes > 0 ? (uint64_t)P->capacity.long_scratch_bytes : (48ull << 30) / (uint64_t)longTokenCount(n, st->batchesDone, st->fragShare);
 			if (const char* env = getenv("GC_TEST_LONG_SCRATCH_GB")) scratchBudget = (uint64_t)std::max(1, atoi(env)) << 30;
 			// (r5: no more lanes than a round can hold without speculation - two work items per read; the late rounds' speculation stays below that, and a round that does exceed
 			// it runs persistent waves. A 2 000 x 50 kb batch reserved 48 GB for rounds of 4 000 extensions, a 10 k x 10 kb batch 48 GB for 20 000: now 20 and 27 GB)
 			scratchLanes = std::min<uint64_t>(std::min<uint64_t>(workCapacity + 64, 2 * n + 128), std::max<uint64_t>(2048, std::min<uint64_t>(65536 + 64, scratchBudget / (waveWords * 8))));
-			// one pass at a time (the default) works in the device's shared scratch; the experiments that let passes overlap keep a scratch per stream
-			longScratchWords = (uint64_t)nGroups * scratchLanes * waveWords;
-			shareLongScratch = nGroups == 1 && (getenv("GC_LONG_TOKEN") ? atoi(getenv("GC_LONG_TOKEN")) : 1) >= 1;   // (token per pass or per round: whoever holds it owns the scratch)
+			// one pass at a time (the default) works in the device's shared scratch; GC_LONG_TOKEN=0 lets passes overlap, each in its stream's own
+			longScratchWords = scratchLanes * waveWords;
+			shareLongScratch = (getenv("GC_LONG_TOKEN") ? atoi(getenv("GC_LONG_TOKEN")) : 1) >= 1;   // (whoever holds the token owns the scratch)
 			if (!shareLongScratch) dLongScratchOwn = st->longScratch.reserve<unsigned long long>(longScratchWords);
-			groupExtendUs.assign(nGroups, 0.0);
-			groupRounds.assign(nGroups, 0);
-			longGroups = nGroups;
 			// reads whose band did not fit the LDS tables (status 5) are rerun with the plain-layout kernel
 		}
-		// What follows the rounds: fallback reruns, the reference's `cont` rule, selection and the NW distance of the best whole-read alignment.
-		// With one read group it runs on the pass's own thread right after the rounds, beside the tail of the fragment pipeline (which ends
-		// 20-30 ms after the pass on cfg2, starved by it), instead of after the join: 16 ms off the batch's critical path.
-		// It writes the reads' long* fields and capacityExceededLong only; the fragment pipeline does not touch those.
-		longPostInThread = P->long_pass && longGroups == 1;
 		// The whole-read pass is the longest leg of the batch: its round loop runs on its own host thread and stream from
 		// here on, while this thread prepares and runs the fragment pipeline.
 	}
@@ -152,118 +131,22 @@
 		return true;
 	}
 
-#ifdef GC_EXPERIMENTS
-	// The round loop without a host round trip per round (r4; an experiment, GC_LONG_ROUNDS=1 - see roundsOnDevice): per round ONE kernel between two extension launches - k_long_round: the previous round's merge,
-	// this round's select, the execution order, the work count to the device and to pinned host memory - and the extension kernel takes its item count from the device
-	// (its grid is sized by a bound: 2 items per read, which the device-side speculation rule respects). Rounds are queued several at a time; the host looks at the published
-	// counts only at the end of a chunk (a round after the last one finds nothing to do and costs a few empty launches). r3's loop queued zero / select / order / publish,
-	// waited for the count, then extend / retry / merge: with five batches in flight each of those launches waited for a wave slot among the other batches' kernels and the
-	// pass took 149 ms for 121 ms of extension kernels.
-	bool roundsOnDevice(uint32_t g) const
+	void runLongRounds()   // the round loop: select -> extend -> merge until no read has a seed left to extend (see gc_kernels.hip, "K3-long in rounds")
 	{
-		if (nGroups != 1 || longExtendTeamSize(1) != 1) return false;
-		for (const char* name : { "GC_LONG_SM", "GC_LONG_LANE", "GC_TEST_LONG_MAX_BLOCKS", "GC_LONG_PLAN" }) if (getenv(name)) return false;   // experiments and test hooks of the host-driven loop
-		if (getenv("GC_LONG_TOKEN") && atoi(getenv("GC_LONG_TOKEN")) == 2) return false;
-		if (!(getenv("GC_LONG_ROUNDS") && atoi(getenv("GC_LONG_ROUNDS")) == 1)) return false;   // GC_LONG_ROUNDS=1 selects it: measured 4-6 % SLOWER than the host-driven loop (DESIGN.md §11), which stays the default
-		(void)g;
-		return true;
-	}
-	void runLongGroupOnDevice(uint32_t g)
-	{
-		const uint64_t r0 = groupBegin[g], nG = groupBegin[g + 1] - r0;
-		if (longTokenTake) longTokenTake();   // (rounds are queued ahead here: the token covers the whole loop)
-		unsigned long long* dLongScratch = shareLongScratch ? longScratchOfToken : dLongScratchOwn;
-		hipStream_t q = st->groupStreams[g];
-		hipEvent_t* ring = st->groupEvents.data() + (size_t)2 * LONG_EVENT_RING * g;
-		auto collect = [&](int slot) { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ring[2 * slot], ring[2 * slot + 1])); groupExtendUs[g] += (double)ms * 1000.0; };
-		const uint64_t w0 = 8 * r0 + 64ull * g, capacity = 8 * nG + 64;
-		unsigned long long* cursorSets = dLongCursor + 32 + 8 * g;   // two sets of four words: [0] work count, [1] round trace cursor, [2] next work slot, [3] length of the retry list
-		const uint64_t traceBudget = groupTraceBegin[g + 1] - groupTraceBegin[g];
-		const int MAX_ROUNDS = 250;
-		unsigned long long* dRoundInfo = st->longRoundInfo.reserve<unsigned long long>(MAX_ROUNDS + 8);   // [0] ticket, [1 + round] work items of the round
-		volatile unsigned long long* hInfo = st->hLongRoundInfo.reserve<unsigned long long>(MAX_ROUNDS + 8);   // [0] rounds published, [2 + round] work items of the round
-		hInfo[0] = 0;
-		const double dbgT0 = nowUs();
-		double dbgWaitUs = 0;
-		launchLongInit(q, dLongJobs + r0, (uint32_t)nG, dLongState + r0);
-		launchZeroWords(q, dRoundInfo, 1);
-		launchZeroWords(q, cursorSets, 8);
-		// the extension launch's grid: every lane of the scratch. Two items per read cover a round without speculation (a round never holds more items than the one before it),
-		// and the device-side rule keeps speculation within gridLimit; a batch whose 2 nG exceed the scratch's lanes runs persistent waves instead
-		const uint64_t laneLimit = std::max<uint64_t>(1, scratchLanes - 64);
-		const bool gridCovers = 2 * nG <= laneLimit;
-		const uint32_t gridLimit = (uint32_t)std::min<uint64_t>(capacity, laneLimit);   // (as many lanes as the scratch has: the late rounds' speculation rule may use them)
-		uint32_t forceCand = 0;
-		if (const char* env = getenv("GC_TEST_LONG_SPECULATE")) forceCand = (uint32_t)std::min(2, std::max(1, atoi(env)));   // test hook: speculate from round 0
-		const char* orderEnv = getenv("GC_TEST_LONG_ORDER");
-		const uint32_t orderMode = orderEnv ? (uint32_t)atoi(orderEnv) : 1u;
-		int queued = 0, timed = 0, done = -1;
-		while (done < 0 && queued < MAX_ROUNDS) {
-			const int chunk = queued == 0 ? 6 : 2;   // cfg2 needs six rounds; beyond that two at a time
-			for (int k = 0; k < chunk && queued < MAX_ROUNDS; k++, queued++) {
-				const uint32_t round = (uint32_t)queued;
-				unsigned long long* cur = cursorSets + 4 * (round & 1u);
-				launchLongRound(q, G->dev, dLongJobs + r0, (uint32_t)nG, dLongSeeds, (uint32_t)P->min_cluster_size, round, forceCand, gridLimit, dLongState + r0, dLongAlns, dLongCells, dLongCursor, cellBudget, maxAlignments,
-					dLongWork + w0, dWorkLen + w0, dCandSeed + w0, dLongWorkResults + w0, dRoundTrace + groupTraceBegin[g], cursorSets, dRoundInfo + 1, dRoundInfo, dOrder + w0, (uint32_t)maxReadLen, orderMode,
-					(unsigned long long*)hInfo, capacity);
-				if (timed >= LONG_EVENT_RING) collect(timed % LONG_EVENT_RING);
-				hipEvent_t ev0 = ring[2 * (timed % LONG_EVENT_RING)], ev1 = ring[2 * (timed % LONG_EVENT_RING) + 1];
-				HIP_CHECK(hipEventRecord(ev0, q));
-				launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dOrder + w0, gridCovers ? gridLimit : (uint32_t)std::min<uint64_t>(capacity, 0xffffffffull), dLongScratch + (uint64_t)g * scratchLanes * waveWords, 1, gridLimit,
-					dRoundTrace + groupTraceBegin[g], cur + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cur + 2, 0, cur, dRetryList + w0, cur + 3, gridCovers);
-				// extensions whose band outgrew the 64-entry register tables: second try with the LDS/HBM tables (two lanes per wave); the list is almost always empty
-				if (!gridCovers) launchZeroWords(q, cur + 2, 1);   // (persistent waves used the slot counter)
-				const uint32_t retryBlocks = std::min<uint32_t>(16, (uint32_t)std::max<uint64_t>(1, laneLimit / 2));
-				launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dRetryList + w0, (uint32_t)std::min<uint64_t>(capacity, 0xffffffffull), dLongScratch + (uint64_t)g * scratchLanes * waveWords, 2, retryBlocks,
-					dRoundTrace + groupTraceBegin[g], cur + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cur + 2, EXT_LDS_CAP, cur + 3);
-				HIP_CHECK(hipEventRecord(ev1, q));
-				timed++;
-			}
-			const double tWait0 = nowUs();
-			syncStream(q);
-			dbgWaitUs += nowUs() - tWait0;
-			if ((int)hInfo[0] != queued) throw std::runtime_error("internal: the whole-read rounds did not publish their counts");
-			for (int r = 0; r < queued && done < 0; r++) if (hInfo[2 + r] == 0) done = r;   // round `done` found no seed left to extend (its merge of the round before ran)
-		}
-		if (done < 0) throw std::runtime_error("whole-read pass: more rounds than the round loop queues");
-		groupRounds[g] += (uint32_t)done;
-		launchLongFinish(q, (uint32_t)nG, dLongState + r0, hLongResults + r0);
-		syncStream(q);
-		for (int k = std::max(0, timed - LONG_EVENT_RING); k < timed; k++) collect(k % LONG_EVENT_RING);
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] whole-read rounds (queued ahead): %.1f ms in all, %.1f ms waiting at the chunks' ends, %d rounds with work, %d queued\n", (nowUs() - dbgT0) / 1e3, dbgWaitUs / 1e3, done, queued);
-	}
-
-#endif
-
-	void runLongGroup(uint32_t g)   // the round loop of one read group: select -> extend -> merge until no read has a seed left to extend (see gc_kernels.hip, "K3-long in rounds")
-	{
-		const uint64_t r0 = groupBegin[g], nG = groupBegin[g + 1] - r0;
-		if (nG == 0) return;
-#ifdef GC_EXPERIMENTS
-		if (roundsOnDevice(g)) { runLongGroupOnDevice(g); return; }
-#endif
-		unsigned long long* dLongScratch = nullptr;   // (set when the token is taken - before the first extension launch; round token: under the lock, every round)
-		hipStream_t q = st->groupStreams[g];
-		hipEvent_t* ring = st->groupEvents.data() + (size_t)2 * LONG_EVENT_RING * g;
+		if (n == 0) return;
+		unsigned long long* dLongScratch = nullptr;   // (set when the token is taken - before the first extension launch)
+		hipStream_t q = st->roundStream;
+		hipEvent_t* ring = st->roundEvents;
 		// the rounds' extension time: read a ring slot's pair before the slot is reused (its round is complete by then: every round's
 		// work count has been awaited since) and what is left after the last round
-		auto collect = [&](int slot) { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ring[2 * slot], ring[2 * slot + 1])); groupExtendUs[g] += (double)ms * 1000.0; };
+		auto collect = [&](int slot) { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ring[2 * slot], ring[2 * slot + 1])); longExtendUs += (double)ms * 1000.0; };
 		int timedRounds = 0;
-		const uint64_t w0 = 8 * r0 + 64ull * g, capacity = 8 * nG + 64;   // this group's slice of the work arrays
-		unsigned long long* cursor = dLongCursor + 32 + 8 * g;
-		volatile unsigned long long* hCursor = hLongSmall + 32 + 8 * g;
-		const uint64_t traceBudget = groupTraceBegin[g + 1] - groupTraceBegin[g];
+		unsigned long long* cursor = dLongCursor + 32;
+		volatile unsigned long long* hCursor = hLongSmall + 32;
 		double dbgWaitUs = 0;
 		const double dbgT0 = nowUs();
-		launchLongInit(q, dLongJobs + r0, (uint32_t)nG, dLongState + r0);
+		launchLongInit(q, dLongJobs, (uint32_t)n, dLongState);
 		uint32_t lastWork = 0xffffffffu;
-		// GC_LONG_TOKEN=2: the token (and with it the device's extension scratch) is held per round - from the moment a round's extension kernel is queued until
-		// that kernel has finished - so that the small kernels and the host round trip between two rounds of one batch run beside another batch's extension kernel
-		int deviceNow = 0;
-		HIP_CHECK(hipGetDevice(&deviceNow));
-		const bool roundToken = expEnv("GC_LONG_TOKEN") && atoi(expEnv("GC_LONG_TOKEN")) == 2;   // (experiments build only; read per batch: the tests switch modes inside one process)
-		std::unique_lock<std::mutex> roundLock(g_longRoundToken[deviceNow & 15], std::defer_lock);
-		hipEvent_t roundExtendDone = nullptr;
 
 		for (int round = 0; round < 4096; round++) {
 			launchZeroWords(q, cursor, 4);   // [0] work count, [1] round trace cursor, [2] next work slot, [3] length of the retry list
@@ -271,43 +154,26 @@
 			// remaining reads try several seeds per round (exact: k_long_merge re-checks them in order)
 			// (the number of work items stays below what round 0 had: active reads x candidates <= n)
 			uint32_t maxCand = 1;
-			if (round > 0 && lastWork > 0) maxCand = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(1, (2 * nG) / lastWork));
+			if (round > 0 && lastWork > 0) maxCand = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(1, (2 * n) / lastWork));
 			if (round > 0 && lastWork < 8192) maxCand = 8;   // fewer work items than wave slots: the round costs one extension's latency whatever it holds
 			// at most lastWork/2 reads are still active, so this keeps the round within the work arrays (8 per read) and the trace budget (4 seeds' worth per read)
-			if (round > 0 && lastWork > 0) maxCand = (uint32_t)std::min<uint64_t>(maxCand, std::max<uint64_t>(1, (8 * nG) / lastWork));
+			if (round > 0 && lastWork > 0) maxCand = (uint32_t)std::min<uint64_t>(maxCand, std::max<uint64_t>(1, (8 * n) / lastWork));
 			if (const char* env = getenv("GC_TEST_LONG_SPECULATE")) maxCand = (uint32_t)std::min(2, std::max(1, atoi(env)));   // test hook: speculate from round 0
-			// speculation plan (r4): candidates per read in rounds 0, 1, 2, ... (the last entry repeats), a floor under the rule above; still bounded by the work arrays
-			// and the trace budget (at most nG / 2... reads x candidates <= 4 nG). Why: rounds 3-5 of cfg2 hold fewer work items than the chip has wave slots and cost one
-			// extension's latency (~17 ms) each - 98 % of the reads extend a second seed and 81 % a third, so asking for two seeds per read from round 0 on
-			// merges rounds at a few per cent of wasted extensions (k_long_merge drops a candidate that an alignment accepted before it explains).
-#ifdef GC_EXPERIMENTS
-			{
-				static const std::vector<int> plan = []() { std::vector<int> v; const char* e = getenv("GC_LONG_PLAN"); std::string t = e ? e : GC_LONG_PLAN_DEFAULT; size_t at = 0; while (at < t.size()) { v.push_back(std::max(1, std::min(8, atoi(t.c_str() + at)))); size_t c = t.find(',', at); if (c == std::string::npos) break; at = c + 1; } if (v.empty()) v.push_back(1); return v; }();
-				const uint32_t floorCand = (uint32_t)plan[std::min<size_t>((size_t)round, plan.size() - 1)];
-				const uint64_t active = round == 0 ? nG : std::max<uint64_t>(1, std::min<uint64_t>(nG, lastWork / 2));
-				if (!getenv("GC_TEST_LONG_SPECULATE")) maxCand = (uint32_t)std::min<uint64_t>(std::max(maxCand, floorCand), std::max<uint64_t>(1, (4 * nG) / active));
-			}
-#endif
-			launchLongSelect(q, G->dev, dLongJobs + r0, (uint32_t)nG, dLongSeeds, R->totalBases, (uint32_t)P->min_cluster_size, maxCand, dLongState + r0, dLongAlns, dLongCells, dLongWork + w0, dWorkLen + w0, dCandSeed + w0, cursor, capacity);
+			launchLongSelect(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, R->totalBases, (uint32_t)P->min_cluster_size, maxCand, dLongState, dLongAlns, dLongCells, dLongWork, dWorkLen, dCandSeed, cursor, workCapacity);
 			{
 				// execution order: longest extensions first, so the round's tail is made of short ones (GC_TEST_LONG_ORDER=0: as emitted)
 				const char* mode = getenv("GC_TEST_LONG_ORDER");
-				launchLongOrder(q, dWorkLen + w0, cursor, dOrder + w0, (uint32_t)maxReadLen, mode ? (uint32_t)atoi(mode) : 1u);
+				launchLongOrder(q, dWorkLen, cursor, dOrder, (uint32_t)maxReadLen, mode ? (uint32_t)atoi(mode) : 1u);
 			}
 			launchPublish(q, cursor, (unsigned long long*)hCursor, 2);
 			const double tWait0 = nowUs();
-			if (roundLock.owns_lock()) { syncEvent(roundExtendDone); roundLock.unlock(); }   // the previous round's extension kernel has finished: the merge and this round's set-up need no token
 			syncStream(q);
 			dbgWaitUs += nowUs() - tWait0;
 			uint32_t nWorkItems = (uint32_t)hCursor[0];
 			if (nWorkItems == 0) break;
 			if (!dLongScratch) {
-				if (longTokenTake) longTokenTake();
+				longTokenTake();
 				dLongScratch = shareLongScratch ? longScratchOfToken : dLongScratchOwn;
-			}
-			if (roundToken && nGroups == 1) {
-				roundLock.lock();
-				if (shareLongScratch) dLongScratch = g_longScratch[deviceNow & 15].buffer[0].reserve<unsigned long long>(longScratchWords);
 			}
 			uint32_t team = longExtendTeamSize(nWorkItems);
 			uint32_t blocks = std::min<uint32_t>((nWorkItems + team - 1) / team, (uint32_t)std::max<uint64_t>(1, (scratchLanes - 64) / team));
@@ -315,91 +181,36 @@
 			if (timedRounds >= LONG_EVENT_RING) collect(timedRounds % LONG_EVENT_RING);
 			hipEvent_t ev0 = ring[2 * (timedRounds % LONG_EVENT_RING)], ev1 = ring[2 * (timedRounds % LONG_EVENT_RING) + 1];
 			HIP_CHECK(hipEventRecord(ev0, q));
-			// The experiments build (`make -C graphchainer_amd/csrc experiments`) can replace the extension step by one of the two measured-and-rejected layouts:
-			// GC_LONG_SM=1 (DESIGN.md §11: one extension per LANE as per-lane state machines, k_long_extend_sm in gc_sm.hip, 6x slower; what outgrows its tables -
-			// EXT_SM_DECLINED - is listed and rerun one extension per wave) or GC_LONG_LANE=1 (one extension per LANE with the plain-layout core and a per-lane HBM slab, 6.9x slower)
-#ifdef GC_EXPERIMENTS
-			const bool useSm = team == 1 && getenv("GC_LONG_SM") && atoi(getenv("GC_LONG_SM")) == 1;
-			const bool useLane = !useSm && team == 1 && getenv("GC_LONG_LANE") && atoi(getenv("GC_LONG_LANE")) == 1;
-			// GC_LONG_SPLIT=p (r5 experiment, VERDICT r4 item 3: "use the idle vector issue port"): the round's last p % of the work items (the shortest - the list is sorted
-			// longest first) go to the multi-lane instantiation (GC_LONG_SPLIT_TEAM lanes per wave, 16: divergent lanes, i.e. vector instructions, LDS tables) on a second
-			// stream, beside the one-extension-per-wave kernel that saturates the CUs' scalar units
-			uint32_t nVector = 0, vectorTeam = 16;
-			if (const char* env = getenv("GC_LONG_SPLIT_TEAM")) { const int v = atoi(env); if (v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) vectorTeam = (uint32_t)v; }
-			if (const char* env = getenv("GC_LONG_SPLIT")) {
-				const uint64_t want = (uint64_t)nWorkItems * (uint64_t)std::max(0, std::min(90, atoi(env))) / 100 / vectorTeam * vectorTeam;
-				if (team == 1 && nGroups == 1 && nWorkItems >= 4096 && want >= vectorTeam && (uint64_t)nWorkItems + vectorTeam + 64 <= scratchLanes && (uint64_t)blocks * team >= nWorkItems) nVector = (uint32_t)want;
-			}
-			if (useSm) {
-				launchLongExtendSm(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dOrder + w0, nWorkItems, (uint8_t*)(dLongScratch + (uint64_t)g * scratchLanes * waveWords), scratchLanes * waveWords * 8,
-					dRoundTrace + groupTraceBegin[g], cursor + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cursor + 2);
-				launchZeroWords(q, cursor + 2, 2);   // [2] next slot, [3] length of the list
-				launchLongRetryList(q, dLongWorkResults + w0, nWorkItems, 6u /* EXT_SM_DECLINED */, dRetryList + w0, cursor + 3);
-				const uint32_t declinedBlocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(nWorkItems, 8192), std::max<uint64_t>(1, scratchLanes - 64));
-				launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dRetryList + w0, nWorkItems, dLongScratch + (uint64_t)g * scratchLanes * waveWords, 1, declinedBlocks,
-					dRoundTrace + groupTraceBegin[g], cursor + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cursor + 2, 6u, cursor + 3);
-			} else if (useLane) {
-				launchLongExtendLane(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dOrder + w0, nWorkItems, (uint8_t*)(dLongScratch + (uint64_t)g * scratchLanes * waveWords), scratchLanes * waveWords * 8,
-					dRoundTrace + groupTraceBegin[g], cursor + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8);
-			} else if (nVector) {
-				if (!st->splitStream) { createStream(&st->splitStream, 1); for (auto& e : st->splitEv) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-				const uint32_t nScalar = nWorkItems - nVector;
-				HIP_CHECK(hipEventRecord(st->splitEv[0], q));
-				HIP_CHECK(hipStreamWaitEvent(st->splitStream, st->splitEv[0], 0));
-				launchLongExtend(st->splitStream, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dOrder + w0 + nScalar, nVector, dLongScratch + (uint64_t)nScalar * waveWords, vectorTeam, nVector / vectorTeam,
-					dRoundTrace + groupTraceBegin[g], cursor + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cursor + 2, 0, nullptr, nullptr, nullptr);
-				HIP_CHECK(hipEventRecord(st->splitEv[1], st->splitStream));
-				launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dOrder + w0, nScalar, dLongScratch, 1, nScalar,
-					dRoundTrace + groupTraceBegin[g], cursor + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cursor + 2, 0, nullptr, dRetryList + w0, cursor + 3);
-				HIP_CHECK(hipStreamWaitEvent(q, st->splitEv[1], 0));
-			} else
-#else
-			const bool useSm = false, useLane = false;
-#endif
-			launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dOrder + w0, nWorkItems, dLongScratch + (uint64_t)g * scratchLanes * waveWords, team, blocks,
-				dRoundTrace + groupTraceBegin[g], cursor + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cursor + 2, 0, nullptr, team == 1 ? dRetryList + w0 : nullptr, cursor + 3);
-			if (team == 1 && !useLane) {
+			launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork, dOrder, nWorkItems, dLongScratch, team, blocks,
+				dRoundTrace, cursor + 1, roundTraceBudget, dLongWorkResults, dLongCursor + 8, cursor + 2, 0, nullptr, team == 1 ? dRetryList : nullptr, cursor + 3);
+			if (team == 1) {
 				// extensions whose band outgrew the 64-entry register tables: second try with the LDS/HBM tables (two lanes per wave,
 				// 28 + 228 entries); waves whose items are fine leave at once. Beyond that the read goes to the plain-layout fallback.
 				// (those items are listed first - almost always none - so that the retry is a handful of waves that fetch from the list, not
 				// one wave per pair of work items that looks at a status and leaves: that cost 0.5-2 ms of every round)
-				if (useSm || (uint64_t)blocks * team < nWorkItems) {   // (the list is the extension kernel's own, unless the state-machine path or persistent waves used the slot counter)
-					launchZeroWords(q, cursor + 2, useSm ? 2 : 1);   // [2] next slot, [3] length of the retry list
-#ifdef GC_EXPERIMENTS
-					if (useSm) launchLongRetryList(q, dLongWorkResults + w0, nWorkItems, EXT_LDS_CAP, dRetryList + w0, cursor + 3);
-#endif
-				}
+				if ((uint64_t)blocks * team < nWorkItems) launchZeroWords(q, cursor + 2, 1);   // (persistent waves used the slot counter; the retry list is the extension kernel's own)
 				uint32_t retryBlocks = std::min<uint32_t>(128, (uint32_t)std::max<uint64_t>(1, (scratchLanes - 64) / 2));   // (persistent waves over a list that is almost always empty on 10 kb reads; 50 kb CLR-like reads on a genome-sized graph list a few dozen per round, and one such extension lasts 10-50 ms)
-				launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork + w0, dRetryList + w0, nWorkItems, dLongScratch + (uint64_t)g * scratchLanes * waveWords, 2, retryBlocks,
-					dRoundTrace + groupTraceBegin[g], cursor + 1, traceBudget, dLongWorkResults + w0, dLongCursor + 8, cursor + 2, EXT_LDS_CAP, cursor + 3);
+				launchLongExtend(q, G->dev, G->devTables, R->devMasks, lcfg, dLongWork, dRetryList, nWorkItems, dLongScratch, 2, retryBlocks,
+					dRoundTrace, cursor + 1, roundTraceBudget, dLongWorkResults, dLongCursor + 8, cursor + 2, EXT_LDS_CAP, cursor + 3);
 			}
 			HIP_CHECK(hipEventRecord(ev1, q));
-			roundExtendDone = ev1;
-			launchLongMerge(q, G->dev, dLongJobs + r0, (uint32_t)nG, dLongSeeds, dCandSeed + w0, dLongWorkResults + w0, dRoundTrace + groupTraceBegin[g], maxAlignments, dLongState + r0, dLongAlns, dLongCells, dLongCursor, cellBudget);
+			launchLongMerge(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, dCandSeed, dLongWorkResults, dRoundTrace, maxAlignments, dLongState, dLongAlns, dLongCells, dLongCursor, cellBudget);
 			lastWork = nWorkItems;
 			// no wait here: the next round's select / order / publish queue up right behind the merge, and the only host round trip per
 			// round is the work count above (with a second wait after the merge the stream drained twice per round, and each refill
 			// waited behind whatever other batches had queued on the device)
 			timedRounds++;
-			groupRounds[g]++;
+			longRounds++;
 		}
 		// (the last round's count has come down: every extension kernel of the pass is complete, the scratch is free)
-		if (longTokenDrop) longTokenDrop();
+		longTokenDrop();
 		// the per-read results go straight into pinned host memory (the kernel writes them across PCIe): a copy-engine transfer here queued behind
 		// the other batch's bulk downloads for 30-50 ms while this pass still held the device's whole-read token
-		launchLongFinish(q, (uint32_t)nG, dLongState + r0, hLongResults + r0);
+		launchLongFinish(q, (uint32_t)n, dLongState, hLongResults);
 		const double dbgT1 = nowUs();
 		syncStream(q);
 		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] whole-read rounds: %.1f ms in all, %.1f ms waiting for the rounds' work counts, %.1f ms in the last wait, %d rounds\n", (nowUs() - dbgT0) / 1e3, dbgWaitUs / 1e3, (nowUs() - dbgT1) / 1e3, timedRounds);
 		for (int k = std::max(0, timedRounds - LONG_EVENT_RING); k < timedRounds; k++) collect(k % LONG_EVENT_RING);
-	}
-
-	void finishLongGroups()   // after the group threads joined
-	{
-		double us = 0; uint32_t rounds = 0;
-		for (uint32_t g = 0; g < nGroups; g++) { us += groupExtendUs[g]; rounds = std::max(rounds, groupRounds[g]); }
-		res->kernel_us[4] = us;
-		res->counters_long[6] = rounds;
 	}
 
 	uint64_t longFallback()   // reads whose band did not fit the wave layout's tables are rerun with the plain-layout kernel; returns how many
@@ -568,15 +379,6 @@
 			for (int i = 0; i < 11; i++) fprintf(stderr, "[gc stamps] %-16s %6.2f%%  %.3e lane-cycles\n", names[i], 100.0 * hLongSmall[16 + i] / (total > 0 ? total : 1), (double)hLongSmall[16 + i]);
 		}
 #endif
-#ifdef GC_SM_STAMPS
-		{
-			static const char* names[5] = { "B (tile boundary)", "COL (column)", "BT (bt boundary)", "WALK (cell)", "housekeeping+vote" };
-			double total = 0;
-			for (int i = 0; i < 5; i++) total += (double)hLongSmall[16 + i];
-			for (int i = 0; i < 5; i++) fprintf(stderr, "[gc sm stamps] %-18s %6.2f%% of wave-cycles, %.3e executions, %.0f cycles each, %.2f lanes served per execution\n", names[i], 100.0 * hLongSmall[16 + i] / (total > 0 ? total : 1),
-				(double)hLongSmall[21 + i], (double)hLongSmall[16 + i] / std::max<double>(1, (double)hLongSmall[21 + i]), (double)hLongSmall[26 + i] / std::max<double>(1, (double)hLongSmall[21 + i]));
-		}
-#endif
 		if (const char* env = getenv("GC_TEST_FAIL_LONG")) {   // test hook shared with the oracle: this read's whole-read pass "asserts"
 			long idx = atol(env);
 			if (idx >= 0 && (uint64_t)idx < n) hLongResults[idx].status = 1;
@@ -604,76 +406,68 @@
 		if (P->long_pass) {
 			int device = 0;
 			HIP_CHECK(hipGetDevice(&device));
-			for (uint32_t g = 0; g < longGroups; g++)
-				longThreads.emplace_back([&, device, g]() {
-					// (declared outside the try block: on an exception the catch below waits for the pass's kernels BEFORE the token - and with it the device's shared scratch - is released)
-					TokenHold token;
-					try {
-						HIP_CHECK(hipSetDevice(device));
-						int tokenMode = getenv("GC_LONG_TOKEN") ? atoi(getenv("GC_LONG_TOKEN")) : 1;   // 0 none, 1 one pass at a time (2, experiments build: one round's extension kernel at a time)
-#ifndef GC_EXPERIMENTS
-						if (tokenMode != 0) tokenMode = 1;
-#endif
-						const double tTokenAsk = nowUs();
-						const bool early = expEnv("GC_LONG_TOKEN_EARLY") && atoi(expEnv("GC_LONG_TOKEN_EARLY")) == 1;
-						bool held = false;   // between take and drop (with or without a token to hold: GC_LONG_TOKEN=0 has none)
-						auto stampBegin = [&]() { double now = nowUs(), seen = longWallBeginUs.load(); while ((seen == 0.0 || now < seen) && !longWallBeginUs.compare_exchange_weak(seen, now)) {} };
-						auto stampEnd = [&]() { double now = nowUs(), seen = longWallEndUs.load(); while (now > seen && !longWallEndUs.compare_exchange_weak(seen, now)) {} };
-						auto take = [&, device, tokenMode, tTokenAsk]() {
-							if (held) return;
-							const double tAsk = nowUs();
-							if (tokenMode == 1 && longGroups == 1) {
-								const int passesSideBySide = longTokenCount(n, st->batchesDone, st->fragShare);
-								token.lock(g_longPassToken[device & 15], passesSideBySide, passesSideBySide == 1);   // (a pass that fills the chip: alone on the device)
-								if (token.slot > 0 && shareLongScratch) {   // the second token's scratch is only grown when the device has the room: otherwise this pass waits for the first token like any other
-									const DeviceBuffer& have = g_longScratch[device & 15].buffer[token.slot];
-									size_t freeBytes = 0, totalBytes = 0;
-									const uint64_t need = longScratchWords * sizeof(unsigned long long);
-									if (have.bytes < need && (hipMemGetInfo(&freeBytes, &totalBytes) != hipSuccess || freeBytes + have.bytes < need + need / 8 + (6ull << 30))) { token.unlock(); token.lock(g_longPassToken[device & 15], 1, false); }
-								}
+			longThread = std::thread([&, device]() {
+				// (declared outside the try block: on an exception the catch below waits for the pass's kernels BEFORE the token - and with it the device's shared scratch - is released)
+				TokenHold token;
+				try {
+					HIP_CHECK(hipSetDevice(device));
+					const bool oneAtATime = !(getenv("GC_LONG_TOKEN") && atoi(getenv("GC_LONG_TOKEN")) == 0);   // GC_LONG_TOKEN=0: no token, passes overlap; anything else: one pass at a time (read per batch: the tests switch modes inside one process)
+					const double tTokenAsk = nowUs();
+					bool held = false;   // between take and drop (with or without a token to hold: GC_LONG_TOKEN=0 has none)
+					longTokenTake = [&, device, oneAtATime, tTokenAsk]() {
+						if (held) return;
+						const double tAsk = nowUs();
+						if (oneAtATime) {
+							const int passesSideBySide = longTokenCount(n, st->batchesDone, st->fragShare);
+							token.lock(g_longPassToken[device & 15], passesSideBySide, passesSideBySide == 1);   // (a pass that fills the chip: alone on the device)
+							if (token.slot > 0 && shareLongScratch) {   // the second token's scratch is only grown when the device has the room: otherwise this pass waits for the first token like any other
+								const DeviceBuffer& have = g_longScratch[device & 15].buffer[token.slot];
+								size_t freeBytes = 0, totalBytes = 0;
+								const uint64_t need = longScratchWords * sizeof(unsigned long long);
+								if (have.bytes < need && (hipMemGetInfo(&freeBytes, &totalBytes) != hipSuccess || freeBytes + have.bytes < need + need / 8 + (6ull << 30))) { token.unlock(); token.lock(g_longPassToken[device & 15], 1, false); }
 							}
-							if (shareLongScratch && tokenMode == 1) {
-								if (!token.owns_lock()) throw std::runtime_error("internal: shared whole-read scratch without the token");
-								try {
-									longScratchOfToken = g_longScratch[device & 15].buffer[token.slot].reserve<unsigned long long>(longScratchWords);
-								} catch (const DeviceError&) {
-									// (the check above and this reservation are not one step: another stream may have taken the memory in between) - the second token's scratch does not
-									// fit after all: this pass takes its turn on the first token's instead of failing the batch
-									if (token.slot == 0) throw;
-									(void)hipGetLastError();
-									token.unlock();
-									token.lock(g_longPassToken[device & 15], 1, false);
-									longScratchOfToken = g_longScratch[device & 15].buffer[0].reserve<unsigned long long>(longScratchWords);
-								}
+						}
+						if (shareLongScratch && oneAtATime) {
+							if (!token.owns_lock()) throw std::runtime_error("internal: shared whole-read scratch without the token");
+							try {
+								longScratchOfToken = g_longScratch[device & 15].buffer[token.slot].reserve<unsigned long long>(longScratchWords);
+							} catch (const DeviceError&) {
+								// (the check above and this reservation are not one step: another stream may have taken the memory in between) - the second token's scratch does not
+								// fit after all: this pass takes its turn on the first token's instead of failing the batch
+								if (token.slot == 0) throw;
+								(void)hipGetLastError();
+								token.unlock();
+								token.lock(g_longPassToken[device & 15], 1, false);
+								longScratchOfToken = g_longScratch[device & 15].buffer[0].reserve<unsigned long long>(longScratchWords);
 							}
-							held = true;
-							if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc token] stream %p pass began %.1f asked %.1f got %.1f (call began %.1f)\n", (void*)st, tTokenAsk / 1e3, tAsk / 1e3, nowUs() / 1e3, tCall / 1e3);
-							stampBegin();   // (whole_read_pass_wall: from the token to its release)
-						};
-						auto drop = [&]() {
-							if (!held) return;
-							held = false;
-							stampEnd();
-							if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc token] stream %p released %.1f\n", (void*)st, nowUs() / 1e3);
-							token.unlock();   // the next batch's pass may start; what follows is this batch's own tail
-						};
-						if (longGroups == 1 && !early) { longTokenTake = take; longTokenDrop = drop; }
-						else if (longGroups == 1) take();
-						else stampBegin();
-						runLongGroup(g);
-						while (longGroups == 1 && growLongCells()) runLongGroup(g);   // the cell pool overflowed: again, with room
-						if (longGroups == 1) { longTokenTake = nullptr; longTokenDrop = nullptr; drop(); }
-						else stampEnd();
-						if (longPostInThread) afterLongPass();
-						passThreadCpuMs = threadCpuMs();   // (the thread's whole life: it is created per batch)
-					} catch (...) {
-						longErrors[g] = std::current_exception();
-						if (longGroups == 1) { longTokenTake = nullptr; longTokenDrop = nullptr; }   // (they refer to this thread's locals)
-						// the token is released when this lambda returns: a kernel of this pass may still be writing to the shared scratch
-						if (g < st->groupStreams.size()) (void)hipStreamSynchronize(st->groupStreams[g]);
-						(void)hipStreamSynchronize(st->longStream);
-					}
-				});
+						}
+						held = true;
+						if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc token] stream %p pass began %.1f asked %.1f got %.1f (call began %.1f)\n", (void*)st, tTokenAsk / 1e3, tAsk / 1e3, nowUs() / 1e3, tCall / 1e3);
+						if (longWallBeginUs == 0.0) longWallBeginUs = nowUs();   // (whole_read_pass_wall: from the pass's first take of the token - a pool rerun takes it again - to its last release)
+					};
+					longTokenDrop = [&]() {
+						if (!held) return;
+						held = false;
+						longWallEndUs = nowUs();
+						if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc token] stream %p released %.1f\n", (void*)st, nowUs() / 1e3);
+						token.unlock();   // the next batch's pass may start; what follows is this batch's own tail
+					};
+					runLongRounds();
+					while (growLongCells()) runLongRounds();   // the cell pool overflowed: again, with room
+					longTokenDrop();
+					longTokenTake = nullptr; longTokenDrop = nullptr;
+					// What follows the rounds runs here, beside the tail of the fragment pipeline (which ends 20-30 ms after the pass on cfg2, starved by it), instead of after the
+					// join: 16 ms off the batch's critical path. It writes the reads' long* fields and capacityExceededLong only; the fragment pipeline does not touch those.
+					afterLongPass();
+					passThreadCpuMs = threadCpuMs();   // (the thread's whole life: it is created per batch)
+				} catch (...) {
+					longError = std::current_exception();
+					longTokenTake = nullptr; longTokenDrop = nullptr;   // (they refer to this thread's locals)
+					// the token is released when this lambda returns: a kernel of this pass may still be writing to the shared scratch
+					if (st->roundStream) (void)hipStreamSynchronize(st->roundStream);
+					(void)hipStreamSynchronize(st->longStream);
+				}
+			});
 		}
 	}
 

@@ -224,21 +224,21 @@
 
 	}
 
-	// ---------------- the pass thread ends (its after-pass stage included unless it ran on this thread)
+	// ---------------- the pass thread ends (its after-pass stage included)
 	void joinWholeReadPass()
 	{
 		// ---------------- whole-read pass results
 		tJoined = nowUs();
 		if (P->long_pass) {
 			double tJoin0 = nowUs();
-			for (auto& t : longThreads) t.join();
+			longThread.join();
 			tJoined = nowUs();
 			cpuJoined = processCpuMs();
 			if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] main thread waited %.1f ms for the whole-read pass\n", (tJoined - tJoin0) / 1e3);
-			for (auto& e : longErrors) if (e) std::rethrow_exception(e);
-			finishLongGroups();
-			res->kernel_us[5] = longWallEndUs.load() - (longWallBeginUs.load() > 0.0 ? longWallBeginUs.load() : tLongWall0);   // whole-read pass, wall clock from the first group's start to the last group's end
-			if (!longPostInThread) afterLongPass();
+			if (longError) std::rethrow_exception(longError);
+			res->kernel_us[4] = longExtendUs;
+			res->counters_long[6] = longRounds;
+			res->kernel_us[5] = longWallEndUs - (longWallBeginUs > 0.0 ? longWallBeginUs : tLongWall0);   // whole-read pass, wall clock from the token to its release
 			for (uint64_t r = 0; r < n; r++) if (glue[r].capacityExceededLong) glue[r].capacityExceeded = true;
 			if (P->keep_traces) {
 				const uint64_t cellsUsed = std::min<uint64_t>(hLongSmall[0], cellBudget);   // (the cursor counts refused requests too: a full pool leaves it beyond the pool's end)

@@ -12,7 +12,7 @@ struct BatchRun {
 	const gc::AlignmentGraph& hg;
 	WorkerPool& pool;
 	std::vector<ReadGlue>& glue;             // per-read host records, storage reused across batches
-	const hipStream_t stream;                // the fragment pipeline's stream (the whole-read pass has st->longStream / st->groupStreams)
+	const hipStream_t stream;                // the fragment pipeline's stream (the whole-read pass has st->longStream / st->roundStream)
 	int evIdx = 0;
 	double tTotal = 0;
 	// ---- what the stages hand on (set by the stage named in the comment of each group)
@@ -40,23 +40,22 @@ struct BatchRun {
 	unsigned long long* longScratchOfToken = nullptr;   // the device's shared extension scratch, set by the pass once it holds the token
 	// r4: the token is taken when the pass's FIRST extension kernel is about to be queued and given back when the last round's count (zero) has come down: a pass's first
 	// init / select / order / publish and the host's wait for the work count (each a launch that queues among the other batches' kernels), and its k_long_finish at the
-	// end, no longer sit between two passes' extension kernels (GC_LONG_TOKEN_EARLY=1: around the whole pass, as before)
-	std::function<void()> longTokenTake, longTokenDrop;
+	// end, no longer sit between two passes' extension kernels
+	std::function<void()> longTokenTake, longTokenDrop;   // (set by the pass thread for its round loop)
 	uint64_t longScratchWords = 0;
 	bool shareLongScratch = false;
-	uint32_t longGroups = 0;
-	std::vector<double> groupExtendUs; std::vector<uint32_t> groupRounds; std::vector<uint64_t> groupBegin, groupTraceBegin;   // (the pass thread works through pointers into these)
+	double longExtendUs = 0; uint32_t longRounds = 0;   // the rounds' extension kernels (event pairs) and how many rounds had work, reruns of the pass included
 	const gc::EValueModel evalueModel { 0.7 };   // src/Aligner.cpp:478-482 (precise clipping is out of scope)
 	struct DecisionPointers { EdPair* hPairs = nullptr; int64_t* hOut = nullptr; EdPair* dPairs = nullptr; int64_t* dOut = nullptr; char* dLetters = nullptr; uint32_t* dLettersLen = nullptr; } decisionPtr[2];
-	bool longPostInThread = false;
-	// ... the whole-read pass's own buffers and sizes (prepareWholeReadPass sets them; runLongGroup / growLongCells / longFallback / finishLongGroups run on the pass thread)
+	// ... the whole-read pass's own buffers and sizes (prepareWholeReadPass sets them; runLongRounds / growLongCells / longFallback / afterLongPass run on the pass thread)
 	LongJob* hJobs = nullptr;
 	bool cellPoolPinned = 0;
 	uint64_t waveWords = 0;
 	LongJob* dLongJobs = nullptr;
 	LongAln* dLongAlns = nullptr;
-	uint32_t nGroups = 0;
 	uint32_t cursorWords = 0;
+	uint64_t workCapacity = 0;       // entries of the rounds' work arrays
+	uint64_t roundTraceBudget = 0;   // words of the rounds' trace pool
 	unsigned long long* dLongCursor = nullptr;
 	LongState* dLongState = nullptr;
 	LongWork* dLongWork = nullptr;
@@ -72,12 +71,12 @@ struct BatchRun {
 	unsigned long long* dLongScratchOwn = nullptr;   // (this stream's own scratch: only without the one-pass-at-a-time token)
 	uint64_t maxReadLen = 1;
 	// startWholeReadPass()
-	std::vector<std::thread> longThreads;
+	std::thread longThread;
 	double passThreadCpuMs = 0;   // GC_DEBUG_TIMES: CPU time of the pass thread (read after the join)
-	std::vector<std::exception_ptr> longErrors;
+	std::exception_ptr longError;
 	double tLongWall0 = 0;
-	std::atomic<double> longWallBeginUs { 0.0 };   // when the pass got the device's token (waiting for another batch's pass is not its own time)
-	std::atomic<double> longWallEndUs { 0.0 };
+	double longWallBeginUs = 0.0;   // when the pass first got the device's token (waiting for another batch's pass is not its own time; 0: not yet); written by the pass thread, read after the join
+	double longWallEndUs = 0.0;     // when it last gave the token back
 	// fragmentPipeline()
 	double tDev = 0;
 	uint32_t nWork = 0;
@@ -132,8 +131,8 @@ struct BatchRun {
 
 	BatchRun(const gc_graph* G, const gc_seeder* S, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result* res, double tCall, double cpuCall)
 		: G(G), S(S), st(st), R(R), P(P), res(res), tCall(tCall), cpuCall(cpuCall), cpuJoined(cpuCall), n(R->offsets.size() - 1), hg(G->host), pool(WorkerPool::batch()), glue(st->glue),
-		  stream(st->stream), longErrors(16) {}
-	~BatchRun() { for (auto& t : longThreads) if (t.joinable()) t.join(); }   // (an exception on the main thread must not leave the pass thread behind with dangling state)
+		  stream(st->stream) {}
+	~BatchRun() { if (longThread.joinable()) longThread.join(); }   // (an exception on the main thread must not leave the pass thread behind with dangling state)
 	BatchRun(const BatchRun&) = delete;
 	BatchRun& operator=(const BatchRun&) = delete;
 

@@ -823,8 +823,8 @@ int gc_stream_create(gc_stream** out)
 		requireDevice();
 		HIP_CHECK(hipGetDevice(&st->device));
 		if (st->device < 0 || st->device >= 16) throw std::runtime_error("gc_stream_create: device index beyond the 16 per-device slots of the whole-read token and scratch");
-		createStream(&st->stream, 0);       // non-blocking: uploads of another batch on the null stream do not serialise with this one
-		createStream(&st->longStream, 0);
+		createStream(&st->stream);       // non-blocking: uploads of another batch on the null stream do not serialise with this one
+		createStream(&st->longStream);
 		for (auto& e : st->ev) HIP_CHECK(hipEventCreate(&e));
 		for (auto& e : st->fragEv) HIP_CHECK(hipEventCreate(&e));
 		for (auto& e : st->longEv) HIP_CHECK(hipEventCreate(&e));
@@ -955,7 +955,7 @@ void gc_result_free(gc_result* r)
 
 // One batch through the whole path, stage by stage (r3: this was one 1 200-line function). A BatchRun holds what the stages share - the call's arguments, the sizes the seed
 // stage leaves behind, the device and pinned-host buffers a later stage reads again - and every stage is one member function, in the batch's order:
-//   seeds -> prepareWholeReadPass -> startWholeReadPass (the pass runs on its own host thread and stream from there: runLongGroup, then afterLongPass) -> [main thread, meanwhile]
+//   seeds -> prepareWholeReadPass -> startWholeReadPass (the pass runs on its own host thread and stream from there: runLongRounds, then afterLongPass) -> [main thread, meanwhile]
 //   fragmentPipeline -> resultsBack -> stitchAndChainDistances -> joinWholeReadPass -> chainedAlignments -> assemble.
 // Capacities are per read (flags in the result), errors of the reference's own making per read or fragment (failed_assertion); only invalid arguments and device errors fail
 // the call (they throw; gc_align_batch turns that into its return code, and ~BatchRun joins the pass thread first).

@@ -131,13 +131,6 @@ struct TokenHold {
 	void unlock() { if (slot >= 0) { tokens->release(slot); slot = -1; } }
 	~TokenHold() { unlock(); }
 };
-// Switches of measured-and-rejected alternatives (a token per round, read groups, the lane-per-extension kernel, ...) exist only in the experiments build
-// (`make -C graphchainer_amd/csrc experiments`, -DGC_EXPERIMENTS): the product library does not read them. INTEGRATION.md §7 lists the switches that remain.
-#ifdef GC_EXPERIMENTS
-inline const char* expEnv(const char* name) { return getenv(name); }
-#else
-inline const char* expEnv(const char*) { return nullptr; }
-#endif
 // r5: how many passes may run side by side on a device is decided per batch. A pass whose rounds cannot fill the chip - round 0 holds two work items per read, k_long_extend<1> has
 // 5 120 wave slots (256 CUs x 4 SIMDs x 5 waves) - shares the device with a second one: 2 000 x 50 kb reads on a 192 Mbp graph 4.0-4.2 k -> 5.0-5.3 k reads/s (`gpurun_out/r5_cfg5_tok`);
 // a pass that fills it (10 k x 10 kb: 20 000 items) keeps the device to itself (two side by side measured slower in r4). GC_LONG_TOKENS=1|2 overrides (read per batch: the tests switch
@@ -152,7 +145,6 @@ inline int longTokenCount(uint64_t nReads, uint64_t streamBatchesDone, double ex
 	// (a stream's first batch sizes its buffers - pools that rerun and grow: a second scratch taken while the device still looks empty cost config 5 at 960 Mbp its fifth stream)
 	return streamBatchesDone > 0 && 2 * nReads + 128 <= LONG_WAVE_SLOTS && extensionsPerBase < 0.2 ? 2 : 1;
 }
-inline std::mutex g_longRoundToken[16];   // GC_LONG_TOKEN=2 (experiment): the token handed over per round
 // The pass's extension scratch (up to 48 GB: one region per resident wave) is only touched while the token is held, so the gc_streams of a device share ONE
 // (r3: 85 -> 37 GB per stream for 10 k x 10 kb batches, which is what lets five batches be in flight on a 288 GB device instead of three). It belongs to the
 // token: reserved (grown) by the pass that holds it, freed when the device's last gc_stream goes.
@@ -563,9 +555,6 @@ struct EditDistanceRun {
 };
 
 inline constexpr int LONG_EVENT_RING = 8;
-#ifndef GC_LONG_PLAN_DEFAULT
-#define GC_LONG_PLAN_DEFAULT "1"   // candidates per read and round of the whole-read pass (GC_LONG_PLAN; see runLongGroup)
-#endif
 struct gc_stream {
 	std::vector<ReadGlue> glue;   // per-read host records of the batch in flight (storage reused)
 	int device = 0;             // the device the stream was created on; gc_align_batch selects it for the calling thread
@@ -577,8 +566,6 @@ struct gc_stream {
 	// whole-read pass: runs on its own stream, concurrently with the fragment kernels
 	hipStream_t longStream = nullptr;
 	hipEvent_t longEv[2] {};
-	hipStream_t splitStream = nullptr;   // experiments build (GC_LONG_SPLIT): the multi-lane share of a whole-read round
-	hipEvent_t splitEv[2] {};
 	DeviceBuffer edPathNodes, edJobs, edLetters, edLettersLen, edPairs, edOut;
 	PinnedBuffer hEdPathNodes, hEdJobs, hEdPairs, hEdOut;
 	DeviceBuffer outJobs, outRecs, outOffsets, outMapSizes, outPathText, outCigarText, outVgBytes, outTotals;   // output encoding on the device (gc_output.hip)
@@ -603,13 +590,12 @@ struct gc_stream {
 	uint64_t batchesDone = 0;                 // batches this stream has finished (a second whole-read token is only taken from the second batch on: the first sizes the stream's buffers)
 	bool poolsRerun = false;                  // the last batch ran its fragment pipeline again with larger pools: the next one gives back what that overshot
 	double traceCellsPerSlot = 0, pathWordsPerSlot = 0;   // what this stream's batches have used of the fragment pipeline's trace pool / anchor path pool per anchor slot (0: no batch yet)
-	std::vector<hipStream_t> groupStreams;   // read groups of the whole-read pass run their round loops concurrently
-	std::vector<hipEvent_t> groupEvents;     // 2 * LONG_EVENT_RING per group
+	hipStream_t roundStream = nullptr;       // the round loop of the whole-read pass (created by the stream's first pass; longStream carries the pass's uploads, reruns and decision)
+	hipEvent_t roundEvents[2 * LONG_EVENT_RING] {};   // a ring of (begin, end) pairs around the rounds' extension launches
 	DeviceBuffer longSeeds, longJobs, longAlns, longResults, longScratch, longCells, longCursor, longJobsFallback, longResultsFallback, longScratchFallback;
 	DeviceBuffer gluePerRead, glueCursors, glueOut, glueSeedCap, glueSeedOff, glueWinCapOff, glueU32[8], glueSort, gluePos, glueWin;   // seed glue on the device (gc_seedglue.hip)
 	PinnedBuffer hGlueOut, hGlueWinCapOff, hGlueSmall;
-	DeviceBuffer longState, longWork, longWorkResults, longRoundTrace, longCandSeed, longWorkLen, longOrder, longRoundInfo;
-	PinnedBuffer hLongRoundInfo;
+	DeviceBuffer longState, longWork, longWorkResults, longRoundTrace, longCandSeed, longWorkLen, longOrder;
 	PinnedBuffer hLongSeeds, hLongJobs, hLongAlns, hLongResults, hLongSmall, hLongCells;
 	// every device allocation of the stream with its size (GC_DEBUG_TIMES: "[gc mem]" lines; the whole-read decision's and the edit-distance runs' own buffers are listed by their owners)
 	template <typename F> void forEachDeviceBuffer(F f) const
@@ -631,7 +617,7 @@ struct gc_stream {
 		f("glueWinCapOff", glueWinCapOff.bytes); f("glueU32[0]", glueU32[0].bytes); f("glueU32[1]", glueU32[1].bytes); f("glueU32[2]", glueU32[2].bytes); f("glueU32[3]", glueU32[3].bytes);
 		f("glueU32[4]", glueU32[4].bytes); f("glueU32[5]", glueU32[5].bytes); f("glueU32[6]", glueU32[6].bytes); f("glueU32[7]", glueU32[7].bytes); f("glueSort", glueSort.bytes);
 		f("gluePos", gluePos.bytes); f("glueWin", glueWin.bytes); f("longState", longState.bytes); f("longWork", longWork.bytes); f("longWorkResults", longWorkResults.bytes);
-		f("longRoundTrace", longRoundTrace.bytes); f("longCandSeed", longCandSeed.bytes); f("longWorkLen", longWorkLen.bytes); f("longOrder", longOrder.bytes); f("longRoundInfo", longRoundInfo.bytes);
+		f("longRoundTrace", longRoundTrace.bytes); f("longCandSeed", longCandSeed.bytes); f("longWorkLen", longWorkLen.bytes); f("longOrder", longOrder.bytes);
 		for (int k = 0; k < 2; k++) { f("edLong.letters", edLong[k].letters.bytes); f("edLong.jobs+pairs+out", edLong[k].jobs.bytes + edLong[k].lettersLen.bytes + edLong[k].pairs.bytes + edLong[k].out.bytes); }
 	}
 	~gc_stream()
@@ -639,12 +625,10 @@ struct gc_stream {
 		for (auto& e : ev) if (e) (void)hipEventDestroy(e);
 		for (auto& e : fragEv) if (e) (void)hipEventDestroy(e);
 		for (auto& e : longEv) if (e) (void)hipEventDestroy(e);
-		for (auto& e : groupEvents) if (e) (void)hipEventDestroy(e);
-		for (auto& q : groupStreams) if (q) (void)hipStreamDestroy(q);
+		for (auto& e : roundEvents) if (e) (void)hipEventDestroy(e);
+		if (roundStream) (void)hipStreamDestroy(roundStream);
 		if (stream) (void)hipStreamDestroy(stream);
 		if (longStream) (void)hipStreamDestroy(longStream);
-		if (splitStream) (void)hipStreamDestroy(splitStream);
-		for (auto& e : splitEv) if (e) (void)hipEventDestroy(e);
 	}
 };
 
@@ -954,20 +938,8 @@ inline uint32_t editDistanceUnit(uint32_t k, uint32_t readLen)
 	while (unit < 16 && k >= editDistanceMaxK(unit) && (readLen + 64 * unit - 1) / (64 * unit) > 64) unit *= 2;
 	return unit;
 }
-// Streams of the fragment pipeline / the edit distances (role 0) and of the whole-read rounds (role 1). GC_STREAM_PRIORITY=frag|long raises one
-// side's queue priority (experiment): the whole-read kernel holds 7 of a SIMD's 8 wave slots for milliseconds per wave, so
-// whatever shares the device with it runs on what is left.
-inline void createStream(hipStream_t* q, int role)
-{
-	static const int mode = []() { const char* e = expEnv("GC_STREAM_PRIORITY"); return !e ? 0 : !strcmp(e, "frag") ? 1 : !strcmp(e, "long") ? 2 : 0; }();
-	int least = 0, greatest = 0;
-	if (mode && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-		const bool high = (mode == 1 && role == 0) || (mode == 2 && role == 1);
-		HIP_CHECK(hipStreamCreateWithPriority(q, hipStreamNonBlocking, high ? greatest : least));
-		return;
-	}
-	HIP_CHECK(hipStreamCreateWithFlags(q, hipStreamNonBlocking));
-}
+// Every stream of the library (fragment pipeline, edit distances, whole-read pass) is non-blocking with the default priority.
+inline void createStream(hipStream_t* q) { HIP_CHECK(hipStreamCreateWithFlags(q, hipStreamNonBlocking)); }
 
 inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair* hPairs, int64_t* hOut, uint32_t nPairs, EdPair* dPairs, int64_t* dOut, const EdRead* dReads, const char* dBases,
 	const uint64_t* dEqMasks, const char* dLetters, const uint32_t* dLettersLen, const std::function<uint32_t(uint32_t)>& readLen, bool kIsBound = false)
@@ -1021,7 +993,7 @@ inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 	HIP_CHECK(hipEventRecord(run.ready, stream));
 	for (int c = 0; c < 8; c++) {
 		if (!count[c]) continue;
-		if (!run.streams[c]) createStream(&run.streams[c], 0);
+		if (!run.streams[c]) createStream(&run.streams[c]);
 		HIP_CHECK(hipStreamWaitEvent(run.streams[c], run.ready, 0));
 		if (c == 7) launchEditDistanceBlock(run.streams[c], blockThreads, dPairs + begin[c], count[c], dReads, dBases, dEqMasks, dLetters, dLettersLen, dOut + begin[c]);
 		else if (c < 2) launchEditDistanceTeam(run.streams[c], c == 0 ? 3u : 2u, dPairs + begin[c], count[c], dReads, dBases, dEqMasks, dLetters, dLettersLen, dOut + begin[c]);

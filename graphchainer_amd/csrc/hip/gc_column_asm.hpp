@@ -1,6 +1,7 @@
 // The column loop of one (node, slice) tile of the one-extension-per-wave whole-read kernel as ONE asm statement per (KIND, MODE)
 // (computeTileW's lean path, gc_device_wave.hpp). Same arithmetic, same column order and same lane contents as the
-// C++ lambda it replaces (GC_LEAN_ASMLOOP=0 compiles that one); what changes is the per-column overhead around the recurrence:
+// C++ lambda it replaced (commit 555b2d3 holds that one; computeTileW's generic loop, myersStep per column, is the readable statement
+// of the recurrence); what changes is the per-column overhead around the recurrence:
 //
 // - match mask: the four masks sit in eight consecutive SGPRs and the column's 2-bit code, kept pre-shifted left by one, indexes them:
 //   s_and_b32 m0, codes, 6 / s_lshr_b64 codes, 2 / s_movrels_b64 - three instructions where two s_bitcmp1 + three s_cselect_b64 + the

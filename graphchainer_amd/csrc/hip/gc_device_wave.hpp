@@ -22,47 +22,9 @@
 namespace gcdev {
 
 
-// The scalar-lean forms of the one-extension-per-wave instantiation's hot loops (r2 / r3): each GC_LEAN_* names one rewrite whose plain twin stays in the source as
-// the readable statement of the same step, as the code of the multi-lane instantiations (the register-table retry runs LANES = 2) and of the host compile. The product build
-// always takes the lean forms; only the experiments build (-DGC_EXPERIMENTS) may switch one off for an A/B (`make variant FLAGS="-DGC_EXPERIMENTS -DGC_LEAN_WALK=0"`).
-#ifndef GC_EXPERIMENTS
-#if defined(GC_LEAN_COLUMNS) || defined(GC_LEAN_WALK) || defined(GC_LEAN_PUSH) || defined(GC_LEAN_TABLES) || defined(GC_LEAN_COLMIN) || defined(GC_LEAN_MERGE) || defined(GC_LEAN_POP) || defined(GC_LEAN_KINDS) || defined(GC_LEAN_DIAGRUN)
-#error "GC_LEAN_* can only be set in the experiments build (-DGC_EXPERIMENTS)"
-#endif
-#endif
-#ifndef GC_LEAN_COLUMNS
-#define GC_LEAN_COLUMNS 1   // column loop: match mask by s_cselect_b64, carries by s_bfe_u64, the column's consumers in one vector epilogue per tile
-#endif
-#ifndef GC_LEAN_WALK
-#define GC_LEAN_WALK 1      // backtrace walk on bit masks made by one vector pass per tile
-#endif
-#ifndef GC_LEAN_PUSH
-#define GC_LEAN_PUSH 1      // trace cells through v_writelane
-#endif
-#ifndef GC_LEAN_TABLES
-#define GC_LEAN_TABLES 1    // band-table entries through v_writelane
-#endif
-#ifndef GC_LEAN_COLMIN
-#define GC_LEAN_COLMIN 1    // minimum of a tile's end column with lane = row
-#endif
-#ifndef GC_LEAN_MERGE
-#define GC_LEAN_MERGE 1     // mergeTwoSlices with lane = row
-#endif
-#ifndef GC_LEAN_POP
-#define GC_LEAN_POP 1       // the pop of the pending queue as a wave minimum over the lanes' component numbers (r3)
-#endif
-#ifndef GC_LEAN_KINDS
-#define GC_LEAN_KINDS 1     // three copies of the column loop: general / node in the previous slice with nothing forced / node new in this slice (constant carries)
-#endif
-#ifndef GC_LEAN_UNROLL
-#define GC_LEAN_UNROLL 1
-#endif
-#ifndef GC_LEAN_ASMLOOP
-#define GC_LEAN_ASMLOOP 1   // the column loop of a tile as one asm statement (gc_column_asm.hpp): indexed mask select, unrolled twice; 0 compiles the lambda below it (A/B partner: make variant NAME=noasm FLAGS=-DGC_LEAN_ASMLOOP=0)
-#endif
-#ifndef GC_LEAN_DIAGRUN
-#define GC_LEAN_DIAGRUN 1   // the backtrace's diagonal runs inside a tile resolved by one ballot and emitted by the vector pipe
-#endif
+// The hot loops of the one-extension-per-wave instantiation (REGCOLS) have scalar-lean forms on the device (r2 / r3): the match mask by an indexed select, carries by
+// s_bfe_u64, table entries and trace cells through v_writelane, lane = row for a column's minimum and the merge of two slices, the backtrace walk on bit masks. Beside each stands
+// its plain form: the readable statement of the same step, and the code of the multi-lane instantiations (the register-table retry runs LANES = 2) and of the host compile.
 #ifndef WAVE_CAP
 #define WAVE_CAP 28
 #endif
@@ -143,7 +105,7 @@ struct LaneLdsT {   // one lane's view
 	}
 	__device__ __forceinline__ void set(uint32_t t, uint32_t e, const Entry& x) const
 	{
-#if GC_LEAN_TABLES && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 		if (REGCOLS) {   // seven v_writelane with the entry index in M0 (the values are uniform: straight from SGPRs, no compare, no moves)
 			const uint32_t es = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);
 			const uint32_t v0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x.w0), v1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x.w1), v2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x.w2);
@@ -203,7 +165,7 @@ struct LaneLdsT {   // one lane's view
 	// the pending entry with the smallest componentNumber (the reference's priority queue pops by it, src/ComponentPriorityQueue.h; the first of equals, as the scalar scan picks)
 	__device__ __forceinline__ uint32_t qArgMin(uint32_t n) const
 	{
-#if GC_LEAN_POP && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 		if (REGCOLS) {
 			// entry e sits in lane e: a wave minimum by DPP and one ballot instead of a scalar loop of readlane / compare / select per entry (~25 scalar instructions per tile on cfg2)
 			const uint32_t mine = threadIdx.x < n ? tw[2][1] : 0xffffffffu;
@@ -409,7 +371,7 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 	TileResult r;
 	r.minScore = ws.score;   // (sic) before the merge with the row above, ...Common.h:968 vs :1052-1058
 	r.minOffset = 0;
-#if GC_LEAN_MERGE && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 	if (prevExists && wsBefore(ws) > prevStartScore) ws = LANE_TABLES::eqInLanes ? wsMergeWave(ws, wsSource(prevStartScore)) : wsMerge(ws, wsSource(prevStartScore));
 #else
 	if (prevExists && wsBefore(ws) > prevStartScore) ws = wsMerge(ws, wsSource(prevStartScore));
@@ -443,10 +405,10 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 	if (COLUMNS) tables.colSet(0, ws);
 	uint64_t forceEq = prevExists ? ~0ull : ~1ull;
 	if (preambleOnly) { preambleOnly->prevHP = prevHP; preambleOnly->prevHN = prevHN; preambleOnly->forceEq = forceEq; preambleOnly->forceUntil = forceUntil; return r; }   // (stored-column backtrace: no column loop)
-#if GC_LEAN_COLUMNS && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 	// One extension per wave: every value below is uniform and the loop is the kernel's scalar-issue bottleneck (80 % of its SALU
 	// instructions, 60 per column as the compiler writes the generic loop further down). Same arithmetic with the per-column overhead cut:
-	// the match mask picked by three s_cselect_b64 on the running 2-bit code (instead of eight 32-bit selects), the carries of the row above
+	// the match mask picked by an indexed select (s_movrels_b64) on the running 2-bit code (instead of eight 32-bit selects), the carries of the row above
 	// and the forced-first-row flag fetched with one s_bfe_u64 each on a running field descriptor, loop-invariant masks folded into the four
 	// match masks, and the bottom row's horizontal deltas parked in lane `pos` of a VGPR (one v_writelane per column, two ballots per tile)
 	// instead of two 64-bit shift-or pairs. Not taken for IUPAC nodes and for the read's last slice (row-limited minimum).
@@ -459,75 +421,16 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 		// them - HP / HN, the column scores, their minimum and where, the end score - is made once per tile by the vector pipe (ballots, a
 		// wave prefix sum, a wave minimum): eight scalar instructions per column less, about thirty vector instructions per tile more.
 		uint32_t plusWord = 0, minusWord = 0;
-		// two copies of the loop: most tiles sit on a node that was in the previous slice with nothing to repair (forceUntil == 0), and their
-		// columns carry no forced first row - three scalar instructions per column less than the general copy
-		// KIND 0: the general copy. KIND 1: the node was in the previous slice and nothing had to be repaired (forceUntil == 0): no forced first row.
-		// KIND 2: the node is new in this slice (47 % of the DP's columns on cfg2): the row above contributes the constant carries (+1, 0) and
-		// every column's first row is forced - three s_bfe_u64 and two ORs less per column.
+		// three copies of the loop, each one asm statement (gc_column_asm.hpp; the generic loop further down states the same recurrence in C++).
+		// KIND 0: the general copy. KIND 1: the node was in the previous slice and nothing had to be repaired (forceUntil == 0): no forced first row -
+		// most tiles, three scalar instructions per column less. KIND 2: the node is new in this slice (47 % of the DP's columns on cfg2): the row above
+		// contributes the constant carries (+1, 0) and every column's first row is forced - three s_bfe_u64 and two ORs less per column.
 		auto columnLoop = [&, &plusWord = plusWord, &minusWord = minusWord, &tables = tables](auto kindTag) __attribute__((always_inline)) {   // (explicit captures: asm operands alone do not make a generic lambda capture)
-		constexpr int KIND = decltype(kindTag)::value;
-#if GC_LEAN_ASMLOOP
-		// the loop below as one asm statement per (KIND, MODE): same columns in the same order, 3.5 to 4.5 scalar instructions per column less
-		gcColumnLoopAsm<KIND, MODE>(eA, eC, eG, eT, VP, VN, prevHP, prevHN, forced, gcUniform64(seq.w0), gcUniform64(seq.w1), nodeLength, plusWord, minusWord, tables.cr);
-#else
-		// the column counter carries the field width of s_bfe_u64's descriptor in bit 16 (offset = bits 5:0, width = bits 22:16), and goes into M0
-		// as it is: v_writelane takes the lane from M0's low six bits
-		int pos = 1 | (1 << 16);
-#pragma unroll 1
-		for (int half = 0; half < 2; half++) {
-			uint64_t codes = half ? seq.w1 : (seq.w0 >> 2);
-			codes = gcUniform64(codes);
-			const int end = (half ? nodeLength : (nodeLength < 32 ? nodeLength : 32)) | (1 << 16);
-#pragma unroll GC_LEAN_UNROLL
-			for (; pos < end; pos++) {
-				uint64_t lo, hi, Eq, hinP = 1, hinN = 0, f = 0;
-				const uint32_t posS = (uint32_t)__builtin_amdgcn_readfirstlane(pos);
-				const uint32_t desc = posS;
-				asm("s_bitcmp1_b32 %3, 0\n\ts_cselect_b64 %0, %5, %4\n\ts_cselect_b64 %1, %7, %6\n\ts_bitcmp1_b32 %3, 1\n\ts_cselect_b64 %2, %1, %0"
-					: "=&s"(lo), "=&s"(hi), "=&s"(Eq) : "s"((uint32_t)codes), "s"(eA), "s"(eC), "s"(eG), "s"(eT) : "scc");
-				if (KIND != 2) {
-					asm("s_bfe_u64 %0, %1, %2" : "=s"(hinP) : "s"(prevHP), "s"(desc) : "scc");
-					asm("s_bfe_u64 %0, %1, %2" : "=s"(hinN) : "s"(prevHN), "s"(desc) : "scc");
-				}
-				if (KIND == 0) asm("s_bfe_u64 %0, %1, %2" : "=s"(f) : "s"(forced), "s"(desc) : "scc");
-				codes >>= 2;
-				const uint64_t Xv = Eq | VN;
-				if (KIND != 2) Eq |= hinN;
-				const uint64_t Xh = (((Eq & VP) + VP) ^ VP) | Eq;
-				const uint64_t Ph = VN | ~(Xh | VP);
-				const uint64_t Mh = VP & Xh;
-				const uint64_t sPh = (Ph << 1) | hinP, sMh = KIND != 2 ? ((Mh << 1) | hinN) : (Mh << 1);
-				if (KIND == 0) { VP = (sMh | ~(Xv | sPh)) & ~f; VN = (sPh & Xv) | f; }
-				else if (KIND == 1) { VP = sMh | ~(Xv | sPh); VN = sPh & Xv; }
-				else {
-					// (r6) a node that is new in this slice enters with its first row forced (VP bit 0 clear, VN bit 0 set: every incoming column was forced when it was pushed, and the
-					// pointwise minimum of forced columns is forced), its match masks have bit 0 cleared (forceEq) and its carries are (+1, 0): then Xv and sPh both have bit 0 set,
-					// sMh has it clear, and the recurrence itself leaves VP bit 0 clear and VN bit 0 set - the two forcing operations of the general copy are no-ops here
-					VP = sMh | ~(Xv | sPh); VN = sPh & Xv;
-				}
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-				// (two SGPR operands exceed gfx9's constant bus; M0 as lane select does not count)
-				if (MODE == 0) {
-					asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %3, m0\n\tv_writelane_b32 %1, %4, m0" : "+v"(plusWord), "+v"(minusWord) : "s"(posS), "s"((uint32_t)(Ph >> 32)), "s"((uint32_t)(Mh >> 32)) : "m0");
-				} else {
-					// backtrace recompute / column store: the column itself goes to lane pos of the column registers (its score follows after the loop)
-					asm("s_mov_b32 m0, %6\n\tv_writelane_b32 %0, %7, m0\n\tv_writelane_b32 %1, %8, m0\n\tv_writelane_b32 %2, %9, m0\n\tv_writelane_b32 %3, %10, m0\n\tv_writelane_b32 %4, %11, m0\n\tv_writelane_b32 %5, %12, m0"
-						: "+v"(tables.cr[0]), "+v"(tables.cr[1]), "+v"(tables.cr[2]), "+v"(tables.cr[3]), "+v"(plusWord), "+v"(minusWord)
-						: "s"(posS), "s"((uint32_t)VP), "s"((uint32_t)(VP >> 32)), "s"((uint32_t)VN), "s"((uint32_t)(VN >> 32)), "s"((uint32_t)(Ph >> 32)), "s"((uint32_t)(Mh >> 32)) : "m0");
-				}
-#pragma clang diagnostic pop
-			}
-		}
-#endif
+			gcColumnLoopAsm<decltype(kindTag)::value, MODE>(eA, eC, eG, eT, VP, VN, prevHP, prevHN, forced, gcUniform64(seq.w0), gcUniform64(seq.w1), nodeLength, plusWord, minusWord, tables.cr);
 		};
-#if GC_LEAN_KINDS
 		if (!prevExists) columnLoop(std::integral_constant<int, 2>());
 		else if (forceUntil == 0) columnLoop(std::integral_constant<int, 1>());
 		else columnLoop(std::integral_constant<int, 0>());
-#else
-		columnLoop(std::integral_constant<int, 0>());
-#endif
 		const uint64_t HP = __ballot((int32_t)plusWord < 0), HN = __ballot((int32_t)minusWord < 0);   // lanes 0 and >= nodeLength still hold 0
 		out.HP = HP; out.HN = HN;
 		out.eVP = VP; out.eVN = VN; out.eScore = ws.score + popc64(HP) - popc64(HN);
@@ -558,9 +461,7 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 				r.minOffset = minKey & 63u;
 			}
 		}
-#if GC_LEAN_WALK
 		if (COLUMNS) tables.setWalkMasks(seq.w0, seq.w1, eq, forceEq, prevHN);
-#endif
 		return r;
 	}
 	if (COLUMNS && LANE_TABLES::eqInLanes) tables.walkMasks = false;
@@ -667,9 +568,9 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				} else { hinP = 1; hinN = 0; }
 				NodeSeq nseq = loadNodeSeq(g, target);
 				uint64_t hp, hn;
-#if GC_LEAN_COLUMNS && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 				uint64_t eqFirst;
-				if (REGCOLS && !nseq.ambiguous) {   // the first column's match mask by the same three scalar selects as in the column loop
+				if (REGCOLS && !nseq.ambiguous) {   // the first column's match mask by three scalar selects on its 2-bit code
 					uint64_t lo, hi;
 					const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)nseq.w0);
 					const uint64_t mA = gcUniform64(eq.a), mC = gcUniform64(eq.c), mG = gcUniform64(eq.g), mT = gcUniform64(eq.t);
@@ -687,7 +588,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				L.qSet(slot, target, g.componentNumber[target], add);
 				nPending++;
 			} else {
-#if GC_LEAN_MERGE && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 				L.qSetWs(slot, REGCOLS ? wsMergeWave(L.qWs(slot), add) : wsMerge(L.qWs(slot), add));
 #else
 				L.qSetWs(slot, wsMerge(L.qWs(slot), add));
@@ -754,7 +655,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				else if (tr.flatMin == flatMin) flatOffset |= 0x80000000u;
 			}
 			WS newEnd = itemEnd(out);
-#if GC_LEAN_COLUMNS && GC_LEAN_COLMIN && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 			int32_t newEndMin;
 			if (REGCOLS) {
 				// minimum over rows -1..63 of the tile's end column, all rows at once (lane r: the value of row r from two masked popcounts; wave
@@ -864,7 +765,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		if (REGCOLS && count && threadIdx.x < count) wsx.base[(wsx.traceBase(nTrace - count, which)) * wsx.lanes + wsx.lane + threadIdx.x] = (unsigned long long)tbLo | ((unsigned long long)tbHi << 32);
 	};
 	auto pushTraceW = [&](Cell c, bool sw) __attribute__((always_inline)) -> bool {
-#if GC_LEAN_WALK && GC_LEAN_PUSH && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 		if (REGCOLS) {
 			// cell into lane (nTrace mod 64) of the register pair; the room check happens once per 64 cells, at the flush (a trace that
 			// outgrows its buffer is noticed at the block's end or at the final flush instead of at the cell - same verdict, EXT_OVERFLOW)
@@ -1018,9 +919,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				L.cr[4] = (uint32_t)(curIt.sScore + popc64(curIt.HP & upToC) - popc64(curIt.HN & upToC));
 				const NodeSeq seq = loadNodeSeq(g, curNode);
 				L.walkMasks = false;
-#if GC_LEAN_WALK
 				if (!seq.ambiguous) L.setWalkMasks(seq.w0, seq.w1, eq, pre.forceEq, pre.prevHN);
-#endif
 			} else
 #endif
 			{
@@ -1128,7 +1027,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			here = nxt;
 			continue;
 		}
-#if GC_LEAN_WALK && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 		if (REGCOLS && L.walkMasks) {
 			// (row masks of the tile's columns are in the lanes, see setWalkMasks: the walk only tests bits)
 			uint32_t hori = here.offset;
@@ -1137,7 +1036,6 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			L.loadWalkMasks(hori, up, diag, left);
 			uint32_t unfit = 0;   // a cell none of whose three predecessors fits: the reference's assertion; reported after the tile's walk
 			while (hori > 0 && vert > 0) {
-#if GC_LEAN_DIAGRUN
 				// Most steps are diagonal, in runs: from (hori, vert) the walk goes diagonally as long as, in column hori - i, the cell of row vert - i
 				// has no step up and a fitting diagonal predecessor. Column c keeps its masks in lane c, so lane c tests its own bit c - (hori - vert)
 				// and one ballot shows the whole run; its cells (node, hori - 1 - k, row vert - 1 - k) are written by the lanes of the trace staging
@@ -1172,7 +1070,6 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 						continue;
 					}
 				}
-#endif
 				const uint32_t u = (uint32_t)(up >> vert) & 1u, d = (uint32_t)(diag >> vert) & 1u, l = (uint32_t)(left >> vert) & 1u;
 				unfit |= (u | d | l) ^ 1u;
 				vert -= (int)(u | d);                                        // up: vertical == scoreHere - 1; else diagonal == scoreHere - (match ? 0 : 1)

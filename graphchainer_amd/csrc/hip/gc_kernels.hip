@@ -1204,56 +1204,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES =
 	}
 }
 
-#ifdef GC_EXPERIMENTS   // (`make -C graphchainer_amd/csrc experiments`: measured and rejected alternatives are not part of the product library)
-// The measurement VERDICT r3 asked for (GC_LONG_LANE=1, experiments build): the same rounds, but every LANE takes one work item and runs the
-// plain-layout core (extendSeedT, gc_device.hpp: the core of k_extend and k_long_pass) with its band state in a per-lane HBM slab - no LDS tables, no
-// state machine, <= 128 VGPRs (4 waves per SIMD). Work items arrive longest first (k_long_order), so a wave's 64 extensions have about the same number of
-// slices. What outgrows the slab answers EXT_OVERFLOW and its read goes to the plain-layout fallback like any other overflow.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_long_extend_lane(DGraph g, const CorrectnessTables* __restrict__ ct, const uint64_t* __restrict__ masks, ExtendConfig cfg,
-	const LongWork* __restrict__ work, const uint32_t* __restrict__ order, uint32_t nWork, uint8_t* __restrict__ scratch, uint64_t slabBytes,
-	unsigned long long* __restrict__ tracePool, unsigned long long* __restrict__ traceCursor, uint64_t traceCapacity, LongWorkResult* __restrict__ results, unsigned long long* __restrict__ counters)
-{
-	const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t stride = gridDim.x * blockDim.x;
-	LaneScratch sc = laneScratch(scratch + (uint64_t)tid * slabBytes, cfg);
-	ExtCounters cnt {};
-	for (uint32_t slot = tid; slot < nWork; slot += stride) {
-		const uint32_t w = order[slot];
-		LongWork it = work[w];
-		LongWorkResult res { 0, 0, EXT_FAILED, 0, 0 };
-		if (it.seqLen > 0) {
-			uint32_t nTrace = 0;
-			int32_t score = 0;
-			EqSource eqSrc { masks + it.maskOff, it.maskWords, it.startBit };
-			res.status = extendSeedT(g, *ct, eqSrc, cfg, sc, (int)it.seqLen, it.node, it.offset, nTrace, score, cnt);
-			res.score = score;
-			res.pad = cnt.flattenTie;
-			if (res.status == EXT_OK) {
-				unsigned long long base = atomicAdd(traceCursor, (unsigned long long)nTrace);
-				if (base + nTrace <= traceCapacity) {
-					for (uint32_t i = 0; i < nTrace; i++) {
-						const TraceCell c = sc.trace[i];
-						tracePool[base + i] = packCell(Cell { c.node, c.offsetAndSwitch & 255u, c.seqPos }, (c.offsetAndSwitch >> 8) & 1u);
-					}
-					res.traceOff = base;
-					res.traceLen = nTrace;
-				} else res.status = EXT_OVERFLOW;
-			}
-		}
-		results[w] = res;
-	}
-	if (cnt.extensions) {
-		atomicAdd(&counters[0], cnt.dpTiles);
-		atomicAdd(&counters[1], cnt.recomputeTiles);
-		atomicAdd(&counters[2], cnt.columnSteps);
-		atomicAdd(&counters[3], cnt.traceItems);
-		atomicAdd(&counters[4], cnt.extensions);
-		atomicAdd(&counters[5], cnt.backtraceTiles);
-	}
-}
-
-#endif
-
 // One wave per read: the decisions are taken redundantly by all lanes (uniform control flow, lane 0 does the single
 // writes), the trace -> cell conversion - the bulk of the work, ~1.5 cells per read base - runs 64 cells at a time.
 __device__ __forceinline__ void longMergeRead(const DGraph& g, const uint32_t r, const uint32_t lane, const LongJob* __restrict__ jobs, const LongSeed* __restrict__ seeds, const uint32_t* __restrict__ candSeed,
@@ -1382,81 +1332,6 @@ __global__ void __launch_bounds__(GC_ORDER_THREADS) k_long_order(const uint32_t*
 	__syncthreads();
 	for (uint32_t i = tid; i < n; i += T) { uint32_t b = workLen[i] >> shift; order[atomicAdd(&start[1023 - (b < 1023 ? b : 1023)], 1u)] = i; }
 }
-
-#ifdef GC_EXPERIMENTS
-// One launch per round instead of five (r4): the previous round's merge, this round's select, the execution order and the hand-over of the round's work count.
-// One wave per read runs the read's merge and then its select (both only touch that read's state); every wave then takes a ticket, and the wave that takes the
-// last one - all work items of the round are in place by then - sorts them into execution order (longest first, 64 lanes over an LDS histogram of 1024 length
-// classes) and publishes the count: to the device (roundInfo[round]: the next round's speculation rule reads it, and the extension kernel takes its item count from the
-// round's cursor set) and to pinned host memory. The cursors come in two sets that alternate with the round's parity; a round zeroes the NEXT round's set (its last
-// users - the previous round's select and extension kernels - are complete in stream order). With that the host can queue several rounds without waiting for any
-// count: between two extension kernels of a pass sit this kernel and the (almost always empty) retry, not zero / select / order / publish / host round trip / merge,
-// each of which waited for a wave slot among the other batches' kernels (r3: 28 ms of a pass's 149 with five batches in flight).
-__global__ void __launch_bounds__(64) k_long_round(DGraph g, const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, uint32_t minClusterSize, uint32_t round, uint32_t forceCand,
-	uint32_t gridLimit, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, uint32_t maxAlignments,
-	LongWork* work, uint32_t* workLen, uint32_t* candSeed, const LongWorkResult* results, const unsigned long long* tracePool,
-	unsigned long long* cursorSets, unsigned long long* roundInfo, unsigned long long* ticket, uint32_t* order, uint32_t orderShift, uint32_t orderMode,
-	volatile unsigned long long* hostInfo, uint64_t workCapacity)
-{
-	__shared__ uint32_t hist[1024];
-	const uint32_t r = blockIdx.x, lane = threadIdx.x;
-	unsigned long long* cur = cursorSets + 4 * (round & 1u);
-	unsigned long long* next = cursorSets + 4 * ((round + 1u) & 1u);
-	if (r == 0 && lane < 4) next[lane] = 0;
-	// candidates per read (the host loop's rule, on the device): one; several once few reads are still active (exact: the merge re-checks them in order), within
-	// what the work arrays, the trace budget (four seeds' worth per read) and the extension launch's grid hold
-	uint32_t maxCand = 1;
-	if (round > 0) {
-		const uint64_t lastWork = roundInfo[round - 1];
-		if (lastWork > 0) {
-			maxCand = (uint32_t)min((uint64_t)8, max((uint64_t)1, (2ull * nReads) / lastWork));
-			if (lastWork < 8192) maxCand = 8;
-			maxCand = (uint32_t)min((uint64_t)maxCand, max((uint64_t)1, (8ull * nReads) / lastWork));
-			maxCand = (uint32_t)min((uint64_t)maxCand, max((uint64_t)1, (uint64_t)gridLimit / lastWork));   // at most lastWork / 2 reads are active: 2 x maxCand items each
-		}
-	}
-	if (forceCand) maxCand = forceCand;
-	if (r < nReads) {
-		// the candidates' seed indices are double-buffered by the round's parity: this read's select writes the new round's list while other reads' merges still read the previous round's
-		// (everything else a select writes - work items, lengths - no merge reads; the extension results and traces a merge reads are written by the extension kernels, between the rounds)
-		if (round > 0) { longMergeRead(g, r, lane, jobs, seeds, candSeed + (uint64_t)((round - 1u) & 1u) * workCapacity, results, tracePool, maxAlignments, state, alns, cellPool, cellCursor, cellCapacity); __threadfence_block(); }
-		longSelectRead(g, r, lane, jobs, seeds, minClusterSize, maxCand, state, alns, cellPool, work, workLen, candSeed + (uint64_t)(round & 1u) * workCapacity, cur, workCapacity);
-	}
-	__threadfence();   // this wave's work items before its ticket
-	uint32_t last = 0;
-	if (lane == 0) last = atomicAdd(ticket, 1ull) == (unsigned long long)gridDim.x - 1 ? 1u : 0u;
-	last = __shfl(last, 0);
-	if (!last) return;
-	__threadfence();
-	const uint32_t n = (uint32_t)atomicAdd(cur, 0ull);
-	const volatile uint32_t* lens = workLen;
-	if (orderMode == 0) { for (uint32_t i = lane; i < n; i += 64) order[i] = i; }
-	else {
-		for (uint32_t b = lane; b < 1024; b += 64) hist[b] = 0;
-		__syncthreads();
-		for (uint32_t i = lane; i < n; i += 64) { const uint32_t b = lens[i] >> orderShift; atomicAdd(&hist[1023 - (b < 1023 ? b : 1023)], 1u); }
-		__syncthreads();
-		// exclusive scan of the 1024 classes: 16 per lane, a wave scan of the lanes' sums
-		uint32_t mine[16], sum = 0;
-		for (int k = 0; k < 16; k++) { mine[k] = hist[lane * 16 + k]; sum += mine[k]; }
-		uint32_t incl = sum;
-		for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d); if ((int)lane >= d) incl += o; }
-		uint32_t at = incl - sum;
-		for (int k = 0; k < 16; k++) { hist[lane * 16 + k] = at; at += mine[k]; }
-		__syncthreads();
-		for (uint32_t i = lane; i < n; i += 64) { const uint32_t b = lens[i] >> orderShift; order[atomicAdd(&hist[1023 - (b < 1023 ? b : 1023)], 1u)] = i; }
-	}
-	if (lane == 0) {
-		roundInfo[round] = n;
-		*ticket = 0;
-		hostInfo[2 + round] = n;
-		__threadfence_system();
-		hostInfo[0] = round + 1;   // rounds published so far
-		__threadfence_system();
-	}
-}
-
-#endif
 
 // copies a few cursor words into pinned host memory through the compute queue (a copy-engine transfer would queue behind bulk uploads)
 __global__ void k_publish(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, uint32_t nWords)
@@ -1591,24 +1466,15 @@ uint32_t longExtendTeamSize(uint32_t nWork)
 
 void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint64_t* masks, const ExtendConfig& cfg, const LongWork* work, const uint32_t* order, uint32_t nWork,
 	unsigned long long* scratch, uint32_t lanes, uint32_t blocks, unsigned long long* tracePool, unsigned long long* traceCursor, uint64_t traceCapacity, LongWorkResult* results, unsigned long long* counters,
-	unsigned long long* nextSlot, uint32_t retryStatus, const unsigned long long* nWorkOnDevice, uint32_t* capListOut, unsigned long long* capCountOut, bool gridCoversCount)
+	unsigned long long* nextSlot, uint32_t retryStatus, const unsigned long long* nWorkOnDevice, uint32_t* capListOut, unsigned long long* capCountOut)
 {
 	if (!nWork) return;
 	uint64_t words = longWaveWordsPerLane(cfg);
-	// fewer lanes than work items (or a count only the device knows): waves loop and fetch - unless the caller vouches that the grid covers whatever the count turns out to be
-	// (gridCoversCount: the sync-free round loop, whose launches are sized by a bound; waves beyond the count leave at once)
-	const bool persistent = (nWorkOnDevice && !gridCoversCount) || (uint64_t)blocks * lanes < nWork;
-	// GC_LONG_WAVES_PER_SIMD=w (experiment): an unused dynamic LDS allocation per wave caps the kernel at w waves per SIMD, leaving wave slots
-	// and registers to the fragment pipeline's kernels that share the device with it
-#ifdef GC_EXPERIMENTS
-	static const uint32_t ldsPad = []() { const char* e = getenv("GC_LONG_WAVES_PER_SIMD"); int w = e ? atoi(e) : 0; return (w >= 1 && w <= 7) ? (uint32_t)((160u * 1024u / (4u * (uint32_t)w)) & ~255u) : 0u; }();
-	const uint32_t pad = lanes == 1 ? ldsPad : 0;
-#else
-	const uint32_t pad = 0;
-#endif
+	// fewer lanes than work items (or a count only the device knows): waves loop and fetch
+	const bool persistent = nWorkOnDevice || (uint64_t)blocks * lanes < nWork;
 	// the band controls (gc_params::ramp_bandwidth / max_cells_per_slice) run in their own instantiation: the default one is compiled as before
 	const bool band = cfg.bandControls();
-#define GC_LAUNCH_ONE(N, P, B) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_extend<N, P, B>), dim3(blocks), dim3(64), pad, stream, g, ct, masks, cfg, work, order, nWork, scratch, words, tracePool, traceCursor, traceCapacity, results, counters, nextSlot, retryStatus, nWorkOnDevice, capListOut, capCountOut)
+#define GC_LAUNCH_ONE(N, P, B) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_extend<N, P, B>), dim3(blocks), dim3(64), 0, stream, g, ct, masks, cfg, work, order, nWork, scratch, words, tracePool, traceCursor, traceCapacity, results, counters, nextSlot, retryStatus, nWorkOnDevice, capListOut, capCountOut)
 #define GC_LAUNCH_TEAM(N) do { if (band) { if (persistent) GC_LAUNCH_ONE(N, true, true); else GC_LAUNCH_ONE(N, false, true); } \
 	else if (persistent) GC_LAUNCH_ONE(N, true, false); else GC_LAUNCH_ONE(N, false, false); } while (0)
 	switch (lanes) {
@@ -1623,20 +1489,6 @@ void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 #undef GC_LAUNCH_TEAM
 #undef GC_LAUNCH_ONE
 }
-#ifdef GC_EXPERIMENTS
-void launchLongExtendLane(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint64_t* masks, const ExtendConfig& cfg, const LongWork* work, const uint32_t* order, uint32_t nWork,
-	uint8_t* scratch, uint64_t scratchBytes, unsigned long long* tracePool, unsigned long long* traceCursor, uint64_t traceCapacity, LongWorkResult* results, unsigned long long* counters)
-{
-	if (!nWork) return;
-	const uint64_t slab = extendSlabBytes(cfg);
-	uint64_t lanes = ((uint64_t)nWork + 63) / 64 * 64;
-	const uint64_t fit = scratchBytes / slab / 64 * 64;   // lanes whose slabs fit the scratch: a larger round strides
-	if (lanes > fit) lanes = fit;
-	if (lanes > 256ull * 16 * 64) lanes = 256ull * 16 * 64;
-	if (lanes == 0) return;
-	hipLaunchKernelGGL(k_long_extend_lane, dim3((uint32_t)(lanes / 64)), dim3(64), 0, stream, g, ct, masks, cfg, work, order, nWork, scratch, slab, tracePool, traceCursor, traceCapacity, results, counters);
-}
-#endif
 // Work items of the fragment pass, built where they are used (src/GraphAligner.h:499-511 per seed of a fragment window): the host sorts each
 // read's seeds and cuts the windows (order-critical, host/gc_glue.cpp) and hands over 16 B per fragment and per seed; one thread per fragment
 // expands its seed window into the per-slot records - the seed in fragment order and the two extensions (backward: reverse complement of the
@@ -1679,37 +1531,11 @@ void launchBuildFragmentWork(hipStream_t stream, const DGraph& g, const Fragment
 {
 	if (nFrags) hipLaunchKernelGGL(k_build_fragment_work, dim3((nFrags + 255) / 256), dim3(256), 0, stream, g, frags, fragFirstSeed, nFrags, readSeeds, readOffsets, totalBases, splitLen, fragSeeds, work, results);
 }
-#ifdef GC_EXPERIMENTS   // (only the state-machine experiment lists its declined items this way; the product's extension kernel writes its own retry list)
-// work items of a round whose extension ended with `status` (EXT_LDS_CAP: the band outgrew the register tables), as a list for the retry launch:
-// almost always empty, so the retry costs one small kernel and a handful of waves instead of one wave per pair of work items
-__global__ void __launch_bounds__(256) k_long_retry_list(const LongWorkResult* __restrict__ results, uint32_t nWork, uint32_t status, uint32_t* __restrict__ list, unsigned long long* __restrict__ listCount)
-{
-	const uint32_t w = blockIdx.x * 256 + threadIdx.x;
-	if (w < nWork && results[w].status == status) list[atomicAdd(listCount, 1ull)] = w;
-}
-void launchLongRetryList(hipStream_t stream, const LongWorkResult* results, uint32_t nWork, uint32_t status, uint32_t* list, unsigned long long* listCount)
-{
-	if (nWork) hipLaunchKernelGGL(k_long_retry_list, dim3((nWork + 255) / 256), dim3(256), 0, stream, results, nWork, status, list, listCount);
-}
-#endif
 void launchLongMerge(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, const uint32_t* candSeed, const LongWorkResult* results,
 	const unsigned long long* tracePool, uint32_t maxAlignments, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity)
 {
 	if (nReads) hipLaunchKernelGGL(k_long_merge, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, candSeed, results, tracePool, maxAlignments, state, alns, cellPool, cellCursor, cellCapacity);
 }
-#ifdef GC_EXPERIMENTS
-void launchLongRound(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, uint32_t minClusterSize, uint32_t round, uint32_t forceCand, uint32_t gridLimit,
-	LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, uint32_t maxAlignments, LongWork* work, uint32_t* workLen, uint32_t* candSeed,
-	const LongWorkResult* results, const unsigned long long* tracePool, unsigned long long* cursorSets, unsigned long long* roundInfo, unsigned long long* ticket, uint32_t* order, uint32_t maxLen, uint32_t orderMode,
-	unsigned long long* hostInfo, uint64_t workCapacity)
-{
-	if (!nReads) return;
-	uint32_t shift = 0;
-	while ((maxLen >> shift) > 1023) shift++;
-	hipLaunchKernelGGL(k_long_round, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, minClusterSize, round, forceCand, gridLimit, state, alns, cellPool, cellCursor, cellCapacity, maxAlignments,
-		work, workLen, candSeed, results, tracePool, cursorSets, roundInfo, ticket, order, shift, orderMode, (volatile unsigned long long*)hostInfo, workCapacity);
-}
-#endif
 void launchLongOrder(hipStream_t stream, const uint32_t* workLen, const unsigned long long* workCount, uint32_t* order, uint32_t maxLen, uint32_t mode)
 {
 	uint32_t shift = 0;

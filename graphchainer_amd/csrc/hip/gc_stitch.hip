@@ -29,7 +29,7 @@
 
 namespace gcdev {
 
-// A second, smaller size class of the search tables was measured in r4 and is NOT the default (GC_STITCH_SMALL=1 selects it for reads up to 16 kb): with 512 instead of 1 024
+// A second, smaller size class of the search tables was measured in r4 and not kept (its code is gone): with 512 instead of 1 024
 // visited nodes per bridge search (20 KB of LDS per wave instead of 29.5, seven waves per CU instead of five) 39 % of cfg2's reads overflowed the search and went to the
 // host's stitching (3 915 of 10 000: a failed search for an upstream anchor walks several hundred nodes before the rank pruning ends it), and with a 1 024-slot node set as well
 // a piece's ~450 split nodes no longer fitted: host CPU per batch 0.36 -> 0.8-0.9 s for 2-3 % of batch time (`gpurun_out/r4_rounds`, `r4_rounds2`, `r4_e2etimes`).
@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(64) k_stitch(DGraph g, const ReadChainJob* __r
 	}
 }
 
-// sizeClass: 0 the default tables (2 048-slot node set, 1 024 visited nodes per bridge search: reads up to ~16 kb), 1 the half-size search (measured in r4, not kept: experiments build),
+// sizeClass: 0 the default tables (2 048-slot node set, 1 024 visited nodes per bridge search: reads up to ~16 kb),
 // 3 (r5) the class of long reads: the default class's LDS plus a node set and a wide-search area in HBM scratch (`spill`: stitchSpillWordsPerBlock() words per block of the launch,
 // stitchSpillBlocks(nReads) blocks; zeroed here before every launch - the tables' generation stamps start again with each launch)
 void launchStitch(hipStream_t stream, const DGraph& g, const ReadChainJob* jobs, uint32_t nReads, const AnchorRec* anchors, const Fragment* frags, const uint32_t* fragStatus,
@@ -413,9 +413,6 @@ void launchStitch(hipStream_t stream, const DGraph& g, const ReadChainJob* jobs,
 		(void)hipMemsetAsync(spill, 0, (size_t)blocks * stitchSpillWordsPerBlock() * sizeof(unsigned long long), stream);
 		GC_LAUNCH_STITCH(STITCH_SET_SIZE_LARGE, STITCH_BFS_CAP_LARGE, true);
 	}
-#ifdef GC_EXPERIMENTS
-	else if (sizeClass == 1) GC_LAUNCH_STITCH(STITCH_SET_SIZE_LARGE, STITCH_BFS_CAP_LARGE / 2, false);
-#endif
 	else GC_LAUNCH_STITCH(STITCH_SET_SIZE_LARGE, STITCH_BFS_CAP_LARGE, false);
 #undef GC_LAUNCH_STITCH
 }

@@ -42,7 +42,7 @@ typedef struct gc_reads gc_reads;     /* a batch of reads uploaded to HBM */
  * Every table is PER EXTENSION or PER READ, never per batch, and what outgrows one never fails the call: the work is rerun with more room (second launch, other
  * kernel layout, larger pool) and, only if that overflows too, the READ is flagged in gc_result::capacity_exceeded and reported without the affected part.
  * 0 = automatic (the values in brackets, derived from the batch's longest read L); set a field only to trade memory against reruns on unusual inputs
- * (dense variant clusters, very noisy long reads). The same knobs exist as GC_* environment variables for experiments; the environment wins. */
+ * (dense variant clusters, very noisy long reads). The same knobs exist as GC_TEST_* environment variables for tests; the environment wins. */
 typedef struct gc_capacities {
 	int64_t ext_max_items;          /* fragment extensions (k_extend): (slice, node) tiles per extension [72; the retry launch has 16x] (GC_TEST_EXT_MAX_ITEMS) */
 	int64_t ext_max_pending;        /* ... entries of the per-slice node queue [48; retry 16x] (GC_TEST_EXT_MAX_PENDING) */

@@ -547,11 +547,11 @@ double gco_align_timed(void* hv, const char* bases, const uint64_t* off, int n, 
 
 const char* gco_gaf(void* hv, int merge) { return ((OracleHandle*)hv)->gaf[merge ? 1 : 0].c_str(); }
 const char* gco_json(void* hv) { return ((OracleHandle*)hv)->json.c_str(); }
-// the inflated GAM stream of the last gco_align call; *groupOff / *nGroups: the groups' boundaries (nGroups + 1 offsets)
-const char* gco_gam(void* hv, uint64_t* len, const uint64_t** groupOff, uint64_t* nGroups)
+// the inflated GAM stream of the last gco_align call; *groupOff / *gamGroups: the groups' boundaries (gamGroups + 1 offsets)
+const char* gco_gam(void* hv, uint64_t* len, const uint64_t** groupOff, uint64_t* gamGroups)
 {
 	OracleHandle* h = (OracleHandle*)hv;
-	*len = h->gam.size(); *groupOff = h->gamGroupOff.data(); *nGroups = h->gamGroupOff.size() - 1;
+	*len = h->gam.size(); *groupOff = h->gamGroupOff.data(); *gamGroups = h->gamGroupOff.size() - 1;
 	return h->gam.data();
 }
 

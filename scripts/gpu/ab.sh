@@ -7,7 +7,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
-    libname=${v%%:*}; tag=${v##*:}           # "exp:split20" = library exp, environment AB_ENV_split20; a plain name is both
+    libname=${v%%:*}; tag=${v##*:}           # "parent:tok0" = library parent, environment AB_ENV_tok0; a plain name is both
     lib=$GRAFT_REPO_ROOT/graphchainer_amd/libgraphchainer_amd_$libname.so
     if [ "$libname" = prod ]; then lib=$GRAFT_REPO_ROOT/graphchainer_amd/libgraphchainer_amd.so; fi
     envvar="AB_ENV_$tag"                     # AB_ENV_<tag>="K=V K=V": environment switches of that variant only

@@ -1341,7 +1341,7 @@ def test_batches_in_flight_equal_serial_and_oracle(gca, tmp_path, monkeypatch, t
     """The mode bench.py times: several gc_align_batch calls in flight on ONE device, each on its own gc_stream and host thread
     (run_queue with workers > 1, the reference's -t workers over one queue, src/Aligner.cpp:1267-1270), whole-read pass on, with the
     settings of the per-device whole-read token: none ("0"), per pass with the r5 rule ("1": batches this small may run two passes side by side, each in a scratch of its
-    own), and the rule overridden to one or two tokens ("one", "two"; the per-round token lives in the experiments build). Four different read sets go through three
+    own), and the rule overridden to one or two tokens ("one", "two"). Four different read sets go through three
     Aligners concurrently, twice each; every result array must equal the oracle's AND the same Aligner's serial answer."""
     from graphchainer_amd.synth import SynthGraph
     from graphchainer_amd.workqueue import ReadQueue, run_queue

@@ -211,28 +211,6 @@ def test_gaf_and_json_encoders_equal_the_oracle_encoders_on_the_cpu(tmp_path):
         assert expected_reads >= 5 and out.stdout == want, (merge, out.stdout[:200], want[:200])
 
 
-def test_state_machine_extension_core_equals_oracle(tmp_path):
-    """The per-lane state machine of the experimental kernel k_long_extend_sm (graphchainer_amd/csrc/hip/gc_sm_core.hpp) is plain C++:
-    tests/sm_host/sm_host_test.cpp compiles its phase functions with g++, drives ONE lane on the CPU and compares status, score and every trace
-    cell of several hundred extensions (10 kb ONT-like reads on a graph with repeats and multi-allelic sites, both directions, two band
-    widths) with the oracle's getReverseTraceFromSeed."""
-    exe = tmp_path / "sm_host_test"
-    src = os.path.join(ROOT, "tests", "sm_host", "sm_host_test.cpp")
-    host = os.path.join(ROOT, "graphchainer_amd", "csrc", "host")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-w", "-I/opt/rocm/include", src, os.path.join(host, "gc_graph.cpp"), os.path.join(host, "gc_minimizer.cpp"), "-o", str(exe), "-lpthread"], check=True, timeout=600)
-    sg = SynthGraph(300_000, seed=43, repeats=4, repeat_len=2000, multi_allelic=0.1)
-    gfa = str(tmp_path / "g.gfa")
-    sg.write_gfa(gfa)
-    reads = sg.sample_reads(10, 8000, seed=8) + sg.sample_reads(3, 8000, seed=9, sv_fraction=1.0)
-    (tmp_path / "reads.txt").write_bytes(b"\n".join(reads) + b"\n")
-    for args in (["4"], ["3", "5"]):
-        out = subprocess.run([str(exe), gfa, str(tmp_path / "reads.txt")] + args, capture_output=True, text=True, timeout=900)
-        assert out.returncode == 0 and "SM_HOST_OK" in out.stdout, out.stdout + out.stderr
-        fields = out.stdout.split()
-        equal = int(fields[fields.index("equal") + 1])
-        assert equal > 60, out.stdout
-
-
 def test_fragment_extension_core_equals_oracle(tmp_path):
     """The per-lane state machine of the fragment extension kernel k_extend (graphchainer_amd/csrc/hip/gc_frag_core.hpp, r6) is plain C++ over a memory policy:
     tests/frag_host/frag_host_test.cpp compiles its phase functions with g++, drives ONE lane on the CPU over the kernel's own word layout (queue and ring overlaid,

@@ -49,7 +49,7 @@ def test_product_does_not_touch_the_oracle():
 
 def test_every_environment_switch_of_the_product_is_documented():
     """the product library reads a fixed set of GC_* variables, and INTEGRATION.md §7 is the one table that lists them. Every name the sources read
-    (getenv / capacityOr; expEnv names exist only in the experiments build and are listed there as such) must appear in INTEGRATION.md, and DESIGN.md stays one
+    (getenv / capacityOr) must appear in INTEGRATION.md, and DESIGN.md stays one
     document with one numbering below 100 KB."""
     import re
     names = set()
@@ -59,13 +59,11 @@ def test_every_environment_switch_of_the_product_is_documented():
             continue
         for f in files:
             if f.endswith((".hip", ".hpp", ".cpp", ".h", ".inc")):
-                names.update(re.findall(r'(?:getenv|expEnv|capacityOr)\("(GC_[A-Z0-9_]+)"', open(os.path.join(dirpath, f), errors="ignore").read()))
+                names.update(re.findall(r'(?:getenv|capacityOr)\("(GC_[A-Z0-9_]+)"', open(os.path.join(dirpath, f), errors="ignore").read()))
     assert len(names) > 30
     # r6 ("50 distinct getenv in the product"): what a HOST may set is at most 25 variables; everything a test uses to force a rare path or a small table is named
-    # GC_TEST_*; the rest exists only inside #ifdef GC_EXPERIMENTS (the measured-and-rejected alternatives, listed as such in INTEGRATION.md §7)
-    experiments_only = {"GC_LONG_SM", "GC_LONG_LANE", "GC_LONG_ROUNDS", "GC_LONG_PLAN", "GC_LONG_SPLIT", "GC_LONG_SPLIT_TEAM", "GC_LONG_WAVES_PER_SIMD", "GC_LONG_TOKEN_EARLY", "GC_STITCH_SMALL",
-                        "GC_LONG_GROUPS", "GC_STREAM_PRIORITY", "GC_LONG_MAX_LANES"}
-    product = sorted(n for n in names if not n.startswith("GC_TEST_") and n not in experiments_only)
+    # GC_TEST_* (the switches of the measured-and-rejected alternatives went with their code)
+    product = sorted(n for n in names if not n.startswith("GC_TEST_"))
     assert len(product) <= 25, product
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     shorthand = {"GC_TEST_EXT_MAX_PENDING": "GC_TEST_EXT_MAX_ITEMS / _PENDING / _TRACE", "GC_TEST_EXT_MAX_TRACE": "GC_TEST_EXT_MAX_ITEMS / _PENDING / _TRACE"}
