@@ -8,8 +8,12 @@
 		maxReadLen = 1;
 		for (uint64_t r = 0; r < n; r++) maxReadLen = std::max<uint64_t>(maxReadLen, R->offsets[r + 1] - R->offsets[r]);
 		// alignments kept per read: the reference has no limit; 32 is far above what 10 kb reads produce (3.6 seeds extended on average), longer
-		// and noisier reads get room in proportion. A read that still exceeds it is flagged (capacity_exceeded), the batch goes on.
-		maxAlignments = (uint32_t)std::max<uint64_t>(32, maxReadLen / 512);
+		// and noisier reads get room in proportion. A read that needs more (a read inside a tandem array collects 40-130) ends with status 3 and runs
+		// again with four times the slots (growAlnSlots), so the common read pays for 32 and no read is cut short at them.
+		firstAlnCap = (uint32_t)std::max<uint64_t>(32, maxReadLen / 512);
+		if (const char* env = getenv("GC_TEST_LONG_MAX_ALIGNMENTS")) firstAlnCap = (uint32_t)std::max(1, std::min(1 << 16, atoi(env)));   // test hook: a tiny first capacity, so that ordinary reads take the rerun too
+		alnSlots = n * (uint64_t)firstAlnCap;
+		if (P->long_pass && alnSlots >= 0xffffffffull) throw std::runtime_error("batch too large for the whole-read pass");
 		// Decision for a set of reads whose whole-read alignments are final: the reference's alignment order, the GreedyLength
 		// selection, and (queued, not awaited) the path letters + NW edit distance of the best alignment. (Tried: deciding the
 		// reads that are already finished when the rounds turn latency-bound, so these kernels run beside the last rounds - the
@@ -37,12 +41,12 @@
 				LongJob& j = hJobs[r];
 				j.maskOff = R->maskOff[r];
 				j.maskWords = R->maskWords[r];
-				j.pad = 0;
+				j.alnCap = firstAlnCap;
 				j.readOff = R->offsets[r];
 				j.readLen = (uint32_t)(R->offsets[r + 1] - R->offsets[r]);
 				j.seedBegin = (uint32_t)gl.longSeedBegin;
 				j.seedEnd = (uint32_t)at;
-				j.alnBegin = (uint32_t)(r * maxAlignments);
+				j.alnBegin = (uint32_t)(r * firstAlnCap);
 			});
 			lcfg.bandwidth = P->bandwidth;
 			lcfg.rampBandwidth = P->ramp_bandwidth;
@@ -60,7 +64,7 @@
 			waveWords = longWaveWordsPerLane(lcfg);
 			if (!deviceGlue) dLongSeeds = st->longSeeds.reserve<LongSeed>(nLongSeeds);
 			dLongJobs = st->longJobs.reserve<LongJob>(n);
-			dLongAlns = st->longAlns.reserve<LongAln>(n * maxAlignments);
+			dLongAlns = st->longAlns.reserve<LongAln>(alnSlots);
 			LongReadResult* dLongResults = st->longResults.reserve<LongReadResult>(n);
 			dLongCells = st->longCells.reserve<LongCell>(cellBudget, true);
 			// the rounds are serial (select -> extend -> merge, the host decides when to stop) and have a stream of their own beside the pass's stream
@@ -71,7 +75,7 @@
 			// cursors: [0] cell pool, [8..15] counters (+ [16..31] profiling stamps), the round loop's at [32..35]: work count, round trace cursor, next work slot, length of the retry list
 			cursorWords = 32 + 8 * 16;
 			dLongCursor = st->longCursor.reserve<unsigned long long>(cursorWords);
-			hLongAlns = st->hLongAlns.reserve<LongAln>(n * maxAlignments);
+			hLongAlns = st->hLongAlns.reserve<LongAln>(alnSlots);
 			hLongResults = st->hLongResults.reserve<LongReadResult>(n);
 			hLongSmall = st->hLongSmall.reserve<unsigned long long>(cursorWords);
 			ls = st->longStream;
@@ -126,6 +130,51 @@
 		st->longCellsPerBase = next;
 		cellBudget = cellBudgetFor(next);
 		dLongCells = st->longCells.reserve<LongCell>(cellBudget, true);
+		HIP_CHECK(hipMemsetAsync(dLongCursor, 0, cursorWords * sizeof(unsigned long long), ls));
+		syncStream(ls);
+		return true;
+	}
+
+	// Reads that found more alignments than they had slots for (status 3): each gets four times as many, in new slots behind the ones in use (the old ones are left unused),
+	// and runs again - after the rounds the whole pass (growLongAlns), after the plain-layout reruns those reads alone (longFallback; keep: the other reads' alignments
+	// are in the block and move with it). An alignment comes from a seed of its own, so a read with as many slots as seeds cannot run out; the limit beyond which a read is
+	// flagged instead is LONG_ALN_SLOTS_MAX per read and 2^32 slots per batch. Returns false when none of the reads can be given more.
+	static constexpr uint32_t LONG_ALN_SLOTS_MAX = 1u << 16;
+	bool growAlnSlots(const std::vector<uint32_t>& reads, bool keep)
+	{
+		uint64_t total = alnSlots;
+		std::vector<std::pair<uint32_t, uint32_t>> grown;   // (read, its new number of slots)
+		for (uint32_t r : reads) {
+			const uint32_t cap = hJobs[r].alnCap, limit = std::min<uint32_t>(LONG_ALN_SLOTS_MAX, std::max<uint32_t>(1, hJobs[r].seedEnd - hJobs[r].seedBegin));
+			if (cap >= limit) continue;
+			const uint32_t next = (uint32_t)std::min<uint64_t>(limit, 4ull * cap);
+			if (total + next >= 0xffffffffull) continue;
+			grown.push_back({ r, next });
+			total += next;
+		}
+		if (grown.empty()) return false;
+		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc mem] %zu reads found more whole-read alignments than they had slots for and run again: %llu -> %llu slots in the batch\n", grown.size(), (unsigned long long)alnSlots, (unsigned long long)total);
+		if (keep && total * sizeof(LongAln) > st->longAlns.bytes) {
+			DeviceBuffer larger;
+			LongAln* dLarger = larger.reserve<LongAln>(total);
+			HIP_CHECK(hipMemcpyAsync(dLarger, dLongAlns, alnSlots * sizeof(LongAln), hipMemcpyDeviceToDevice, ls));
+			syncStream(ls);
+			std::swap(st->longAlns.ptr, larger.ptr); std::swap(st->longAlns.bytes, larger.bytes);
+		}
+		dLongAlns = st->longAlns.reserve<LongAln>(total);
+		uint64_t at = alnSlots;
+		for (const auto& g : grown) { hJobs[g.first].alnBegin = (uint32_t)at; hJobs[g.first].alnCap = g.second; at += g.second; }
+		alnSlots = total;
+		HIP_CHECK(hipMemcpyAsync(dLongJobs, hJobs, n * sizeof(LongJob), hipMemcpyHostToDevice, ls));
+		syncStream(ls);
+		return true;
+	}
+
+	bool growLongAlns()   // whole-read pass thread, after the rounds: reads with status 3 get more slots and the pass's cursors are reset; false when there is nothing to grow
+	{
+		std::vector<uint32_t> full;
+		for (uint64_t r = 0; r < n; r++) if (hLongResults[r].status == 3) full.push_back((uint32_t)r);
+		if (full.empty() || !growAlnSlots(full, false)) return false;
 		HIP_CHECK(hipMemsetAsync(dLongCursor, 0, cursorWords * sizeof(unsigned long long), ls));
 		syncStream(ls);
 		return true;
@@ -194,7 +243,7 @@
 					dRoundTrace, cursor + 1, roundTraceBudget, dLongWorkResults, dLongCursor + 8, cursor + 2, EXT_LDS_CAP, cursor + 3);
 			}
 			HIP_CHECK(hipEventRecord(ev1, q));
-			launchLongMerge(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, dCandSeed, dLongWorkResults, dRoundTrace, maxAlignments, dLongState, dLongAlns, dLongCells, dLongCursor, cellBudget);
+			launchLongMerge(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, dCandSeed, dLongWorkResults, dRoundTrace, dLongState, dLongAlns, dLongCells, dLongCursor, cellBudget);
 			lastWork = nWorkItems;
 			// no wait here: the next round's select / order / publish queue up right behind the merge, and the only host round trip per
 			// round is the work count above (with a second wait after the merge the stream drained twice per round, and each refill
@@ -229,7 +278,7 @@
 			// overflow runs the pass again (growLongCells); here the pool grows IN PLACE - a larger block, the cells already written copied over - and only the reads that were
 			// refused run again, in this batch (r5 flagged them and gave the room to the stream's next batch: a read's output depended on its stream's history - ADVICE r5)
 			std::vector<uint32_t> now = redo;
-			for (int attempt = 0; !now.empty(); attempt++) {
+			for (int cellGrowths = 0; !now.empty(); ) {
 				std::vector<LongJob> subJobs(now.size());
 				for (size_t i = 0; i < now.size(); i++) subJobs[i] = hJobs[now[i]];
 				uint64_t lanes = (now.size() + 63) / 64 * 64;
@@ -237,17 +286,24 @@
 				LongReadResult* dSubResults = st->longResultsFallback.reserve<LongReadResult>(now.size());
 				uint8_t* dSlab = st->longScratchFallback.reserve<uint8_t>(lanes * lslab);
 				HIP_CHECK(hipMemcpyAsync(dSubJobs, subJobs.data(), now.size() * sizeof(LongJob), hipMemcpyHostToDevice, ls));
-				launchLongPass(ls, G->dev, G->devTables, G->devIupac, fcfg, dSubJobs, (uint32_t)now.size(), dLongSeeds, R->devBases, R->totalBases, (uint32_t)P->min_cluster_size, maxAlignments,
+				launchLongPass(ls, G->dev, G->devTables, G->devIupac, fcfg, dSubJobs, (uint32_t)now.size(), dLongSeeds, R->devBases, R->totalBases, (uint32_t)P->min_cluster_size,
 					dSlab, lslab, dLongCells, dLongCursor, cellBudget, dLongAlns, dSubResults, dLongCursor + 8);
 				std::vector<LongReadResult> subResults(now.size());
 				HIP_CHECK(hipMemcpyAsync(subResults.data(), dSubResults, now.size() * sizeof(LongReadResult), hipMemcpyDeviceToHost, ls));
 				HIP_CHECK(hipMemcpyAsync(hLongSmall, dLongCursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, ls));
 				syncStream(ls);
-				std::vector<uint32_t> refused;
-				for (size_t i = 0; i < now.size(); i++) { hLongResults[now[i]] = subResults[i]; if (subResults[i].status == 4) refused.push_back(now[i]); }
-				if (refused.empty() || cellPoolPinned || attempt >= 3) break;   // (a pinned pool flags the reads: the caller asked for that much and no more)
+				std::vector<uint32_t> refused, full;
+				for (size_t i = 0; i < now.size(); i++) {
+					hLongResults[now[i]] = subResults[i];
+					if (subResults[i].status == 4) refused.push_back(now[i]);
+					if (subResults[i].status == 3) full.push_back(now[i]);
+				}
+				// reads that ran out of alignment slots here (the rounds never finished them, so nobody knew their count): more slots, and again with the refused ones
+				if (!full.empty() && !growAlnSlots(full, true)) full.clear();
+				if (refused.empty() || cellPoolPinned || cellGrowths >= 3) { now.swap(full); continue; }   // (a pinned pool flags the reads: the caller asked for that much and no more)
 				const uint64_t used = std::min<uint64_t>(hLongSmall[0], cellBudget), next = std::min<uint64_t>(256, st->longCellsPerBase * 2);
-				if (next == st->longCellsPerBase || cellBudgetFor(next) * sizeof(LongCell) > (64ull << 30)) break;
+				if (next == st->longCellsPerBase || cellBudgetFor(next) * sizeof(LongCell) > (64ull << 30)) { now.swap(full); continue; }
+				cellGrowths++;
 				if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc mem] the plain-layout reruns of %zu reads found the merged-trace pool full: %llu -> %llu cells per read base, %.2f G cells kept\n", refused.size(), (unsigned long long)st->longCellsPerBase, (unsigned long long)next, used / 1e9);
 				DeviceBuffer larger;
 				LongCell* dLarger = larger.reserve<LongCell>(cellBudgetFor(next), true);
@@ -260,9 +316,11 @@
 				cellBudget = cellBudgetFor(next);
 				dLongCells = (LongCell*)st->longCells.ptr;
 				now.swap(refused);
+				now.insert(now.end(), full.begin(), full.end());
 			}
 		}
-		if (n) HIP_CHECK(hipMemcpyAsync(hLongAlns, dLongAlns, n * maxAlignments * sizeof(LongAln), hipMemcpyDeviceToHost, ls));
+		hLongAlns = st->hLongAlns.reserve<LongAln>(alnSlots);   // (more than prepareWholeReadPass reserved when reads were given more slots)
+		if (n) HIP_CHECK(hipMemcpyAsync(hLongAlns, dLongAlns, alnSlots * sizeof(LongAln), hipMemcpyDeviceToHost, ls));
 		HIP_CHECK(hipMemcpyAsync(hLongSmall, dLongCursor, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ls));
 		syncStream(ls);
 		return (uint64_t)redo.size();
@@ -281,7 +339,7 @@
 			gl.longSelected.clear();
 			const uint32_t nAln = nAlnOf(r);
 			for (uint32_t a = 0; a < nAln; a++) {
-				gl.longAlns.push_back(hLongAlns[(uint64_t)r * maxAlignments + a]);
+				gl.longAlns.push_back(hLongAlns[(uint64_t)hJobs[r].alnBegin + a]);
 				std::sort(gl.longAlns.begin(), gl.longAlns.end(), [](const LongAln& l, const LongAln& rr) { return l.start < rr.start; });
 			}
 			struct Item { uint32_t start, end, score, index; };
@@ -388,7 +446,8 @@
 		// (:702-703); the alignments found before the throw are lost with the exception.
 		for (uint64_t r = 0; r < n; r++) if (hLongResults[r].status == 1) { hLongResults[r].nAlignments = 0; glue[r].longFailed = true; }
 		// capacities of this library, not of the reference: 2 extension scratch (even with the fallback's four-fold room), 3 more alignments than
-		// maxAlignments, 4 the merged-trace cell pool (GC_TEST_LONG_CELLS_PER_BASE). The read keeps what was found up to there and is flagged.
+		// LONG_ALN_SLOTS_MAX (every smaller number of slots was rerun with more, growAlnSlots), 4 the merged-trace cell pool (GC_TEST_LONG_CELLS_PER_BASE).
+		// The read keeps what was found up to there and is flagged.
 		for (uint64_t r = 0; r < n; r++) if (hLongResults[r].status >= 2 && hLongResults[r].status <= 4) glue[r].capacityExceededLong = true;
 		{
 			std::vector<uint32_t> all(n);
@@ -453,7 +512,7 @@
 						token.unlock();   // the next batch's pass may start; what follows is this batch's own tail
 					};
 					runLongRounds();
-					while (growLongCells()) runLongRounds();   // the cell pool overflowed: again, with room
+					while (growLongCells() || growLongAlns()) runLongRounds();   // the cell pool overflowed, or reads ran out of alignment slots: again, with room
 					longTokenDrop();
 					longTokenTake = nullptr; longTokenDrop = nullptr;
 					// What follows the rounds runs here, beside the tail of the fragment pipeline (which ends 20-30 ms after the pass on cfg2, starved by it), instead of after the

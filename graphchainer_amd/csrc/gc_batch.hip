@@ -31,7 +31,8 @@ struct BatchRun {
 	unsigned long long* dCursors = nullptr;
 	unsigned long long* dCounters = nullptr;
 	// prepareWholeReadPass()
-	uint32_t maxAlignments = 0;
+	uint32_t firstAlnCap = 0;                     // alignment slots every read starts with
+	uint64_t alnSlots = 0;                        // slots of the batch: n * firstAlnCap, plus the new slots of reads that outgrew theirs (growAlnSlots)
 	LongAln* hLongAlns = nullptr;
 	unsigned long long* hLongSmall = nullptr;
 	LongReadResult* hLongResults = nullptr;

@@ -884,7 +884,7 @@ __device__ inline uint32_t endToEndScore(LongAln* mine, uint32_t nAln, uint32_t 
 template <bool BAND>   // BAND: the band controls of cfg (extendSeedT<.., true>)
 __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTables* __restrict__ ct, const uint8_t* __restrict__ iupac, ExtendConfig cfg,
 	const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, const char* __restrict__ bases, uint64_t rcBase,
-	uint32_t minClusterSize, uint32_t maxAlignments, uint8_t* __restrict__ scratch, uint64_t slabBytes,
+	uint32_t minClusterSize, uint8_t* __restrict__ scratch, uint64_t slabBytes,
 	LongCell* __restrict__ cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity,
 	LongAln* __restrict__ alns, LongReadResult* __restrict__ results, unsigned long long* __restrict__ counters)
 {
@@ -943,7 +943,7 @@ __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTab
 			if (stB == EXT_OVERFLOW || stF == EXT_OVERFLOW) { status = 2; break; }
 			bool hasB = stB == EXT_OK, hasF = stF == EXT_OK;
 			if (!hasB && !hasF) continue;   // alignmentFailed()
-			if (nAln >= maxAlignments) { status = 3; break; }
+			if (nAln >= job.alnCap) { status = 3; break; }
 			uint32_t useB = hasB ? (hasF ? nB - 1 : nB) : 0;
 			uint32_t total = useB + (hasF ? nF : 0);
 			unsigned long long base = atomicAdd(cellCursor, (unsigned long long)total);
@@ -1207,7 +1207,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES =
 // One wave per read: the decisions are taken redundantly by all lanes (uniform control flow, lane 0 does the single
 // writes), the trace -> cell conversion - the bulk of the work, ~1.5 cells per read base - runs 64 cells at a time.
 __device__ __forceinline__ void longMergeRead(const DGraph& g, const uint32_t r, const uint32_t lane, const LongJob* __restrict__ jobs, const LongSeed* __restrict__ seeds, const uint32_t* __restrict__ candSeed,
-	const LongWorkResult* __restrict__ results, const unsigned long long* __restrict__ tracePool, uint32_t maxAlignments,
+	const LongWorkResult* __restrict__ results, const unsigned long long* __restrict__ tracePool,
 	LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity)
 {
 	LongState st = state[r];
@@ -1242,7 +1242,7 @@ __device__ __forceinline__ void longMergeRead(const DGraph& g, const uint32_t r,
 		uint32_t nB = rb.traceLen, nF = rf.traceLen;
 		uint32_t useB = hasB ? (hasF ? nB - 1 : nB) : 0;
 		uint32_t total = useB + (hasF ? nF : 0);
-		if (st.nAln >= maxAlignments) { st.status = 3; break; }
+		if (st.nAln >= job.alnCap) { st.status = 3; break; }
 		unsigned long long base = 0;
 		if (lane == 0) base = atomicAdd(cellCursor, (unsigned long long)total);
 		base = __shfl(base, 0);
@@ -1292,13 +1292,13 @@ __device__ __forceinline__ void longMergeRead(const DGraph& g, const uint32_t r,
 }
 
 __global__ void __launch_bounds__(64) k_long_merge(DGraph g, const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, const uint32_t* __restrict__ candSeed,
-	const LongWorkResult* __restrict__ results, const unsigned long long* __restrict__ tracePool, uint32_t maxAlignments,
+	const LongWorkResult* __restrict__ results, const unsigned long long* __restrict__ tracePool,
 	LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity)
 {
 	GC_RAISE_PRIO();
 	const uint32_t r = blockIdx.x;
 	if (r >= nReads) return;
-	longMergeRead(g, r, threadIdx.x, jobs, seeds, candSeed, results, tracePool, maxAlignments, state, alns, cellPool, cellCursor, cellCapacity);
+	longMergeRead(g, r, threadIdx.x, jobs, seeds, candSeed, results, tracePool, state, alns, cellPool, cellCursor, cellCapacity);
 }
 
 // Execution order of a round's work items: longest extensions first (a counting sort over 1024 length classes, one block;
@@ -1532,9 +1532,9 @@ void launchBuildFragmentWork(hipStream_t stream, const DGraph& g, const Fragment
 	if (nFrags) hipLaunchKernelGGL(k_build_fragment_work, dim3((nFrags + 255) / 256), dim3(256), 0, stream, g, frags, fragFirstSeed, nFrags, readSeeds, readOffsets, totalBases, splitLen, fragSeeds, work, results);
 }
 void launchLongMerge(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, const uint32_t* candSeed, const LongWorkResult* results,
-	const unsigned long long* tracePool, uint32_t maxAlignments, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity)
+	const unsigned long long* tracePool, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity)
 {
-	if (nReads) hipLaunchKernelGGL(k_long_merge, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, candSeed, results, tracePool, maxAlignments, state, alns, cellPool, cellCursor, cellCapacity);
+	if (nReads) hipLaunchKernelGGL(k_long_merge, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, candSeed, results, tracePool, state, alns, cellPool, cellCursor, cellCapacity);
 }
 void launchLongOrder(hipStream_t stream, const uint32_t* workLen, const unsigned long long* workCount, uint32_t* order, uint32_t maxLen, uint32_t mode)
 {
@@ -1558,16 +1558,16 @@ void launchLongFinish(hipStream_t stream, uint32_t nReads, const LongState* stat
 uint64_t longSlabBytes(const ExtendConfig& cfg) { return (extendSlabBytes(cfg) + sizeof(TraceCell) * (uint64_t)cfg.maxTrace + 63) & ~63ull; }
 
 void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint8_t* iupac, const ExtendConfig& cfg, const LongJob* jobs, uint32_t nReads,
-	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint32_t maxAlignments, uint8_t* scratch, uint64_t slabBytes,
+	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint8_t* scratch, uint64_t slabBytes,
 	LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, LongAln* alns, LongReadResult* results, unsigned long long* counters)
 {
 	if (nReads == 0) return;
 	uint32_t blocks = (nReads + 63) / 64;
 	if (cfg.bandControls())
-		hipLaunchKernelGGL(k_long_pass<true>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, maxAlignments, scratch, slabBytes,
+		hipLaunchKernelGGL(k_long_pass<true>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, scratch, slabBytes,
 			cellPool, cellCursor, cellCapacity, alns, results, counters);
 	else
-		hipLaunchKernelGGL(k_long_pass<false>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, maxAlignments, scratch, slabBytes,
+		hipLaunchKernelGGL(k_long_pass<false>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, scratch, slabBytes,
 			cellPool, cellCursor, cellCapacity, alns, results, counters);
 }
 

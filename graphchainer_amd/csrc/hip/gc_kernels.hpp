@@ -120,11 +120,12 @@ struct LongSeed {    // a seed in goodness order (after OrderSeeds); 16 bytes: 3
 
 struct LongJob {     // one read
 	uint64_t maskOff;               // word offset of the read's match masks: [strand][base][maskWords]
-	uint32_t maskWords, pad;
+	uint32_t maskWords;
+	uint32_t alnCap;                // alignments this read may keep: the slots at alnBegin (a read that needs more ends with status 3 and runs again with more, gc_batch_long.inc)
 	uint64_t readOff;               // forward bases at bases[readOff..], reverse complement at bases[rcBase + readOff..]
 	uint32_t readLen;
 	uint32_t seedBegin, seedEnd;    // into the LongSeed array
-	uint32_t alnBegin;              // this read's slots in the alignment output (capacity maxAlignments)
+	uint32_t alnBegin;              // this read's slots in the alignment output (capacity alnCap)
 };
 
 struct LongCell {    // merged trace cell in the reference's output coordinates
@@ -207,7 +208,7 @@ void launchChain(hipStream_t stream, const DGraph& g, const ReadChainJob* jobs, 
 	uint32_t fewestSlots = 0);   // fewestSlots: the batch's smallest read in anchor slots (0: unknown) - when no read can fit an LDS class that launch is skipped
 
 void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint8_t* iupac, const ExtendConfig& cfg, const LongJob* jobs, uint32_t nReads,
-	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint32_t maxAlignments, uint8_t* scratch, uint64_t slabBytes,
+	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint8_t* scratch, uint64_t slabBytes,
 	LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, LongAln* alns, LongReadResult* results, unsigned long long* counters);
 uint64_t longSlabBytes(const ExtendConfig& cfg);
 uint64_t longWaveWordsPerLane(const ExtendConfig& cfg);
@@ -220,7 +221,7 @@ void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 	unsigned long long* nextSlot, uint32_t retryStatus = 0, const unsigned long long* nWorkOnDevice = nullptr, uint32_t* capListOut = nullptr, unsigned long long* capCountOut = nullptr);
 	// nWorkOnDevice: `order` is a list whose length only the device knows (the retry list; then nWork is its upper bound)
 void launchLongMerge(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, const uint32_t* candSeed, const LongWorkResult* results,
-	const unsigned long long* tracePool, uint32_t maxAlignments, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity);
+	const unsigned long long* tracePool, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity);
 // ---- path sequences + NW edit distances (gc_editdist.hip)
 struct PathSeqJob {   // one path to spell out as letters
 	uint64_t srcOff;              // first LongCell (whole-read alignment) or first path node (stitched chain)

@@ -207,8 +207,9 @@ typedef struct gc_result {
 	/* per read flags */
 	uint8_t*  failed_assertion;   /* [n_reads] the reference would have thrown on this read */
 	uint8_t*  capacity_exceeded;  /* [n_reads] 1: a capacity of THIS library was exceeded for the read (an extension with more tiles than even the
-	                               *    retry launch holds, more whole-read alignments than max(32, longest read / 512), a full cell pool, an NW band
-	                               *    beyond the kernel's range): its results are incomplete. The reference has no such limits; the batch always
+	                               *    retry launch holds, a full cell pool, an NW band beyond the kernel's range, more than 65 536 whole-read alignments -
+	                               *    a read starts with max(32, longest read / 512) alignment slots and, when it finds more alignments, runs again with
+	                               *    four times as many, up to its number of seeds): its results are incomplete. The reference has no such limits; the batch always
 	                               *    completes and every other read is unaffected. */
 	uint64_t* seeds_extended;     /* [n_reads] fragment pass (stats.seedsExtended, src/Aligner.cpp:705) */
 	uint64_t* seeds_extended_long; /* [n_reads] whole-read pass (AlignmentResult::seedsExtended) */
