@@ -21,6 +21,7 @@ EXPORTED_SYMBOLS = [
     "gc_params_default", "gc_graph_create_from_gfa", "gc_graph_create", "gc_graph_destroy", "gc_graph_num_nodes",
     "gc_graph_size_bp", "gc_graph_array", "gc_graph_trim_host", "gc_seeder_create", "gc_seeder_destroy", "gc_seeder_array",
     "gc_stream_create", "gc_stream_destroy", "gc_reads_upload", "gc_reads_destroy", "gc_align_batch",
+    "gc_seeds_upload", "gc_seeds_destroy", "gc_align_batch_seeded",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
 ]
@@ -98,6 +99,9 @@ def load_library():
     lib.gc_reads_upload.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, _P(C.c_void_p)]
     lib.gc_reads_destroy.argtypes = [C.c_void_p]
     lib.gc_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(GcParams), _P(_P(GcResult))]
+    lib.gc_seeds_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_void_p)]
+    lib.gc_seeds_destroy.argtypes = [C.c_void_p]
+    lib.gc_align_batch_seeded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(GcParams), _P(_P(GcResult))]
     lib.gc_result_free.argtypes = [_P(GcResult)]
     lib.gc_params_default.argtypes = [_P(GcParams)]
     lib.gc_free.argtypes = [C.c_void_p]
@@ -382,6 +386,41 @@ class ReadBatch:
             pass
 
 
+# gc_seed_hit (include/graphchainer_amd.h): SeedHit as a seeder hands it over, src/GraphAlignerWrapper.h:14
+SEED_HIT_DTYPE = np.dtype([("node_id", np.int32), ("node_offset", np.uint32), ("seq_pos", np.uint32), ("match_len", np.uint32), ("raw_goodness", np.uint32), ("reverse", np.uint32)])
+
+
+class SeedBatch:
+    """A read batch's seed hits from the caller's own seeder (a seeds file, MEM matches, filtered minimizer hits), resolved and resident in HBM (gc_seeds_upload).
+    hits_per_read: per read of `batch`, in the order its seeder returned them, a structured array of SEED_HIT_DTYPE or a list of
+    (node_id, node_offset, seq_pos, match_len, raw_goodness, reverse) tuples. Read-only afterwards; may be shared by aligners, like the ReadBatch it belongs to."""
+
+    def __init__(self, graph, batch, hits_per_read):
+        self.lib = load_library()
+        self.handle = C.c_void_p()
+        per_read = []
+        for hits in hits_per_read:
+            if isinstance(hits, np.ndarray) and hits.dtype.names:
+                per_read.append(np.ascontiguousarray(hits.astype(SEED_HIT_DTYPE, copy=False)))
+            else:
+                per_read.append(np.array([tuple(int(x) for x in h) for h in hits], dtype=SEED_HIT_DTYPE))
+        self.offsets = np.zeros(len(per_read) + 1, dtype=np.uint64)
+        self.offsets[1:] = np.cumsum([len(h) for h in per_read], dtype=np.uint64) if per_read else []
+        self.hits = np.concatenate(per_read) if per_read else np.zeros(0, dtype=SEED_HIT_DTYPE)
+        _check(self.lib.gc_seeds_upload(graph.handle, batch.handle, self.hits.ctypes.data if len(self.hits) else None, self.offsets.ctypes.data, len(per_read), C.byref(self.handle)))
+
+    def close(self):
+        if self.handle:
+            self.lib.gc_seeds_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 _RESULT_FIELDS = {
     # name: (count expression)
     "read_seed_off": "n+1", "seed_node": "seeds", "seed_offset": "seeds", "seed_seqpos": "seeds", "seed_goodness": "seeds",
@@ -424,8 +463,9 @@ class BatchResult(dict):
 class Aligner:
     """Batched stand-in for the reference's per-read hot path (src/Aligner.cpp:601-922)."""
 
-    def __init__(self, graph, seeder, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1):
+    def __init__(self, graph, seeder=None, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1):
         """capacities: {field of gc_capacities: value} for the device-side tables (default: all automatic).
+        seeder: the MinimizerSeeder, or None for a caller that brings its own seeds to every batch (align_batch(batch, seeds=SeedBatch(...))).
         device_output: gc_params::device_output - 1 / 2: the final alignments' GAF path and CIGAR text (= / X or M items), + 4: their vg::Path bytes, written
         by the device from the traces it holds; align_batch(gaf_names=...) then needs no keep_traces.
         ramp_bandwidth / max_cells_per_slice: the reference's -B / -C (gc_params; 0 and -1: off)."""
@@ -459,12 +499,17 @@ class Aligner:
         self.stream = C.c_void_p()
         _check(self.lib.gc_stream_create(C.byref(self.stream)))
 
-    def align_batch(self, batch, gaf_names=None, cigar_match_mismatch_merge=False, other_formats=False, formats=None, gam_level=None):
-        """Runs the hot path for a ReadBatch; returns a dict of arrays. With gaf_names (one id per read; needs long_pass and
+    def align_batch(self, batch, seeds=None, gaf_names=None, cigar_match_mismatch_merge=False, other_formats=False, formats=None, gam_level=None):
+        """Runs the hot path for a ReadBatch; returns a dict of arrays. seeds: a SeedBatch made for this batch - its hits replace the seeder's. With gaf_names (one id per read; needs long_pass and
         keep_traces or device_output) the dict also holds "gaf" (bytes: the reference's GAF lines) and "gaf_chained_skipped"; with other_formats also "json" (JSON
         lines) and "gam" (gzip members of framed vg::Alignment messages; gam_level: their zlib level, or GAM_DEVICE_HUFFMAN for the device's deflate)."""
         res = _P(GcResult)()
-        _check(self.lib.gc_align_batch(self.graph.handle, self.seeder.handle, self.stream, batch.handle, C.byref(self.params), C.byref(res)))
+        if seeds is not None:   # the caller's own hits in place of the minimizer seeder (gc_align_batch_seeded; seed_density does not apply)
+            _check(self.lib.gc_align_batch_seeded(self.graph.handle, self.stream, batch.handle, seeds.handle, C.byref(self.params), C.byref(res)))
+        elif self.seeder is None:
+            raise ValueError("this Aligner has no seeder: pass seeds=SeedBatch(graph, batch, hits_per_read)")
+        else:
+            _check(self.lib.gc_align_batch(self.graph.handle, self.seeder.handle, self.stream, batch.handle, C.byref(self.params), C.byref(res)))
         holder = _ResultHolder(self.lib, res)
         if True:
             gaf = None

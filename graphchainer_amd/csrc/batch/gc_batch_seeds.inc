@@ -3,11 +3,11 @@
 	// ---------------- K1 seed lookup, then the glue between it and the extension kernels (on the device; GC_DEVICE_GLUE=0: on the host)
 	void seeds()
 	{
-		// ---------------- K1: seed lookup
-		uint32_t* dTmp = st->tmp.reserve<uint32_t>(R->totalBases);
-		uint2* dMatches = st->matches.reserve<uint2>(R->totalBases);
-		uint32_t* dReadMatchOff = st->readMatchOff.reserve<uint32_t>(n);
-		uint32_t* dReadMatchCount = st->readMatchCount.reserve<uint32_t>(n);
+		// ---------------- K1: seed lookup (not with the caller's own hits, H: they were resolved when they were uploaded, and the glue starts from them)
+		uint32_t* dTmp = H ? nullptr : st->tmp.reserve<uint32_t>(R->totalBases);
+		uint2* dMatches = H ? nullptr : st->matches.reserve<uint2>(R->totalBases);
+		uint32_t* dReadMatchOff = H ? nullptr : st->readMatchOff.reserve<uint32_t>(n);
+		uint32_t* dReadMatchCount = H ? nullptr : st->readMatchCount.reserve<uint32_t>(n);
 		dCursors = st->cursors.reserve<unsigned long long>(8);
 		dCounters = st->counters.reserve<unsigned long long>(8);
 		hSmall = st->hSmall.reserve<unsigned long long>(16 + 2 * n);
@@ -16,23 +16,24 @@
 		HIP_CHECK(hipMemsetAsync(dCursors, 0, 8 * sizeof(unsigned long long), stream));
 		HIP_CHECK(hipMemsetAsync(dCounters, 0, 8 * sizeof(unsigned long long), stream));
 		mark();   // 0
-		launchSeedLookup(stream, S->dev, R->devBases, R->devOffsets, (uint32_t)n, (uint64_t*)dCursors, dReadMatchOff, dReadMatchCount, dMatches, R->totalBases, dTmp, R->totalBases, R->devChunkRead, R->devPacked, R->devInvalid);
+		if (!H) launchSeedLookup(stream, S->dev, R->devBases, R->devOffsets, (uint32_t)n, (uint64_t*)dCursors, dReadMatchOff, dReadMatchCount, dMatches, R->totalBases, dTmp, R->totalBases, R->devChunkRead, R->devPacked, R->devInvalid);
 		mark();   // 1
 		// The glue between the seed lookup and the extension kernels (hit expansion, seed ordering, fragment windows) runs on the device
 		// (gc_seedglue.hip: one wave per read, the reference's three unstable sorts replayed with libstdc++'s own algorithm); GC_DEVICE_GLUE=0
 		// keeps the r2 host path (host/gc_glue.cpp: same results, 1 CPU-second and two bulk transfers per 10 k reads).
-		deviceGlue = !(getenv("GC_DEVICE_GLUE") && atoi(getenv("GC_DEVICE_GLUE")) == 0);
+		deviceGlue = H || !(getenv("GC_DEVICE_GLUE") && atoi(getenv("GC_DEVICE_GLUE")) == 0);   // (gc_align_batch_seeded refuses GC_DEVICE_GLUE=0)
 		if (glue.size() < n) glue.resize(n);
 		gc::KmerMatch* matches = nullptr;
 		tGlue = 0;
 		// what both paths leave behind for the rest of the batch
 		if (deviceGlue) {
 			unsigned long long* dGlueCursors = st->glueCursors.reserve<unsigned long long>(8);
-			uint32_t* dSeedCap = st->glueSeedCap.reserve<uint32_t>(n);
-			uint32_t* dSeedOff = st->glueSeedOff.reserve<uint32_t>(n + 1);
+			// where a read's seeds begin in the per-seed arrays: the running sum of the reads' seed bounds, or the caller's read_hit_off
+			uint32_t* dSeedCap = H ? nullptr : st->glueSeedCap.reserve<uint32_t>(n);
+			uint32_t* dSeedOff = H ? H->devReadHitOff : st->glueSeedOff.reserve<uint32_t>(n + 1);
 			unsigned long long* hGlueSmall = st->hGlueSmall.reserve<unsigned long long>(8);
 			HIP_CHECK(hipMemsetAsync(dGlueCursors, 0, 8 * sizeof(unsigned long long), stream));
-			launchSeedCaps(stream, S->dev, (uint32_t)n, R->devReadInvalid, dMatches, dReadMatchOff, dReadMatchCount, dSeedCap, dSeedOff, dGlueCursors + 5);
+			if (!H) launchSeedCaps(stream, S->dev, (uint32_t)n, R->devReadInvalid, dMatches, dReadMatchOff, dReadMatchCount, dSeedCap, dSeedOff, dGlueCursors + 5);
 			HIP_CHECK(hipMemcpyAsync(hSmall, dCursors, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
 			HIP_CHECK(hipMemcpyAsync(hGlueSmall, dGlueCursors, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
 			// capacity of the per-read window staging: one window per fragment position (host: the lengths are known)
@@ -51,13 +52,13 @@
 			res->kernel_us[0] = elapsedUs(0, 1);
 			res->host_us[2] = nowUs() - tTotal;   // K1 + its transfers, wall
 			tGlue = nowUs();
-			const uint64_t nMatchesDev = hSmall[0], seedCap = hGlueSmall[5];
+			const uint64_t nMatchesDev = hSmall[0], seedCap = H ? H->nHits : hGlueSmall[5];
 			if (nMatchesDev > R->totalBases) throw std::runtime_error("seed lookup overflowed its buffer");
 			if (seedCap >= 0xfffffff0ull) throw std::runtime_error("batch too large: more than 2^32 seed occurrences; split the batch");
 			nSeedsTotal = seedCap;
 			GlueStaging stg;
 			uint32_t** u32s[8] = { &stg.mPos, &stg.mStartLo, &stg.mStartHi, &stg.sSeqPos, &stg.sNode, &stg.sOffset, &stg.sGood, &stg.sCluster };
-			for (int k = 0; k < 8; k++) *u32s[k] = st->glueU32[k].reserve<uint32_t>(seedCap);
+			for (int k = 0; k < 8; k++) *u32s[k] = H && k < 6 ? nullptr : st->glueU32[k].reserve<uint32_t>(seedCap);   // (the caller's hits: only what the glue computes per seed - goodness, cluster size)
 			stg.sortBuf = (GlueElem*)st->glueSort.reserve<uint8_t>(seedCap * glueElemBytes());
 			stg.sortScratch = st->gluePos.reserve<uint32_t>(3 * seedCap + 64 * n + 64);
 			stg.winBuf = st->glueWin.reserve<uint32_t>(4 * winCap);
@@ -69,7 +70,9 @@
 			GlueRead* dGlueOut = st->glueOut.reserve<GlueRead>(n);
 			GlueRead* hGlueOut = st->hGlueOut.reserve<GlueRead>(n);
 			jobs = st->hJobs.reserve<ReadChainJob>(n);
-			launchSeedGlue(stream, S->dev, G->dev, R->devOffsets, (uint32_t)n, R->devReadInvalid, dMatches, dReadMatchOff, dReadMatchCount, dSeedOff, dWinCapOff, P->seed_density,
+			if (H) launchSeedGlueHits(stream, G->dev, R->devOffsets, (uint32_t)n, R->devReadInvalid, H->dev, dSeedOff, dWinCapOff, (uint32_t)P->split_len, (uint32_t)P->split_gap, P->long_pass != 0, stg,
+				st->gluePerRead.reserve<uint32_t>(6 * (n + 1)), dLongSeeds, dReadSeeds, dFrags, dFragFirstSeed, dJobs, dGlueOut, dGlueCursors);
+			else launchSeedGlue(stream, S->dev, G->dev, R->devOffsets, (uint32_t)n, R->devReadInvalid, dMatches, dReadMatchOff, dReadMatchCount, dSeedOff, dWinCapOff, P->seed_density,
 				(uint32_t)P->split_len, (uint32_t)P->split_gap, P->long_pass != 0, stg, st->gluePerRead.reserve<uint32_t>(6 * (n + 1)), dLongSeeds, dReadSeeds, dFrags, dFragFirstSeed, dJobs, dGlueOut, dGlueCursors);
 			if (n) HIP_CHECK(hipMemcpyAsync(hGlueOut, dGlueOut, n * sizeof(GlueRead), hipMemcpyDeviceToHost, stream));
 			if (n) HIP_CHECK(hipMemcpyAsync(jobs, dJobs, n * sizeof(ReadChainJob), hipMemcpyDeviceToHost, stream));

@@ -1,6 +1,7 @@
 // The C entry points of include/graphchainer_amd.h except gc_align_batch (gc_batch.hip): graphs, seeders, index cache, read batches, streams, edit distances, output formats.
 #include "gc_runtime.hpp"
 #include "host/gc_stageclock.hpp"
+#include "hip/gc_seedhits_core.hpp"
 #include <malloc.h>
 
 extern "C" {
@@ -935,6 +936,74 @@ int gc_reads_upload(const char* bases, const uint64_t* offsets, uint64_t n, gc_r
 	return GC_OK;
 }
 void gc_reads_destroy(gc_reads* r) { delete r; }
+
+// ---- seed hits from the host's own seeder -------------------------------------------------------------------
+int gc_seeds_upload(const gc_graph* G, const gc_reads* R, const gc_seed_hit* hits, const uint64_t* read_hit_off, uint64_t n_reads, gc_seeds** out)
+{
+	static_assert(sizeof(gc_seed_hit) == sizeof(SeedHit) && sizeof(SeedHit) == 24, "gc_seed_hit is what k_seed_resolve reads");
+	// host checks first: a malformed call is GC_ERR_INVALID whether or not a device is present
+	if (!G || !R || !read_hit_off || !out) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	if (n_reads != R->offsets.size() - 1) return fail(GC_ERR_INVALID, "gc_seeds_upload: n_reads differs from the read batch's");
+	if (read_hit_off[0] != 0) return fail(GC_ERR_INVALID, "gc_seeds_upload: read_hit_off must start at 0");
+	for (uint64_t r = 0; r < n_reads; r++) if (read_hit_off[r + 1] < read_hit_off[r]) return fail(GC_ERR_INVALID, "gc_seeds_upload: read_hit_off decreases at read " + std::to_string(r));
+	const uint64_t nHits = read_hit_off[n_reads];
+	if (nHits >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_seeds_upload: 2^32 hits or more; split the batch");
+	if (nHits && !hits) return fail(GC_ERR_INVALID, "null argument");
+	for (uint64_t r = 0; r < n_reads; r++) {
+		// the seed goodness is a 32-bit word: a cluster's matching base pairs are at most its first seed's match_len plus the read positions it spans, and any hit of the cluster
+		// adds its own raw goodness to them (src/GraphAligner.h:273-287)
+		const uint64_t len = R->offsets[r + 1] - R->offsets[r];
+		uint64_t longest = 0, best = 0, bestAt = 0;
+		for (uint64_t i = read_hit_off[r]; i < read_hit_off[r + 1]; i++) {
+			if (hits[i].match_len > 0x7fffffffu) return fail(GC_ERR_INVALID, "gc_seeds_upload: read " + std::to_string(r) + " hit " + std::to_string(i - read_hit_off[r]) + ": match_len of 2^31 or more");
+			longest = std::max<uint64_t>(longest, hits[i].match_len);
+			if (hits[i].raw_goodness >= best) { best = hits[i].raw_goodness; bestAt = i; }
+		}
+		if (longest + len + best > 0xffffffffull)
+			return fail(GC_ERR_INVALID, "gc_seeds_upload: read " + std::to_string(r) + " hit " + std::to_string(bestAt - read_hit_off[r]) + ": raw_goodness too large for the 32-bit seed goodness (match_len + read length + raw_goodness must stay below 2^32)");
+	}
+	gc_seeds* H = new gc_seeds();
+	int rc = guarded([&]() {
+		requireDevice();
+		HIP_CHECK(hipGetDevice(&H->device));
+		H->nHits = nHits;
+		H->readOffsets = R->offsets;
+		std::vector<uint32_t> off32(n_reads + 1);
+		for (uint64_t r = 0; r <= n_reads; r++) off32[r] = (uint32_t)read_hit_off[r];
+		size_t at = 0;
+		auto part = [&](size_t bytes) { const size_t here = at; at += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return here; };
+		const size_t oOff = part((n_reads + 1) * sizeof(uint32_t)), oArrays = part(5 * nHits * sizeof(uint32_t)), oBad = part(sizeof(unsigned long long)), oHits = part(nHits * sizeof(SeedHit));
+		HIP_CHECK(hipMalloc(&H->block, at));
+		char* D = (char*)H->block;
+		H->devReadHitOff = (uint32_t*)(D + oOff);
+		uint32_t* arrays = (uint32_t*)(D + oArrays);
+		H->dev = SeedHitArrays { arrays, arrays + nHits, arrays + 2 * nHits, arrays + 3 * nHits, arrays + 4 * nHits };
+		unsigned long long* dBad = (unsigned long long*)(D + oBad);
+		SeedHit* dHits = (SeedHit*)(D + oHits);   // (the raw records stay in the block's tail: 24 B per hit beside the 20 B the glue reads)
+		hipStream_t q = threadStream(H->device);
+		unsigned long long bad = ~0ull;
+		HIP_CHECK(hipMemcpyAsync(H->devReadHitOff, off32.data(), (n_reads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+		HIP_CHECK(hipMemcpyAsync(dBad, &bad, sizeof(bad), hipMemcpyHostToDevice, q));
+		if (nHits) HIP_CHECK(hipMemcpyAsync(dHits, hits, nHits * sizeof(SeedHit), hipMemcpyHostToDevice, q));
+		const SeedLookup lookup { G->dev.origSize, G->dev.lookupOff, G->dev.lookup, G->dev.nodeOffset, (uint32_t)G->hOrigSize.size() };
+		launchSeedResolve(q, lookup, dHits, nHits, H->devReadHitOff, (uint32_t)n_reads, R->devOffsets, H->dev, dBad);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipMemcpyAsync(&bad, dBad, sizeof(bad), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		if (bad != ~0ull) {
+			const uint64_t i = bad >> 2;
+			const uint64_t r = (uint64_t)(std::upper_bound(read_hit_off, read_hit_off + n_reads + 1, i) - read_hit_off) - 1;
+			const char* what[] = { "", "no such node in the graph", "node_offset is not inside the original node", "seq_pos is not inside the read" };
+			return fail(GC_ERR_INVALID, "gc_seeds_upload: read " + std::to_string(r) + " hit " + std::to_string(i - read_hit_off[r]) + ": " + what[bad & 3]);
+		}
+		return (int)GC_OK;
+	});
+	if (rc != GC_OK) { delete H; return rc; }
+	*out = H;
+	return GC_OK;
+}
+void gc_seeds_destroy(gc_seeds* s) { delete s; }
 
 // ---- the batch pipeline -----------------------------------------------------------------------------------
 

@@ -498,6 +498,17 @@ struct gc_reads {
 	~gc_reads() { g_readDeviceBlocks.put(deviceBlock, deviceBlockBytes, device); }
 };
 
+// a read batch's seed hits from the host's own seeder (gc_seeds_upload), resolved by k_seed_resolve: read-only afterwards, shared by streams
+struct gc_seeds {
+	int device = 0;
+	uint64_t nHits = 0;
+	std::vector<uint64_t> readOffsets;     // the read batch's offsets [n+1]: the hits' seq_pos were checked against these lengths
+	uint32_t* devReadHitOff = nullptr;     // [n+1] the caller's read_hit_off: where a read's seeds begin in every per-seed array of the batch
+	SeedHitArrays dev {};                  // [nHits] each, carved from one allocation
+	void* block = nullptr;
+	~gc_seeds() { if (block) (void)hipFree(block); }
+};
+
 struct StitchedPath { std::vector<uint32_t> nodes; uint32_t firstOffset = 0, lastOffset = 0; uint64_t cells = 0; };
 
 struct ReadGlue {

@@ -169,6 +169,17 @@ void launchSeedGlue(hipStream_t stream, const SeedIndex& idx, const DGraph& g, c
 	const uint32_t* readMatchCount, const uint32_t* readSeedOff, const uint32_t* winCapOff, double density, uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st,
 	uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed, ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors);
 uint64_t glueElemBytes();
+// ---- caller-supplied seed hits (gc_seeds_upload, gc_align_batch_seeded; gc_seedhits.hip) ----
+struct SeedHit;
+struct SeedLookup;
+struct SeedHitArrays { uint32_t *node, *offset, *seqPos, *matchLen, *raw; };   // a batch's resolved hits in the caller's order: split node, offset in it, SeedHit::seqPos / matchLen / rawSeedGoodness
+// one hit per lane: GetUnitigNode + the split node's offset subtracted, bounds checked first; *firstBad (preset to all ones) ends as the smallest (hit index << 2 | SeedHitStatus) of the refused hits
+void launchSeedResolve(hipStream_t stream, const SeedLookup& lookup, const SeedHit* hits, uint64_t nHits, const uint32_t* readHitOff, uint32_t nReads, const uint64_t* readOff, const SeedHitArrays& out,
+	unsigned long long* firstBad);
+// k_seed_glue from resolved hits instead of minimizer matches: readSeedOff = the caller's read_hit_off
+void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* readOff, uint32_t nReads, const uint8_t* invalidRead, const SeedHitArrays& hits, const uint32_t* readSeedOff, const uint32_t* winCapOff,
+	uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st, uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed,
+	ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors);
 // test entry: arrays of (key << 32 | index) elements sorted by key with the wave-cooperative replay of std::sort (gc_stdsort_wave.hpp); scratch: 3 words per element + 64 per array
 void launchTestStdSort(hipStream_t stream, unsigned long long* elems, const uint64_t* off, uint32_t nArrays, uint32_t* scratch, long depthLimit);
 

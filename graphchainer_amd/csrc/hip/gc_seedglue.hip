@@ -12,6 +12,7 @@
 #include "gc_kernels.hpp"
 #include "gc_stdsort.hpp"
 #include "gc_stdsort_wave.hpp"
+#include "gc_seedhits_core.hpp"
 #include <climits>
 
 namespace gcdev {
@@ -28,6 +29,15 @@ struct ByChainDiagonal {
 		return dl < dr;
 	}
 };
+// caller-supplied hits: (chain, diagonal, then the caller's index) - no two elements compare equal, so the order is the one a stable sort of the hits gives
+struct ByChainDiagonalId {
+	__host__ __device__ __forceinline__ bool operator()(const GlueElem& l, const GlueElem& r) const
+	{
+		if (l.k0 != r.k0) return l.k0 < r.k0;
+		const uint64_t dl = (uint64_t)l.k1lo | ((uint64_t)l.k1hi << 32), dr = (uint64_t)r.k1lo | ((uint64_t)r.k1hi << 32);
+		return dl != dr ? dl < dr : l.id < r.id;
+	}
+};
 struct U32Less { __host__ __device__ __forceinline__ bool operator()(uint32_t l, uint32_t r) const { return l < r; } };
 struct HiLess { __host__ __device__ __forceinline__ bool operator()(uint64_t l, uint64_t r) const { return (uint32_t)(l >> 32) < (uint32_t)(r >> 32); } };   // (key << 32 | id) elements, compared by key alone
 
@@ -39,6 +49,8 @@ struct GlueCounts { uint32_t *nSeeds, *nFrags, *nSlots, *failed; };
 
 // Any-order sorts (the clusters' (chain, diagonal) order and the positions inside a cluster: only the sorted VALUES matter) run on all 64 lanes:
 // bitonic sort of the structure-of-arrays (k0, k2:k1, id) in LDS, m = the power of two >= n (the tail is padded with maximal keys by the caller).
+// TIE_BY_ID: elements with equal keys are ordered by id (the order is then the same whatever the network does with equal keys)
+template <bool TIE_BY_ID = false>
 __device__ __forceinline__ void glueBitonic(glue_lds_u32* k0, glue_lds_u32* k1, glue_lds_u32* k2, glue_lds_u32* id, uint32_t m, uint32_t lane)
 {
 	for (uint32_t k = 2; k <= m; k <<= 1) {
@@ -47,9 +59,11 @@ __device__ __forceinline__ void glueBitonic(glue_lds_u32* k0, glue_lds_u32* k1, 
 				const uint32_t x = i ^ j;
 				if (x > i) {
 					const uint32_t a0 = k0[i], a1 = k1[i], a2 = k2[i], b0 = k0[x], b1 = k1[x], b2 = k2[x];
-					const bool aGreater = a0 != b0 ? a0 > b0 : (a2 != b2 ? a2 > b2 : a1 > b1);
+					bool aGreater = a0 != b0 ? a0 > b0 : (a2 != b2 ? a2 > b2 : a1 > b1);
 					const bool ascending = (i & k) == 0;
-					if (aGreater == ascending && !(a0 == b0 && a1 == b1 && a2 == b2)) {
+					bool same = a0 == b0 && a1 == b1 && a2 == b2;
+					if (TIE_BY_ID && same) { const uint32_t ai = id[i], bi = id[x]; aGreater = ai > bi; same = ai == bi; }
+					if (aGreater == ascending && !same) {
 						const uint32_t ai = id[i], bi = id[x];
 						k0[i] = b0; k1[i] = b1; k2[i] = b2; id[i] = bi;
 						k0[x] = a0; k1[x] = a1; k2[x] = a2; id[x] = ai;
@@ -88,8 +102,9 @@ __device__ __forceinline__ void glueWindows(Key key, uint32_t nS, uint32_t len, 
 // The same windows by all lanes (r5). The two pointers of src/Aligner.cpp:672-679 do not depend on the window before: sr(l) = the seeds with key + matchLen <= l + splitLen - an upper
 // bound in the sorted keys - and sl(l) = min(sr(l), first seed with key >= l): the pointer sl only ever waits at sr, and what it waits for is monotone in l. So a lane takes a
 // fragment position, two binary searches give its window, and ballots / wave scans number the non-empty windows and their anchor slots in position order.
-template <class Key>
-__device__ __forceinline__ void glueWindowsWave(Key key, uint32_t nS, uint32_t len, uint32_t splitLen, uint32_t splitGap, uint32_t matchLen, uint32_t* win, uint32_t lane,
+// end(i) = the running maximum of key + matchLen up to seed i (with one matchLen for all seeds: key(i) + matchLen itself) - see seedWindow, gc_seedhits_core.hpp.
+template <class Key, class End>
+__device__ __forceinline__ void glueWindowsWave(Key key, End end, uint32_t nS, uint32_t len, uint32_t splitLen, uint32_t splitGap, uint32_t* win, uint32_t lane,
 	uint32_t& nFout, uint32_t& slotsOut, unsigned long long& budgetOut, uint32_t& widestOut)
 {
 	uint32_t nF = 0, slots = 0, widest = 0;
@@ -99,14 +114,7 @@ __device__ __forceinline__ void glueWindowsWave(Key key, uint32_t nS, uint32_t l
 		const uint64_t f = f0 + lane;
 		const uint64_t l = f * splitGap;
 		uint32_t sl = 0, sr = 0;
-		if (f < nPos) {
-			uint32_t lo = 0, hi = nS;   // first seed with key + matchLen > l + splitLen
-			while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)key(mid) + matchLen <= l + splitLen) lo = mid + 1; else hi = mid; }
-			sr = lo;
-			lo = 0; hi = sr;            // first seed with key >= l (not beyond sr)
-			while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)key(mid) < l) lo = mid + 1; else hi = mid; }
-			sl = lo;
-		}
+		if (f < nPos) seedWindow(end, key, nS, l, splitLen, sl, sr);   // sr: first seed with end > l + splitLen; sl: first seed with key >= l (not beyond sr)
 		const bool has = sl < sr;
 		const unsigned long long which = __ballot(has);
 		const uint32_t mine = sr - sl;
@@ -162,13 +170,21 @@ __device__ __forceinline__ void glueDensityCut(uint32_t nM, uint64_t maxHits, ui
 // (no LDS image, so as many blocks per CU as wave slots) takes the rest on HBM arrays (50 kb reads carry ~2 200 seeds). The serial sorts are bound by
 // the latency of a lane's dependent accesses, so what counts for the long reads is how many run at once: a 4096-element LDS image (96 KB, one block
 // per CU) measured 820 ms per 2 000 x 50 kb reads against 231 ms for the HBM arrays at six blocks per CU.
-template <uint32_t GLUE_LDS_ELEMS, uint32_t SKIP_UP_TO>
+// HITS (gc_align_batch_seeded): the read's seeds are the caller's resolved hits (k_seed_resolve, gc_seedhits.hip) in the caller's order instead of expanded minimizer matches - no
+// addMinimizers; every seed has a matchLen of its own (the clusters' matching base pairs, the fragment windows), and a hit with matchLen < 2 fails the read as the reference's
+// assertion does (src/GraphAligner.h:280). readSeedOff is then the caller's read_hit_off. Where the reference's two cluster sorts leave the order of equal keys to std::sort - which
+// only matters when hits of one cluster share a read position and differ in matchLen - the order here is that of a stable sort (by diagonal, then by position).
+template <uint32_t GLUE_LDS_ELEMS, uint32_t SKIP_UP_TO, bool HITS = false>
 __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const uint64_t* __restrict__ readOff, uint32_t nReads, const uint8_t* __restrict__ invalidRead,
 	const uint2* __restrict__ matches, const uint32_t* __restrict__ readMatchOff, const uint32_t* __restrict__ readMatchCount, const uint32_t* __restrict__ readSeedOff, const uint32_t* __restrict__ winCapOff,
 	double density, uint32_t splitLen, uint32_t splitGap, uint32_t longPass, GlueStaging st,
-	LongSeed* __restrict__ longSeeds, FragSeed* __restrict__ readSeeds, GlueCounts counts, unsigned long long* __restrict__ cursors)
+	LongSeed* __restrict__ longSeeds, FragSeed* __restrict__ readSeeds, GlueCounts counts, unsigned long long* __restrict__ cursors, SeedHitArrays hits = SeedHitArrays {})
 {
 	GC_RAISE_PRIO();
+	// per seed, expansion order (HITS: the caller's order; read-only and shared between streams - what the glue computes per seed goes to the staging as before)
+	const uint32_t* const sSeqPos = HITS ? hits.seqPos : st.sSeqPos;
+	const uint32_t* const sNode = HITS ? hits.node : st.sNode;
+	const uint32_t* const sOffset = HITS ? hits.offset : st.sOffset;
 	// one LDS image, reused along the read's pass: [0] k0 (offsets of the kept hits / chain / cluster id), [1] k1, [2] k2 (diagonal; the 8-byte
 	// elements of the three order-critical sorts alias these two), [3] id, [4] cluster sums (first: cluster ids in sorted order), [5] cluster sizes
 	__shared__ uint32_t lds[6 * GLUE_LDS_ELEMS];
@@ -188,9 +204,10 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 	for (uint32_t r = blockIdx.x; r < nReads; r += gridDim.x) {
 		__syncthreads();
 		const uint32_t len = (uint32_t)(readOff[r + 1] - readOff[r]);
-		const uint32_t nM = invalidRead[r] ? 0u : readMatchCount[r];
-		const uint32_t mOff = readMatchOff[r], sOff = readSeedOff[r];
-		const uint32_t cap = readSeedOff[r + 1] - sOff;   // bound of the read's seed list: the sum of its hits' occurrence counts
+		uint32_t nM = invalidRead[r] ? 0u : (HITS ? 0u : readMatchCount[r]);
+		const uint32_t mOff = HITS ? 0u : readMatchOff[r], sOff = readSeedOff[r];
+		const uint32_t cap = readSeedOff[r + 1] - sOff;   // bound of the read's seed list: the sum of its hits' occurrence counts (HITS: the read's hits, all of them seeds)
+		if constexpr (HITS) nM = invalidRead[r] ? 0u : cap;
 		if (SKIP_UP_TO ? cap <= SKIP_UP_TO : cap > GLUE_LDS_ELEMS) continue;   // (the other instantiation's read)
 		uint32_t* const win = st.winBuf + 4ull * winCapOff[r];
 		uint32_t nS = 0, nF = 0, slots = 0, widest = 0;
@@ -200,6 +217,8 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 		if (density == -1) maxHits = ~0ull;
 		if (nM > 0 && cap <= GLUE_LDS_ELEMS) {
 			// ================= the usual case: everything the serial parts touch is in LDS
+			if constexpr (HITS) nS = nM;
+			else {
 			// ---- addMinimizers: count and first occurrence of every hit (matches come in read order)
 			for (uint32_t i = lane; i < nM; i += 64) {
 				const uint2 m = matches[mOff + i];
@@ -233,6 +252,7 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 			}
 			__threadfence();
 			__syncthreads();
+			}
 			if (nS > 0) {
 				// ---- orderSeedsByChaining: diagonal of every seed on its chain (:245-262)
 				uint32_t m = 2;
@@ -240,9 +260,10 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 				uint32_t bad = 0;
 				for (uint32_t s = lane; s < m; s += 64) {
 					if (s < nS) {
-						const uint32_t node = st.sNode[sOff + s], pos = st.sSeqPos[sOff + s];
-						const uint64_t base = g.chainApproxPos[node] + st.sOffset[sOff + s];
+						const uint32_t node = sNode[sOff + s], pos = sSeqPos[sOff + s];
+						const uint64_t base = g.chainApproxPos[node] + sOffset[sOff + s];
 						if (base < pos) bad = 1;   // the reference asserts (:259)
+						if (HITS && hits.matchLen[sOff + s] < 2) bad = 1;   // ... and here (:280, thisEnd > thisStart)
 						const uint64_t diagonal = base - pos;
 						eK0[s] = g.chainNumber[node]; eK1[s] = (uint32_t)diagonal; eK2[s] = (uint32_t)(diagonal >> 32); eId[s] = s;
 					} else { eK0[s] = 0xffffffffu; eK1[s] = 0xffffffffu; eK2[s] = 0xffffffffu; eId[s] = 0xffffffffu; }
@@ -252,7 +273,7 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 				if (!failed) {
 					// clusters: same chain, neighbouring diagonals at most 100 apart (:263-292). The reference builds them with a hash map and two unstable
 					// sorts; a cluster's goodness depends only on the multiset of its seeds' read positions, so any sort by (chain, diagonal) gives the same values
-					glueBitonic(eK0, eK1, eK2, eId, m, lane);
+					glueBitonic<HITS>(eK0, eK1, eK2, eId, m, lane);
 					if (lane == 0) {
 						uint32_t cid = 0, prevChain = eK0[0];
 						uint64_t prevDiag = (uint64_t)eK1[0] | ((uint64_t)eK2[0] << 32);
@@ -268,7 +289,8 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					}
 					__syncthreads();
 					const uint32_t nClusters = shared[2];
-					for (uint32_t i = lane; i < nS; i += 64) { eK0[i] = sSum[i]; eK1[i] = st.sSeqPos[sOff + eId[i]]; eK2[i] = 0; }
+					// (HITS: by (cluster, position, place in the order above); the position is then in eK2)
+					for (uint32_t i = lane; i < nS; i += 64) { const uint32_t pos = sSeqPos[sOff + eId[i]]; eK0[i] = sSum[i]; eK1[i] = HITS ? i : pos; eK2[i] = HITS ? pos : 0; }
 					__syncthreads();
 					// positions inside every cluster in ascending order, then a cluster's matching base pairs: a seed adds the part of its k-mer that
 					// the previous one (by position) does not cover (:270-284)
@@ -278,6 +300,11 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					for (uint32_t i = lane; i < nS; i += 64) {
 						const uint32_t c = eK0[i];
 						uint32_t add = matchLen - 1;
+						if constexpr (HITS) {   // signed, as the reference has it (:277-281): seqPos - matchLen + 1 may be negative
+							const int thisEnd = (int)eK2[i], thisStart = thisEnd - (int)hits.matchLen[sOff + eId[i]] + 1;
+							const int lastEnd = i > 0 && eK0[i - 1] == c ? (int)eK2[i - 1] : INT_MIN;
+							add = (uint32_t)(thisEnd - (thisStart > lastEnd ? thisStart : lastEnd));
+						} else
 						if (i > 0 && eK0[i - 1] == c) { const uint32_t d = eK1[i] - eK1[i - 1]; add = d < add ? d : add; }
 						atomicAdd((uint32_t*)&lds[4 * GLUE_LDS_ELEMS + c], add);
 						atomicAdd((uint32_t*)&lds[5 * GLUE_LDS_ELEMS + c], 1u);
@@ -287,7 +314,7 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					for (uint32_t i = lane; i < nS; i += 64) {
 						const uint32_t c = eK0[i], s = sOff + eId[i];
 						const uint32_t size = sCnt[c];
-						st.sGood[s] = sSum[c] + st.sGood[s];
+						st.sGood[s] = sSum[c] + (HITS ? hits.raw[s] : st.sGood[s]);
 						st.sCluster[s] = size < 65535 ? size : 65535;
 					}
 					__threadfence();
@@ -301,10 +328,10 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					// the whole-read pass's seed list, and the next sort's keys (it runs on this order, src/Aligner.cpp:667)
 					for (uint32_t i = lane; i < nS; i += 64) {
 						const uint32_t id = (uint32_t)s64[i], s = sOff + id;
-						const uint32_t pos = st.sSeqPos[s];
+						const uint32_t pos = sSeqPos[s];
 						if (longPass) {
 							LongSeed ls;
-							ls.node = st.sNode[s]; ls.seqPos = pos; ls.goodness = st.sGood[s]; ls.clusterSize = (uint16_t)st.sCluster[s]; ls.offset = (uint8_t)st.sOffset[s]; ls.pad = 0;
+							ls.node = sNode[s]; ls.seqPos = pos; ls.goodness = st.sGood[s]; ls.clusterSize = (uint16_t)st.sCluster[s]; ls.offset = (uint8_t)sOffset[s]; ls.pad = 0;
 							longSeeds[sOff + i] = ls;
 						}
 						s64[i] = ((uint64_t)pos << 32) | id;
@@ -313,9 +340,24 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					gcsort::gcStdSortWave<uint64_t>(s64, nS, HiLess(), sortScratch, lane);   // seeds by read position, the reference's unstable sort (src/Aligner.cpp:667)
 					for (uint32_t i = lane; i < nS; i += 64) {
 						const uint32_t s = sOff + (uint32_t)s64[i];
-						readSeeds[sOff + i] = FragSeed { st.sNode[s], st.sOffset[s], st.sSeqPos[s], st.sGood[s] };   // (pad carries the goodness: the seed_* result arrays)
+						readSeeds[sOff + i] = FragSeed { sNode[s], sOffset[s], sSeqPos[s], st.sGood[s] };   // (pad carries the goodness: the seed_* result arrays)
 					}
-					glueWindowsWave([&](uint32_t i) { return (uint32_t)(s64[i] >> 32); }, nS, len, splitLen, splitGap, matchLen, win, lane, nF, slots, budget, widest);
+					if constexpr (HITS) {
+						// the running maximum of the seeds' ends, in the idle first array: one wave scan per 64 seeds
+						uint32_t carry = 0;
+						for (uint32_t base = 0; base < nS; base += 64) {
+							const uint32_t i = base + lane;
+							uint32_t v = 0;
+							if (i < nS) { const uint64_t e = s64[i]; v = (uint32_t)(e >> 32) + hits.matchLen[sOff + (uint32_t)e]; }
+							for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d); v = seedMaxScanStep(v, o, lane, d); }
+							v = v > carry ? v : carry;
+							if (i < nS) eK0[i] = v;
+							carry = __shfl(v, 63);
+						}
+						__syncthreads();
+						glueWindowsWave([&](uint32_t i) { return (uint32_t)(s64[i] >> 32); }, [&](uint32_t i) { return (uint32_t)eK0[i]; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
+					} else
+					glueWindowsWave([&](uint32_t i) { return (uint32_t)(s64[i] >> 32); }, [&](uint32_t i) { return (uint64_t)(uint32_t)(s64[i] >> 32) + matchLen; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
 				}
 			}
 		} else if (nM > 0) {
@@ -324,6 +366,8 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 			// read on a 960 Mbp graph)
 			GlueElem* a = st.sortBuf + sOff;
 			uint32_t* const scratch = st.sortScratch + 3ull * sOff + 64ull * r;   // waveSortScratchWords(cap) <= 3 cap + 64; between the sorts: cluster sums and sizes
+			if constexpr (HITS) nS = nM;
+			else {
 			for (uint32_t i = lane; i < nM; i += 64) {
 				const uint2 m = matches[mOff + i];
 				const uint64_t start = idx.startPos[m.y];
@@ -355,12 +399,14 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 			}
 			__threadfence_block();
 			__syncthreads();
+			}
 			if (nS > 0) {
 				uint32_t bad = 0;
 				for (uint32_t s = lane; s < nS; s += 64) {
-					const uint32_t node = st.sNode[sOff + s], pos = st.sSeqPos[sOff + s];
-					const uint64_t base = g.chainApproxPos[node] + st.sOffset[sOff + s];
+					const uint32_t node = sNode[sOff + s], pos = sSeqPos[sOff + s];
+					const uint64_t base = g.chainApproxPos[node] + sOffset[sOff + s];
 					if (base < pos) bad = 1;
+					if (HITS && hits.matchLen[sOff + s] < 2) bad = 1;
 					const uint64_t diagonal = base - pos;
 					a[s] = GlueElem { g.chainNumber[node], (uint32_t)diagonal, (uint32_t)(diagonal >> 32), s };
 				}
@@ -370,7 +416,8 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 				if (!failed) {
 					// clusters (:263-292): same chain, neighbouring diagonals at most 100 apart. A cluster's goodness depends only on the multiset of its seeds' read positions, so
 					// any sort by (chain, diagonal) and any sort by (cluster, position) give the reference's values (the LDS path uses bitonic sorts for the same reason)
-					gcsort::gcStdSortWave<GlueElem>(a, nS, ByChainDiagonal(), scratch, lane);
+					if constexpr (HITS) gcsort::gcStdSortWave<GlueElem>(a, nS, ByChainDiagonalId(), scratch, lane);
+					else gcsort::gcStdSortWave<GlueElem>(a, nS, ByChainDiagonal(), scratch, lane);
 					uint32_t cidBefore = 0, tailChain = 0;
 					uint64_t tailDiag = 0;
 					for (uint32_t base = 0; base < nS; base += 64) {
@@ -385,7 +432,7 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 						const unsigned long long opened = __ballot(opens);
 						const uint32_t cid = cidBefore + (uint32_t)__popcll(opened & ((2ull << lane) - 1ull));
 						tailChain = __shfl(x.k0, 63); tailDiag = __shfl(dx, 63);   // (before the elements are overwritten: the next 64 compare with this one's last)
-						if (i < nS) a[i] = GlueElem { cid, st.sSeqPos[sOff + x.id], 0, x.id };
+						if (i < nS) a[i] = HITS ? GlueElem { cid, i, sSeqPos[sOff + x.id], x.id } : GlueElem { cid, sSeqPos[sOff + x.id], 0, x.id };   // (HITS: position, then the place in the order above)
 						cidBefore += (uint32_t)__popcll(opened);
 					}
 					const uint32_t nClusters = cidBefore + 1;
@@ -401,6 +448,12 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					for (uint32_t i = lane; i < nS; i += 64) {
 						const GlueElem x = a[i];
 						uint32_t add = matchLen - 1;
+						if constexpr (HITS) {
+							const int thisEnd = (int)x.k1hi, thisStart = thisEnd - (int)hits.matchLen[sOff + x.id] + 1;
+							int lastEnd = INT_MIN;
+							if (i > 0) { const GlueElem y = a[i - 1]; if (y.k0 == x.k0) lastEnd = (int)y.k1hi; }
+							add = (uint32_t)(thisEnd - (thisStart > lastEnd ? thisStart : lastEnd));
+						} else
 						if (i > 0) { const GlueElem y = a[i - 1]; if (y.k0 == x.k0) { const uint32_t d = x.k1lo - y.k1lo; add = d < add ? d : add; } }
 						atomicAdd(&cSum[x.k0], add);
 						atomicAdd(&cCnt[x.k0], 1u);
@@ -410,7 +463,7 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					for (uint32_t i = lane; i < nS; i += 64) {
 						const GlueElem x = a[i];
 						const uint32_t s = sOff + x.id, size = cCnt[x.k0];
-						st.sGood[s] = cSum[x.k0] + st.sGood[s];
+						st.sGood[s] = cSum[x.k0] + (HITS ? hits.raw[s] : st.sGood[s]);
 						st.sCluster[s] = size < 65535 ? size : 65535;
 					}
 					__threadfence_block();
@@ -427,21 +480,34 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 						const uint32_t s = sOff + a[i].id;
 						if (longPass) {
 							LongSeed ls;
-							ls.node = st.sNode[s]; ls.seqPos = st.sSeqPos[s]; ls.goodness = st.sGood[s]; ls.clusterSize = (uint16_t)st.sCluster[s]; ls.offset = (uint8_t)st.sOffset[s]; ls.pad = 0;
+							ls.node = sNode[s]; ls.seqPos = sSeqPos[s]; ls.goodness = st.sGood[s]; ls.clusterSize = (uint16_t)st.sCluster[s]; ls.offset = (uint8_t)sOffset[s]; ls.pad = 0;
 							longSeeds[sOff + i] = ls;
 						}
-						a[i].k0 = st.sSeqPos[s];
+						a[i].k0 = sSeqPos[s];
 					}
 					__threadfence_block();
 					__syncthreads();
 					gcsort::gcStdSortWave<GlueElem>(a, nS, ByK0(), scratch, lane);   // seeds by read position (src/Aligner.cpp:667)
 					for (uint32_t i = lane; i < nS; i += 64) {
 						const uint32_t s = sOff + a[i].id;
-						readSeeds[sOff + i] = FragSeed { st.sNode[s], st.sOffset[s], st.sSeqPos[s], st.sGood[s] };
+						readSeeds[sOff + i] = FragSeed { sNode[s], sOffset[s], sSeqPos[s], st.sGood[s] };
+					}
+					if constexpr (HITS) {   // the running maximum of the seeds' ends, in the elements' second word
+						uint32_t carry = 0;
+						for (uint32_t base = 0; base < nS; base += 64) {
+							const uint32_t i = base + lane;
+							uint32_t v = 0;
+							if (i < nS) { const GlueElem e = a[i]; v = e.k0 + hits.matchLen[sOff + e.id]; }
+							for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d); v = seedMaxScanStep(v, o, lane, d); }
+							v = v > carry ? v : carry;
+							if (i < nS) a[i].k1lo = v;
+							carry = __shfl(v, 63);
+						}
 					}
 					__threadfence_block();
 					__syncthreads();
-					glueWindowsWave([&](uint32_t i) { return a[i].k0; }, nS, len, splitLen, splitGap, matchLen, win, lane, nF, slots, budget, widest);
+					if constexpr (HITS) glueWindowsWave([&](uint32_t i) { return a[i].k0; }, [&](uint32_t i) { return a[i].k1lo; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
+					else glueWindowsWave([&](uint32_t i) { return a[i].k0; }, [&](uint32_t i) { return (uint64_t)a[i].k0 + matchLen; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
 				}
 			}
 		}
@@ -570,6 +636,26 @@ void launchSeedGlue(hipStream_t stream, const SeedIndex& idx, const DGraph& g, c
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1, 1024>), dim3(blocks), dim3(64), 0, stream, idx, g, readOff, nReads, invalidRead, matches, readMatchOff, readMatchCount, readSeedOff, winCapOff, density, splitLen, splitGap, longPass ? 1u : 0u, st,
 		longSeeds, readSeeds, counts, cursors);
 	// where every read's fragments and anchor slots begin: exclusive scans in read order (cursors[0] = fragments, [1] = slots of the batch)
+	hipLaunchKernelGGL(k_exclusive_scan_u32, dim3(2), dim3(256), 0, stream, (const uint32_t*)counts.nFrags, nReads, fragOff, cursors, (const uint32_t*)counts.nSlots, slotOff, cursors + 1);
+	hipLaunchKernelGGL(k_glue_emit, dim3(blocks), dim3(64), 0, stream, readOff, nReads, readSeedOff, winCapOff, (const uint32_t*)st.winBuf, counts, (const uint32_t*)fragOff, (const uint32_t*)slotOff, splitLen, splitGap, frags, fragFirstSeed, jobs, out);
+}
+
+// the same from the caller's resolved hits (gc_align_batch_seeded): readSeedOff is the caller's read_hit_off, so a read's capacity is its hit count
+void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* readOff, uint32_t nReads, const uint8_t* invalidRead, const SeedHitArrays& hits, const uint32_t* readSeedOff, const uint32_t* winCapOff,
+	uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st, uint32_t* perRead, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed, ReadChainJob* jobs, GlueRead* out,
+	unsigned long long* cursors)
+{
+	if (!nReads) return;
+	const uint32_t blocks = nReads < 16384 ? nReads : 16384;
+	const uint64_t stride = (uint64_t)nReads + 1;
+	GlueCounts counts { perRead, perRead + stride, perRead + 2 * stride, perRead + 3 * stride };
+	uint32_t* fragOff = perRead + 4 * stride;
+	uint32_t* slotOff = perRead + 5 * stride;
+	const SeedIndex none {};
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1024, 0, true>), dim3(blocks), dim3(64), 0, stream, none, g, readOff, nReads, invalidRead, (const uint2*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, readSeedOff, winCapOff,
+		-1.0, splitLen, splitGap, longPass ? 1u : 0u, st, longSeeds, readSeeds, counts, cursors, hits);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1, 1024, true>), dim3(blocks), dim3(64), 0, stream, none, g, readOff, nReads, invalidRead, (const uint2*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, readSeedOff, winCapOff,
+		-1.0, splitLen, splitGap, longPass ? 1u : 0u, st, longSeeds, readSeeds, counts, cursors, hits);
 	hipLaunchKernelGGL(k_exclusive_scan_u32, dim3(2), dim3(256), 0, stream, (const uint32_t*)counts.nFrags, nReads, fragOff, cursors, (const uint32_t*)counts.nSlots, slotOff, cursors + 1);
 	hipLaunchKernelGGL(k_glue_emit, dim3(blocks), dim3(64), 0, stream, readOff, nReads, readSeedOff, winCapOff, (const uint32_t*)st.winBuf, counts, (const uint32_t*)fragOff, (const uint32_t*)slotOff, splitLen, splitGap, frags, fragFirstSeed, jobs, out);
 }

@@ -37,6 +37,7 @@ typedef struct gc_graph gc_graph;     /* AlignmentGraph + MPC index, resident in
 typedef struct gc_seeder gc_seeder;   /* MinimizerSeeder index, resident in HBM */
 typedef struct gc_stream gc_stream;   /* per-worker reusable state (HIP stream + arenas) */
 typedef struct gc_reads gc_reads;     /* a batch of reads uploaded to HBM */
+typedef struct gc_seeds gc_seeds;     /* a read batch's seed hits from the host's own seeder, resolved and resident in HBM */
 
 /* Capacities of the device-side tables one batch uses. The reference grows std::vectors and hash maps as it goes; a kernel works in tables sized before the launch.
  * Every table is PER EXTENSION or PER READ, never per batch, and what outgrows one never fails the call: the work is rerun with more room (second launch, other
@@ -174,6 +175,29 @@ void gc_stream_destroy(gc_stream* st);
 int gc_reads_upload(const char* bases, const uint64_t* offsets, uint64_t n, gc_reads** out);
 void gc_reads_destroy(gc_reads* r);
 
+/* ---- seed hits from the host's own seeder ----------------------------------------------------------- */
+/* SeedHit as a seeder hands it over (src/GraphAlignerWrapper.h:14): what Seeder::getSeeds returns whether the hits come from minimizers, MUM / MEM matches or a
+ * seeds file (src/Aligner.cpp:87-108), before OrderSeeds. */
+typedef struct gc_seed_hit {
+	int32_t  node_id;            /* SeedHit::nodeID (bigraph id / 2) */
+	uint32_t node_offset;        /* offset in the ORIENTED original node (bigraph id 2*node_id + reverse) */
+	uint32_t seq_pos;            /* read position the seed cell is aligned with */
+	uint32_t match_len;
+	uint32_t raw_goodness;       /* rawSeedGoodness */
+	uint32_t reverse;            /* 0 / 1 */
+} gc_seed_hit;
+
+/* Uploads and resolves the hits of a read batch: read i has hits[read_hit_off[i] .. read_hit_off[i+1]), in the order its seeder returned them - the reference's unstable sorts
+ * are replayed on that order, so it is part of the contract. Every hit is resolved on the device as orderSeedsByChaining does (GetUnitigNode and the split node's offset,
+ * src/GraphAligner.h:250-252). The result is read-only and may be shared by streams, like a gc_reads; it belongs to `reads` (same lengths) and to `g`.
+ * GC_ERR_INVALID, checked on the host before a device is needed: a null pointer, offsets that do not start at 0 or decrease, n_reads other than the batch's, 2^32 hits or
+ * more, a match_len of 2^31 or more, a raw_goodness that could overflow the 32-bit seed goodness (match_len + read length + raw_goodness must stay below 2^32).
+ * GC_ERR_INVALID from the device, with the first such hit's read and index in gc_last_error and nothing clamped: a node id that is not in the graph, node_offset >= the
+ * original node's size, seq_pos >= the read's length. Hits the reference asserts on (match_len < 2, src/GraphAligner.h:280; chainApproxPos + offset < seq_pos, :253)
+ * are accepted here and set the read's failed_assertion in the batch. */
+int gc_seeds_upload(const gc_graph* g, const gc_reads* reads, const gc_seed_hit* hits, const uint64_t* read_hit_off /* [n_reads+1] */, uint64_t n_reads, gc_seeds** out);
+void gc_seeds_destroy(gc_seeds* s);
+
 /* ---- the hot path ---------------------------------------------------------------------------------- */
 
 /* Flat (CSR) result of one batch. All arrays are host memory owned by the result; free with
@@ -274,6 +298,12 @@ typedef struct gc_result {
  * MinimizerSeeder::getSeeds, OrderSeeds, AlignOneWay, AlignmentGraph::colinearChaining. */
 int gc_align_batch(const gc_graph* g, const gc_seeder* s, gc_stream* st, const gc_reads* reads, const gc_params* params, gc_result** out);
 void gc_result_free(gc_result* r);
+/* The same from the host's own seed hits (gc_seeds_upload) in place of MinimizerSeeder::getSeeds: OrderSeeds, the fragment windows and everything after them run on those hits,
+ * each with its own match_len. No gc_seeder is needed - a host with its own seeds never builds or uploads the minimizer index. params->seed_density is not used (it belongs to
+ * MinimizerSeeder::getSeeds); min_cluster_size and everything else behave as in gc_align_batch. Where the reference leaves the order of equal keys inside a seed cluster to
+ * std::sort (hits of one cluster at one read position with different match_len) the cluster's matching base pairs follow a stable sort. Needs the device seed glue
+ * (GC_DEVICE_GLUE=0: GC_ERR_INVALID). */
+int gc_align_batch_seeded(const gc_graph* g, gc_stream* st, const gc_reads* reads, const gc_seeds* seeds, const gc_params* params, gc_result** out);
 
 /* gc_result_free keeps the large arrays of freed results (trace cells, output text: up to 24 GB in all) for the next batch's result - fresh memory of that size is
  * mapped and zero-filled page by page every batch otherwise; gc_reads_destroy and the device deflate keep their device / pinned blocks the same way (up to 24 GB and 4 GB per cache).

@@ -19,6 +19,8 @@
 //   AlignOneWay       -> whole read: every alignment of the sloppy pass with its trace; fragment (offset = l): the anchors of
 //                        that fragment as alignment items with their traces
 //   colinearChaining  -> the chain over exactly those anchors
+// The seedHits a caller passes to AlignOneWay are not read (the replay is of the library's own minimizer seeds). A host with seeds of its own - filtered, from a seeds file,
+// from a MEM seeder - calls gc_seeds_upload + gc_align_batch_seeded (include/graphchainer_amd.h) instead of going through this header.
 // A batch of one read leaves the GPU mostly idle: this is the drop-in for linking and checking, INTEGRATION.md §3 (batching
 // the dequeued reads) is the form to run. Error convention: a read the reference would have dropped with an
 // AssertionFailure (src/Aligner.cpp:585-592,695-703) comes back with what the reference would have kept - nothing after
