@@ -47,7 +47,8 @@
 				for (uint32_t k = w.sl; k < w.sr; k++, slot++) {
 					// trace cells the two extensions of this seed may need: backward p rows, forward split_len - 1 - p (src/GraphAligner.h:499-511)
 					const uint32_t p = gl.seeds[k].seqPos - w.l, q = (uint32_t)P->split_len - 1 - p;
-					budget += (p ? p + 24 : 0) + (q ? q + 24 : 0);
+					// (rows + 1 + score cells: the HMM keeps a one-slice extension only below a score of 24; under force_global the score reaches the rows)
+					budget += P->force_global ? (p ? 2 * p + 1 : 0) + (q ? 2 * q + 1 : 0) : (p ? p + 24 : 0) + (q ? q + 24 : 0);
 				}
 				fr.seedEnd = (uint32_t)slot;
 				windowSeeds[worker] = std::max(windowSeeds[worker], w.sr - w.sl);
@@ -101,6 +102,7 @@
 		// (which the backtrace reads) included (src/GraphAlignerBitvectorBanded.h:544,572-576,608). --tangle-effort goes to the cores as it is.
 		if (P->ramp_bandwidth > P->bandwidth) cfg.bandwidth = P->ramp_bandwidth;
 		cfg.maxCells = P->max_cells_per_slice < 0 || P->max_cells_per_slice >= 0xffffffffll ? ~0u : (uint32_t)P->max_cells_per_slice;   // (no slice reaches 2^32 - 1 cells)
+		cfg.forceGlobal = P->force_global != 0;
 		cfg.maxSlices = 3;
 		cfg.maxItems = 72;
 		cfg.maxPending = 48;
@@ -184,7 +186,7 @@
 			if (fragKernel) {
 				unsigned long long* claims = dFragClaims + 2 * (nExtendRounds++ & 3u);
 				if (nExtendRounds > 4) launchZeroWords(stream, claims, 2);
-				launchExtendFrag(stream, G->dev, G->devTables, cfg.bandwidth, dWork, nWork, fragReads, dResults, dFragItems, fragWaves, dTrace, dCursors + 1, traceBudget, dCounters, sel, claims, dFragRetry, claims + 1, dFragClaims + 8, cfg.maxCells);
+				launchExtendFrag(stream, G->dev, G->devTables, cfg.bandwidth, dWork, nWork, fragReads, dResults, dFragItems, fragWaves, dTrace, dCursors + 1, traceBudget, dCounters, sel, claims, dFragRetry, claims + 1, dFragClaims + 8, cfg.maxCells, cfg.forceGlobal != 0);
 				ExtSelection declined;
 				declined.mode = 2; declined.list = dFragRetry; declined.listCount = claims + 1;
 				// What the kernel declined (233 of cfg2's 4.4 M extensions) goes to the plain-layout kernel on the large slabs - when there is anything: its count comes to the host

@@ -54,7 +54,9 @@
 			lcfg.maxSlices = (uint32_t)(maxReadLen / 64 + 3);
 			lcfg.maxItems = (uint32_t)std::max<uint64_t>(8192, (maxReadLen / 64 + 3) * 24);   // (slice, node) tiles of one extension: ~8 per slice on cfg2, room for 24
 			lcfg.maxPending = 96;
-			lcfg.maxTrace = (uint32_t)(maxReadLen + maxReadLen / 2 + 512);
+			lcfg.forceGlobal = P->force_global != 0;
+			// (an extension's trace: rows + 1 + score cells. force_global keeps every slice, so the score reaches the rows)
+			lcfg.maxTrace = P->force_global ? (uint32_t)(2 * maxReadLen + 2 + 512) : (uint32_t)(maxReadLen + maxReadLen / 2 + 512);
 			// column store of the one-extension-per-wave kernel: the DP keeps every column (16 B) so that the backtrace loads its tiles' columns back instead of
 			// recomputing them (45 % of the kernel's column steps). ~2.1 columns per read row on cfg2; an extension that needs more than this room ends
 			// with EXT_OVERFLOW and its read goes to the plain-layout kernel, which recomputes. GC_TEST_LONG_MAX_COLS=0: no store (the r2 behaviour).
@@ -93,7 +95,7 @@
 			dRetryList = st->longRetryList.reserve<uint32_t>(workCapacity);   // work items whose band outgrew the register tables (per round)
 			dOrder = st->longOrder.reserve<uint32_t>(workCapacity);       // learns the round's work count (k_publish: no copy-engine transfer in the round loop)
 			roundTraceBudget = 0;
-			for (uint64_t r = 0; r < n; r++) { uint64_t len = R->offsets[r + 1] - R->offsets[r]; roundTraceBudget += 4 * (len + len / 2 + 1024); }   // up to four candidate seeds' worth per read (the speculation rule of the round loop keeps rounds within it)
+			for (uint64_t r = 0; r < n; r++) { uint64_t len = R->offsets[r + 1] - R->offsets[r]; roundTraceBudget += 4 * ((P->force_global ? 2 * len + 2 : len + len / 2) + 1024); }   // up to four candidate seeds' worth per read (the speculation rule of the round loop keeps rounds within it); a seed's two traces: len + 1 + score cells
 			dRoundTrace = st->longRoundTrace.reserve<unsigned long long>(roundTraceBudget);
 			// extension scratch: one region per lane of a resident wave (persistent waves fetch work items)
 			// (bounded by a memory budget: 0.8 MB per lane for 10 kb reads, 2.4 MB for 50 kb reads; GC_TEST_LONG_SCRATCH_GB overrides the 48 GB)

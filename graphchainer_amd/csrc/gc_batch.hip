@@ -192,6 +192,7 @@ static int alignBatch(const gc_graph* G, const gc_seeder* S, const gc_seeds* H, 
 	if (P->split_len < 16 || P->split_len > 64 || P->split_gap < 1) return fail(GC_ERR_INVALID, "split_len must be in [16,64] (one 64-row slice per fragment extension) and split_gap >= 1");
 	if (P->ramp_bandwidth < 0 || (P->ramp_bandwidth != 0 && P->ramp_bandwidth <= P->bandwidth)) return fail(GC_ERR_INVALID, "ramp_bandwidth must be 0 (off) or larger than bandwidth (src/AlignerMain.cpp:380-383)");
 	if (P->max_cells_per_slice < -1) return fail(GC_ERR_INVALID, "max_cells_per_slice must be -1 (unlimited) or >= 0");
+	if (P->force_global != 0 && P->force_global != 1) return fail(GC_ERR_INVALID, "force_global must be 0 or 1");
 	{
 		const gc_capacities& c = P->capacity;
 		if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return fail(GC_ERR_INVALID, "gc_params::capacity.reserved must be 0 (was the struct initialised with gc_params_default?)");

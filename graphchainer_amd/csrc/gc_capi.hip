@@ -446,6 +446,7 @@ void gc_params_default(gc_params* p)
 	memset(&p->capacity, 0, sizeof(p->capacity));   // automatic
 	p->ramp_bandwidth = 0;          // off (src/AlignerMain.cpp:147)
 	p->max_cells_per_slice = -1;    // unlimited (src/AlignerMain.cpp:149: SIZE_MAX)
+	p->force_global = 0;            // off (src/AlignerMain.cpp:160)
 }
 
 int gc_graph_create_from_gfa(const char* gfa_path, gc_graph** out)

@@ -209,7 +209,10 @@ struct ExtendConfig {
 	// (32-bit: an 8-byte member would realign the struct every whole-read kernel takes by value. No slice holds 2^32 cells, so ~0u means unlimited)
 	int32_t rampBandwidth = 0;   // rampBandwidth: 0 off, else > bandwidth
 	uint32_t maxCells = ~0u;     // maxCellsPerSlice: ~0u unlimited
-	__host__ __device__ bool bandControls() const { return rampBandwidth != 0 || maxCells != ~0u; }
+	// gc_params::force_global (forceGlobal, ...Banded.h:51,120,587-645): every slice is kept - no stop at a slice that is not correct-from-correct, no rewind of the ramp
+	// (so only slice 0 takes the ramp bandwidth, :544), no removeWronglyAlignedEnd. It changes the slice loop's decisions only, so it runs in the BAND instantiations too.
+	uint32_t forceGlobal = 0;
+	__host__ __device__ bool bandControls() const { return rampBandwidth != 0 || maxCells != ~0u || forceGlobal != 0; }
 };
 enum : uint32_t { SLICE_NOT_VALID = 16u };   // SliceInfo::flags: the slice reached maxCellsPerSlice (DPSlice::scoresNotValid, ...Banded.h:581-584)
 
@@ -580,6 +583,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 	// the kept slice rampRedoIndex (sc.slices[rampRedoIndex + 1]): kept slices and their items are a stack, so rewinding is truncating it.
 	int rampUntil = 0, rampRedoIndex = -1;
 	const bool rampOn = BAND && cfg.rampBandwidth > cfg.bandwidth;
+	const bool keepAll = BAND && cfg.forceGlobal != 0;   // forceGlobal: the whole `if (!forceGlobal)` block of ...Banded.h:587-645 is skipped
 	for (int slice = 0; slice < numSlices; slice++) {
 		const SliceInfo prev = sc.slices[nSlices - 1];
 		int j = prev.j + 64;
@@ -666,8 +670,8 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			if (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u))) rampRedoIndex = slice - 1;
 			if (cells >= cfg.maxCells) cur.flags |= SLICE_NOT_VALID;
 		}
-		if (!(cur.flags & 2u)) break;   // !CorrectFromCorrect: stop, slice not kept (...Banded.h:589-607)
-		if (BAND && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
+		if (!keepAll && !(cur.flags & 2u)) break;   // !CorrectFromCorrect: stop, slice not kept (...Banded.h:589-607)
+		if (BAND && !keepAll && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
 			// ...Banded.h:608-644: not currently correct - redo from the snapshot with the ramp bandwidth up to this slice. (rampRedoIndex >= 0 here: the
 			// snapshot is taken at slice rampUntil + 1 at the latest, before this test)
 			rampUntil = slice;
@@ -678,8 +682,8 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 		}
 		sc.slices[nSlices++] = cur;
 	}
-	// removeWronglyAlignedEnd, ...Common.h:1231-1241
-	{
+	// removeWronglyAlignedEnd, ...Common.h:1231-1241 (not called with forceGlobal, ...Banded.h:51,120)
+	if (!keepAll) {
 		bool currentlyCorrect = (sc.slices[nSlices - 1].flags & 1u) != 0;
 		while (!currentlyCorrect) {
 			currentlyCorrect = (sc.slices[nSlices - 1].flags & 4u) != 0;

@@ -492,9 +492,10 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 // Full seed extension, wave layout. Trace goes to trace region `which` of the wave scratch (start cell first).
 // BAND: the band controls (gc_params::ramp_bandwidth / max_cells_per_slice) as extendSeedT<.., true> has them. The ramp's rewind and the cell limit's break run here; an
 // extension that keeps a slice flagged scoresNotValid answers EXT_OVERFLOW (its read goes to the plain-layout fallback, whose backtrace has the flagged rules).
+// forceGlobal (gc_params::force_global, BAND only): every slice is kept - no stop, no snapshot or rewind (slice 0 alone takes the ramp bandwidth), no removeWronglyAlignedEnd.
 template <bool REGCOLS, bool BAND = false>
 __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const CorrectnessTables& ct, const EqSource& eqSrc, int bandwidthCfg, lds_u32* lds, const WaveScratch& wsx,
-	int len, uint32_t startNode, uint32_t startOffset, uint32_t which, uint32_t& nTrace, int32_t& score, ExtCounters& cnt, int rampBandwidth = 0, uint32_t maxCells = ~0u)
+	int len, uint32_t startNode, uint32_t startOffset, uint32_t which, uint32_t& nTrace, int32_t& score, ExtCounters& cnt, int rampBandwidth = 0, uint32_t maxCells = ~0u, bool forceGlobal = false)
 {
 	const LaneLdsT<REGCOLS> L { lds, wsx.lane, wsx.lanes, wsx.spillBase(), {}, wsx.regCap < 64 ? wsx.regCap : 64u, { 0, 0, 0, 0, 0 }, 0, 0 };
 	uint32_t status = EXT_OK;
@@ -536,6 +537,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 	// which go to the trace region - unused until the backtrace
 	int rampUntil = 0, rampRedoIndex = -1;
 	const bool rampOn = BAND && rampBandwidth > bandwidthCfg;
+	const bool keepAll = BAND && forceGlobal;   // the `if (!forceGlobal)` block of ...Banded.h:587-645 is skipped
 	double snapCorrect = 0, snapFalse = 0;
 	uint32_t snapCols = 0;
 	Eq4 eq;
@@ -708,7 +710,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			cur.flags = (curCorrect > curFalse ? 1u : 0u) | (cfc ? 2u : 0u) | (ffc ? 4u : 0u) | flatTie;
 		}
 		if (BAND) {
-			if (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u))) {   // ...Banded.h:572-576: the previous slice is the snapshot
+			if (!keepAll && (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u)))) {   // ...Banded.h:572-576: the previous slice is the snapshot (never returned to with forceGlobal)
 				if (nPrev > wsx.maxTrace) return EXT_OVERFLOW;
 				rampRedoIndex = slice - 1;
 				snapCorrect = prevCorrect; snapFalse = prevFalse; snapCols = sliceCols;
@@ -716,8 +718,8 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			}
 			if (cells >= maxCells) cur.flags |= SLICE_NOT_VALID;   // ...Banded.h:581-584 (>=)
 		}
-		if (!(cur.flags & 2u)) break;
-		if (BAND && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
+		if (!keepAll && !(cur.flags & 2u)) break;
+		if (BAND && !keepAll && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
 			// ...Banded.h:608-644: redo from the snapshot with the ramp bandwidth up to this slice - truncate the slice and item stacks and the column store to it, and reload
 			// the previous-slice table (entry e = item first + e) and the correctness state (rampRedoIndex >= 0: the snapshot is taken at slice rampUntil + 1 at the latest)
 			rampUntil = slice;
@@ -741,8 +743,8 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		GC_MARK(5);
 	}
 	GC_MARK(5);   // slice epilogue (HMM, slice record)
-	// removeWronglyAlignedEnd
-	{
+	// removeWronglyAlignedEnd (not called with forceGlobal, ...Banded.h:51,120)
+	if (!keepAll) {
 		bool currentlyCorrect = (loadSlice(wsx, nSlices - 1).flags & 1u) != 0;
 		while (!currentlyCorrect) {
 			currentlyCorrect = (loadSlice(wsx, nSlices - 1).flags & 4u) != 0;

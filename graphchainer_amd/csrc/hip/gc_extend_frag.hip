@@ -68,7 +68,7 @@ template <bool CELLS>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_extend(DGraph g, const CorrectnessTables* __restrict__ ct, int32_t bandwidth,
 	const ExtItem* __restrict__ work, uint32_t nWork, const FragReads reads, ExtResult* __restrict__ results, uint4* __restrict__ itemScratch,
 	PoolCell* __restrict__ tracePool, unsigned long long* __restrict__ traceCursor, uint64_t traceCapacity, unsigned long long* __restrict__ counters, ExtSelection sel,
-	unsigned long long* __restrict__ claim, uint32_t* __restrict__ retryList, unsigned long long* __restrict__ retryCount, unsigned long long* __restrict__ stamps, uint32_t maxCells)
+	unsigned long long* __restrict__ claim, uint32_t* __restrict__ retryList, unsigned long long* __restrict__ retryCount, unsigned long long* __restrict__ stamps, uint32_t maxCells, uint32_t forceGlobal)
 {
 	__shared__ uint32_t ldsWords[FRAG_WORDS * 64];
 	__shared__ uint32_t waveCounters[8];
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
 	if (lane < 8) waveCounters[lane] = 0;
 	FragParams P;
 	P.bandwidth = bandwidth;
-	P.keepMask = __ballot(fragSliceKept(*ct, (int)lane));
+	P.keepMask = forceGlobal ? ~0ull : __ballot(fragSliceKept(*ct, (int)lane));   // gc_params::force_global: the slice is kept whatever its minimum (...Banded.h:51,587)
 	if (CELLS) P.maxCells = maxCells;
 	FragMem<FragDevStore> m;
 	m.lds = ldsWords + lane;
@@ -246,7 +246,7 @@ uint32_t extendFragWaves()
 
 void launchExtendFrag(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, int32_t bandwidth, const ExtItem* work, uint32_t nWork, const FragReads& reads, ExtResult* results,
 	uint4* itemScratch, uint32_t scratchWaves, PoolCell* tracePool, unsigned long long* traceCursor, uint64_t traceCapacity, unsigned long long* counters, ExtSelection sel, unsigned long long* claim,
-	uint32_t* retryList, unsigned long long* retryCount, unsigned long long* stamps, uint64_t maxCells)
+	uint32_t* retryList, unsigned long long* retryCount, unsigned long long* stamps, uint64_t maxCells, bool forceGlobal)
 {
 	if (nWork == 0) return;
 	const uint32_t upper = sel.mode == 1 ? 2 * sel.nFrags : nWork;
@@ -255,9 +255,9 @@ void launchExtendFrag(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 	if (waves == 0) return;
 	// (a fragment's slice has at most GC_FRAG_ITEMS tiles of 64 columns: a larger limit is never reached here)
 	if (maxCells < 0xffffull)
-		hipLaunchKernelGGL(k_extend<true>, dim3(waves), dim3(64), 0, stream, g, ct, bandwidth, work, nWork, reads, results, itemScratch, tracePool, traceCursor, traceCapacity, counters, sel, claim, retryList, retryCount, stamps, (uint32_t)maxCells);
+		hipLaunchKernelGGL(k_extend<true>, dim3(waves), dim3(64), 0, stream, g, ct, bandwidth, work, nWork, reads, results, itemScratch, tracePool, traceCursor, traceCapacity, counters, sel, claim, retryList, retryCount, stamps, (uint32_t)maxCells, forceGlobal ? 1u : 0u);
 	else
-		hipLaunchKernelGGL(k_extend<false>, dim3(waves), dim3(64), 0, stream, g, ct, bandwidth, work, nWork, reads, results, itemScratch, tracePool, traceCursor, traceCapacity, counters, sel, claim, retryList, retryCount, stamps, 0u);
+		hipLaunchKernelGGL(k_extend<false>, dim3(waves), dim3(64), 0, stream, g, ct, bandwidth, work, nWork, reads, results, itemScratch, tracePool, traceCursor, traceCapacity, counters, sel, claim, retryList, retryCount, stamps, 0u, forceGlobal ? 1u : 0u);
 }
 
 } // namespace gcdev

@@ -44,7 +44,9 @@ enum : uint32_t { TF_START = 1u, TF_WALK = 2u };   // Lane::tileFlags: the tile 
 
 struct FragParams {
 	int32_t bandwidth;
-	uint64_t keepMask;       // bit i: a slice whose minimum is min(i, 63) above the initial slice's is kept and currently correct (the HMM's one step)
+	uint64_t keepMask;       // bit i: a slice whose minimum is min(i, 63) above the initial slice's is kept and currently correct (the HMM's one step); all ones with
+	                         // gc_params::force_global, where the score reaches the rows: the trace reservation rows + 2 + score, the ring's refills and the counters' 16-bit halves
+	                         // (at most GC_FRAG_ITEMS tiles of 64 columns on either side) do not depend on the score's size
 	uint32_t maxCells = 0xffffffffu;   // maxCellsPerSlice (0xffffffff: unlimited). The ramp needs nothing here: a fragment extension is one slice, run at the ramp bandwidth
 };
 

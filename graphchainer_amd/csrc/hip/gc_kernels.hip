@@ -1170,7 +1170,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES =
 			int32_t score = 0;
 			EqSource eqSrc { masks + it.maskOff, it.maskWords, it.startBit };
 			if (BAND) res.status = extendSeedWave<LANES == 1, true>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt,
-				cfg.rampBandwidth, cfg.maxCells);
+				cfg.rampBandwidth, cfg.maxCells, cfg.forceGlobal != 0);
 			else res.status = extendSeedWave<LANES == 1>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt);
 			res.score = score;
 			res.pad = cnt.flattenTie;   // (k_long_merge adds the flags of the extensions the reference would have run to the read's count)

@@ -167,7 +167,7 @@ void launchSeedCaps(hipStream_t stream, const SeedIndex& idx, uint32_t nReads, c
 // [2] trace cells the fragment extensions may need, [3] most slots of a read, [4] most seeds of a window)
 void launchSeedGlue(hipStream_t stream, const SeedIndex& idx, const DGraph& g, const uint64_t* readOff, uint32_t nReads, const uint8_t* invalidRead, const uint2* matches, const uint32_t* readMatchOff,
 	const uint32_t* readMatchCount, const uint32_t* readSeedOff, const uint32_t* winCapOff, double density, uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st,
-	uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed, ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors);
+	uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed, ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors, bool forceGlobal = false);   // forceGlobal: gc_params::force_global (the trace cells of cursors[2] are sized for it)
 uint64_t glueElemBytes();
 // ---- caller-supplied seed hits (gc_seeds_upload, gc_align_batch_seeded; gc_seedhits.hip) ----
 struct SeedHit;
@@ -179,7 +179,7 @@ void launchSeedResolve(hipStream_t stream, const SeedLookup& lookup, const SeedH
 // k_seed_glue from resolved hits instead of minimizer matches: readSeedOff = the caller's read_hit_off
 void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* readOff, uint32_t nReads, const uint8_t* invalidRead, const SeedHitArrays& hits, const uint32_t* readSeedOff, const uint32_t* winCapOff,
 	uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st, uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed,
-	ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors);
+	ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors, bool forceGlobal = false);
 // test entry: arrays of (key << 32 | index) elements sorted by key with the wave-cooperative replay of std::sort (gc_stdsort_wave.hpp); scratch: 3 words per element + 64 per array
 void launchTestStdSort(hipStream_t stream, unsigned long long* elems, const uint64_t* off, uint32_t nArrays, uint32_t* scratch, long depthLimit);
 
@@ -190,7 +190,7 @@ uint32_t extendFragWaves();                        // resident waves of the kern
 uint64_t extendFragScratchBytes(uint32_t waves);
 void launchExtendFrag(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, int32_t bandwidth, const ExtItem* work, uint32_t nWork, const FragReads& reads, ExtResult* results,
 	uint4* itemScratch, uint32_t scratchWaves, PoolCell* tracePool, unsigned long long* traceCursor, uint64_t traceCapacity, unsigned long long* counters, ExtSelection sel, unsigned long long* claim,
-	uint32_t* retryList, unsigned long long* retryCount, unsigned long long* stamps = nullptr, uint64_t maxCells = ~0ull);   // (maxCells: ExtendConfig::maxCells; stamps: eight words of the profiling build, -DGC_FRAG_STAMPS) claim, retryCount: zeroed words of this launch's own; retryList [nWork]: the declined items, for launchExtend with a list selection
+	uint32_t* retryList, unsigned long long* retryCount, unsigned long long* stamps = nullptr, uint64_t maxCells = ~0ull, bool forceGlobal = false);   // (maxCells, forceGlobal: ExtendConfig's; stamps: eight words of the profiling build, -DGC_FRAG_STAMPS) claim, retryCount: zeroed words of this launch's own; retryList [nWork]: the declined items, for launchExtend with a list selection
 void launchBuildNodeRecs(hipStream_t stream, const DGraph& g, NodeRec* out);   // DGraph::nodeRec from the arrays already uploaded
 uint64_t extendSlabBytes(const ExtendConfig& cfg);
 uint32_t extendGridLanes(uint32_t nWork);

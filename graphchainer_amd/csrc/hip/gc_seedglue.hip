@@ -75,10 +75,14 @@ __device__ __forceinline__ void glueBitonic(glue_lds_u32* k0, glue_lds_u32* k1, 
 	}
 }
 
+// Trace cells an extension of `rows` read rows may need: rows + 1 + its score. The correctness HMM keeps a one-slice extension only below a score of 24; under
+// gc_params::force_global every slice is kept and the score reaches `rows`. (The host's twin: batch/gc_batch_fragments.inc.)
+__device__ __forceinline__ uint32_t glueTraceCells(uint32_t rows, bool forceGlobal) { return rows ? (forceGlobal ? 2 * rows + 1 : rows + 24) : 0u; }
+
 // fragment windows (src/Aligner.cpp:672-679): two pointers over the position-sorted seeds; key(i) = read position of seed i in that order.
 // Leaves (l, sl, sr, first slot) per window in `win`, and the counts the batch needs.
 template <class Key>
-__device__ __forceinline__ void glueWindows(Key key, uint32_t nS, uint32_t len, uint32_t splitLen, uint32_t splitGap, uint32_t matchLen, uint32_t* win, uint32_t& nFout, uint32_t& slotsOut, unsigned long long& budgetOut, uint32_t& widestOut)
+__device__ __forceinline__ void glueWindows(Key key, uint32_t nS, uint32_t len, uint32_t splitLen, uint32_t splitGap, uint32_t matchLen, uint32_t* win, uint32_t& nFout, uint32_t& slotsOut, unsigned long long& budgetOut, uint32_t& widestOut, bool forceGlobal = false)
 {
 	uint32_t sl = 0, sr = 0, nF = 0, slots = 0, widest = 0;
 	unsigned long long budget = 0;
@@ -90,7 +94,7 @@ __device__ __forceinline__ void glueWindows(Key key, uint32_t nS, uint32_t len, 
 		for (uint32_t k = sl; k < sr; k++) {
 			// trace cells the two extensions of this seed may need: backward p rows, forward split_len - 1 - p (src/GraphAligner.h:499-511)
 			const uint32_t p = key(k) - (uint32_t)l, q = splitLen - 1 - p;
-			budget += (p ? p + 24 : 0) + (q ? q + 24 : 0);
+			budget += glueTraceCells(p, forceGlobal) + glueTraceCells(q, forceGlobal);
 		}
 		widest = widest > sr - sl ? widest : sr - sl;
 		slots += sr - sl;
@@ -105,7 +109,7 @@ __device__ __forceinline__ void glueWindows(Key key, uint32_t nS, uint32_t len, 
 // end(i) = the running maximum of key + matchLen up to seed i (with one matchLen for all seeds: key(i) + matchLen itself) - see seedWindow, gc_seedhits_core.hpp.
 template <class Key, class End>
 __device__ __forceinline__ void glueWindowsWave(Key key, End end, uint32_t nS, uint32_t len, uint32_t splitLen, uint32_t splitGap, uint32_t* win, uint32_t lane,
-	uint32_t& nFout, uint32_t& slotsOut, unsigned long long& budgetOut, uint32_t& widestOut)
+	uint32_t& nFout, uint32_t& slotsOut, unsigned long long& budgetOut, uint32_t& widestOut, bool forceGlobal)
 {
 	uint32_t nF = 0, slots = 0, widest = 0;
 	unsigned long long budget = 0;
@@ -126,7 +130,7 @@ __device__ __forceinline__ void glueWindowsWave(Key key, End end, uint32_t nS, u
 			win[4 * at] = (uint32_t)l; win[4 * at + 1] = sl; win[4 * at + 2] = sr; win[4 * at + 3] = slots + incl - mine;
 			for (uint32_t k = sl; k < sr; k++) {   // trace cells the two extensions of this seed may need: backward p rows, forward split_len - 1 - p (src/GraphAligner.h:499-511)
 				const uint32_t p = key(k) - (uint32_t)l, q = splitLen - 1 - p;
-				b += (p ? p + 24 : 0) + (q ? q + 24 : 0);
+				b += glueTraceCells(p, forceGlobal) + glueTraceCells(q, forceGlobal);
 			}
 		}
 		uint32_t w = has ? mine : 0u;
@@ -177,10 +181,11 @@ __device__ __forceinline__ void glueDensityCut(uint32_t nM, uint64_t maxHits, ui
 template <uint32_t GLUE_LDS_ELEMS, uint32_t SKIP_UP_TO, bool HITS = false>
 __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const uint64_t* __restrict__ readOff, uint32_t nReads, const uint8_t* __restrict__ invalidRead,
 	const uint2* __restrict__ matches, const uint32_t* __restrict__ readMatchOff, const uint32_t* __restrict__ readMatchCount, const uint32_t* __restrict__ readSeedOff, const uint32_t* __restrict__ winCapOff,
-	double density, uint32_t splitLen, uint32_t splitGap, uint32_t longPass, GlueStaging st,
+	double density, uint32_t splitLen, uint32_t splitGap, uint32_t passFlags, GlueStaging st,
 	LongSeed* __restrict__ longSeeds, FragSeed* __restrict__ readSeeds, GlueCounts counts, unsigned long long* __restrict__ cursors, SeedHitArrays hits = SeedHitArrays {})
 {
 	GC_RAISE_PRIO();
+	const bool longPass = (passFlags & 1u) != 0, forceGlobal = (passFlags & 2u) != 0;   // gc_params::long_pass / force_global (the latter sizes the trace budget)
 	// per seed, expansion order (HITS: the caller's order; read-only and shared between streams - what the glue computes per seed goes to the staging as before)
 	const uint32_t* const sSeqPos = HITS ? hits.seqPos : st.sSeqPos;
 	const uint32_t* const sNode = HITS ? hits.node : st.sNode;
@@ -355,9 +360,9 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 							carry = __shfl(v, 63);
 						}
 						__syncthreads();
-						glueWindowsWave([&](uint32_t i) { return (uint32_t)(s64[i] >> 32); }, [&](uint32_t i) { return (uint32_t)eK0[i]; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
+						glueWindowsWave([&](uint32_t i) { return (uint32_t)(s64[i] >> 32); }, [&](uint32_t i) { return (uint32_t)eK0[i]; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest, forceGlobal);
 					} else
-					glueWindowsWave([&](uint32_t i) { return (uint32_t)(s64[i] >> 32); }, [&](uint32_t i) { return (uint64_t)(uint32_t)(s64[i] >> 32) + matchLen; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
+					glueWindowsWave([&](uint32_t i) { return (uint32_t)(s64[i] >> 32); }, [&](uint32_t i) { return (uint64_t)(uint32_t)(s64[i] >> 32) + matchLen; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest, forceGlobal);
 				}
 			}
 		} else if (nM > 0) {
@@ -506,8 +511,8 @@ __global__ void __launch_bounds__(64) k_seed_glue(SeedIndex idx, DGraph g, const
 					}
 					__threadfence_block();
 					__syncthreads();
-					if constexpr (HITS) glueWindowsWave([&](uint32_t i) { return a[i].k0; }, [&](uint32_t i) { return a[i].k1lo; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
-					else glueWindowsWave([&](uint32_t i) { return a[i].k0; }, [&](uint32_t i) { return (uint64_t)a[i].k0 + matchLen; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest);
+					if constexpr (HITS) glueWindowsWave([&](uint32_t i) { return a[i].k0; }, [&](uint32_t i) { return a[i].k1lo; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest, forceGlobal);
+					else glueWindowsWave([&](uint32_t i) { return a[i].k0; }, [&](uint32_t i) { return (uint64_t)a[i].k0 + matchLen; }, nS, len, splitLen, splitGap, win, lane, nF, slots, budget, widest, forceGlobal);
 				}
 			}
 		}
@@ -623,7 +628,7 @@ void launchSeedCaps(hipStream_t stream, const SeedIndex& idx, uint32_t nReads, c
 
 void launchSeedGlue(hipStream_t stream, const SeedIndex& idx, const DGraph& g, const uint64_t* readOff, uint32_t nReads, const uint8_t* invalidRead, const uint2* matches, const uint32_t* readMatchOff,
 	const uint32_t* readMatchCount, const uint32_t* readSeedOff, const uint32_t* winCapOff, double density, uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st,
-	uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed, ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors)
+	uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed, ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors, bool forceGlobal)
 {
 	if (!nReads) return;
 	const uint32_t blocks = nReads < 16384 ? nReads : 16384;
@@ -631,9 +636,9 @@ void launchSeedGlue(hipStream_t stream, const SeedIndex& idx, const DGraph& g, c
 	GlueCounts counts { perRead, perRead + stride, perRead + 2 * stride, perRead + 3 * stride };
 	uint32_t* fragOff = perRead + 4 * stride;
 	uint32_t* slotOff = perRead + 5 * stride;
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1024, 0>), dim3(blocks), dim3(64), 0, stream, idx, g, readOff, nReads, invalidRead, matches, readMatchOff, readMatchCount, readSeedOff, winCapOff, density, splitLen, splitGap, longPass ? 1u : 0u, st,
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1024, 0>), dim3(blocks), dim3(64), 0, stream, idx, g, readOff, nReads, invalidRead, matches, readMatchOff, readMatchCount, readSeedOff, winCapOff, density, splitLen, splitGap, (longPass ? 1u : 0u) | (forceGlobal ? 2u : 0u), st,
 		longSeeds, readSeeds, counts, cursors);
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1, 1024>), dim3(blocks), dim3(64), 0, stream, idx, g, readOff, nReads, invalidRead, matches, readMatchOff, readMatchCount, readSeedOff, winCapOff, density, splitLen, splitGap, longPass ? 1u : 0u, st,
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1, 1024>), dim3(blocks), dim3(64), 0, stream, idx, g, readOff, nReads, invalidRead, matches, readMatchOff, readMatchCount, readSeedOff, winCapOff, density, splitLen, splitGap, (longPass ? 1u : 0u) | (forceGlobal ? 2u : 0u), st,
 		longSeeds, readSeeds, counts, cursors);
 	// where every read's fragments and anchor slots begin: exclusive scans in read order (cursors[0] = fragments, [1] = slots of the batch)
 	hipLaunchKernelGGL(k_exclusive_scan_u32, dim3(2), dim3(256), 0, stream, (const uint32_t*)counts.nFrags, nReads, fragOff, cursors, (const uint32_t*)counts.nSlots, slotOff, cursors + 1);
@@ -643,7 +648,7 @@ void launchSeedGlue(hipStream_t stream, const SeedIndex& idx, const DGraph& g, c
 // the same from the caller's resolved hits (gc_align_batch_seeded): readSeedOff is the caller's read_hit_off, so a read's capacity is its hit count
 void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* readOff, uint32_t nReads, const uint8_t* invalidRead, const SeedHitArrays& hits, const uint32_t* readSeedOff, const uint32_t* winCapOff,
 	uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st, uint32_t* perRead, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed, ReadChainJob* jobs, GlueRead* out,
-	unsigned long long* cursors)
+	unsigned long long* cursors, bool forceGlobal)
 {
 	if (!nReads) return;
 	const uint32_t blocks = nReads < 16384 ? nReads : 16384;
@@ -653,9 +658,9 @@ void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* rea
 	uint32_t* slotOff = perRead + 5 * stride;
 	const SeedIndex none {};
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1024, 0, true>), dim3(blocks), dim3(64), 0, stream, none, g, readOff, nReads, invalidRead, (const uint2*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, readSeedOff, winCapOff,
-		-1.0, splitLen, splitGap, longPass ? 1u : 0u, st, longSeeds, readSeeds, counts, cursors, hits);
+		-1.0, splitLen, splitGap, (longPass ? 1u : 0u) | (forceGlobal ? 2u : 0u), st, longSeeds, readSeeds, counts, cursors, hits);
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seed_glue<1, 1024, true>), dim3(blocks), dim3(64), 0, stream, none, g, readOff, nReads, invalidRead, (const uint2*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, readSeedOff, winCapOff,
-		-1.0, splitLen, splitGap, longPass ? 1u : 0u, st, longSeeds, readSeeds, counts, cursors, hits);
+		-1.0, splitLen, splitGap, (longPass ? 1u : 0u) | (forceGlobal ? 2u : 0u), st, longSeeds, readSeeds, counts, cursors, hits);
 	hipLaunchKernelGGL(k_exclusive_scan_u32, dim3(2), dim3(256), 0, stream, (const uint32_t*)counts.nFrags, nReads, fragOff, cursors, (const uint32_t*)counts.nSlots, slotOff, cursors + 1);
 	hipLaunchKernelGGL(k_glue_emit, dim3(blocks), dim3(64), 0, stream, readOff, nReads, readSeedOff, winCapOff, (const uint32_t*)st.winBuf, counts, (const uint32_t*)fragOff, (const uint32_t*)slotOff, splitLen, splitGap, frags, fragFirstSeed, jobs, out);
 }

@@ -94,6 +94,11 @@ typedef struct gc_params {
 	int64_t max_cells_per_slice; /* -C, --tangle-effort, maxCellsPerSlice (src/AlignerMain.cpp:96,149,249): -1 (default) unlimited; 0 and up literal
 	                             *    (< -1: GC_ERR_INVALID). A slice stops taking nodes once its DP cells pass this count, and a slice that reaches it
 	                             *    is backtraced with the "scores not valid" rules (src/GraphAlignerBitvectorBanded.h:400-405,579-584, ...Common.h:599-804). */
+	int32_t force_global;       /* --global-alignment, forceGlobal (src/AlignerMain.cpp:66,160,299): 0 (default) off, 1 on (anything else: GC_ERR_INVALID).
+	                             *    Every extension of the whole-read pass and of the fragment pass keeps all its slices: it does not stop at a slice that
+	                             *    is not "correct from correct" and does not drop a wrongly aligned end, so a successful extension reaches the read's
+	                             *    (the fragment's) end however poor its score (src/GraphAlignerBitvectorBanded.h:51,120,587-645). With ramp_bandwidth
+	                             *    only the first slice runs at the ramp band (:544: nothing rewinds); max_cells_per_slice acts as without the flag. */
 } gc_params;
 
 void gc_params_default(gc_params* p);

@@ -66,7 +66,7 @@ inline std::vector<int64_t> graphArray(const gc_graph* g, const char* name)
 
 // Once, after gc_graph_create* / gc_seeder_create (src/Aligner.cpp:1137-1162). `params` as INTEGRATION.md §2 fills them; the shim
 // turns on what the replay needs (whole-read pass, traces, seeds). The band controls -B / -C go in params.ramp_bandwidth and
-// params.max_cells_per_slice (src/AlignerMain.cpp:248-249); AlignOneWay then accepts exactly those values.
+// params.max_cells_per_slice (src/AlignerMain.cpp:248-249), --global-alignment in params.force_global (:299); AlignOneWay then accepts exactly those values.
 inline void bind(gc_graph* graph, gc_seeder* seeder, gc_params params)
 {
 	Binding& b = binding();
@@ -212,10 +212,9 @@ inline AlignmentResult AlignOneWay(const AlignmentGraph&, const std::string& /*s
 	long long l = -1, long long /*r*/ = -1, long long offset = 0, const std::string* wholeRead = nullptr)
 {
 	// Options of this signature the kernels do not implement are refused, not ignored: a caller that asks for them would silently get the default behaviour otherwise.
-	// (--precise-clipping / X-drop: src/GraphAlignerBitvectorBanded.h:61-68,703-; forceGlobal: :587.)
+	// (--precise-clipping / X-drop: src/GraphAlignerBitvectorBanded.h:61-68,703-.)
 	if (preciseClipping || Xdropcutoff > 0) throw std::invalid_argument("gcshim::AlignOneWay: --precise-clipping / X-drop are not built (DESIGN.md section 9)");
-	if (forceGlobal) throw std::invalid_argument("gcshim::AlignOneWay: forced global alignment is not built (DESIGN.md section 9)");
-	// The replayed batch ran with the band controls given to bind(): a call must ask for the same ones. The reference turns the ramp on only when it is wider than
+	// The replayed batch ran with the band controls and the forced global alignment (forceGlobal, src/GraphAlignerBitvectorBanded.h:587) given to bind(): a call must ask for the same ones. The reference turns the ramp on only when it is wider than
 	// the band (src/GraphAlignerBitvectorBanded.h:544), and SIZE_MAX cells per slice is its "unlimited" (src/AlignerMain.cpp:149), the -1 of gc_params.
 	const gc_params& bound = binding().params;
 	if ((int64_t)initialBandwidth != (int64_t)bound.bandwidth) throw std::invalid_argument("gcshim::AlignOneWay: the bandwidth differs from the one given to gcshim::bind()");
@@ -223,6 +222,7 @@ inline AlignmentResult AlignOneWay(const AlignmentGraph&, const std::string& /*s
 	if (ramp != (int64_t)bound.ramp_bandwidth) throw std::invalid_argument("gcshim::AlignOneWay: the ramp bandwidth differs from the one given to gcshim::bind()");
 	const int64_t cells = maxCellsPerSlice == std::numeric_limits<size_t>::max() ? -1 : (int64_t)maxCellsPerSlice;
 	if (cells != bound.max_cells_per_slice) throw std::invalid_argument("gcshim::AlignOneWay: the cell limit per slice differs from the one given to gcshim::bind()");
+	if ((forceGlobal ? 1 : 0) != (int)bound.force_global) throw std::invalid_argument("gcshim::AlignOneWay: the forced global alignment differs from the one given to gcshim::bind()");
 	AlignmentResult out;
 	if (l < 0) {
 		const gc_result& r = session().of(sequence);
