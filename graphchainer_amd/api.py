@@ -37,7 +37,12 @@ class GcParams(C.Structure):
     _fields_ = [("bandwidth", C.c_int32), ("split_len", C.c_int32), ("split_gap", C.c_int32), ("colinear_gap", C.c_int64),
                 ("seed_density", C.c_double), ("min_cluster_size", C.c_int32), ("long_pass", C.c_int32), ("keep_traces", C.c_int32), ("keep_seeds", C.c_int32), ("stitch", C.c_int32), ("edit_distances", C.c_int32),
                 ("chain_traces", C.c_int32), ("device_output", C.c_int32), ("e_cutoff", C.c_double), ("capacity", GcCapacities),
-                ("ramp_bandwidth", C.c_int32), ("max_cells_per_slice", C.c_int64), ("force_global", C.c_int32)]
+                ("ramp_bandwidth", C.c_int32), ("max_cells_per_slice", C.c_int64), ("force_global", C.c_int32),
+                ("seed_extend_density", C.c_double), ("extra_heuristic", C.c_int32), ("colinear_chaining", C.c_int32), ("selection_method", C.c_int32)]
+
+
+# gc_params::selection_method: the reference's SelectionMethod in its own order (GC_SELECT_* of include/graphchainer_amd.h)
+SELECT_GREEDY_LENGTH, SELECT_GREEDY_SCORE, SELECT_GREEDY_E, SELECT_SCHEDULE_INVERSE_E_SUM, SELECT_SCHEDULE_INVERSE_E_PRODUCT, SELECT_SCHEDULE_SCORE, SELECT_SCHEDULE_LENGTH, SELECT_ALL = range(8)
 
 
 _P = C.POINTER
@@ -463,14 +468,18 @@ class BatchResult(dict):
 class Aligner:
     """Batched stand-in for the reference's per-read hot path (src/Aligner.cpp:601-922)."""
 
-    def __init__(self, graph, seeder=None, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1, force_global=False):
+    def __init__(self, graph, seeder=None, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1, force_global=False, seed_extend_density=-1.0, extra_heuristic=False, colinear_chaining=True, selection_method=0):
         """capacities: {field of gc_capacities: value} for the device-side tables (default: all automatic).
         seeder: the MinimizerSeeder, or None for a caller that brings its own seeds to every batch (align_batch(batch, seeds=SeedBatch(...))).
         device_output: gc_params::device_output - 1 / 2: the final alignments' GAF path and CIGAR text (= / X or M items), + 4: their vg::Path bytes, written
         by the device from the traces it holds; align_batch(gaf_names=...) then needs no keep_traces.
         ramp_bandwidth / max_cells_per_slice: the reference's -B / -C (gc_params; 0 and -1: off).
         force_global: the reference's --global-alignment (gc_params::force_global): every extension of both passes keeps all its slices, so an alignment
-        reaches the read's end however poor its score. An int other than 0 / 1 is passed on as it is (and refused by the library)."""
+        reaches the read's end however poor its score. An int other than 0 / 1 is passed on as it is (and refused by the library).
+        seed_extend_density / extra_heuristic: the reference's --seeds-extend-density / --extra-heuristic for the whole-read pass (gc_params; -1: all seeds).
+        A density other than -1 needs colinear_chaining=False.
+        colinear_chaining=False: --no-colinear-chaining, plain GraphAligner - seeding and the whole-read pass alone (needs long_pass=True); the anchor, chain, path
+        and chain-trace arrays come back empty, both edit distances -1, and long_index holds SelectAlignments(selection_method: one of SELECT_*)."""
         self.lib = load_library()
         self.graph = graph
         self.seeder = seeder
@@ -495,6 +504,10 @@ class Aligner:
         self.params.ramp_bandwidth = int(ramp_bandwidth)
         self.params.max_cells_per_slice = int(max_cells_per_slice)
         self.params.force_global = int(force_global)
+        self.params.seed_extend_density = float(seed_extend_density)
+        self.params.extra_heuristic = int(extra_heuristic)
+        self.params.colinear_chaining = int(colinear_chaining)
+        self.params.selection_method = int(selection_method)
         for name, value in (capacities or {}).items():
             if name not in dict(GcCapacities._fields_) or name == "reserved":
                 raise ValueError("no such capacity: " + name)

@@ -47,6 +47,10 @@
 				j.seedBegin = (uint32_t)gl.longSeedBegin;
 				j.seedEnd = (uint32_t)at;
 				j.alnBegin = (uint32_t)(r * firstAlnCap);
+				// size_t extendSeeds = seedExtendDensity * sequence.size() + 1, in double and then truncated; -1: the read's seed count (src/GraphAligner.h:121-122)
+				j.extendSeeds = j.seedEnd - j.seedBegin;
+				if (P->seed_extend_density != -1) j.extendSeeds = (uint32_t)std::min<double>(4294967295.0, P->seed_extend_density * (double)j.readLen + 1);
+				j.pad = 0;
 			});
 			lcfg.bandwidth = P->bandwidth;
 			lcfg.rampBandwidth = P->ramp_bandwidth;
@@ -210,7 +214,7 @@
 			// at most lastWork/2 reads are still active, so this keeps the round within the work arrays (8 per read) and the trace budget (4 seeds' worth per read)
 			if (round > 0 && lastWork > 0) maxCand = (uint32_t)std::min<uint64_t>(maxCand, std::max<uint64_t>(1, (8 * n) / lastWork));
 			if (const char* env = getenv("GC_TEST_LONG_SPECULATE")) maxCand = (uint32_t)std::min(2, std::max(1, atoi(env)));   // test hook: speculate from round 0
-			launchLongSelect(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, R->totalBases, (uint32_t)P->min_cluster_size, maxCand, dLongState, dLongAlns, dLongCells, dLongWork, dWorkLen, dCandSeed, cursor, workCapacity);
+			launchLongSelect(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, R->totalBases, (uint32_t)P->min_cluster_size, (uint32_t)P->extra_heuristic, maxCand, dLongState, dLongAlns, dLongCells, dLongWork, dWorkLen, dCandSeed, cursor, workCapacity);
 			{
 				// execution order: longest extensions first, so the round's tail is made of short ones (GC_TEST_LONG_ORDER=0: as emitted)
 				const char* mode = getenv("GC_TEST_LONG_ORDER");
@@ -245,7 +249,7 @@
 					dRoundTrace, cursor + 1, roundTraceBudget, dLongWorkResults, dLongCursor + 8, cursor + 2, EXT_LDS_CAP, cursor + 3);
 			}
 			HIP_CHECK(hipEventRecord(ev1, q));
-			launchLongMerge(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, dCandSeed, dLongWorkResults, dRoundTrace, dLongState, dLongAlns, dLongCells, dLongCursor, cellBudget);
+			launchLongMerge(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, dCandSeed, dLongWorkResults, dRoundTrace, dLongState, dLongAlns, dLongCells, dLongCursor, cellBudget, (uint32_t)P->extra_heuristic);
 			lastWork = nWorkItems;
 			// no wait here: the next round's select / order / publish queue up right behind the merge, and the only host round trip per
 			// round is the work count above (with a second wait after the merge the stream drained twice per round, and each refill
@@ -288,7 +292,7 @@
 				LongReadResult* dSubResults = st->longResultsFallback.reserve<LongReadResult>(now.size());
 				uint8_t* dSlab = st->longScratchFallback.reserve<uint8_t>(lanes * lslab);
 				HIP_CHECK(hipMemcpyAsync(dSubJobs, subJobs.data(), now.size() * sizeof(LongJob), hipMemcpyHostToDevice, ls));
-				launchLongPass(ls, G->dev, G->devTables, G->devIupac, fcfg, dSubJobs, (uint32_t)now.size(), dLongSeeds, R->devBases, R->totalBases, (uint32_t)P->min_cluster_size,
+				launchLongPass(ls, G->dev, G->devTables, G->devIupac, fcfg, dSubJobs, (uint32_t)now.size(), dLongSeeds, R->devBases, R->totalBases, (uint32_t)P->min_cluster_size, (uint32_t)P->extra_heuristic,
 					dSlab, lslab, dLongCells, dLongCursor, cellBudget, dLongAlns, dSubResults, dLongCursor + 8);
 				std::vector<LongReadResult> subResults(now.size());
 				HIP_CHECK(hipMemcpyAsync(subResults.data(), dSubResults, now.size() * sizeof(LongReadResult), hipMemcpyDeviceToHost, ls));
@@ -333,7 +337,7 @@
 	{
 		// the reference re-sorts its alignment list by alignmentStart after every accepted alignment
 		// (src/GraphAligner.h:183); replaying that on the acceptance-ordered list gives its final order. Then the
-		// GreedyLength selection (src/Aligner.cpp:636-639, src/AlignmentSelection.cpp:12-50) with the same unstable sort.
+		// selection (host/gc_selection.hpp) with the same unstable sort.
 		auto selectOne = [&](size_t i, size_t) {
 			const uint32_t r = subset[i];
 			ReadGlue& gl = glue[r];
@@ -344,39 +348,18 @@
 				gl.longAlns.push_back(hLongAlns[(uint64_t)hJobs[r].alnBegin + a]);
 				std::sort(gl.longAlns.begin(), gl.longAlns.end(), [](const LongAln& l, const LongAln& rr) { return l.start < rr.start; });
 			}
-			struct Item { uint32_t start, end, score, index; };
-			std::vector<Item> sorted;
+			// SelectAlignments (host/gc_selection.hpp): --E-cutoff first, then GreedyLength (with chaining the whole-read side is always that, src/Aligner.cpp:636-639)
+			// or gc_params::selection_method (without chaining, :927-930); the indices come in the order the reference returns the alignments
+			std::vector<gc::SelectItem> items;
+			for (const LongAln& al : gl.longAlns) items.push_back(gc::SelectItem { al.start, al.end, al.score });
 			const size_t readLen = R->offsets[r + 1] - R->offsets[r];
-			for (uint32_t a = 0; a < gl.longAlns.size(); a++) {
-				// --E-cutoff: SelectECutoff runs before the greedy selection and keeps the list's order (src/AlignmentSelection.cpp:57-61,91-99)
-				if (!evalueModel.keeps(P->e_cutoff, hg.SizeInBP(), readLen, gl.longAlns[a].end - gl.longAlns[a].start, gl.longAlns[a].score)) continue;
-				sorted.push_back(Item { gl.longAlns[a].start, gl.longAlns[a].end, gl.longAlns[a].score, a });
-			}
-			std::sort(sorted.begin(), sorted.end(), [](const Item& l, const Item& rr) {
-				if ((l.end - l.start) > (rr.end - rr.start)) return true;
-				if ((rr.end - rr.start) > (l.end - l.start)) return false;
-				return l.score < rr.score;
-			});
-			auto incompatible = [](const Item& l, const Item& rr) {
-				float minOverlapLen = std::min(l.end - l.start, rr.end - rr.start) * 0.05f;
-				size_t ls = l.start, le = l.end, rs = rr.start, re = rr.end;
-				if (ls > rs) { std::swap(ls, rs); std::swap(le, re); }
-				int overlap = 0;
-				if (le > rs) overlap = (int)(le - rs);
-				return overlap > minOverlapLen;
-			};
-			std::vector<Item> kept;
-			for (const Item& it : sorted) {
-				bool ok = true;
-				for (const Item& k : kept) if (incompatible(it, k)) { ok = false; break; }
-				if (ok) { kept.push_back(it); gl.longSelected.push_back(it.index); }
-			}
+			gl.longSelected = gc::selectAlignments(items, P->colinear_chaining ? (int)gc::SelectGreedyLength : (int)P->selection_method, hg.SizeInBP(), readLen, P->e_cutoff, evalueModel);
 		};
 		if (usePool) pool.run(subset.size(), selectOne); else for (size_t i = 0; i < subset.size(); i++) selectOne(i, 0);
 		auto& D = st->edLong[slot];
 		D.nPairs = 0;
 		D.pairRead.clear();
-		if (!P->edit_distances || subset.empty()) return;
+		if (!P->edit_distances || !P->colinear_chaining || subset.empty()) return;   // (without chaining the reference computes no distance: long_edit_distance stays -1)
 		// edit distance of the best whole-read alignment's path against the read (edlibAlign at src/Aligner.cpp:645)
 		const size_t m = subset.size();
 		PathSeqJob* hJobsPS = D.hJobs.reserve<PathSeqJob>(m);

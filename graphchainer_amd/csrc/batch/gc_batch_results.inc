@@ -224,6 +224,18 @@
 
 	}
 
+	// ---------------- gc_params::colinear_chaining == 0 (--no-colinear-chaining, src/Aligner.cpp:596-600): the fragment extension, anchors, chaining, stitching and the chain's
+	// NW distance are neither launched nor allocated; the result assembly reads all-zero per-read records in their place, so every such array comes back empty
+	void withoutChaining()
+	{
+		zeroWords.assign(n + 1, 0); zeroLongs.assign(2 * n + 4, 0); zeroPerRead.assign(n + 1, make_uint4(0, 0, 0, 0));
+		deviceAnchors = true; anchorTraces = P->keep_traces == 1;   // (the result keeps its one-entry anchor_trace_off)
+		hAnchorPerRead = zeroPerRead.data(); hAnchorOff = zeroLongs.data();
+		denseAnchors = densePathWords = 0;
+		readTies = chainLen = chainStatus = zeroWords.data();
+		chainScore = zeroLongs.data();
+	}
+
 	// ---------------- the pass thread ends (its after-pass stage included)
 	void joinWholeReadPass()
 	{

@@ -126,6 +126,8 @@ struct BatchRun {
 	// stitchAndChainDistances()
 	const PathSeqJob* chainLetterJobs = nullptr;   // per read: where its stitched path's letters are in dChainLetters
 	const char* dChainLetters = nullptr;
+	// withoutChaining()
+	std::vector<uint32_t> zeroWords; std::vector<unsigned long long> zeroLongs; std::vector<uint4> zeroPerRead;
 	// joinWholeReadPass()
 	double tJoined = 0;
 	const LongCell* longCells = nullptr;   // keep_traces: the merged traces in pinned staging (a pageable destination made this copy 2-3 s per 10 k reads)
@@ -158,6 +160,7 @@ struct BatchRun {
 		seeds(); stageDone(0);
 		prepareWholeReadPass(); stageDone(1);
 		startWholeReadPass(); stageDone(2);
+		if (!P->colinear_chaining) { withoutChaining(); joinWholeReadPass(); stageDone(6); encodeOutput(); stageDone(8); assemble(); stageDone(9); st->batchesDone++; return; }
 		fragmentPipeline(); stageDone(3);
 		resultsBack(); stageDone(4);
 		// r5: the trace pool and the anchor path pool are sized by what the stream's batches have used, not by every slot's worst case (a 2 000 x 50 kb batch on a 960 Mbp
@@ -193,6 +196,12 @@ static int alignBatch(const gc_graph* G, const gc_seeder* S, const gc_seeds* H, 
 	if (P->ramp_bandwidth < 0 || (P->ramp_bandwidth != 0 && P->ramp_bandwidth <= P->bandwidth)) return fail(GC_ERR_INVALID, "ramp_bandwidth must be 0 (off) or larger than bandwidth (src/AlignerMain.cpp:380-383)");
 	if (P->max_cells_per_slice < -1) return fail(GC_ERR_INVALID, "max_cells_per_slice must be -1 (unlimited) or >= 0");
 	if (P->force_global != 0 && P->force_global != 1) return fail(GC_ERR_INVALID, "force_global must be 0 or 1");
+	if (P->colinear_chaining != 0 && P->colinear_chaining != 1) return fail(GC_ERR_INVALID, "colinear_chaining must be 0 or 1");
+	if (P->colinear_chaining == 0 && !P->long_pass) return fail(GC_ERR_INVALID, "colinear_chaining == 0 needs long_pass: without chaining the whole-read pass is all there is");
+	if (P->extra_heuristic != 0 && P->extra_heuristic != 1) return fail(GC_ERR_INVALID, "extra_heuristic must be 0 or 1");
+	if (P->selection_method < 0 || P->selection_method > GC_SELECT_ALL) return fail(GC_ERR_INVALID, "selection_method must be one of GC_SELECT_* (0..7)");
+	if (std::isnan(P->seed_extend_density) || (P->seed_extend_density <= 0 && P->seed_extend_density != -1)) return fail(GC_ERR_INVALID, "seed_extend_density must be -1 (all seeds) or > 0 (src/AlignerMain.cpp:405)");
+	if (P->seed_extend_density != -1 && P->colinear_chaining == 1) return fail(GC_ERR_INVALID, "seed_extend_density must be -1 with colinear_chaining == 1: chaining tries all seeds (src/AlignerMain.cpp:204,449-453)");
 	{
 		const gc_capacities& c = P->capacity;
 		if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return fail(GC_ERR_INVALID, "gc_params::capacity.reserved must be 0 (was the struct initialised with gc_params_default?)");

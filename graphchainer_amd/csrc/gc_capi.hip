@@ -447,6 +447,10 @@ void gc_params_default(gc_params* p)
 	p->ramp_bandwidth = 0;          // off (src/AlignerMain.cpp:147)
 	p->max_cells_per_slice = -1;    // unlimited (src/AlignerMain.cpp:149: SIZE_MAX)
 	p->force_global = 0;            // off (src/AlignerMain.cpp:160)
+	p->seed_extend_density = -1;    // all seeds (chaining mode: tryAllSeeds, src/AlignerMain.cpp:204,449-453)
+	p->extra_heuristic = 0;         // off (src/AlignerMain.cpp:170,192)
+	p->colinear_chaining = 1;       // on; 0 is --no-colinear-chaining (src/AlignerMain.cpp:176,198-199)
+	p->selection_method = GC_SELECT_GREEDY_LENGTH;
 }
 
 int gc_graph_create_from_gfa(const char* gfa_path, gc_graph** out)

@@ -13,6 +13,7 @@
 #include "host/gc_output.hpp"
 #include "host/gc_index_cache.hpp"
 #include "host/gc_correctness.hpp"
+#include "host/gc_selection.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>

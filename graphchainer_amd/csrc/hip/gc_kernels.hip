@@ -857,6 +857,17 @@ __device__ inline int onTrace(const LongCell* trace, uint32_t n, uint32_t seqPos
 // sorted by alignmentStart; if the first starts at 0, later alignments whose start is <= the running end extend it;
 // if the union reaches the read's end the minimum seedGoodness of the contributing alignments becomes the cut-off.
 // Visiting in ascending start makes the outcome independent of the order among equal starts, so no sort is needed.
+// The two rules that end AlignOneWay's scan (src/GraphAligner.h:127,132), on the state as it stands before the seed. extraHeuristic: gc_params::extra_heuristic
+// (nondeterministicOptimizations); extendSeeds: the read's seed budget (LongJob::extendSeeds).
+__device__ __forceinline__ bool seedCutEndToEnd(uint32_t goodness, uint32_t e2eScore, uint32_t extraHeuristic)
+{
+	return goodness < e2eScore || (extraHeuristic && goodness == e2eScore);
+}
+__device__ __forceinline__ bool seedCutBudget(uint32_t goodness, uint32_t extended, uint32_t extendSeeds, uint32_t worstExtended, uint32_t extraHeuristic)
+{
+	return extended >= extendSeeds && (extraHeuristic || goodness < worstExtended);
+}
+
 __device__ inline uint32_t endToEndScore(LongAln* mine, uint32_t nAln, uint32_t readLen, uint32_t current)
 {
 	bool anyAtZero = false;
@@ -884,7 +895,7 @@ __device__ inline uint32_t endToEndScore(LongAln* mine, uint32_t nAln, uint32_t 
 template <bool BAND>   // BAND: the band controls of cfg (extendSeedT<.., true>)
 __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTables* __restrict__ ct, const uint8_t* __restrict__ iupac, ExtendConfig cfg,
 	const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, const char* __restrict__ bases, uint64_t rcBase,
-	uint32_t minClusterSize, uint8_t* __restrict__ scratch, uint64_t slabBytes,
+	uint32_t minClusterSize, uint32_t extraHeuristic, uint8_t* __restrict__ scratch, uint64_t slabBytes,
 	LongCell* __restrict__ cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity,
 	LongAln* __restrict__ alns, LongReadResult* __restrict__ results, unsigned long long* __restrict__ counters)
 {
@@ -897,6 +908,7 @@ __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTab
 		LongAln* mine = alns + job.alnBegin;
 		uint32_t nAln = 0, extended = 0, status = 0, ties = 0;
 		uint32_t e2eScore = 0;   // seedScoreForEndToEndAln
+		uint32_t worstExtended = 0;   // worstExtendedSeedScore
 		const int L = (int)job.readLen;
 		// Lanes of a wave must reach the expensive part (the extension) together: a plain loop over seeds would let
 		// every lane extend at a different iteration and serialise the wave's extensions. So each lane first advances
@@ -907,11 +919,12 @@ __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTab
 			LongSeed sd {};
 			for (; status == 0 && si < job.seedEnd && !have; si++) {
 				sd = seeds[si];
-				if (sd.goodness < e2eScore) { si = job.seedEnd; break; }   // aligned end to end, skip the rest (:127-131)
+				if (seedCutEndToEnd(sd.goodness, e2eScore, extraHeuristic)) { si = job.seedEnd; break; }   // aligned end to end, skip the rest (:127-131)
+				if (seedCutBudget(sd.goodness, extended, job.extendSeeds, worstExtended, extraHeuristic)) { si = job.seedEnd; break; }   // enough seeds extended (:132-136)
 				if (sd.clusterSize < minClusterSize) continue;              // :141-146
 				bool skip = false;
 				for (uint32_t a = 0; a < nAln; a++)                          // sloppy overlap rule (:147-161)
-					if (mine[a].start <= sd.seqPos && mine[a].end >= sd.seqPos && mine[a].goodness > sd.goodness) { skip = true; break; }
+					if (mine[a].start <= sd.seqPos && mine[a].end >= sd.seqPos && (extraHeuristic || mine[a].goodness > sd.goodness)) { skip = true; break; }
 				if (skip) continue;
 				int32_t compareNode = g.nodeIDs[sd.node];
 				uint32_t compareOffset = g.nodeOffset[sd.node] + sd.offset;
@@ -925,6 +938,7 @@ __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTab
 			}
 			if (!__any(have)) break;
 			if (!have) continue;
+			worstExtended = sd.goodness;   // :175-176, failed extensions included
 			extended++;
 			// getAlignmentFromSeed (:567-626): backward on revcomp(read[0..p)), forward on read(p..]
 			const int p = (int)sd.seqPos;
@@ -1013,16 +1027,16 @@ __global__ void __launch_bounds__(256) k_long_init(const LongJob* __restrict__ j
 	GC_RAISE_PRIO();
 	uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= nReads) return;
-	LongState st { jobs[r].seedBegin, 0, 0, 0, 0, 0, 0, 0 };
+	LongState st { jobs[r].seedBegin, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 	state[r] = st;
 }
 
 // Skip rules of AlignOneWay for one seed against alignments [aFrom, aTo) of the read (:147-173).
 // Returns 0 extend, 1 skip, 2 the reference asserts.
-__device__ inline int seedSkipped(const DGraph& g, const LongSeed& sd, const LongAln* mine, uint32_t aFrom, uint32_t aTo, const LongCell* cellPool)
+__device__ inline int seedSkipped(const DGraph& g, const LongSeed& sd, const LongAln* mine, uint32_t aFrom, uint32_t aTo, const LongCell* cellPool, uint32_t extraHeuristic)
 {
-	for (uint32_t a = aFrom; a < aTo; a++)                          // sloppy overlap rule (:147-161)
-		if (mine[a].start <= sd.seqPos && mine[a].end >= sd.seqPos && mine[a].goodness > sd.goodness) return 1;
+	for (uint32_t a = aFrom; a < aTo; a++)                          // sloppy overlap rule (:147-161; with extra_heuristic whatever the goodness, :152)
+		if (mine[a].start <= sd.seqPos && mine[a].end >= sd.seqPos && (extraHeuristic || mine[a].goodness > sd.goodness)) return 1;
 	int32_t compareNode = g.nodeIDs[sd.node];
 	uint32_t compareOffset = g.nodeOffset[sd.node] + sd.offset;
 	for (uint32_t a = aFrom; a < aTo; a++) {                        // exactAlignmentPart (:163-173)
@@ -1039,9 +1053,12 @@ __device__ inline int seedSkipped(const DGraph& g, const LongSeed& sd, const Lon
 // when few reads are still active and the chip is idle) further seeds are emitted speculatively: they pass the skip
 // rules against the alignments known now; k_long_merge re-checks each of them against the alignments added before it
 // in the same round, so the outcome equals one-seed-per-round.
+// The two rules that end the scan are ballots on the state the last merge committed: seeds come in falling goodness, so a seed they cut stays cut
+// whatever the candidates in front of it become. The seed budget counts extensions, and the merge may skip a pending candidate, so on the PENDING
+// count the scan only stops emitting (si stays on the seed; the next round sees it with the committed count) - it never ends there.
 #define LONG_MAX_CANDIDATES 8
 __device__ __forceinline__ void longSelectRead(const DGraph& g, const uint32_t r, const uint32_t lane, const LongJob* __restrict__ jobs, const LongSeed* __restrict__ seeds, uint32_t minClusterSize,
-	uint32_t maxCandidates, LongState* __restrict__ state, const LongAln* __restrict__ alns, const LongCell* __restrict__ cellPool, LongWork* __restrict__ work, uint32_t* __restrict__ workLen, uint32_t* __restrict__ candSeed,
+	uint32_t extraHeuristic, uint32_t maxCandidates, LongState* __restrict__ state, const LongAln* __restrict__ alns, const LongCell* __restrict__ cellPool, LongWork* __restrict__ work, uint32_t* __restrict__ workLen, uint32_t* __restrict__ candSeed,
 	unsigned long long* __restrict__ workCount, uint64_t workCapacity)
 {
 	LongState st = state[r];
@@ -1057,10 +1074,11 @@ __device__ __forceinline__ void longSelectRead(const DGraph& g, const uint32_t r
 		const uint32_t idx = si + lane;
 		const bool valid = idx < job.seedEnd;
 		LongSeed sd = seeds[valid ? idx : si];
-		const bool cut = valid && sd.goodness < st.e2eScore;                     // aligned end to end (:127-131)
+		const bool cut = valid && (seedCutEndToEnd(sd.goodness, st.e2eScore, extraHeuristic)                                       // aligned end to end (:127-131)
+			|| seedCutBudget(sd.goodness, st.extended, job.extendSeeds, st.worstExtended, extraHeuristic));                          // enough seeds extended (:132-136)
 		const bool small = sd.clusterSize < minClusterSize;                       // :141-146
 		int sk = 1;
-		if (valid && !cut && !small) sk = seedSkipped(g, sd, mine, 0, st.nAln, cellPool);
+		if (valid && !cut && !small) sk = seedSkipped(g, sd, mine, 0, st.nAln, cellPool, extraHeuristic);
 		const uint64_t cutMask = __ballot(cut), assertMask = __ballot(sk == 2), candMask = __ballot(sk == 0);
 		const uint32_t nValid = job.seedEnd - si < 64 ? job.seedEnd - si : 64;
 		const uint32_t firstCut = cutMask ? (uint32_t)__ffsll((unsigned long long)cutMask) - 1 : 64;
@@ -1069,6 +1087,7 @@ __device__ __forceinline__ void longSelectRead(const DGraph& g, const uint32_t r
 		for (; b < limit; b++) {   // the reference's scan, in seed order (uniform across the wave)
 			if ((assertMask >> b) & 1) { st.status = 1; stop = true; break; }
 			if ((candMask >> b) & 1) {
+				if (nCand > 0 && st.extended + nCand >= job.extendSeeds) { stop = true; break; }   // the pending candidates may fill the budget: no more this round
 				for (uint32_t k = 0; k < LONG_MAX_CANDIDATES; k++) if (k == nCand) cand[k] = si + b;
 				nCand++;
 				if (nCand == maxCandidates) { b++; stop = true; break; }
@@ -1104,13 +1123,13 @@ __device__ __forceinline__ void longSelectRead(const DGraph& g, const uint32_t r
 	if (lane == 0) state[r] = st;
 }
 __global__ void __launch_bounds__(64) k_long_select(DGraph g, const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, uint64_t rcBase, uint32_t minClusterSize,
-	uint32_t maxCandidates, LongState* __restrict__ state, const LongAln* __restrict__ alns, const LongCell* __restrict__ cellPool, LongWork* __restrict__ work, uint32_t* __restrict__ workLen, uint32_t* __restrict__ candSeed,
+	uint32_t extraHeuristic, uint32_t maxCandidates, LongState* __restrict__ state, const LongAln* __restrict__ alns, const LongCell* __restrict__ cellPool, LongWork* __restrict__ work, uint32_t* __restrict__ workLen, uint32_t* __restrict__ candSeed,
 	unsigned long long* __restrict__ workCount, uint64_t workCapacity)
 {
 	GC_RAISE_PRIO();
 	const uint32_t r = blockIdx.x, lane = threadIdx.x;
 	if (r >= nReads) return;
-	longSelectRead(g, r, lane, jobs, seeds, minClusterSize, maxCandidates, state, alns, cellPool, work, workLen, candSeed, workCount, workCapacity);
+	longSelectRead(g, r, lane, jobs, seeds, minClusterSize, extraHeuristic, maxCandidates, state, alns, cellPool, work, workLen, candSeed, workCount, workCapacity);
 }
 
 // LANES = active lanes per wave ("team"). The pass is latency-bound and leaves most of the chip idle, so when there
@@ -1208,7 +1227,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES =
 // writes), the trace -> cell conversion - the bulk of the work, ~1.5 cells per read base - runs 64 cells at a time.
 __device__ __forceinline__ void longMergeRead(const DGraph& g, const uint32_t r, const uint32_t lane, const LongJob* __restrict__ jobs, const LongSeed* __restrict__ seeds, const uint32_t* __restrict__ candSeed,
 	const LongWorkResult* __restrict__ results, const unsigned long long* __restrict__ tracePool,
-	LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity)
+	LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity, uint32_t extraHeuristic)
 {
 	LongState st = state[r];
 	if (st.candCount == 0 || st.status != 0) return;
@@ -1222,11 +1241,14 @@ __device__ __forceinline__ void longMergeRead(const DGraph& g, const uint32_t r,
 		LongSeed sd = seeds[seedIdx];
 		if (c > 0) {
 			// re-check against what this round added before this candidate (the select kernel checked the older alignments)
-			if (sd.goodness < st.e2eScore) { st.si = job.seedEnd; break; }
-			int sk = seedSkipped(g, sd, mine, nAlnAtSelect, st.nAln, cellPool);
+			// (:127 and :132 first, on the state the candidates before this one have left)
+			if (seedCutEndToEnd(sd.goodness, st.e2eScore, extraHeuristic)) { st.si = job.seedEnd; break; }
+			if (seedCutBudget(sd.goodness, st.extended, job.extendSeeds, st.worstExtended, extraHeuristic)) { st.si = job.seedEnd; break; }
+			int sk = seedSkipped(g, sd, mine, nAlnAtSelect, st.nAln, cellPool, extraHeuristic);
 			if (sk == 2) { st.status = 1; break; }
 			if (sk == 1) continue;
 		}
+		st.worstExtended = sd.goodness;   // :175-176, failed extensions included
 		st.extended++;
 		const LongWorkResult rb = results[2 * pair], rf = results[2 * pair + 1];
 		const int p = (int)sd.seqPos;
@@ -1293,12 +1315,12 @@ __device__ __forceinline__ void longMergeRead(const DGraph& g, const uint32_t r,
 
 __global__ void __launch_bounds__(64) k_long_merge(DGraph g, const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, const uint32_t* __restrict__ candSeed,
 	const LongWorkResult* __restrict__ results, const unsigned long long* __restrict__ tracePool,
-	LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity)
+	LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* __restrict__ cellCursor, uint64_t cellCapacity, uint32_t extraHeuristic)
 {
 	GC_RAISE_PRIO();
 	const uint32_t r = blockIdx.x;
 	if (r >= nReads) return;
-	longMergeRead(g, r, threadIdx.x, jobs, seeds, candSeed, results, tracePool, state, alns, cellPool, cellCursor, cellCapacity);
+	longMergeRead(g, r, threadIdx.x, jobs, seeds, candSeed, results, tracePool, state, alns, cellPool, cellCursor, cellCapacity, extraHeuristic);
 }
 
 // Execution order of a round's work items: longest extensions first (a counting sort over 1024 length classes, one block;
@@ -1447,12 +1469,12 @@ void launchLongInit(hipStream_t stream, const LongJob* jobs, uint32_t nReads, Lo
 {
 	if (nReads) hipLaunchKernelGGL(k_long_init, dim3((nReads + 255) / 256), dim3(256), 0, stream, jobs, nReads, state);
 }
-void launchLongSelect(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, uint64_t rcBase, uint32_t minClusterSize, uint32_t maxCandidates,
+void launchLongSelect(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, uint64_t rcBase, uint32_t minClusterSize, uint32_t extraHeuristic, uint32_t maxCandidates,
 	LongState* state, const LongAln* alns, const LongCell* cellPool, LongWork* work, uint32_t* workLen, uint32_t* candSeed, unsigned long long* workCount, uint64_t workCapacity)
 {
 	if (maxCandidates < 1) maxCandidates = 1;
 	if (maxCandidates > LONG_MAX_CANDIDATES) maxCandidates = LONG_MAX_CANDIDATES;
-	if (nReads) hipLaunchKernelGGL(k_long_select, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, rcBase, minClusterSize, maxCandidates, state, alns, cellPool, work, workLen, candSeed, workCount, workCapacity);
+	if (nReads) hipLaunchKernelGGL(k_long_select, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, rcBase, minClusterSize, extraHeuristic, maxCandidates, state, alns, cellPool, work, workLen, candSeed, workCount, workCapacity);
 }
 uint32_t longExtendTeamSize(uint32_t nWork)
 {
@@ -1532,9 +1554,9 @@ void launchBuildFragmentWork(hipStream_t stream, const DGraph& g, const Fragment
 	if (nFrags) hipLaunchKernelGGL(k_build_fragment_work, dim3((nFrags + 255) / 256), dim3(256), 0, stream, g, frags, fragFirstSeed, nFrags, readSeeds, readOffsets, totalBases, splitLen, fragSeeds, work, results);
 }
 void launchLongMerge(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, const uint32_t* candSeed, const LongWorkResult* results,
-	const unsigned long long* tracePool, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity)
+	const unsigned long long* tracePool, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, uint32_t extraHeuristic)
 {
-	if (nReads) hipLaunchKernelGGL(k_long_merge, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, candSeed, results, tracePool, state, alns, cellPool, cellCursor, cellCapacity);
+	if (nReads) hipLaunchKernelGGL(k_long_merge, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, candSeed, results, tracePool, state, alns, cellPool, cellCursor, cellCapacity, extraHeuristic);
 }
 void launchLongOrder(hipStream_t stream, const uint32_t* workLen, const unsigned long long* workCount, uint32_t* order, uint32_t maxLen, uint32_t mode)
 {
@@ -1558,16 +1580,16 @@ void launchLongFinish(hipStream_t stream, uint32_t nReads, const LongState* stat
 uint64_t longSlabBytes(const ExtendConfig& cfg) { return (extendSlabBytes(cfg) + sizeof(TraceCell) * (uint64_t)cfg.maxTrace + 63) & ~63ull; }
 
 void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint8_t* iupac, const ExtendConfig& cfg, const LongJob* jobs, uint32_t nReads,
-	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint8_t* scratch, uint64_t slabBytes,
+	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint32_t extraHeuristic, uint8_t* scratch, uint64_t slabBytes,
 	LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, LongAln* alns, LongReadResult* results, unsigned long long* counters)
 {
 	if (nReads == 0) return;
 	uint32_t blocks = (nReads + 63) / 64;
 	if (cfg.bandControls())
-		hipLaunchKernelGGL(k_long_pass<true>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, scratch, slabBytes,
+		hipLaunchKernelGGL(k_long_pass<true>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, extraHeuristic, scratch, slabBytes,
 			cellPool, cellCursor, cellCapacity, alns, results, counters);
 	else
-		hipLaunchKernelGGL(k_long_pass<false>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, scratch, slabBytes,
+		hipLaunchKernelGGL(k_long_pass<false>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, extraHeuristic, scratch, slabBytes,
 			cellPool, cellCursor, cellCapacity, alns, results, counters);
 }
 

@@ -126,6 +126,8 @@ struct LongJob {     // one read
 	uint32_t readLen;
 	uint32_t seedBegin, seedEnd;    // into the LongSeed array
 	uint32_t alnBegin;              // this read's slots in the alignment output (capacity alnCap)
+	uint32_t extendSeeds;           // the seed budget of AlignOneWay (src/GraphAligner.h:121-122): gc_params::seed_extend_density x readLen + 1, or the read's seed count for -1
+	uint32_t pad;
 };
 
 struct LongCell {    // merged trace cell in the reference's output coordinates
@@ -147,7 +149,7 @@ struct LongAln {     // one accepted alignment, in acceptance order
 struct LongReadResult { uint32_t nAlignments, seedsExtended, status, pad; };   // pad (r5): the read's flatten ties (extensions whose last-slice minimum was tied between nodes)
 
 // round-based whole-read pass: per-read state carried between rounds, and the per-round work items
-struct LongState { uint32_t si, nAln, extended, status, e2eScore, candBegin, candCount, pad1; };   // candBegin/candCount: this round's candidate seeds (pairs of work items)
+struct LongState { uint32_t si, nAln, extended, status, e2eScore, candBegin, candCount, pad1, worstExtended, pad2; };   // worstExtended: goodness of the last seed extended (worstExtendedSeedScore); pad1: the read's flatten ties;   // candBegin/candCount: this round's candidate seeds (pairs of work items)
 struct LongWork {    // one direction of one seed extension
 	uint64_t maskOff;             // word offset of this read+strand's four match-mask bit vectors
 	uint32_t maskWords, startBit; // words per bit vector; read position (on that strand) of row 0
@@ -219,12 +221,12 @@ void launchChain(hipStream_t stream, const DGraph& g, const ReadChainJob* jobs, 
 	uint32_t fewestSlots = 0);   // fewestSlots: the batch's smallest read in anchor slots (0: unknown) - when no read can fit an LDS class that launch is skipped
 
 void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint8_t* iupac, const ExtendConfig& cfg, const LongJob* jobs, uint32_t nReads,
-	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint8_t* scratch, uint64_t slabBytes,
-	LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, LongAln* alns, LongReadResult* results, unsigned long long* counters);
+	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint32_t extraHeuristic, uint8_t* scratch, uint64_t slabBytes,
+	LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, LongAln* alns, LongReadResult* results, unsigned long long* counters);   // extraHeuristic: gc_params::extra_heuristic, here and in the select / merge launches
 uint64_t longSlabBytes(const ExtendConfig& cfg);
 uint64_t longWaveWordsPerLane(const ExtendConfig& cfg);
 void launchLongInit(hipStream_t stream, const LongJob* jobs, uint32_t nReads, LongState* state);
-void launchLongSelect(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, uint64_t rcBase, uint32_t minClusterSize, uint32_t maxCandidates,
+void launchLongSelect(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, uint64_t rcBase, uint32_t minClusterSize, uint32_t extraHeuristic, uint32_t maxCandidates,
 	LongState* state, const LongAln* alns, const LongCell* cellPool, LongWork* work, uint32_t* workLen, uint32_t* candSeed, unsigned long long* workCount, uint64_t workCapacity);
 uint32_t longExtendTeamSize(uint32_t nWork);
 void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint64_t* masks, const ExtendConfig& cfg, const LongWork* work, const uint32_t* order, uint32_t nWork,
@@ -232,7 +234,7 @@ void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 	unsigned long long* nextSlot, uint32_t retryStatus = 0, const unsigned long long* nWorkOnDevice = nullptr, uint32_t* capListOut = nullptr, unsigned long long* capCountOut = nullptr);
 	// nWorkOnDevice: `order` is a list whose length only the device knows (the retry list; then nWork is its upper bound)
 void launchLongMerge(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, const uint32_t* candSeed, const LongWorkResult* results,
-	const unsigned long long* tracePool, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity);
+	const unsigned long long* tracePool, LongState* state, LongAln* alns, LongCell* cellPool, unsigned long long* cellCursor, uint64_t cellCapacity, uint32_t extraHeuristic);
 // ---- path sequences + NW edit distances (gc_editdist.hip)
 struct PathSeqJob {   // one path to spell out as letters
 	uint64_t srcOff;              // first LongCell (whole-read alignment) or first path node (stitched chain)

@@ -99,7 +99,28 @@ typedef struct gc_params {
 	                             *    is not "correct from correct" and does not drop a wrongly aligned end, so a successful extension reaches the read's
 	                             *    (the fragment's) end however poor its score (src/GraphAlignerBitvectorBanded.h:51,120,587-645). With ramp_bandwidth
 	                             *    only the first slice runs at the ramp band (:544: nothing rewinds); max_cells_per_slice acts as without the flag. */
+	double  seed_extend_density; /* --seeds-extend-density, seedExtendDensity of the WHOLE-READ AlignOneWay (src/GraphAligner.h:121-136): the pass stops once
+	                             *    size_t(density x read length + 1) seeds have been extended (failed extensions count) and the next seed scores below the last one
+	                             *    extended. -1 (default): all seeds. <= 0 and not -1, or NaN: GC_ERR_INVALID (src/AlignerMain.cpp:405). With colinear_chaining == 1
+	                             *    anything but -1 is GC_ERR_INVALID: the reference's front end sets tryAllSeeds with chaining (:204) and then overrides the density
+	                             *    (:449-453); this library refuses where the reference overrides. The fragment pass never sees it (its budget is the window's seeds). */
+	int32_t extra_heuristic;    /* --extra-heuristic, nondeterministicOptimizations (src/GraphAligner.h:127,132,152): 0 (default) off, 1 on (else GC_ERR_INVALID).
+	                             *    Whole-read pass only: a seed as good as the end-to-end cut-off ends the scan too (the cut-off starts at 0: a seed of goodness 0
+	                             *    ends it before anything is extended), a full seed budget ends it whatever the next seed's goodness, and a seed inside an
+	                             *    alignment is skipped whatever that alignment's goodness. It has no effect in the fragment pass: that call is not sloppy and its
+	                             *    budget is the window's seed count, so neither :127 nor :132 can fire there and :152 is not reached. */
+	int32_t colinear_chaining;  /* 1 (default): chaining mode. 0: --no-colinear-chaining (src/AlignerMain.cpp:198-199, src/Aligner.cpp:596-600,927-930), plain
+	                             *    GraphAligner: seeding and the whole-read pass alone, then SelectAlignments(selection_method). No fragment extension, anchors,
+	                             *    chains, stitching, NW distances or chained trace are computed: those arrays come back empty (their [n_reads + 1] offsets all 0),
+	                             *    chained_better is 0, chain_edit_distance and long_edit_distance are -1. read_long_off / long_index hold what SelectAlignments
+	                             *    returns, in its order; the writers sort by alignmentStart (:1004). Needs long_pass == 1 (else, or not 0 / 1: GC_ERR_INVALID). */
+	int32_t selection_method;   /* GC_SELECT_* below, the reference's SelectionMethod in its own order (src/AlignmentSelection.h:14-24). Read only when
+	                             *    colinear_chaining == 0; with chaining it has no effect: the whole-read side is always GreedyLength (src/Aligner.cpp:639) and
+	                             *    :904 selects among one alignment. Outside 0..7: GC_ERR_INVALID. */
 } gc_params;
+
+enum { GC_SELECT_GREEDY_LENGTH = 0, GC_SELECT_GREEDY_SCORE = 1, GC_SELECT_GREEDY_E = 2, GC_SELECT_SCHEDULE_INVERSE_E_SUM = 3, GC_SELECT_SCHEDULE_INVERSE_E_PRODUCT = 4,
+       GC_SELECT_SCHEDULE_SCORE = 5, GC_SELECT_SCHEDULE_LENGTH = 6, GC_SELECT_ALL = 7 };
 
 void gc_params_default(gc_params* p);
 

@@ -66,7 +66,8 @@ inline std::vector<int64_t> graphArray(const gc_graph* g, const char* name)
 
 // Once, after gc_graph_create* / gc_seeder_create (src/Aligner.cpp:1137-1162). `params` as INTEGRATION.md §2 fills them; the shim
 // turns on what the replay needs (whole-read pass, traces, seeds). The band controls -B / -C go in params.ramp_bandwidth and
-// params.max_cells_per_slice (src/AlignerMain.cpp:248-249), --global-alignment in params.force_global (:299); AlignOneWay then accepts exactly those values.
+// params.max_cells_per_slice (src/AlignerMain.cpp:248-249), --global-alignment in params.force_global (:299), --seeds-extend-density / --extra-heuristic in
+// params.seed_extend_density / extra_heuristic (:217,247; a density other than -1 needs params.colinear_chaining = 0); AlignOneWay then accepts exactly those values.
 inline void bind(gc_graph* graph, gc_seeder* seeder, gc_params params)
 {
 	Binding& b = binding();
@@ -208,7 +209,7 @@ inline void OrderSeeds(const AlignmentGraph&, std::vector<SeedHit>&) {}
 // starts at `offset` (src/Aligner.cpp:691): `sequence` is then the fragment, and the read it belongs to is the one getSeeds saw last.
 inline AlignmentResult AlignOneWay(const AlignmentGraph&, const std::string& /*seq_id*/, const std::string& sequence, size_t initialBandwidth, size_t rampBandwidth, size_t maxCellsPerSlice, bool /*quietMode*/,
 	bool /*sloppyOptimizations: implied by l < 0, as at src/Aligner.cpp:565,684*/, const std::vector<SeedHit>&, Common::AlignerGraphsizedState&, bool /*lowMemory*/, bool forceGlobal, bool preciseClipping,
-	size_t /*minClusterSize, seedExtendDensity: fixed at bind() time*/, double, bool /*nondeterministicOptimizations*/, double /*preciseClippingIdentityCutoff*/, int Xdropcutoff,
+	size_t /*minClusterSize: fixed at bind() time*/, double seedExtendDensity, bool nondeterministicOptimizations, double /*preciseClippingIdentityCutoff*/, int Xdropcutoff,
 	long long l = -1, long long /*r*/ = -1, long long offset = 0, const std::string* wholeRead = nullptr)
 {
 	// Options of this signature the kernels do not implement are refused, not ignored: a caller that asks for them would silently get the default behaviour otherwise.
@@ -223,6 +224,12 @@ inline AlignmentResult AlignOneWay(const AlignmentGraph&, const std::string& /*s
 	const int64_t cells = maxCellsPerSlice == std::numeric_limits<size_t>::max() ? -1 : (int64_t)maxCellsPerSlice;
 	if (cells != bound.max_cells_per_slice) throw std::invalid_argument("gcshim::AlignOneWay: the cell limit per slice differs from the one given to gcshim::bind()");
 	if ((forceGlobal ? 1 : 0) != (int)bound.force_global) throw std::invalid_argument("gcshim::AlignOneWay: the forced global alignment differs from the one given to gcshim::bind()");
+	// --seeds-extend-density / --extra-heuristic belong to the whole-read call (src/GraphAligner.h:121-161): it accepts the bound values alone. The fragment pass is built for
+	// the chaining presets - every seed of the window is tried (src/AlignerMain.cpp:204,449-453), where the flag cannot change anything - so a fragment call takes the bound
+	// flag and a density of -1 and nothing else.
+	if ((nondeterministicOptimizations ? 1 : 0) != (int)bound.extra_heuristic) throw std::invalid_argument("gcshim::AlignOneWay: nondeterministicOptimizations (--extra-heuristic) differs from the extra_heuristic given to gcshim::bind()");
+	if (l < 0 && seedExtendDensity != bound.seed_extend_density) throw std::invalid_argument("gcshim::AlignOneWay: seedExtendDensity differs from the seed_extend_density given to gcshim::bind()");
+	if (l >= 0 && seedExtendDensity != -1) throw std::invalid_argument("gcshim::AlignOneWay(fragment): the fragment pass tries every seed of its window; seedExtendDensity must be -1");
 	AlignmentResult out;
 	if (l < 0) {
 		const gc_result& r = session().of(sequence);

@@ -1,0 +1,286 @@
+"""tests/graphaligner_model.py (AlignOneWay with --seeds-extend-density / --extra-heuristic, SelectAlignments with its eight methods) on the CPU: at the chaining
+presets it is tests/alignment_model.py and the oracle; the read set of the GPU tests (tests/test_graphaligner_mode_gpu.py imports it from here) gives the new rules
+something to cut, by the model alone; csrc/host/gc_selection.hpp, compiled into a stand-alone program, is held to the model's selection."""
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import graphaligner_model as gm                            # noqa: E402
+import seeding_model                                        # noqa: E402
+from alignment_model import AlignmentModel                  # noqa: E402
+from graphchainer_amd.synth import SynthGraph              # noqa: E402  (test inputs)
+from test_alignment_model import _models                    # noqa: E402
+from test_seeding_model import _inputs, std_sort            # noqa: E402,F401  (the fixture)
+
+DENSITIES = (0.0005, 0.0015, 0.0025)   # size_t(density * length + 1): 1 for every read here; 1 below 667 bases and 2 from there; 1 below 400, 2 below 800 and 3 from there
+
+
+def as_hit(s):
+    return (s["nodeID"], s["nodeOffset"], s["seqPos"], s["matchLen"], s["raw"], int(s["reverse"]))
+
+
+class Inputs:
+    """SynthGraph(40_000, seed=23, repeats=3), the reads of the GPU tests and the models over them, built once. `reads` are seeded by the minimizer index;
+    `seeded_reads` come with caller-supplied hits (`seeded_hits`): the same hit pattern on two copies of the repeat, so that two clusters share one goodness."""
+
+    def __init__(self, directory, std_sort):   # noqa: F811
+        from oracle import Oracle
+        self.std_sort = std_sort
+        self.sg = sg = SynthGraph(40_000, seed=23, repeats=3)
+        self.gfa = os.path.join(str(directory), "g.gfa")
+        sg.write_gfa(self.gfa)
+        bb = self.bb = sg.backbone.tobytes()
+        rng = random.Random(3)
+
+        def rnd(n):
+            return bytes(rng.choice(b"ACGT") for _ in range(n))
+
+        self.oracle = Oracle(self.gfa, long_pass=True)
+        self.graph, self.index = _inputs(self.oracle)
+        base = _models(self.oracle, 10)
+        self.base_model = base
+        self.model = gm.GraphAlignerModel(base.ext, base.g, base.original_size)
+        self.graph_size = int(np.sum(self.oracle.graph_array("nodeLength")))
+        a, b = self._repeat_copies()
+        self.copy_a, self.copy_b = a, b
+        self.seeded_reads = [bb[a:a + 300], bb[a:a + 300] + rnd(300), bb[b + 40:b + 340] + rnd(200)]
+        self.seeded_hits = [self._hits_on_both(a, b, 300, 0), self._hits_on_both(a, b, 300, 0), self._hits_on_both(b + 40, a + 40, 300, 0)]
+        self.reads = sg.sample_reads(3, 700, seed=9, p_del=0.07, p_sub=0.08, p_ins=0.07) + [
+            bb[4000:4500] + bb[20000:20500],                                   # a chimera: two alignments
+            bb[4000:4300] + bb[20000:20300] + bb[33000:33300],                 # three parts
+            bb[7000:7400] + bb[25000:25450],                                   # (two more chimeras: the seed budget needs three reads to cut)
+            bb[2000:2400] + bb[14000:14400] + bb[29000:29400],                 # (three alignments: a budget of 2 cuts as well)
+            bb[30000:30300] + rnd(600),                                        # junk tails: one alignment each
+            rnd(500) + bb[10000:10200],
+            bb[12000:12200] + rnd(300) + bb[12500:12700],
+            bb[15000:15064],
+            bb[17000:17050],
+        ] + self.seeded_reads[:2]                                               # (here as ordinary reads: the minimizers hit every copy of the repeat)
+        self._seeds, self._runs = {}, {}
+
+    def _repeat_copies(self):
+        """Two copies of the repeat, far apart, found in the backbone itself: 300-base windows at most 5 % apart."""
+        arr = np.frombuffer(self.bb, dtype=np.uint8)
+        windows = np.lib.stride_tricks.sliding_window_view(arr, 300)
+        for a in range(0, len(arr) - 300, 250):
+            distance = np.sum(windows != arr[a:a + 300], axis=1)
+            near = [int(b) for b in np.nonzero(distance <= 15)[0] if abs(int(b) - a) > 3000 and 400 < b < len(arr) - 800]
+            if near and 400 < a:
+                return a, near[0]
+        raise AssertionError("no two copies of the repeat")
+
+    def _cell(self, x):
+        """Backbone coordinate -> (segment index = bigraph node id / 2, offset in the segment), or None on a variant site's own base."""
+        sg = self.sg
+        i = int(np.searchsorted(sg.seg_end, x, side="right"))
+        if i >= len(sg.seg_start) or not (sg.seg_start[i] <= x < sg.seg_end[i]):
+            return None
+        node = i + int(np.sum(np.where(sg.is_snp[:i], 2, 1)))           # nodes in file order: a segment, then its site's two alleles or its one insertion
+        return node, x - int(sg.seg_start[i])
+
+    def _hits_on_both(self, a, b, length, raw):
+        """Hits every 30 read bases where the read's base (copy at `a`) equals the other copy's: the read position on its own copy and on the other one."""
+        segments = [l.split(b"\t")[2].strip() for l in open(self.gfa, "rb") if l.startswith(b"S\t")]
+        hits = []
+        for origin in (a, b):
+            for p in range(20, length - 5, 30):
+                ca, cb = self._cell(a + p), self._cell(b + p)
+                if ca is None or cb is None or self.bb[a + p] != self.bb[b + p]:
+                    continue
+                node, off = self._cell(origin + p)
+                assert segments[node][off] == self.bb[a + p]
+                split = self.model.g.unitig_node(2 * node, off)
+                hits.append({"nodeID": node, "nodeOffset": off, "seqPos": p, "matchLen": 15, "raw": raw, "reverse": False, "agNode": split,
+                             "agOffset": off - self.model.g.node_offset[split], "goodness": 0, "cluster": 0})
+        assert len(hits) >= 8 and len(hits) % 2 == 0
+        return hits
+
+    def ordered_seeds(self, seeded, r):
+        key = (seeded, r)
+        if key not in self._seeds:
+            if seeded:
+                hits = [dict(s) for s in self.seeded_hits[r]]
+            else:
+                hits = seeding_model.get_seeds(self.reads[r], self.index, self.graph, 15, 20, 10.0, self.std_sort)
+            self._seeds[key] = seeding_model.order_seeds_by_chaining(hits, self.graph, self.std_sort) if hits else []
+        return self._seeds[key]
+
+    def run(self, seeded, density=-1, flag=False):
+        """Per read (alignments as (start, end, score, trace), seeds extended) of the model; computed once per setting."""
+        key = (seeded, density, flag)
+        if key not in self._runs:
+            out = []
+            reads = self.seeded_reads if seeded else self.reads
+            for r, read in enumerate(reads):
+                seeds = self.ordered_seeds(seeded, r)
+                if not seeds:
+                    out.append(([], 0))
+                    continue
+                alns, extended = self.model.align_one_way(read, seeds, True, seed_extend_density=density, extra_heuristic=flag)
+                out.append(([(a["start"], a["end"], a["score"], [tuple(c) for c in a["trace"]]) for a in alns], extended))
+            self._runs[key] = out
+        return self._runs[key]
+
+    def select(self, alns, method, read_len, e_cutoff=-1):
+        return gm.select_alignments([a[:3] for a in alns], method, self.graph_size, read_len, e_cutoff, self.std_sort)
+
+
+@pytest.fixture(scope="module")
+def inputs(tmp_path_factory, std_sort):   # noqa: F811
+    return Inputs(tmp_path_factory.mktemp("graphaligner"), std_sort)
+
+
+def test_at_the_chaining_presets_the_model_is_the_default_model_and_the_oracle(inputs):
+    """Density -1, flag off: AlignmentModel.align_one_way's alignments and seeds extended, and the oracle's alignments with every trace cell (the oracle reports no
+    count of whole-read seeds extended, so that figure is held to the default model alone); GreedyLength gives the oracle's selection, All the list after the E cut-off."""
+    want = inputs.oracle.align(inputs.reads)
+    got = inputs.run(False)
+    shape = []
+    for r, read in enumerate(inputs.reads):
+        assert not want["failed_assertion"][r]
+        alns, extended = got[r]
+        plain, plain_extended = AlignmentModel.align_one_way(inputs.base_model, read, inputs.ordered_seeds(False, r), True)
+        assert extended == plain_extended
+        assert alns == [(a["start"], a["end"], a["score"], [tuple(c) for c in a["trace"]]) for a in plain]
+        a0, a1 = int(want["read_longall_off"][r]), int(want["read_longall_off"][r + 1])
+        assert len(alns) == a1 - a0, r
+        for k, (start, end, score, trace) in enumerate(alns):
+            a = a0 + k
+            assert (start, end, score) == (int(want["longall_start"][a]), int(want["longall_end"][a]), int(want["longall_score"][a])), (r, k)
+            t0, t1 = int(want["long_trace_off"][a]), int(want["long_trace_off"][a + 1])
+            assert trace == list(zip(want["long_trace_node"][t0:t1].tolist(), want["long_trace_offset"][t0:t1].tolist(), want["long_trace_seqpos"][t0:t1].tolist(),
+                                     [bool(x) for x in want["long_trace_switch"][t0:t1]])), (r, k)
+        s0, s1 = int(want["read_long_off"][r]), int(want["read_long_off"][r + 1])
+        picked = inputs.select(alns, gm.GREEDY_LENGTH, len(read))
+        assert [alns[i][:3] for i in picked] == list(zip(want["long_start"][s0:s1].tolist(), want["long_end"][s0:s1].tolist(), want["long_score"][s0:s1].tolist())), r
+        assert inputs.select(alns, gm.ALL, len(read)) == list(range(len(alns)))
+        ev = gm.EValue()
+        cut = sorted(ev.evalue(inputs.graph_size, len(read), a[1] - a[0], a[2]) for a in alns)
+        if len(cut) > 1 and cut[0] < cut[-1]:
+            assert inputs.select(alns, gm.ALL, len(read), e_cutoff=cut[0]) == [i for i, a in enumerate(alns) if ev.evalue(inputs.graph_size, len(read), a[1] - a[0], a[2]) <= cut[0]]
+        shape.append((len(alns), extended))
+    print("(alignments, seeds extended) per read:", shape)
+    assert min(s[0] for s in shape[3:7]) >= 2 and min(s[0] for s in shape) >= 1     # the chimeras have a second alignment for the seed budget to cut
+
+
+def test_the_seed_budget_has_something_to_cut(inputs):
+    """extendSeeds == 1 (density 0.0005 at these lengths): at least three reads extend fewer seeds than with -1, at least two of them end with another alignment list."""
+    assert {gm.extend_seeds_budget(DENSITIES[0], len(r), 99) for r in inputs.reads} == {1}
+    assert {gm.extend_seeds_budget(d, len(r), 99) for d in DENSITIES for r in inputs.reads} >= {1, 2, 3}
+    full, one = inputs.run(False), inputs.run(False, DENSITIES[0])
+    fewer = [r for r in range(len(inputs.reads)) if one[r][1] < full[r][1]]
+    other = [r for r in fewer if [a[:3] for a in one[r][0]] != [a[:3] for a in full[r][0]]]
+    print("seeds extended with -1:", [x[1] for x in full], "with a budget of 1:", [x[1] for x in one], "fewer:", fewer, "another list:", other)
+    assert len(fewer) >= 3 and len(other) >= 2
+    two = inputs.run(False, DENSITIES[1])
+    assert any(two[r][1] == 2 < full[r][1] for r in range(len(inputs.reads)))       # a budget of 2 cuts a read short
+    assert len(one[3][0]) < len(full[3][0])                 # the chimera loses its second alignment
+
+
+def test_the_extra_heuristic_has_something_to_cut(inputs):
+    """The seeded reads carry one hit pattern on two copies of the repeat: two clusters of one goodness. Off, the second copy's seeds are extended after the first
+    alignment; on, a seed as good as the end-to-end cut-off ends the scan (:127) and a seed inside an alignment is skipped whatever that alignment's goodness (:152)."""
+    for r in range(len(inputs.seeded_reads)):
+        goodness = [s["goodness"] for s in inputs.ordered_seeds(True, r)]
+        assert len(set(goodness)) == 1 and goodness[0] > 0, goodness
+    off, on = inputs.run(True), inputs.run(True, flag=True)
+    differ = [r for r in range(len(inputs.seeded_reads)) if off[r][1] != on[r][1] or [a[:3] for a in off[r][0]] != [a[:3] for a in on[r][0]]]
+    print("off:", [([a[:3] for a in x[0]], x[1]) for x in off], "on:", [([a[:3] for a in x[0]], x[1]) for x in on])
+    assert len(differ) >= 2
+    budget = inputs.run(True, 0.0005, True)                # with the flag a full budget ends the scan whatever the next seed's goodness (:132)
+    assert [x[1] for x in budget] == [1] * len(inputs.seeded_reads)
+    tied = inputs.run(True, 0.0005, False)                 # without it the seeds as good as the last one extended go on
+    assert any(tied[r][1] > 1 for r in range(len(inputs.seeded_reads)))
+
+
+# ---- csrc/host/gc_selection.hpp against the model's selection
+def selection_lists():
+    """0 to 40 alignments per list: exact duplicates, nested and abutting intervals, overlaps on either side of the 5 % cut-off, scores from 0 up. Lengths are
+    multiples of 20 so that 5 % of a length is a whole number, and the scorers' values are either equal (equal length and score) or far apart."""
+    rng = random.Random(11)
+    lists = [[], [(0, 100, 0)], [(0, 200, 3), (0, 200, 3)], [(0, 200, 3), (200, 400, 3)], [(0, 400, 8), (100, 200, 1)],
+             [(0, 200, 4), (190, 390, 4)], [(0, 200, 4), (189, 389, 4)], [(0, 200, 4), (191, 391, 4)], [(0, 100, 0), (100, 200, 0), (200, 300, 0)]]
+    for n in (3, 5, 8, 13, 17, 24, 33, 40):
+        for _ in range(3):
+            alns = []
+            while len(alns) < n:
+                kind = rng.random()
+                length = 20 * rng.randint(1, 40)
+                if alns and kind < 0.15:
+                    alns.append(rng.choice(alns))                                       # an exact duplicate
+                elif alns and kind < 0.3:
+                    s, e, _ = rng.choice(alns)
+                    alns.append((e, e + length, rng.randint(0, length // 4)))           # abutting
+                elif alns and kind < 0.45:
+                    s, e, _ = rng.choice(alns)
+                    if e - s >= 60:
+                        alns.append((s + 20, e - 20, rng.randint(0, (e - s) // 8)))     # nested
+                elif alns and kind < 0.7:
+                    s, e, _ = rng.choice(alns)
+                    shorter = min(e - s, length)
+                    alns.append((e - shorter // 20 - rng.choice((-1, 0, 1)), e - shorter // 20 - rng.choice((-1, 0, 1)) + length, rng.randint(0, length // 4)))   # at the cut-off
+                else:
+                    s = 10 * rng.randint(0, 300)
+                    alns.append((s, s + length, rng.randint(0, length // 4)))
+            lists.append(alns)
+    return lists
+
+
+def _build_selection_program(tmp_path, flags=()):
+    host = os.path.join(ROOT, "graphchainer_amd", "csrc", "host")
+    exe = str(tmp_path / "selection_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *flags, "-I" + host, os.path.join(ROOT, "tests", "selection_host", "selection_test.cpp"),
+                    os.path.join(host, "gc_glue.cpp"), os.path.join(host, "gc_graph.cpp"), "-o", exe, "-lpthread", "-lz"], check=True, timeout=900)
+    return exe
+
+
+def _selection_cases(std_sort, e_cutoffs):   # noqa: F811
+    graph_size, read_size = 40_000, 12_000
+    text, want = [], []
+    for alns in selection_lists():
+        for e_cutoff in e_cutoffs:
+            for method in range(8):
+                text.append(f"{method} {graph_size} {read_size} {e_cutoff!r} {len(alns)} " + " ".join(f"{s} {e} {x}" for s, e, x in alns))
+                want.append(" ".join(str(i) for i in gm.select_alignments(alns, method, graph_size, read_size, e_cutoff, std_sort)))
+    return "\n".join(text) + "\n", want
+
+
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_the_host_selection_equals_the_model(tmp_path, std_sort, sanitize):   # noqa: F811
+    """Every method on every list, without a cut-off and with one (1e-30 drops the short and the poor alignments). The second case is the same program built with
+    the address and undefined-behaviour sanitizers: a stand-alone binary, and it has to run clean."""
+    exe = _build_selection_program(tmp_path, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all") if sanitize else ())
+    text, want = _selection_cases(std_sort, (-1, 1e-30))
+    run = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    got = run.stdout.split("\n")[:-1]
+    assert len(got) == len(want)
+    differ = [i for i in range(len(want)) if got[i].strip() != want[i]]
+    assert not differ, (differ[:5], text.split("\n")[differ[0]], got[differ[0]], want[differ[0]])
+    kept = [len(w.split()) for w in want]
+    assert max(kept) >= 10 and min(kept) == 0
+
+
+def test_gc_params_default_sets_the_chaining_presets():
+    """The four fields sit behind force_global in this order; the defaults are the reference's chaining-mode values."""
+    import ctypes
+    from graphchainer_amd.api import GcParams, load_library
+    p = GcParams()
+    p.seed_extend_density, p.extra_heuristic, p.colinear_chaining, p.selection_method = 0.5, 7, 7, 7
+    load_library().gc_params_default(ctypes.byref(p))
+    assert (p.seed_extend_density, p.extra_heuristic, p.colinear_chaining, p.selection_method) == (-1.0, 0, 1, 0)
+    assert GcParams.force_global.offset < GcParams.seed_extend_density.offset < GcParams.extra_heuristic.offset < GcParams.colinear_chaining.offset < GcParams.selection_method.offset
+    from graphchainer_amd import api
+    assert [api.SELECT_GREEDY_LENGTH, api.SELECT_GREEDY_SCORE, api.SELECT_GREEDY_E, api.SELECT_SCHEDULE_INVERSE_E_SUM, api.SELECT_SCHEDULE_INVERSE_E_PRODUCT,
+            api.SELECT_SCHEDULE_SCORE, api.SELECT_SCHEDULE_LENGTH, api.SELECT_ALL] == list(range(8))
+    header = open(os.path.join(ROOT, "include", "graphchainer_amd.h")).read()
+    for k, name in enumerate(["GREEDY_LENGTH", "GREEDY_SCORE", "GREEDY_E", "SCHEDULE_INVERSE_E_SUM", "SCHEDULE_INVERSE_E_PRODUCT", "SCHEDULE_SCORE", "SCHEDULE_LENGTH", "ALL"]):
+        assert f"GC_SELECT_{name} = {k}" in header
