@@ -73,9 +73,9 @@
 			// by use (device glue; GC_POOLS_WORST_CASE=1 and the host glue path keep the worst case): what the stream's earlier batches needed per slot, with 15 % of slack; a
 			// stream's first batch starts from a low guess (60 trace cells - 8 bytes each since r6, and reserved by rows + 1 + score per extension - and 4 path words per slot of the 103 and 24 the worst case reserves) and
 			// runs its fragment pipeline again with what it asked for when that was short - in the warm-up batch, once per stream - so that the pools are never larger than a batch needs
-			const bool byUse = deviceGlue && !(getenv("GC_POOLS_WORST_CASE") && atoi(getenv("GC_POOLS_WORST_CASE")) == 1);
+			const bool byUse = deviceGlue && !sw.poolsWorstCase;
 			double traceGuess = 60.0, pathGuess = 4.0, slackCells = (double)(1u << 20), slackWords = 4096.0;
-			if (const char* env = getenv("GC_TEST_POOL_FIRST_GUESS")) { traceGuess = std::max(0.0, atof(env)); pathGuess = traceGuess / 8; slackCells = slackWords = 64; }   // test hook: a stream's first batch outgrows its pools
+			if (sw.testPoolFirstGuess) { traceGuess = *sw.testPoolFirstGuess; pathGuess = traceGuess / 8; slackCells = slackWords = 64; }   // test hook: a stream's first batch outgrows its pools
 			traceBudget = byUse ? std::min<uint64_t>(traceWorst, (uint64_t)((double)nSlots * (st->traceCellsPerSlot > 0 ? st->traceCellsPerSlot * 1.15 : traceGuess) + slackCells)) : traceWorst;
 			pathCapacity = byUse ? std::min<uint64_t>(pathWorst, (uint64_t)((double)nSlots * (st->pathWordsPerSlot > 0 ? st->pathWordsPerSlot * 1.15 : pathGuess) + slackWords)) : pathWorst;
 			poolsSized = true;
@@ -86,8 +86,8 @@
 		caps.capTable = std::max(1u, G->maxMpcWidth);
 		caps.capBack = (uint32_t)std::min<uint64_t>(0x7fffffffull, (uint64_t)caps.capAnchors * ((uint64_t)G->maxBackPerNode + G->maxPathsPerNode));   // threshold lists: backward links + paths of the start node
 		res->host_us[0] = nowUs() - tGlue;
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc cpu] %.0f ms of process CPU up to the end of the host glue\n", processCpuMs() - cpuCall);
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] seed expand+order %.1f ms, whole-read setup %.1f ms, fragment windows+arrays %.1f ms (windows %.1f, sizes+buffers %.1f, arrays %.1f)\n", (tOrdered - tGlue) / 1e3, (tLongStarted - tOrdered) / 1e3, (nowUs() - tLongStarted) / 1e3,
+		if (sw.debugTimes) fprintf(stderr, "[gc cpu] %.0f ms of process CPU up to the end of the host glue\n", processCpuMs() - cpuCall);
+		if (sw.debugTimes) fprintf(stderr, "[gc times] seed expand+order %.1f ms, whole-read setup %.1f ms, fragment windows+arrays %.1f ms (windows %.1f, sizes+buffers %.1f, arrays %.1f)\n", (tOrdered - tGlue) / 1e3, (tLongStarted - tOrdered) / 1e3, (nowUs() - tLongStarted) / 1e3,
 			(tWindows - tLongStarted) / 1e3, (tReserved - tWindows) / 1e3, (nowUs() - tReserved) / 1e3);
 
 		// ---------------- K3 / K3b / K4
@@ -107,9 +107,9 @@
 		cfg.maxItems = 72;
 		cfg.maxPending = 48;
 		cfg.maxTrace = 192;
-		cfg.maxItems = (uint32_t)std::max<int64_t>(8, capacityOr("GC_TEST_EXT_MAX_ITEMS", P->capacity.ext_max_items, cfg.maxItems));
-		cfg.maxPending = (uint32_t)std::max<int64_t>(8, capacityOr("GC_TEST_EXT_MAX_PENDING", P->capacity.ext_max_pending, cfg.maxPending));
-		cfg.maxTrace = (uint32_t)std::max<int64_t>(64, capacityOr("GC_TEST_EXT_MAX_TRACE", P->capacity.ext_max_trace, cfg.maxTrace));
+		cfg.maxItems = (uint32_t)std::max<int64_t>(8, capacityOr(sw.testExtMaxItems, P->capacity.ext_max_items, cfg.maxItems));
+		cfg.maxPending = (uint32_t)std::max<int64_t>(8, capacityOr(sw.testExtMaxPending, P->capacity.ext_max_pending, cfg.maxPending));
+		cfg.maxTrace = (uint32_t)std::max<int64_t>(64, capacityOr(sw.testExtMaxTrace, P->capacity.ext_max_trace, cfg.maxTrace));
 		nWork = (uint32_t)(2 * nSlots);
 		uint64_t slabBytes = extendSlabBytes(cfg);
 		uint32_t lanes = extendGridLanes(nWork);
@@ -117,7 +117,7 @@
 		dResults = st->results.reserve<ExtResult>(nWork);
 		// r6: fragments of up to 65 bases (one slice per extension) go through the lockstep kernel (gc_extend_frag.hip); what it declines and every longer fragment through the
 		// plain-layout kernel on per-lane slabs. GC_EXTEND_SLAB=1: the plain-layout kernel for everything, as up to r5 (A/B)
-		const bool fragKernel = P->split_len <= 65 && !(getenv("GC_EXTEND_SLAB") && atoi(getenv("GC_EXTEND_SLAB")) == 1);
+		const bool fragKernel = P->split_len <= 65 && !sw.extendSlab;
 		uint8_t* dScratch = fragKernel ? nullptr : st->scratch.reserve<uint8_t>((uint64_t)lanes * slabBytes);
 		const uint32_t fragWaves = fragKernel ? extendFragWaves() : 0;
 		uint4* dFragItems = fragKernel ? st->fragItems.reserve<uint4>(extendFragScratchBytes(fragWaves) / sizeof(uint4)) : nullptr;
@@ -127,8 +127,8 @@
 		unsigned long long* hFragDeclined = st->hFragDeclined.reserve<unsigned long long>(1);
 		const FragReads fragReads { R->devMasks, R->devMaskOff, R->devMaskWords, R->devOffsets, R->totalBases };
 		if (st->poolsRerun && poolReruns == 0) {   // (the batch after a rerun: see DeviceBuffer::shrinkTo)
-			st->tracePool.shrinkTo(traceBudget * sizeof(PoolCell));
-			st->pathPool.shrinkTo(pathCapacity * sizeof(uint32_t));
+			st->tracePool.shrinkTo(traceBudget * sizeof(PoolCell), sw.testPoolShrinkFloor);
+			st->pathPool.shrinkTo(pathCapacity * sizeof(uint32_t), sw.testPoolShrinkFloor);
 			st->poolsRerun = false;
 		}
 		dTrace = st->tracePool.reserve<PoolCell>(traceBudget, true);
@@ -148,7 +148,7 @@
 		uint32_t fewestSlots = 0xffffffffu;
 		for (uint64_t r = 0; r < n; r++) fewestSlots = std::min(fewestSlots, jobs[r].nSlots);
 		if (!n) fewestSlots = 0;
-		const bool forceChainScratch = getenv("GC_TEST_CHAIN_FORCE_SCRATCH") != nullptr;
+		const bool forceChainScratch = sw.testChainForceScratch;
 		// both launches index the scratch by block (the LDS launch keeps its threshold lists there); a batch of long reads has no LDS launch
 		uint32_t chainBlocks = chainLdsLaunch(fewestSlots, forceChainScratch) ? std::max(chainGridBlocks((uint32_t)n), chainScratchBlocks((uint32_t)n)) : chainScratchBlocks((uint32_t)n);
 		uint8_t* dChainScratch = st->chainScratch.reserve<uint8_t>((uint64_t)std::max(1u, chainBlocks) * chainScratchBytes(caps));
@@ -164,7 +164,7 @@
 		// seed they must extend and queues that seed for the next round (the launches size themselves from counts on the device, no host round
 		// trip); three rounds at most, the last parking round queues everything its fragments have left. On cfg2 the reference extends 47 % of the
 		// seeds the windows hold. GC_EXT_LAZY=0: every seed is extended up front.
-		const bool lazyExtend = !(getenv("GC_EXT_LAZY") && atoi(getenv("GC_EXT_LAZY")) == 0) && nFrags > 0;
+		const bool lazyExtend = sw.extLazy && nFrags > 0;
 		launchBuildFragmentWork(stream, G->dev, dFrags, dFragFirstSeed, (uint32_t)nFrags, dReadSeeds, R->devOffsets, R->totalBases, (uint32_t)P->split_len, dFragSeeds, dWork, lazyExtend ? dResults : nullptr);
 		if (n && !deviceGlue) HIP_CHECK(hipMemcpyAsync(dJobs, jobs, n * sizeof(ReadChainJob), hipMemcpyHostToDevice, stream));
 		mark();   // 2
@@ -174,7 +174,7 @@
 		ExtendConfig big = cfg;
 		auto times16 = [](uint32_t v) { return (uint32_t)std::min<uint64_t>(16ull * v, 0xffffffffull); };   // (saturating: the GC_EXT_* variables are not range-checked like gc_params::capacity)
 		big.maxItems = times16(cfg.maxItems); big.maxPending = times16(cfg.maxPending); big.maxTrace = times16(cfg.maxTrace); big.maxSlices = cfg.maxSlices;
-		if (const char* env = getenv("GC_TEST_EXT_RETRY_MAX_ITEMS")) big.maxItems = (uint32_t)std::max(8, atoi(env));   // test hook: make the retry overflow too
+		if (sw.testExtRetryMaxItems) big.maxItems = *sw.testExtRetryMaxItems;   // test hook: make the retry overflow too
 		const uint32_t retryLanes = 2048;
 		uint8_t* dRetryScratch = st->scratchRetry.reserve<uint8_t>((uint64_t)retryLanes * extendSlabBytes(big));
 		// (r5: every round's extension launches and every k_build_anchors launch sit between an event pair of their own - r4 bracketed "round 0's extensions" and "everything up to
@@ -240,11 +240,11 @@
 			}
 		}
 		mark();   // 4
-		launchChain(stream, G->dev, dJobs, (uint32_t)n, dAnchors, dFrags, dFragStatus, P->split_len, P->split_gap, caps, dChainScratch, dChainOut, dChainLen, dChainScore, dChainStatus, forceChainScratch, fewestSlots);
+		launchChain(stream, G->dev, dJobs, (uint32_t)n, dAnchors, dFrags, dFragStatus, P->split_len, P->split_gap, caps, dChainScratch, dChainOut, dChainLen, dChainScore, dChainStatus, sw.chainPlainScan, forceChainScratch, fewestSlots);
 		mark();   // 5
 		// chain stitching (src/Aligner.cpp:754-822) on the device, right behind the chaining kernel; GC_HOST_STITCH=1 keeps it on the
 		// host workers (the path also taken by reads that do not fit the kernel's tables)
-		deviceStitch = P->stitch && n > 0 && !(getenv("GC_HOST_STITCH") && atoi(getenv("GC_HOST_STITCH")) != 0);
+		deviceStitch = P->stitch && n > 0 && !sw.hostStitch;
 		if (deviceStitch) {
 			stitchDenseCap = stitchDenseWords(nSlots, n);
 			uint32_t* dSlotOf = st->stitchSlotOf.reserve<uint32_t>(std::max<uint64_t>(1, nSlots));
@@ -255,11 +255,10 @@
 			stitchInfo = st->hStitchInfo.reserve<StitchInfo>(n);
 			hStitchCursor = st->hStitchCursor.reserve<unsigned long long>(1);
 			HIP_CHECK(hipMemsetAsync(dCursor, 0, sizeof(unsigned long long), stream));
-			int stitchClass = maxReadLen > 16384 ? 3 : 0;
-			if (const char* env = getenv("GC_STITCH_CLASS")) stitchClass = atoi(env) == 3 ? 3 : 0;
+			const int stitchClass = sw.stitchClass.value_or(maxReadLen > 16384 ? 3 : 0);
 			launchStitch(stream, G->dev, dJobs, (uint32_t)n, dAnchors, dFrags, dFragStatus, dChainOut, dChainLen, dChainStatus, dPathPool, pathCapacity, (long long)P->colinear_gap, dSlotOf,
 				dRegions, dStitchNodes, stitchDenseCap, dCursor, dStitchInfo,
-				(uint32_t)capacityOr("GC_TEST_STITCH_SET_MAX", P->capacity.stitch_set_max, 0), (uint32_t)capacityOr("GC_TEST_STITCH_BFS_CAP", P->capacity.stitch_bfs_cap, 0),
+				(uint32_t)capacityOr(sw.testStitchSetMax, P->capacity.stitch_set_max, 0), (uint32_t)capacityOr(sw.testStitchBfsCap, P->capacity.stitch_bfs_cap, 0),
 				// reads beyond 16 kb: the class whose node set and wide bridge searches live in HBM scratch (r5; gc_stitch.hip) - a 50 kb read's piece holds ~2 500 split nodes, more than the
 				// default class's LDS node set, and every read of config 5 used to be stitched by the host. GC_STITCH_CLASS=0 / 3 forces a class (tests, A/B)
 				stitchClass, stitchClass == 3 ? st->stitchSpill.reserve<unsigned long long>((uint64_t)stitchSpillBlocks((uint32_t)n) * stitchSpillWordsPerBlock()) : nullptr);
@@ -282,7 +281,7 @@
 		// (the cursors count every request, the refused ones included - but a fragment whose extension was refused stops asking, so the need seen is a lower bound: a fifth more, and the loop comes back when that is still short)
 		if (traceShort) traceBudget = std::min<uint64_t>(traceWorst, traceNeed + traceNeed / 5 + (1u << 20));
 		if (pathShort) pathCapacity = std::min<uint64_t>(pathWorst, pathNeed + pathNeed / 5 + 4096);
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc mem] the fragment pipeline runs again: trace pool %.2f G cells needed (now %.2f), anchor path pool %.2f G words needed (now %.2f)\n", traceNeed / 1e9, traceBudget / 1e9, pathNeed / 1e9, pathCapacity / 1e9);
+		if (sw.debugTimes) fprintf(stderr, "[gc mem] the fragment pipeline runs again: trace pool %.2f G cells needed (now %.2f), anchor path pool %.2f G words needed (now %.2f)\n", traceNeed / 1e9, traceBudget / 1e9, pathNeed / 1e9, pathCapacity / 1e9);
 		poolReruns++;
 		st->poolsRerun = true;
 		return true;

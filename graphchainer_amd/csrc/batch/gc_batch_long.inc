@@ -11,7 +11,7 @@
 		// and noisier reads get room in proportion. A read that needs more (a read inside a tandem array collects 40-130) ends with status 3 and runs
 		// again with four times the slots (growAlnSlots), so the common read pays for 32 and no read is cut short at them.
 		firstAlnCap = (uint32_t)std::max<uint64_t>(32, maxReadLen / 512);
-		if (const char* env = getenv("GC_TEST_LONG_MAX_ALIGNMENTS")) firstAlnCap = (uint32_t)std::max(1, std::min(1 << 16, atoi(env)));   // test hook: a tiny first capacity, so that ordinary reads take the rerun too
+		if (sw.testLongMaxAlignments) firstAlnCap = *sw.testLongMaxAlignments;   // test hook: a tiny first capacity, so that ordinary reads take the rerun too
 		alnSlots = n * (uint64_t)firstAlnCap;
 		if (P->long_pass && alnSlots >= 0xffffffffull) throw std::runtime_error("batch too large for the whole-read pass");
 		// Decision for a set of reads whose whole-read alignments are final: the reference's alignment order, the GreedyLength
@@ -27,9 +27,9 @@
 			// merged-trace cells per read base: 8 hold the few partial alignments a 10 kb ONT read collects before its end-to-end one (cfg2 uses ~1.1);
 			// noisy 50 kb CLR reads on a genome with repeats collect 8-9 alignments each and overflowed it (a quarter of the reads flagged, which reads
 			// depending on timing). The stream remembers what its batches needed, and a batch that overflows reruns its pass with three times the room.
-			cellPoolPinned = getenv("GC_TEST_LONG_CELLS_PER_BASE") || P->capacity.long_cells_per_base > 0;
-			uint64_t cellsPerBase = (uint64_t)std::max<int64_t>(2, capacityOr("GC_TEST_LONG_CELLS_PER_BASE", P->capacity.long_cells_per_base, (int64_t)st->longCellsPerBase));
-			if (getenv("GC_TEST_LONG_FORCE_FALLBACK") && !cellPoolPinned) cellsPerBase *= 3;   // (test hook: every read's alignments are made twice, by the rounds and by the fallback kernel, into the same pool)
+			cellPoolPinned = sw.testLongCellsPerBase || P->capacity.long_cells_per_base > 0;
+			uint64_t cellsPerBase = (uint64_t)std::max<int64_t>(2, capacityOr(sw.testLongCellsPerBase, P->capacity.long_cells_per_base, (int64_t)st->longCellsPerBase));
+			if (sw.testLongForceFallback && !cellPoolPinned) cellsPerBase *= 3;   // (test hook: every read's alignments are made twice, by the rounds and by the fallback kernel, into the same pool)
 			cellBudget = cellBudgetFor(cellsPerBase);
 			pool.run(n, [&](size_t r, size_t) {
 				const ReadGlue& gl = glue[r];
@@ -64,9 +64,9 @@
 			// column store of the one-extension-per-wave kernel: the DP keeps every column (16 B) so that the backtrace loads its tiles' columns back instead of
 			// recomputing them (45 % of the kernel's column steps). ~2.1 columns per read row on cfg2; an extension that needs more than this room ends
 			// with EXT_OVERFLOW and its read goes to the plain-layout kernel, which recomputes. GC_TEST_LONG_MAX_COLS=0: no store (the r2 behaviour).
-			lcfg.maxCols = (uint32_t)std::max<int64_t>(0, capacityOr("GC_TEST_LONG_MAX_COLS", P->capacity.long_column_store, (int64_t)(3 * maxReadLen + 4096)));   // (-1 in the parameters, 0 in the environment: no store)
-			lcfg.maxItems = (uint32_t)std::max<int64_t>(64, capacityOr("GC_TEST_LONG_MAX_ITEMS", P->capacity.long_max_items, lcfg.maxItems));
-			if (const char* env = getenv("GC_TEST_LONG_REG_CAP")) lcfg.regCap = (uint32_t)std::max(1, std::min(64, atoi(env)));   // test hook: force the LDS-table retry
+			lcfg.maxCols = (uint32_t)std::max<int64_t>(0, capacityOr(sw.testLongMaxCols, P->capacity.long_column_store, (int64_t)(3 * maxReadLen + 4096)));   // (-1 in the parameters, 0 in the environment: no store)
+			lcfg.maxItems = (uint32_t)std::max<int64_t>(64, capacityOr(sw.testLongMaxItems, P->capacity.long_max_items, lcfg.maxItems));
+			if (sw.testLongRegCap) lcfg.regCap = *sw.testLongRegCap;   // test hook: force the LDS-table retry
 			waveWords = longWaveWordsPerLane(lcfg);
 			if (!deviceGlue) dLongSeeds = st->longSeeds.reserve<LongSeed>(nLongSeeds);
 			dLongJobs = st->longJobs.reserve<LongJob>(n);
@@ -103,14 +103,14 @@
 			dRoundTrace = st->longRoundTrace.reserve<unsigned long long>(roundTraceBudget);
 			// extension scratch: one region per lane of a resident wave (persistent waves fetch work items)
 			// (bounded by a memory budget: 0.8 MB per lane for 10 kb reads, 2.4 MB for 50 kb reads; GC_TEST_LONG_SCRATCH_GB overrides the 48 GB)
-			uint64_t scratchBudget = P->capacity.long_scratch_bytes > 0 ? (uint64_t)P->capacity.long_scratch_bytes : (48ull << 30) / (uint64_t)longTokenCount(n, st->batchesDone, st->fragShare);
-			if (const char* env = getenv("GC_TEST_LONG_SCRATCH_GB")) scratchBudget = (uint64_t)std::max(1, atoi(env)) << 30;
+			uint64_t scratchBudget = P->capacity.long_scratch_bytes > 0 ? (uint64_t)P->capacity.long_scratch_bytes : (48ull << 30) / (uint64_t)longTokenCount(sw.longTokens, n, st->batchesDone, st->fragShare);
+			if (sw.testLongScratchGb) scratchBudget = *sw.testLongScratchGb << 30;
 			// (r5: no more lanes than a round can hold without speculation - two work items per read; the late rounds' speculation stays below that, and a round that does exceed
 			// it runs persistent waves. A 2 000 x 50 kb batch reserved 48 GB for rounds of 4 000 extensions, a 10 k x 10 kb batch 48 GB for 20 000: now 20 and 27 GB)
 			scratchLanes = std::min<uint64_t>(std::min<uint64_t>(workCapacity + 64, 2 * n + 128), std::max<uint64_t>(2048, std::min<uint64_t>(65536 + 64, scratchBudget / (waveWords * 8))));
 			// one pass at a time (the default) works in the device's shared scratch; GC_LONG_TOKEN=0 lets passes overlap, each in its stream's own
 			longScratchWords = scratchLanes * waveWords;
-			shareLongScratch = (getenv("GC_LONG_TOKEN") ? atoi(getenv("GC_LONG_TOKEN")) : 1) >= 1;   // (whoever holds the token owns the scratch)
+			shareLongScratch = sw.shareLongScratch();   // (whoever holds the token owns the scratch)
 			if (!shareLongScratch) dLongScratchOwn = st->longScratch.reserve<unsigned long long>(longScratchWords);
 			// reads whose band did not fit the LDS tables (status 5) are rerun with the plain-layout kernel
 		}
@@ -131,7 +131,7 @@
 		syncStream(ls);
 		const uint64_t asked = hLongSmall[0], bases = std::max<uint64_t>(1, R->totalBases);
 		const uint64_t next = std::max<uint64_t>(st->longCellsPerBase + 2, (asked + asked / 2 + bases - 1) / bases);
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc mem] the whole-read pass runs again: %.2f G merged-trace cells asked for, %.2f G reserved (%llu per read base), now %llu per base\n", asked / 1e9, cellBudget / 1e9, (unsigned long long)st->longCellsPerBase, (unsigned long long)next);
+		if (sw.debugTimes) fprintf(stderr, "[gc mem] the whole-read pass runs again: %.2f G merged-trace cells asked for, %.2f G reserved (%llu per read base), now %llu per base\n", asked / 1e9, cellBudget / 1e9, (unsigned long long)st->longCellsPerBase, (unsigned long long)next);
 		if (next > 256 || cellBudgetFor(next) * sizeof(LongCell) > (64ull << 30)) return false;
 		st->longCellsPerBase = next;
 		cellBudget = cellBudgetFor(next);
@@ -159,7 +159,7 @@
 			total += next;
 		}
 		if (grown.empty()) return false;
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc mem] %zu reads found more whole-read alignments than they had slots for and run again: %llu -> %llu slots in the batch\n", grown.size(), (unsigned long long)alnSlots, (unsigned long long)total);
+		if (sw.debugTimes) fprintf(stderr, "[gc mem] %zu reads found more whole-read alignments than they had slots for and run again: %llu -> %llu slots in the batch\n", grown.size(), (unsigned long long)alnSlots, (unsigned long long)total);
 		if (keep && total * sizeof(LongAln) > st->longAlns.bytes) {
 			DeviceBuffer larger;
 			LongAln* dLarger = larger.reserve<LongAln>(total);
@@ -213,13 +213,10 @@
 			if (round > 0 && lastWork < 8192) maxCand = 8;   // fewer work items than wave slots: the round costs one extension's latency whatever it holds
 			// at most lastWork/2 reads are still active, so this keeps the round within the work arrays (8 per read) and the trace budget (4 seeds' worth per read)
 			if (round > 0 && lastWork > 0) maxCand = (uint32_t)std::min<uint64_t>(maxCand, std::max<uint64_t>(1, (8 * n) / lastWork));
-			if (const char* env = getenv("GC_TEST_LONG_SPECULATE")) maxCand = (uint32_t)std::min(2, std::max(1, atoi(env)));   // test hook: speculate from round 0
+			if (sw.testLongSpeculate) maxCand = *sw.testLongSpeculate;   // test hook: speculate from round 0
 			launchLongSelect(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, R->totalBases, (uint32_t)P->min_cluster_size, (uint32_t)P->extra_heuristic, maxCand, dLongState, dLongAlns, dLongCells, dLongWork, dWorkLen, dCandSeed, cursor, workCapacity);
-			{
-				// execution order: longest extensions first, so the round's tail is made of short ones (GC_TEST_LONG_ORDER=0: as emitted)
-				const char* mode = getenv("GC_TEST_LONG_ORDER");
-				launchLongOrder(q, dWorkLen, cursor, dOrder, (uint32_t)maxReadLen, mode ? (uint32_t)atoi(mode) : 1u);
-			}
+			// execution order: longest extensions first, so the round's tail is made of short ones (GC_TEST_LONG_ORDER=0: as emitted)
+			launchLongOrder(q, dWorkLen, cursor, dOrder, (uint32_t)maxReadLen, sw.testLongOrder);
 			launchPublish(q, cursor, (unsigned long long*)hCursor, 2);
 			const double tWait0 = nowUs();
 			syncStream(q);
@@ -230,9 +227,9 @@
 				longTokenTake();
 				dLongScratch = shareLongScratch ? longScratchOfToken : dLongScratchOwn;
 			}
-			uint32_t team = longExtendTeamSize(nWorkItems);
+			uint32_t team = longExtendTeamSize(nWorkItems, sw.testLongTeam.value_or(0));
 			uint32_t blocks = std::min<uint32_t>((nWorkItems + team - 1) / team, (uint32_t)std::max<uint64_t>(1, (scratchLanes - 64) / team));
-			if (const char* env = getenv("GC_TEST_LONG_MAX_BLOCKS")) blocks = std::min<uint32_t>(blocks, (uint32_t)std::max(1, atoi(env)));   // test hook: force persistent waves
+			if (sw.testLongMaxBlocks) blocks = std::min<uint32_t>(blocks, *sw.testLongMaxBlocks);   // test hook: force persistent waves
 			if (timedRounds >= LONG_EVENT_RING) collect(timedRounds % LONG_EVENT_RING);
 			hipEvent_t ev0 = ring[2 * (timedRounds % LONG_EVENT_RING)], ev1 = ring[2 * (timedRounds % LONG_EVENT_RING) + 1];
 			HIP_CHECK(hipEventRecord(ev0, q));
@@ -264,7 +261,7 @@
 		launchLongFinish(q, (uint32_t)n, dLongState, hLongResults);
 		const double dbgT1 = nowUs();
 		syncStream(q);
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] whole-read rounds: %.1f ms in all, %.1f ms waiting for the rounds' work counts, %.1f ms in the last wait, %d rounds\n", (nowUs() - dbgT0) / 1e3, dbgWaitUs / 1e3, (nowUs() - dbgT1) / 1e3, timedRounds);
+		if (sw.debugTimes) fprintf(stderr, "[gc times] whole-read rounds: %.1f ms in all, %.1f ms waiting for the rounds' work counts, %.1f ms in the last wait, %d rounds\n", (nowUs() - dbgT0) / 1e3, dbgWaitUs / 1e3, (nowUs() - dbgT1) / 1e3, timedRounds);
 		for (int k = std::max(0, timedRounds - LONG_EVENT_RING); k < timedRounds; k++) collect(k % LONG_EVENT_RING);
 	}
 
@@ -272,7 +269,7 @@
 	{
 		syncStream(ls);
 		std::vector<uint32_t> redo;
-		const bool forceAll = getenv("GC_TEST_LONG_FORCE_FALLBACK") != nullptr;   // test hook: run every read through the plain-layout kernel too
+		const bool forceAll = sw.testLongForceFallback;   // test hook: run every read through the plain-layout kernel too
 		// status 5: a slice with more nodes than the wave tables hold; status 2: an extension with more tiles / trace cells than its scratch
 		// (the plain-layout kernel below gets four times the room)
 		for (uint64_t r = 0; r < n; r++) if (hLongResults[r].status == 5 || hLongResults[r].status == 2 || forceAll) redo.push_back((uint32_t)r);
@@ -310,7 +307,7 @@
 				const uint64_t used = std::min<uint64_t>(hLongSmall[0], cellBudget), next = std::min<uint64_t>(256, st->longCellsPerBase * 2);
 				if (next == st->longCellsPerBase || cellBudgetFor(next) * sizeof(LongCell) > (64ull << 30)) { now.swap(full); continue; }
 				cellGrowths++;
-				if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc mem] the plain-layout reruns of %zu reads found the merged-trace pool full: %llu -> %llu cells per read base, %.2f G cells kept\n", refused.size(), (unsigned long long)st->longCellsPerBase, (unsigned long long)next, used / 1e9);
+				if (sw.debugTimes) fprintf(stderr, "[gc mem] the plain-layout reruns of %zu reads found the merged-trace pool full: %llu -> %llu cells per read base, %.2f G cells kept\n", refused.size(), (unsigned long long)st->longCellsPerBase, (unsigned long long)next, used / 1e9);
 				DeviceBuffer larger;
 				LongCell* dLarger = larger.reserve<LongCell>(cellBudgetFor(next), true);
 				if (used) HIP_CHECK(hipMemcpyAsync(dLarger, dLongCells, used * sizeof(LongCell), hipMemcpyDeviceToDevice, ls));
@@ -388,7 +385,7 @@
 		HIP_CHECK(hipMemcpyAsync(dJobsPS, hJobsPS, m * sizeof(PathSeqJob), hipMemcpyHostToDevice, q));
 		launchLongPathSeq(q, G->dev, dJobsPS, (uint32_t)m, dLongCells, dLetters, dLettersLen);
 		auto readLenOf = [R = R](uint32_t r) { return (uint32_t)(R->offsets[r + 1] - R->offsets[r]); };
-		launchEditDistances(D.run, q, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, readLenOf, true);   // (k: the alignment's own bound)
+		launchEditDistances(D.run, q, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, readLenOf, sw.debugTimes, true);   // (k: the alignment's own bound)
 		D.nPairs = nPairs;
 		decisionPtr[slot] = DecisionPointers { hPairs, hOut, dPairs, dOut, dLetters, dLettersLen };
 	}
@@ -399,7 +396,7 @@
 		auto& D = st->edLong[slot];
 		if (!D.nPairs) return;
 		const DecisionPointers& p = decisionPtr[slot];
-		finishEditDistances(D.run, st->longStream, p.hPairs, p.hOut, D.nPairs, p.dPairs, p.dOut, R->devEdReads, R->devBases, R->devEqMasks, p.dLetters, p.dLettersLen);
+		finishEditDistances(D.run, st->longStream, p.hPairs, p.hOut, D.nPairs, p.dPairs, p.dOut, R->devEdReads, R->devBases, R->devEqMasks, p.dLetters, p.dLettersLen, sw.debugTimes);
 		for (uint32_t i = 0; i < D.nPairs; i++) {
 			ReadGlue& gl = glue[D.pairRead[i]];
 			gl.longEditDistance = p.hOut[i];
@@ -422,8 +419,8 @@
 			for (int i = 0; i < 11; i++) fprintf(stderr, "[gc stamps] %-16s %6.2f%%  %.3e lane-cycles\n", names[i], 100.0 * hLongSmall[16 + i] / (total > 0 ? total : 1), (double)hLongSmall[16 + i]);
 		}
 #endif
-		if (const char* env = getenv("GC_TEST_FAIL_LONG")) {   // test hook shared with the oracle: this read's whole-read pass "asserts"
-			long idx = atol(env);
+		if (sw.testFailLong) {   // test hook shared with the oracle: this read's whole-read pass "asserts"
+			const long idx = *sw.testFailLong;
 			if (idx >= 0 && (uint64_t)idx < n) hLongResults[idx].status = 1;
 		}
 		// A whole-read pass that trips one of the reference's live asserts leaves the read with nothing: align_fn's catch sets
@@ -455,14 +452,14 @@
 				TokenHold token;
 				try {
 					HIP_CHECK(hipSetDevice(device));
-					const bool oneAtATime = !(getenv("GC_LONG_TOKEN") && atoi(getenv("GC_LONG_TOKEN")) == 0);   // GC_LONG_TOKEN=0: no token, passes overlap; anything else: one pass at a time (read per batch: the tests switch modes inside one process)
+					const bool oneAtATime = sw.onePassAtATime();   // GC_LONG_TOKEN=0: no token, passes overlap; anything else: one pass at a time
 					const double tTokenAsk = nowUs();
 					bool held = false;   // between take and drop (with or without a token to hold: GC_LONG_TOKEN=0 has none)
 					longTokenTake = [&, device, oneAtATime, tTokenAsk]() {
 						if (held) return;
 						const double tAsk = nowUs();
 						if (oneAtATime) {
-							const int passesSideBySide = longTokenCount(n, st->batchesDone, st->fragShare);
+							const int passesSideBySide = longTokenCount(sw.longTokens, n, st->batchesDone, st->fragShare);
 							token.lock(g_longPassToken[device & 15], passesSideBySide, passesSideBySide == 1);   // (a pass that fills the chip: alone on the device)
 							if (token.slot > 0 && shareLongScratch) {   // the second token's scratch is only grown when the device has the room: otherwise this pass waits for the first token like any other
 								const DeviceBuffer& have = g_longScratch[device & 15].buffer[token.slot];
@@ -486,14 +483,14 @@
 							}
 						}
 						held = true;
-						if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc token] stream %p pass began %.1f asked %.1f got %.1f (call began %.1f)\n", (void*)st, tTokenAsk / 1e3, tAsk / 1e3, nowUs() / 1e3, tCall / 1e3);
+						if (sw.debugTimes) fprintf(stderr, "[gc token] stream %p pass began %.1f asked %.1f got %.1f (call began %.1f)\n", (void*)st, tTokenAsk / 1e3, tAsk / 1e3, nowUs() / 1e3, tCall / 1e3);
 						if (longWallBeginUs == 0.0) longWallBeginUs = nowUs();   // (whole_read_pass_wall: from the pass's first take of the token - a pool rerun takes it again - to its last release)
 					};
 					longTokenDrop = [&]() {
 						if (!held) return;
 						held = false;
 						longWallEndUs = nowUs();
-						if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc token] stream %p released %.1f\n", (void*)st, nowUs() / 1e3);
+						if (sw.debugTimes) fprintf(stderr, "[gc token] stream %p released %.1f\n", (void*)st, nowUs() / 1e3);
 						token.unlock();   // the next batch's pass may start; what follows is this batch's own tail
 					};
 					runLongRounds();

@@ -4,7 +4,7 @@
 	void resultsBack()
 	{
 		// ---------------- results back (pinned staging)
-		deviceAnchors = P->keep_traces != 1 && !(getenv("GC_HOST_ANCHORS") && atoi(getenv("GC_HOST_ANCHORS")) == 1);   // (GC_HOST_ANCHORS=1: test hook, the host's walk over the slots as before r5)
+		deviceAnchors = P->keep_traces != 1 && !sw.hostAnchors;   // (GC_HOST_ANCHORS=1: test hook, the host's walk over the slots as before r5)
 		anchors = st->hAnchors.reserve<AnchorRec>(deviceAnchors ? 1 : nSlots);
 		fragStatus = st->hFragStatus.reserve<uint32_t>(deviceAnchors ? 1 : nFrags);
 		fragExtended = st->hFragExtended.reserve<uint32_t>(deviceAnchors ? 1 : nFrags);
@@ -34,7 +34,7 @@
 		}
 		res->kernel_us[3] = elapsedUs(4, 5);
 		for (int i = 0; i < 8; i++) res->counters[i] = hSmall[8 + i];
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc frag] %llu of %llu fragment extensions handed to the plain-layout kernel\n", hSmall[8 + 6], hSmall[8 + 4]);
+		if (sw.debugTimes) fprintf(stderr, "[gc frag] %llu of %llu fragment extensions handed to the plain-layout kernel\n", hSmall[8 + 6], hSmall[8 + 4]);
 #ifdef GC_FRAG_STAMPS
 		{
 			unsigned long long cyc[8] = { 0 };
@@ -117,7 +117,7 @@
 					return;
 				}
 				hostStitched++;
-				if (deviceStitch && getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc stitch] read %zu goes to the host: reason %u, chain of %u anchors\n", r, stitchInfo[r].status, chainLen[r]);
+				if (deviceStitch && sw.debugTimes) fprintf(stderr, "[gc stitch] read %zu goes to the host: reason %u, chain of %u anchors\n", r, stitchInfo[r].status, chainLen[r]);
 				std::vector<uint32_t> slots;
 				if (deviceAnchors) {   // the read's kept anchors are the dense arrays' [a0, a1): chain index = dense index
 					const uint64_t a0 = hAnchorOff[2 * r], a1 = hAnchorOff[2 * r + 2];
@@ -193,10 +193,10 @@
 			chainLetterJobs = hJobsPS;
 			dChainLetters = dLetters;
 			auto readLenOf = [R = R](uint32_t r) { return (uint32_t)(R->offsets[r + 1] - R->offsets[r]); };
-			launchEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, readLenOf);
+			launchEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, readLenOf, sw.debugTimes);
 			finishChainEditDistances = [=, &pairRead]() {   // waits for the kernels (they run beside the whole-read pass) and reruns the few pairs that need a wider band
-				finishEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen);
-				if (getenv("GC_DEBUG_ED")) for (uint32_t i = 0; i < nPairs && i < 400; i++) {
+				finishEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, sw.debugTimes);
+				if (sw.debugEd) for (uint32_t i = 0; i < nPairs && i < 400; i++) {
 					const uint32_t r = pairRead[i];
 					fprintf(stderr, "[gc ed] read %u len %llu path %llu chain %u scoreSum %u onDevice %d distance %lld\n", r, (unsigned long long)(R->offsets[r + 1] - R->offsets[r]), (unsigned long long)glue[r].stitched.cells,
 						chainLen[r], deviceStitch ? stitchInfo[r].scoreSum : 0u, (int)glue[r].stitchedOnDevice, (long long)hOut[i]);
@@ -218,8 +218,8 @@
 			});
 		}
 		double stitchUs = nowUs() - tStitch;
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc cpu] %.0f ms up to the end of stitching + chain edit distances\n", processCpuMs() - cpuCall);
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] chain stitching + its edit distances %.1f ms (%llu reads stitched on the host)\n", stitchUs / 1e3, (unsigned long long)hostStitched.load());
+		if (sw.debugTimes) fprintf(stderr, "[gc cpu] %.0f ms up to the end of stitching + chain edit distances\n", processCpuMs() - cpuCall);
+		if (sw.debugTimes) fprintf(stderr, "[gc times] chain stitching + its edit distances %.1f ms (%llu reads stitched on the host)\n", stitchUs / 1e3, (unsigned long long)hostStitched.load());
 		res->counters[7] = hostStitched.load();   // reads whose chain was stitched on the host
 
 	}
@@ -246,7 +246,7 @@
 			longThread.join();
 			tJoined = nowUs();
 			cpuJoined = processCpuMs();
-			if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] main thread waited %.1f ms for the whole-read pass\n", (tJoined - tJoin0) / 1e3);
+			if (sw.debugTimes) fprintf(stderr, "[gc times] main thread waited %.1f ms for the whole-read pass\n", (tJoined - tJoin0) / 1e3);
 			if (longError) std::rethrow_exception(longError);
 			res->kernel_us[4] = longExtendUs;
 			res->counters_long[6] = longRounds;
@@ -261,7 +261,7 @@
 			}
 		}
 
-		if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] after the whole-read pass: selection + its edit distances %.1f ms\n", (nowUs() - tJoined) / 1e3);
+		if (sw.debugTimes) fprintf(stderr, "[gc times] after the whole-read pass: selection + its edit distances %.1f ms\n", (nowUs() - tJoined) / 1e3);
 
 	}
 

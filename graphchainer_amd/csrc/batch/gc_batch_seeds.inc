@@ -21,7 +21,7 @@
 		// The glue between the seed lookup and the extension kernels (hit expansion, seed ordering, fragment windows) runs on the device
 		// (gc_seedglue.hip: one wave per read, the reference's three unstable sorts replayed with libstdc++'s own algorithm); GC_DEVICE_GLUE=0
 		// keeps the r2 host path (host/gc_glue.cpp: same results, 1 CPU-second and two bulk transfers per 10 k reads).
-		deviceGlue = H || !(getenv("GC_DEVICE_GLUE") && atoi(getenv("GC_DEVICE_GLUE")) == 0);   // (gc_align_batch_seeded refuses GC_DEVICE_GLUE=0)
+		deviceGlue = H || sw.deviceGlue;   // (gc_align_batch_seeded refuses GC_DEVICE_GLUE=0)
 		if (glue.size() < n) glue.resize(n);
 		gc::KmerMatch* matches = nullptr;
 		tGlue = 0;

@@ -5,6 +5,7 @@ extern "C" {
 
 struct BatchRun {
 	// ---- the call
+	const gc::Switches sw;   // the GC_* switches as they were when the call began (host/gc_switches.hpp)
 	const gc_graph* const G; const gc_seeder* const S; const gc_seeds* const H; gc_stream* const st; const gc_reads* const R; const gc_params* const P; gc_result* const res;   // S: the minimizer index (gc_align_batch), or null and H: the caller's own hits (gc_align_batch_seeded)
 	const double tCall, cpuCall;
 	double cpuJoined;
@@ -132,8 +133,8 @@ struct BatchRun {
 	double tJoined = 0;
 	const LongCell* longCells = nullptr;   // keep_traces: the merged traces in pinned staging (a pageable destination made this copy 2-3 s per 10 k reads)
 
-	BatchRun(const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result* res, double tCall, double cpuCall)
-		: G(G), S(S), H(H), st(st), R(R), P(P), res(res), tCall(tCall), cpuCall(cpuCall), cpuJoined(cpuCall), n(R->offsets.size() - 1), hg(G->host), pool(WorkerPool::batch()), glue(st->glue),
+	BatchRun(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result* res, double tCall, double cpuCall)
+		: sw(sw), G(G), S(S), H(H), st(st), R(R), P(P), res(res), tCall(tCall), cpuCall(cpuCall), cpuJoined(cpuCall), n(R->offsets.size() - 1), hg(G->host), pool(WorkerPool::batch()), glue(st->glue),
 		  stream(st->stream) {}
 	~BatchRun() { if (longThread.joinable()) longThread.join(); }   // (an exception on the main thread must not leave the pass thread behind with dangling state)
 	BatchRun(const BatchRun&) = delete;
@@ -147,7 +148,7 @@ struct BatchRun {
 		res->n_reads = n;
 		tTotal = nowUs();
 		// GC_DEBUG_TIMES: CPU time of THIS thread per stage (the waits poll: what a stage costs the host is not its wall time)
-		const bool cpuStages = getenv("GC_DEBUG_TIMES") != nullptr;
+		const bool cpuStages = sw.debugTimes;
 		double cpuAt = cpuStages ? threadCpuMs() : 0, cpuStage[10] = {}, poolStage[10] = {};
 		uint64_t poolAt = pool.cpuUs.load();
 		const double processAt = processCpuMs();
@@ -190,7 +191,7 @@ struct BatchRun {
 #include "batch/gc_batch_output.inc"   // the chained alignments' traces, the output encoders on the device, the flat result
 };
 
-static int alignBatch(const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result** out)
+static int alignBatch(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result** out)
 {
 	if (P->split_len < 16 || P->split_len > 64 || P->split_gap < 1) return fail(GC_ERR_INVALID, "split_len must be in [16,64] (one 64-row slice per fragment extension) and split_gap >= 1");
 	if (P->ramp_bandwidth < 0 || (P->ramp_bandwidth != 0 && P->ramp_bandwidth <= P->bandwidth)) return fail(GC_ERR_INVALID, "ramp_bandwidth must be 0 (off) or larger than bandwidth (src/AlignerMain.cpp:380-383)");
@@ -226,12 +227,12 @@ static int alignBatch(const gc_graph* G, const gc_seeder* S, const gc_seeds* H, 
 		// (src/Aligner.cpp:904): with a cut-off set the traces are made whatever chain_traces says
 		gc_params effective = *P;
 		if (effective.chain_traces == 0 && effective.e_cutoff >= 0 && effective.stitch && effective.edit_distances) effective.chain_traces = 1;
-		BatchRun batch(G, S, H, st, R, &effective, res, tCall, cpuCall);
+		BatchRun batch(sw, G, S, H, st, R, &effective, res, tCall, cpuCall);
 		batch.run();
 		return (int)GC_OK;
 	});
-	if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] gc_align_batch returned after %.1f ms\n", (nowUs() - tCall) / 1e3);
-	if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc token] stream %p call returned %.1f\n", (void*)st, nowUs() / 1e3);
+	if (sw.debugTimes) fprintf(stderr, "[gc times] gc_align_batch returned after %.1f ms\n", (nowUs() - tCall) / 1e3);
+	if (sw.debugTimes) fprintf(stderr, "[gc token] stream %p call returned %.1f\n", (void*)st, nowUs() / 1e3);
 	if (rc != GC_OK) { gc_result_free(res); return rc; }
 	*out = res;
 	return GC_OK;
@@ -240,7 +241,7 @@ static int alignBatch(const gc_graph* G, const gc_seeder* S, const gc_seeds* H, 
 int gc_align_batch(const gc_graph* G, const gc_seeder* S, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result** out)
 {
 	if (!G || !S || !st || !R || !P || !out) return fail(GC_ERR_INVALID, "null argument");
-	return alignBatch(G, S, nullptr, st, R, P, out);
+	return alignBatch(gc::Switches::fromEnvironment(), G, S, nullptr, st, R, P, out);
 }
 
 int gc_align_batch_seeded(const gc_graph* G, gc_stream* st, const gc_reads* R, const gc_seeds* H, const gc_params* P, gc_result** out)
@@ -248,8 +249,9 @@ int gc_align_batch_seeded(const gc_graph* G, gc_stream* st, const gc_reads* R, c
 	if (!G || !st || !R || !H || !P || !out) return fail(GC_ERR_INVALID, "null argument");
 	if (H->readOffsets != R->offsets) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds were uploaded for another read batch");
 	if (H->device != st->device) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds live on another device than the stream");
-	if (getenv("GC_DEVICE_GLUE") && atoi(getenv("GC_DEVICE_GLUE")) == 0) return fail(GC_ERR_INVALID, "gc_align_batch_seeded needs the device seed glue (GC_DEVICE_GLUE=0 keeps the host glue, which only expands minimizer matches)");
-	return alignBatch(G, nullptr, H, st, R, P, out);
+	const gc::Switches sw = gc::Switches::fromEnvironment();
+	if (!sw.deviceGlue) return fail(GC_ERR_INVALID, "gc_align_batch_seeded needs the device seed glue (GC_DEVICE_GLUE=0 keeps the host glue, which only expands minimizer matches)");
+	return alignBatch(sw, G, nullptr, H, st, R, P, out);
 }
 
 } // extern "C"

@@ -29,11 +29,12 @@ int gc_edit_distance(const char* a, const uint64_t* a_off, const char* b, const 
 		}
 		std::vector<uint64_t> masks(words, 0);
 		for (uint64_t i = 0; i < n_pairs; i++) buildEqMasks(b + b_off[i], reads[i].len, reads[i].words, masks.data() + reads[i].eqOff);
+		const gc::Switches sw = gc::Switches::fromEnvironment();
 		std::vector<EdPair> pairs(n_pairs);
 		for (uint64_t i = 0; i < n_pairs; i++) {
 			uint32_t m = (uint32_t)(a_off[i + 1] - a_off[i]);
 			pairs[i] = EdPair { a_off[i], m, 0, (uint32_t)i, std::max<uint32_t>(64, (m + reads[i].len) / 16) };
-			if (const char* env = getenv("GC_ED_FIRST_K")) pairs[i].k = (uint32_t)std::max(1, atoi(env));   // test hook: the first band, as small as a whole-read alignment's own bound (score + clipped ends + 8)
+			if (sw.edFirstK) pairs[i].k = *sw.edFirstK;   // test hook: the first band, as small as a whole-read alignment's own bound (score + clipped ends + 8)
 		}
 		DeviceBuffer dA, dB, dMasks, dReads, dPairs, dOut;
 		char* pa = dA.reserve<char>(aBytes); char* pb = dB.reserve<char>(bBytes);
@@ -47,8 +48,8 @@ int gc_edit_distance(const char* a, const uint64_t* a_off, const char* b, const 
 		HIP_CHECK(hipMemcpy(pr, reads.data(), n_pairs * sizeof(EdRead), hipMemcpyHostToDevice));
 		EditDistanceRun run;
 		auto readLenOf = [&](uint32_t r) { return reads[r].len; };
-		launchEditDistances(run, nullptr, pairs.data(), out, (uint32_t)n_pairs, pp, po, pr, pb, pm, pa, nullptr, readLenOf, getenv("GC_ED_FIRST_K") != nullptr);   // (the test hook's band picks the kernel class as a whole-read pair's own bound does)
-		finishEditDistances(run, nullptr, pairs.data(), out, (uint32_t)n_pairs, pp, po, pr, pb, pm, pa, nullptr);
+		launchEditDistances(run, nullptr, pairs.data(), out, (uint32_t)n_pairs, pp, po, pr, pb, pm, pa, nullptr, readLenOf, sw.debugTimes, sw.edFirstK.has_value());   // (the test hook's band picks the kernel class as a whole-read pair's own bound does)
+		finishEditDistances(run, nullptr, pairs.data(), out, (uint32_t)n_pairs, pp, po, pr, pb, pm, pa, nullptr, sw.debugTimes);
 		return (int)GC_OK;
 	});
 }
@@ -614,7 +615,7 @@ int gc_graph_array(const gc_graph* G, const char* name, int64_t** out, uint64_t*
 static inline uint32_t hostHashKmer(uint64_t kmer) { kmer *= 0x9E3779B97F4A7C15ull; return (uint32_t)(kmer >> 32); }
 
 // hash table, membership filter and start offsets of a built minimizer index -> HBM
-static void uploadSeeder(gc_seeder* S)
+static void uploadSeeder(gc_seeder* S, std::optional<uint32_t> filterBitsOverride)   // (GC_TEST_SEED_FILTER_BITS)
 {
 	size_t nKeys = S->host.kmers.size();
 	size_t tableSize = 16;
@@ -638,7 +639,7 @@ static void uploadSeeder(gc_seeder* S)
 	// 2^25 bits = 4 MB, which stays in every XCD's L2 (a 32 MB filter missed to the fabric on every probe)
 	uint32_t filterBits = 20;
 	while (filterBits < 28 && (1ull << filterBits) < 8 * nKeys) filterBits++;
-	if (const char* env = getenv("GC_TEST_SEED_FILTER_BITS")) filterBits = (uint32_t)std::max(10, std::min(30, atoi(env)));
+	if (filterBitsOverride) filterBits = *filterBitsOverride;
 	std::vector<uint32_t> filter((1ull << filterBits) / 32, 0);
 	for (size_t i = 0; i < nKeys; i++) { uint32_t fb = (uint32_t)((S->host.kmers[i] * 0xD6E8FEB86659FD93ull) >> (64 - filterBits)); filter[fb >> 5] |= 1u << (fb & 31); }
 	S->dev.filterShift = 64 - filterBits;
@@ -661,10 +662,9 @@ static void uploadSeeder(gc_seeder* S)
 
 // The minimizer index built by the device (gc_minimizer.hip): window scan per bigraph node, one radix sort; the host only cuts the sorted
 // pairs into the k-mer groups. Same index as gc::MinimizerIndex::Build (tests/test_index_cache.py compares them array by array).
-// false = not applicable here (deque longer than the kernel's ring, GC_SEEDER_BUILD=host), the caller builds on the host.
+// false = not applicable here (deque longer than the kernel's ring), the caller builds on the host - as it does under GC_SEEDER_BUILD=host.
 static bool buildSeederOnDevice(const gc_graph* G, gc_seeder* S, size_t k, size_t w, double keepLeastFrequentFraction)
 {
-	if (const char* env = getenv("GC_SEEDER_BUILD")) if (!strcmp(env, "host")) return false;
 	if (w - k + 2 > 32 || k > 15) return false;   // (the device build packs the k-mer into 30 bits of its sort key: longer minimizers are built on the host)
 	const gc::AlignmentGraph& h = G->host;
 	// minimizers ending inside an overlap prefix are skipped (src/MinimizerSeeder.cpp:323-340,369): never the case for the 0M graphs the
@@ -709,8 +709,9 @@ int gc_seeder_create(const gc_graph* g, int32_t k, int32_t w, double keepFractio
 	gc_seeder* S = new gc_seeder();
 	int rc = guarded([&]() {
 		requireDevice();
-		if (!buildSeederOnDevice(g, S, (size_t)k, (size_t)w, keepFraction)) S->host = gc::MinimizerIndex::Build(g->host, (size_t)k, (size_t)w, keepFraction);
-		uploadSeeder(S);
+		const gc::Switches sw = gc::Switches::fromEnvironment();
+		if (sw.seederBuildOnHost || !buildSeederOnDevice(g, S, (size_t)k, (size_t)w, keepFraction)) S->host = gc::MinimizerIndex::Build(g->host, (size_t)k, (size_t)w, keepFraction);
+		uploadSeeder(S, sw.testSeedFilterBits);
 		return (int)GC_OK;
 	});
 	if (rc != GC_OK) { delete S; return rc; }
@@ -781,7 +782,7 @@ int gc_index_load(const char* cache_path, gc_graph** graph_out, gc_seeder** seed
 		uploadGraph(G);
 		if (info.hasSeeder && seeder_out) {
 			if (!seederShapeOk((int64_t)S->host.k, (int64_t)S->host.w)) throw std::runtime_error("index cache holds a minimizer index this library cannot run");
-			uploadSeeder(S);
+			uploadSeeder(S, gc::Switches::fromEnvironment().testSeedFilterBits);
 		} else {
 			delete S;
 			S = nullptr;

@@ -14,6 +14,7 @@
 #include "host/gc_index_cache.hpp"
 #include "host/gc_correctness.hpp"
 #include "host/gc_selection.hpp"
+#include "host/gc_switches.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -82,10 +83,8 @@ struct DeviceBuffer {   // growable device allocation owned by a stream object
 	}
 	void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
 	// a pool that a rerun sized from an overshooting request count comes back to what its batches use: called once, by the batch after the rerun (hipFree drains the device)
-	void shrinkTo(size_t needBytes)
+	void shrinkTo(size_t needBytes, size_t floor)   // (floor: 64 MB; GC_TEST_POOL_SHRINK_FLOOR lets small pools shrink too)
 	{
-		const char* env = getenv("GC_TEST_POOL_SHRINK_FLOOR");   // (test hook, read per call - the tests set it mid-process: small pools shrink too)
-		const size_t floor = env ? (size_t)std::max(0ll, atoll(env)) : (size_t)(64u << 20);
 		if (bytes > needBytes + needBytes / 4 + floor) release();
 	}
 	~DeviceBuffer() { if (ptr) (void)hipFree(ptr); }
@@ -96,7 +95,7 @@ struct DeviceBuffer {   // growable device allocation owned by a stream object
 // seeding, host glue and fragment pipeline overlap the first batch's whole-read pass, and its own pass starts the moment the first
 // one ends - a software pipeline over batches (GC_LONG_TOKEN=0 turns it off).
 // r4 / r5: two tokens per device, each with a scratch of its own, for passes that cannot fill the chip (longTokenCount below)
-inline constexpr int LONG_TOKENS_MAX = 2;
+using gc::LONG_TOKENS_MAX;
 struct PassTokens {
 	std::mutex m;
 	std::condition_variable cv;
@@ -140,9 +139,9 @@ inline constexpr uint64_t LONG_WAVE_SLOTS = 5120;
 // r6: ... and only while the fragment pipeline leaves the device room for it, told by the fragment extensions the stream's previous batch ran per read base (a count, not a time:
 // times under five batches in flight are residencies, and a rule on them would feed back on itself). On a 192 Mbp graph that is 0.09 and two passes side by side gave 4.2 -> 5.0 k
 // reads/s (r5); at 960 Mbp, where chance hits of 15-mers make it 0.42, the second pass that r6's freed memory suddenly had room for cost 4.31 -> 3.63 k (`gpurun_out/r6_cfg5_960p` / `_960q`)
-inline int longTokenCount(uint64_t nReads, uint64_t streamBatchesDone, double extensionsPerBase)
+inline int longTokenCount(std::optional<int> tokensOverride, uint64_t nReads, uint64_t streamBatchesDone, double extensionsPerBase)
 {
-	if (const char* e = getenv("GC_LONG_TOKENS")) return std::max(1, std::min(LONG_TOKENS_MAX, atoi(e)));
+	if (tokensOverride) return *tokensOverride;
 	// (a stream's first batch sizes its buffers - pools that rerun and grow: a second scratch taken while the device still looks empty cost config 5 at 960 Mbp its fifth stream)
 	return streamBatchesDone > 0 && 2 * nReads + 128 <= LONG_WAVE_SLOTS && extensionsPerBase < 0.2 ? 2 : 1;
 }
@@ -164,12 +163,12 @@ inline double processCpuMs() { timespec ts {}; clock_gettime(CLOCK_PROCESS_CPUTI
 // hipEventBlockingSync event (interrupt-driven; measured slower than spinning on this pool's boxes: 255 against 237 ms per batch).
 inline void syncStream(hipStream_t q)
 {
-	static const int mode = getenv("GC_SPIN_SYNC") ? atoi(getenv("GC_SPIN_SYNC")) : 2;
+	const int mode = gc::processSwitches().spinSync;
 	if (mode == 1) { HIP_CHECK(hipStreamSynchronize(q)); return; }
 	if (mode == 2) {
 		// r5: the sleep between polls backs off from 40 us (GC_SYNC_POLL_US) to four times that once a wait has lasted a millisecond: a batch's threads wait ~1 s in all per 150 ms
 		// step, mostly for kernels of tens of milliseconds, and every poll is a runtime call and a nanosleep
-		static const int pollUs = getenv("GC_SYNC_POLL_US") ? std::max(1, atoi(getenv("GC_SYNC_POLL_US"))) : 40;
+		const int pollUs = gc::processSwitches().syncPollUs;
 		int sleepUs = pollUs;
 		for (int spins = 0;; spins++) {
 			const hipError_t e = hipStreamQuery(q);
@@ -195,7 +194,7 @@ inline void syncStream(hipStream_t q)
 // The same for one event (the round token of the whole-read pass is released the moment its extension kernel has finished).
 inline void syncEvent(hipEvent_t ev)
 {
-	static const int pollUs = getenv("GC_SYNC_POLL_US") ? std::max(1, atoi(getenv("GC_SYNC_POLL_US"))) : 40;
+	const int pollUs = gc::processSwitches().syncPollUs;
 	int sleepUs = pollUs;
 	for (int spins = 0;; spins++) {
 		const hipError_t e = hipEventQuery(ev);
@@ -249,10 +248,10 @@ private:
 		// whole process (the whole-read pass's round loop included) then stalls for 50-60 ms. Twice the quota keeps the bursts inside it.
 		const double quota = gc::cpuQuota();
 		if (quota > 0) n = std::min<size_t>(n, std::max<size_t>(4, (size_t)(2 * quota + 0.5)));
-		if (const char* env = getenv("GC_HOST_THREADS")) n = (size_t)std::max(1, atoi(env));
+		if (gc::processSwitches().hostThreads) n = *gc::processSwitches().hostThreads;
 		if (kind == 1) {
 			n = std::min<size_t>(n, quota > 0 ? std::max<size_t>(4, (size_t)(quota / 2 + 0.5)) : 8);
-			if (const char* env = getenv("GC_BATCH_THREADS")) n = (size_t)std::max(1, atoi(env));
+			if (gc::processSwitches().batchThreads) n = *gc::processSwitches().batchThreads;
 		}
 		for (size_t t = 1; t < n; t++) workers.emplace_back([this, t]() { loop(t); });
 	}
@@ -265,7 +264,7 @@ private:
 	void work(size_t id)
 	{
 		const size_t chunk = 4;
-		static const bool account = getenv("GC_DEBUG_TIMES") != nullptr;
+		const bool account = gc::processSwitches().debugTimes;
 		const double cpu0 = account ? threadCpuMs() : 0;
 		try {
 			for (size_t i; (i = next.fetch_add(chunk)) < total;)
@@ -333,8 +332,8 @@ struct ResultBlockCache {
 	static constexpr size_t HEADER = 64, MAX_HELD = 24ull << 30;
 	// test hooks: GC_RESULT_CACHE_MIN=bytes recycles arrays from that size on (default 32 MB), GC_TEST_RESULT_CACHE_POISON=1 fills every array with 0xA5 when it is handed out -
 	// together they show any reader that counts on an array's unwritten part being zero (fresh pages are, recycled ones are not)
-	const size_t BIG = getenv("GC_RESULT_CACHE_MIN") ? (size_t)std::max(1ll, atoll(getenv("GC_RESULT_CACHE_MIN"))) : (32ull << 20);
-	const bool poison = getenv("GC_TEST_RESULT_CACHE_POISON") != nullptr;
+	const size_t BIG = gc::processSwitches().resultCacheMin;
+	const bool poison = gc::processSwitches().testResultCachePoison;
 	std::mutex mutex;
 	std::vector<std::pair<char*, size_t>> blocks;   // (base, capacity in bytes without the header)
 	size_t held = 0;
@@ -656,7 +655,7 @@ inline void buildIupacTable(uint8_t* t)
 	set("Bb", 2 | 4 | 8); set("Dd", 1 | 4 | 8); set("Hh", 1 | 2 | 8); set("Vv", 1 | 2 | 4); set("Nn", 15);
 }
 
-inline void uploadGraph(gc_graph* G)
+inline void uploadGraph(gc_graph* G)   // (reads GC_TEST_UPLOAD_SLICE)
 {
 	const gc::AlignmentGraph& h = G->host;
 	size_t n = h.NodeSize();
@@ -765,8 +764,7 @@ inline void uploadGraph(gc_graph* G)
 		};
 		uint32_t *dBackNode = nullptr, *dBackPath = nullptr, *dBackPos = nullptr;
 		for (uint32_t** p : { &dBackNode, &dBackPath, &dBackPos }) { HIP_CHECK(hipMalloc((void**)p, std::max<size_t>(nBack, 1) * sizeof(uint32_t))); G->allocations.push_back(*p); }
-		size_t sliceLinks = (size_t)64 << 20;
-		if (const char* env = getenv("GC_TEST_UPLOAD_SLICE")) sliceLinks = (size_t)std::max(1, atoi(env));   // test hook: many small slices
+		const size_t sliceLinks = gc::Switches::fromEnvironment().testUploadSlice;   // (test hook: many small slices)
 		std::vector<uint32_t> backNode, backPath, backPos;
 		for (size_t first = 0; first < n;) {
 			size_t last = first;
@@ -843,9 +841,9 @@ inline void uploadGraph(gc_graph* G)
 }
 
 // One capacity: the GC_* environment variable (experiments, test hooks) wins over gc_params::capacity, 0 there means automatic.
-inline int64_t capacityOr(const char* envName, int64_t param, int64_t automatic)
+inline int64_t capacityOr(std::optional<int64_t> env, int64_t param, int64_t automatic)
 {
-	if (const char* env = getenv(envName)) return atoll(env);
+	if (env) return *env;
 	return param != 0 ? param : automatic;
 }
 
@@ -954,7 +952,7 @@ inline uint32_t editDistanceUnit(uint32_t k, uint32_t readLen)
 inline void createStream(hipStream_t* q) { HIP_CHECK(hipStreamCreateWithFlags(q, hipStreamNonBlocking)); }
 
 inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair* hPairs, int64_t* hOut, uint32_t nPairs, EdPair* dPairs, int64_t* dOut, const EdRead* dReads, const char* dBases,
-	const uint64_t* dEqMasks, const char* dLetters, const uint32_t* dLettersLen, const std::function<uint32_t(uint32_t)>& readLen, bool kIsBound = false)
+	const uint64_t* dEqMasks, const char* dLetters, const uint32_t* dLettersLen, const std::function<uint32_t(uint32_t)>& readLen, bool debugTimes, bool kIsBound = false)
 {
 	if (!nPairs) return;
 	if (!run.ready) HIP_CHECK(hipEventCreateWithFlags(&run.ready, hipEventDisableTiming));
@@ -964,8 +962,6 @@ inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 	uint32_t count[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
 	uint32_t blockThreads = 64;        // class 7: threads of a workgroup = the 64-row blocks of the class's longest read
 	uint32_t* begin = run.begin;
-	static const bool halfWaves = !(getenv("GC_ED_HALF") && atoi(getenv("GC_ED_HALF")) == 0);
-	static const bool thirdWaves = halfWaves && !(getenv("GC_ED_THIRD") && atoi(getenv("GC_ED_THIRD")) == 0);
 	for (uint32_t i = 0; i < nPairs; i++) {
 		const uint32_t len = readLen(hPairs[i].read);
 		lenOf[i] = len;
@@ -973,12 +969,12 @@ inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 		uint32_t unit = editDistanceUnit(hPairs[i].k, len), c = 0;
 		while ((1u << c) < unit) c++;
 		c += 2;                                                               // classes 2..6: one pair per wave, units of 1..16 blocks
-		if (halfWaves && unit == 1 && hPairs[i].k < editDistanceMaxK(0) && len <= 131072) {   // class 1: two pairs per wave (small first band)
+		if (unit == 1 && hPairs[i].k < editDistanceMaxK(0) && len <= 131072) {   // class 1: two pairs per wave (small first band)
 			c = 1;
 			// class 0 (r4): three pairs per wave, bands below 1290 - for pairs whose k is a bound (a whole-read pair's k comes from the alignment itself: one sweep, always enough).
 			// A chain pair's k is a guess; tried there whenever length difference + 10 % of the shorter sequence fit, 45 % of cfg2's chain pairs (distances 1 100-1 300) came back
 			// for a second sweep and the two kernels together took 352 ms per nine batches against 311 (`gpurun_out/r4_ring`): chain pairs stay with two per wave
-			if (thirdWaves && kIsBound && len <= 65536 && hPairs[i].k < editDistanceTeamMaxK(3)) c = 0;
+			if (kIsBound && len <= 65536 && hPairs[i].k < editDistanceTeamMaxK(3)) c = 0;
 			// a sweep of these kernels takes columns + units steps whatever the band, as long as the band fits the team's lanes - so the first guess may as well be the widest band that
 			// does (any k >= the distance gives the distance): a chain pair whose guess (length difference + 14 %) was a little short used to pay a failed sweep here, a second
 			// failed sweep with the same guess in the one-pair-per-wave kernel and a third with the doubled band (r3)
@@ -986,8 +982,7 @@ inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 		}
 		// class 7 (r4): a band of half the read or more covers most of the matrix - a chain whose path spells a fraction of its read, a whole-read alignment of a sliver: the pair
 		// gets a workgroup with one thread per 64-row block and the whole matrix (exact, no retry) instead of one wave with up to sixteen blocks per lane and step
-		static const bool blockPairs = !(getenv("GC_ED_BLOCK") && atoi(getenv("GC_ED_BLOCK")) == 0);
-		if (blockPairs && len >= 1 && len <= editDistanceBlockMaxRows() && 2ull * askedK >= len) { hPairs[i].k = askedK; c = 7; blockThreads = std::max(blockThreads, (len + 63u) / 64u); }
+		if (len >= 1 && len <= editDistanceBlockMaxRows() && 2ull * askedK >= len) { hPairs[i].k = askedK; c = 7; blockThreads = std::max(blockThreads, (len + 63u) / 64u); }
 		cls[i] = c;
 		count[c]++;
 	}
@@ -1012,10 +1007,10 @@ inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 		else launchEditDistance(run.streams[c], 1u << (c - 2), dPairs + begin[c], count[c], dReads, dBases, dEqMasks, dLetters, dLettersLen, dOut + begin[c]);
 		HIP_CHECK(hipMemcpyAsync(hOut + begin[c], dOut + begin[c], (size_t)count[c] * sizeof(int64_t), hipMemcpyDeviceToHost, run.streams[c]));
 	}
-	if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] edit distance classes (3 per wave, 2 per wave, units 1..16, workgroup per pair): %u %u %u %u %u %u %u %u\n", count[0], count[1], count[2], count[3], count[4], count[5], count[6], count[7]);
+	if (debugTimes) fprintf(stderr, "[gc times] edit distance classes (3 per wave, 2 per wave, units 1..16, workgroup per pair): %u %u %u %u %u %u %u %u\n", count[0], count[1], count[2], count[3], count[4], count[5], count[6], count[7]);
 }
 inline void finishEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair* hPairs, int64_t* hOut, uint32_t nPairs, EdPair* dPairs, int64_t* dOut, const EdRead* dReads, const char* dBases,
-	const uint64_t* dEqMasks, const char* dLetters, const uint32_t* dLettersLen)
+	const uint64_t* dEqMasks, const char* dLetters, const uint32_t* dLettersLen, bool debugTimes)
 {
 	if (!nPairs) return;
 	for (auto& q : run.streams) if (q) syncStream(q);
@@ -1026,7 +1021,7 @@ inline void finishEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 	}
 	std::vector<EdPair> sub;
 	std::vector<int64_t> subOut;
-	if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc times] edit distance reruns: %zu of %u pairs\n", todo.size(), nPairs);
+	if (debugTimes) fprintf(stderr, "[gc times] edit distance reruns: %zu of %u pairs\n", todo.size(), nPairs);
 	// unit 0 here: the two-pairs-per-wave kernel for what the three-pairs-per-wave kernel handed back (its pairs come first in the grouped order)
 	for (uint32_t unit = 0; unit <= 16 && !todo.empty(); unit = unit ? unit * 2 : 1) {   // (unit 1 for what the two-pairs-per-wave kernel handed back)
 		std::vector<uint32_t> later;
@@ -1038,8 +1033,7 @@ inline void finishEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 		}
 		// r4: from unit 4 on a rerun goes to the workgroup-per-pair kernel when the read fits it (<= 65 536 bases): columns + blocks steps whatever the band, exact - a pair that has failed the
 		// narrower bands is far from its path, and the wide units give it one wave with 4-16 blocks per lane and step (config 5: 145 ms at unit 8, 304 ms at unit 16 per launch)
-		static const bool blockReruns = !(getenv("GC_ED_BLOCK") && atoi(getenv("GC_ED_BLOCK")) == 0);
-		if (unit >= 4 && blockReruns) {
+		if (unit >= 4) {
 			std::vector<uint32_t> wide, rest;
 			uint32_t threads = 64;
 			for (uint32_t i : todo) {

@@ -1442,16 +1442,15 @@ uint32_t chainScratchBlocks(uint32_t nReads) { return nReads < 1024 ? nReads : 1
 bool chainLdsLaunch(uint32_t fewestSlots, bool forceScratch) { return forceScratch || fewestSlots <= 2 * CHAIN_LDS_ANCHORS; }
 
 void launchChain(hipStream_t stream, const DGraph& g, const ReadChainJob* jobs, uint32_t nReads, const AnchorRec* anchors, const Fragment* frags, const uint32_t* fragStatus,
-	int32_t splitLen, int32_t splitGap, ChainCaps caps, uint8_t* scratch, uint32_t* chainOut, uint32_t* chainLen, unsigned long long* chainScore, uint32_t* chainStatus, bool forceScratch, uint32_t fewestSlots)
+	int32_t splitLen, int32_t splitGap, ChainCaps caps, uint8_t* scratch, uint32_t* chainOut, uint32_t* chainLen, unsigned long long* chainScore, uint32_t* chainStatus, bool plainScan, bool forceScratch, uint32_t fewestSlots)
 {
 	if (nReads == 0) return;
 	// (r5) fewestSlots: the batch's smallest read in anchor slots. When even that one is beyond twice the large LDS class, the LDS launch would send every read on - 2 048 blocks of
 	// 53 KB that waited up to 570 ms for LDS room among config 5's kernels to do nothing (`gpurun_out/r5_cfg5_c`): skipped, the scratch launch takes every read
 	const bool ldsLaunch = chainLdsLaunch(fewestSlots, forceScratch);
-	const uint32_t scratchFlags = ((getenv("GC_CHAIN_PLAIN_SCAN") && atoi(getenv("GC_CHAIN_PLAIN_SCAN")) == 1) ? 2u : 0u) | (ldsLaunch ? 0u : 4u);
+	const uint32_t scratchFlags = (plainScan ? 2u : 0u) | (ldsLaunch ? 0u : 4u);
 	// the half-size LDS class when the batch's largest read fits it (its entries are checked per read: a read with more goes to the scratch launch below)
-	static const bool largeOnly = getenv("GC_CHAIN_LARGE") && atoi(getenv("GC_CHAIN_LARGE"));   // (the r3 launch, for A/B)
-	const bool small = !largeOnly && caps.capAnchors <= CHAIN_LDS_ANCHORS / 2 && caps.capTable <= CHAIN_LDS_WIDTH / 2;
+	const bool small = caps.capAnchors <= CHAIN_LDS_ANCHORS / 2 && caps.capTable <= CHAIN_LDS_WIDTH / 2;
 	if (!ldsLaunch) {}
 	else if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<2>), dim3(chainGridBlocks(nReads)), dim3(64), 0, stream, g, jobs, nReads, anchors, frags, fragStatus, splitLen, splitGap, caps, scratch, chainScratchBytes(caps), chainOut, chainLen, chainScore, chainStatus, forceScratch ? 1u : 0u);
 	else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<1>), dim3(chainGridBlocks(nReads)), dim3(64), 0, stream, g, jobs, nReads, anchors, frags, fragStatus, splitLen, splitGap, caps, scratch, chainScratchBytes(caps), chainOut, chainLen, chainScore, chainStatus, forceScratch ? 1u : 0u);
@@ -1476,12 +1475,12 @@ void launchLongSelect(hipStream_t stream, const DGraph& g, const LongJob* jobs, 
 	if (maxCandidates > LONG_MAX_CANDIDATES) maxCandidates = LONG_MAX_CANDIDATES;
 	if (nReads) hipLaunchKernelGGL(k_long_select, dim3(nReads), dim3(64), 0, stream, g, jobs, nReads, seeds, rcBase, minClusterSize, extraHeuristic, maxCandidates, state, alns, cellPool, work, workLen, candSeed, workCount, workCapacity);
 }
-uint32_t longExtendTeamSize(uint32_t nWork)
+uint32_t longExtendTeamSize(uint32_t nWork, uint32_t teamOverride)
 {
 	// Measured on MI355X (cfg2, 20k extensions in the first round): 1 lane per wave 260 ms, 2 lanes 352 ms, 4 lanes 397 ms,
 	// 8 lanes 555 ms for the whole pass. The extension core is branchy serial code; lanes sharing a wave pay for the
 	// union of their paths, and the chip has far more wave slots than a round has extensions. GC_TEST_LONG_TEAM overrides.
-	if (const char* env = getenv("GC_TEST_LONG_TEAM")) { int v = atoi(env); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) return (uint32_t)v; }
+	if (teamOverride) return teamOverride;
 	(void)nWork;
 	return 1;
 }

@@ -217,8 +217,8 @@ uint32_t chainGridBlocks(uint32_t nReads);
 uint32_t chainScratchBlocks(uint32_t nReads);
 bool chainLdsLaunch(uint32_t fewestSlots, bool forceScratch);   // does launchChain run its LDS launch for a batch whose smallest read has this many anchor slots?
 void launchChain(hipStream_t stream, const DGraph& g, const ReadChainJob* jobs, uint32_t nReads, const AnchorRec* anchors, const Fragment* frags, const uint32_t* fragStatus,
-	int32_t splitLen, int32_t splitGap, ChainCaps caps, uint8_t* scratch, uint32_t* chainOut, uint32_t* chainLen, unsigned long long* chainScore, uint32_t* chainStatus, bool forceScratch = false,
-	uint32_t fewestSlots = 0);   // fewestSlots: the batch's smallest read in anchor slots (0: unknown) - when no read can fit an LDS class that launch is skipped
+	int32_t splitLen, int32_t splitGap, ChainCaps caps, uint8_t* scratch, uint32_t* chainOut, uint32_t* chainLen, unsigned long long* chainScore, uint32_t* chainStatus, bool plainScan, bool forceScratch = false,
+	uint32_t fewestSlots = 0);   // plainScan: GC_CHAIN_PLAIN_SCAN=1; fewestSlots: the batch's smallest read in anchor slots (0: unknown) - when no read can fit an LDS class that launch is skipped
 
 void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint8_t* iupac, const ExtendConfig& cfg, const LongJob* jobs, uint32_t nReads,
 	const LongSeed* seeds, const char* bases, uint64_t rcBase, uint32_t minClusterSize, uint32_t extraHeuristic, uint8_t* scratch, uint64_t slabBytes,
@@ -228,7 +228,7 @@ uint64_t longWaveWordsPerLane(const ExtendConfig& cfg);
 void launchLongInit(hipStream_t stream, const LongJob* jobs, uint32_t nReads, LongState* state);
 void launchLongSelect(hipStream_t stream, const DGraph& g, const LongJob* jobs, uint32_t nReads, const LongSeed* seeds, uint64_t rcBase, uint32_t minClusterSize, uint32_t extraHeuristic, uint32_t maxCandidates,
 	LongState* state, const LongAln* alns, const LongCell* cellPool, LongWork* work, uint32_t* workLen, uint32_t* candSeed, unsigned long long* workCount, uint64_t workCapacity);
-uint32_t longExtendTeamSize(uint32_t nWork);
+uint32_t longExtendTeamSize(uint32_t nWork, uint32_t teamOverride);   // teamOverride: GC_TEST_LONG_TEAM, 0 without one
 void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint64_t* masks, const ExtendConfig& cfg, const LongWork* work, const uint32_t* order, uint32_t nWork,
 	unsigned long long* scratch, uint32_t lanes, uint32_t blocks, unsigned long long* tracePool, unsigned long long* traceCursor, uint64_t traceCapacity, LongWorkResult* results, unsigned long long* counters,
 	unsigned long long* nextSlot, uint32_t retryStatus = 0, const unsigned long long* nWorkOnDevice = nullptr, uint32_t* capListOut = nullptr, unsigned long long* capCountOut = nullptr);

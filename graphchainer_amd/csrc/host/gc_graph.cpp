@@ -2,6 +2,7 @@
 // Restates the behaviour of the reference's loaders; every function cites the lines it follows.
 #include "gc_graph.hpp"
 #include "gc_stageclock.hpp"
+#include "gc_switches.hpp"
 #include <cstring>
 #include <cstdio>
 #include <chrono>
@@ -137,7 +138,7 @@ GfaGraph GfaGraph::LoadFromFile(const std::string& path)
 	if (!f.good()) throw std::runtime_error("cannot open GFA file " + path);
 	auto t0 = std::chrono::steady_clock::now();
 	GfaGraph g = LoadFromStream(f);
-	if (getenv("GC_DEBUG_TIMES")) fprintf(stderr, "[gc build] %-28s %8.1f ms\n", "GFA parse", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+	if (Switches::fromEnvironment().debugTimes) fprintf(stderr, "[gc build] %-28s %8.1f ms\n", "GFA parse", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 	return g;
 }
 
@@ -725,7 +726,7 @@ double cpuQuota()
 
 size_t buildThreads()
 {
-	if (const char* env = getenv("GC_BUILD_THREADS")) { long v = atol(env); if (v >= 1) return (size_t)v; }
+	if (const std::optional<size_t> asked = Switches::fromEnvironment().buildThreads) return *asked;
 	size_t n = std::max(1u, std::thread::hardware_concurrency());
 	const double quota = cpuQuota();
 	if (quota > 0) n = std::min<size_t>(n, std::max<size_t>(1, (size_t)(quota + 0.5)));

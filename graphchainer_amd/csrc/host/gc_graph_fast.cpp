@@ -12,6 +12,7 @@
 // in the order AddEdgeNodeId would be called, adjacency lists filled by node range on all threads; (6) Finalize() as before.
 #include "gc_graph.hpp"
 #include "gc_stageclock.hpp"
+#include "gc_switches.hpp"
 #include "gc_hashorder.hpp"
 
 #include <algorithm>
@@ -215,7 +216,7 @@ inline uint32_t complementSet(uint32_t s) { return ((s & 1) << 3) | ((s & 2) << 
 
 AlignmentGraph AlignmentGraph::BuildFromGFAFile(const std::string& path)
 {
-	if (const char* env = getenv("GC_BUILD_REFERENCE_CONTAINERS")) if (atoi(env) == 1) { GfaGraph gfa = GfaGraph::LoadFromFile(path); return BuildFromGFA(gfa); }
+	if (Switches::fromEnvironment().buildReferenceContainers) { GfaGraph gfa = GfaGraph::LoadFromFile(path); return BuildFromGFA(gfa); }
 	StageClock clock;
 	const size_t threads = buildThreads();
 	// ---- (1) the file, its lines, their fields

@@ -1,6 +1,7 @@
 // Start-up stage timing on stderr (GC_DEBUG_TIMES): milliseconds per stage and the process's resident memory when the stage ends
 // (what decides how large a graph a host can build: DESIGN.md §10, config 5).
 #pragma once
+#include "gc_switches.hpp"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -22,7 +23,7 @@ inline double residentGiB()   // VmRSS of /proc/self/status; 0 when unreadable
 struct StageClock {
 	const char* tag;
 	std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-	const bool on = getenv("GC_DEBUG_TIMES") != nullptr;
+	const bool on = Switches::fromEnvironment().debugTimes;
 	explicit StageClock(const char* tag_ = "gc build") : tag(tag_) {}
 	void lap(const char* what)
 	{

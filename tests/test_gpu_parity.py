@@ -50,6 +50,13 @@ def run_case(gca, gfa, reads, long_pass=False, **kw):
     capacities = kw.pop("capacities", None)
     keep_traces = kw.pop("keep_traces", True)
     aligner = gca.Aligner(graph, seeder, keep_traces=keep_traces, keep_seeds=True, long_pass=long_pass, chain_traces=2, capacities=capacities, **kw)
+    got = align_comparable(aligner, graph, reads)
+    want = Oracle(gfa, long_pass=long_pass, **kw).align(reads)
+    return got, want
+
+
+def align_comparable(aligner, graph, reads):
+    """One align_reads call, in the shape the oracle's result has."""
     got = {k: (v.astype(np.int64) if v.dtype.kind in "ui" and k not in ("counters", "counters_long") else v) for k, v in aligner.align_reads(reads).items()}
     expand_stitched_path(got, graph.array("nodeLength"))
     mark_missing_chain_alignments(got)
@@ -57,8 +64,7 @@ def run_case(gca, gfa, reads, long_pass=False, **kw):
     sel = np.repeat(got["read_longall_off"][:-1], np.diff(got["read_long_off"])) + got["long_index"]
     for key in ("start", "end", "score"):
         got["long_" + key] = got["longall_" + key][sel]
-    want = Oracle(gfa, long_pass=long_pass, **kw).align(reads)
-    return got, want
+    return got
 
 
 def mark_missing_chain_alignments(got):
@@ -209,6 +215,27 @@ def test_whole_read_pass_plain_layout_fallback(gca, tmp_path, monkeypatch):
     got, want = run_case(gca, gfa, reads, long_pass=True)
     compare(got, want, COMPARE_KEYS + LONG_KEYS)
     assert int(got["counters_long"][7]) == len(reads)
+
+
+def test_switches_are_read_per_call(gca, tmp_path, monkeypatch):
+    """A per-call switch is read when the call begins, not once per process: one aligner, three calls, GC_TEST_LONG_FORCE_FALLBACK unset, set, unset again. The counter of
+    reads that went through the plain-layout kernel follows the variable, and the results do not change."""
+    from graphchainer_amd.synth import SynthGraph
+    monkeypatch.delenv("GC_TEST_LONG_FORCE_FALLBACK", raising=False)
+    sg = SynthGraph(60_000, seed=7)
+    gfa = str(tmp_path / "g.gfa")
+    sg.write_gfa(gfa)
+    reads = sg.sample_reads(8, 3000, seed=11)
+    graph = gca.AlignmentGraph(gfa)
+    aligner = gca.Aligner(graph, gca.MinimizerSeeder(graph), keep_traces=True, keep_seeds=True, long_pass=True, chain_traces=2)
+    first = align_comparable(aligner, graph, reads)
+    monkeypatch.setenv("GC_TEST_LONG_FORCE_FALLBACK", "1")
+    second = align_comparable(aligner, graph, reads)
+    monkeypatch.delenv("GC_TEST_LONG_FORCE_FALLBACK")
+    third = align_comparable(aligner, graph, reads)
+    assert [int(r["counters_long"][7]) for r in (first, second, third)] == [0, len(reads), 0]
+    compare(second, first, COMPARE_KEYS + LONG_KEYS)
+    compare(third, first, COMPARE_KEYS + LONG_KEYS)
 
 
 def test_whole_read_pass_speculative_rounds(gca, tmp_path, monkeypatch):
