@@ -38,7 +38,7 @@ class GcParams(C.Structure):
                 ("seed_density", C.c_double), ("min_cluster_size", C.c_int32), ("long_pass", C.c_int32), ("keep_traces", C.c_int32), ("keep_seeds", C.c_int32), ("stitch", C.c_int32), ("edit_distances", C.c_int32),
                 ("chain_traces", C.c_int32), ("device_output", C.c_int32), ("e_cutoff", C.c_double), ("capacity", GcCapacities),
                 ("ramp_bandwidth", C.c_int32), ("max_cells_per_slice", C.c_int64), ("force_global", C.c_int32),
-                ("seed_extend_density", C.c_double), ("extra_heuristic", C.c_int32), ("colinear_chaining", C.c_int32), ("selection_method", C.c_int32)]
+                ("seed_extend_density", C.c_double), ("extra_heuristic", C.c_int32), ("colinear_chaining", C.c_int32), ("selection_method", C.c_int32), ("fast_mode", C.c_int32)]
 
 
 # gc_params::selection_method: the reference's SelectionMethod in its own order (GC_SELECT_* of include/graphchainer_amd.h)
@@ -224,6 +224,38 @@ def evalue(min_identity, database_size, query_size, alignment_length, num_edits)
     lib.gc_evalue.argtypes = [C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     _check(lib.gc_evalue(min_identity, database_size, query_size, alignment_length, num_edits, out.ctypes.data))
     return out
+
+
+def format_gaf_trace(graph, name, read, node, offset, seqpos, switch, merge=False):
+    """GAF line (bytes, no newline) of one alignment given as a trace in output coordinates (gc_format_gaf_trace: GraphAlignerGAFAlignment::traceToAlignment; host only)."""
+    lib = load_library()
+    node = np.ascontiguousarray(node, dtype=np.int32)
+    offset = np.ascontiguousarray(offset, dtype=np.uint32)
+    seqpos = np.ascontiguousarray(seqpos, dtype=np.uint32)
+    switch = np.ascontiguousarray(switch, dtype=np.uint8)
+    assert len(node) == len(offset) == len(seqpos) == len(switch)
+    read = read if isinstance(read, bytes) else read.encode()
+    text, length = C.c_void_p(), C.c_uint64()
+    lib.gc_format_gaf_trace.restype = C.c_int
+    lib.gc_format_gaf_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _P(C.c_void_p), _P(C.c_uint64)]
+    _check(lib.gc_format_gaf_trace(graph.handle, name if isinstance(name, bytes) else name.encode(), read, len(read), node.ctypes.data, offset.ctypes.data, seqpos.ctypes.data,
+                                   switch.ctypes.data, len(node), int(bool(merge)), C.byref(text), C.byref(length)))
+    line = C.string_at(text.value, int(length.value))
+    lib.gc_free(text)
+    return line
+
+
+def graph_letters(graph, node, offset):
+    """The graph letter under each (bigraph node id, offset in the original node) (gc_graph_letters: TraceItem's graphCharacter; host only) as bytes."""
+    lib = load_library()
+    node = np.ascontiguousarray(node, dtype=np.int32)
+    offset = np.ascontiguousarray(offset, dtype=np.uint32)
+    assert len(node) == len(offset)
+    out = C.create_string_buffer(max(len(node), 1))
+    lib.gc_graph_letters.restype = C.c_int
+    lib.gc_graph_letters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p]
+    _check(lib.gc_graph_letters(graph.handle, node.ctypes.data, offset.ctypes.data, len(node), out))
+    return out.raw[:len(node)]
 
 
 def _fetch_array(fn, handle, name):
@@ -468,7 +500,7 @@ class BatchResult(dict):
 class Aligner:
     """Batched stand-in for the reference's per-read hot path (src/Aligner.cpp:601-922)."""
 
-    def __init__(self, graph, seeder=None, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1, force_global=False, seed_extend_density=-1.0, extra_heuristic=False, colinear_chaining=True, selection_method=0):
+    def __init__(self, graph, seeder=None, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1, force_global=False, seed_extend_density=-1.0, extra_heuristic=False, colinear_chaining=True, selection_method=0, fast_mode=False):
         """capacities: {field of gc_capacities: value} for the device-side tables (default: all automatic).
         seeder: the MinimizerSeeder, or None for a caller that brings its own seeds to every batch (align_batch(batch, seeds=SeedBatch(...))).
         device_output: gc_params::device_output - 1 / 2: the final alignments' GAF path and CIGAR text (= / X or M items), + 4: their vg::Path bytes, written
@@ -479,7 +511,9 @@ class Aligner:
         seed_extend_density / extra_heuristic: the reference's --seeds-extend-density / --extra-heuristic for the whole-read pass (gc_params; -1: all seeds).
         A density other than -1 needs colinear_chaining=False.
         colinear_chaining=False: --no-colinear-chaining, plain GraphAligner - seeding and the whole-read pass alone (needs long_pass=True); the anchor, chain, path
-        and chain-trace arrays come back empty, both edit distances -1, and long_index holds SelectAlignments(selection_method: one of SELECT_*)."""
+        and chain-trace arrays come back empty, both edit distances -1, and long_index holds SelectAlignments(selection_method: one of SELECT_*).
+        fast_mode: the reference's --fast-mode (gc_params::fast_mode): the chained alignment is the stitched path itself, cell j at read position min(y, x + j), and
+        chain_edit_distance counts its differing letters instead of an NW distance; no effect without chaining. An int other than 0 / 1 is refused by the library."""
         self.lib = load_library()
         self.graph = graph
         self.seeder = seeder
@@ -508,6 +542,7 @@ class Aligner:
         self.params.extra_heuristic = int(extra_heuristic)
         self.params.colinear_chaining = int(colinear_chaining)
         self.params.selection_method = int(selection_method)
+        self.params.fast_mode = int(fast_mode)
         for name, value in (capacities or {}).items():
             if name not in dict(GcCapacities._fields_) or name == "reserved":
                 raise ValueError("no such capacity: " + name)

@@ -8,7 +8,8 @@
 		// (or all with chain_traces == 2) are traced: the path does not change the edit distance that decides.
 		double tChainTrace = nowUs();
 		uint64_t nChainTraced = 0;
-		if (P->stitch && P->edit_distances && chainLetterJobs) {
+		if (fastChainJobs) { nChainTraced = fastChainedAlignments(); }
+		else if (P->stitch && P->edit_distances && chainLetterJobs) {
 			auto beats = [&](const ReadGlue& gl) { return gl.longSelected.empty() || gl.longEditDistance > gl.chainEditDistance; };   // :905
 			std::vector<uint32_t> cand;
 			for (uint64_t r = 0; r < n; r++) {
@@ -89,6 +90,66 @@
 		}
 		if (sw.debugTimes) fprintf(stderr, "[gc times] chained alignment traces: %llu reads, %.1f ms\n", (unsigned long long)nChainTraced, (nowUs() - tChainTrace) / 1e3);
 
+	}
+
+	// ---------------- gc_params::fast_mode (src/Aligner.cpp:834-843,880-905): the chained alignment is the stitched piece itself, cell j at read position min(y, x + j). Its score
+	// (k_fast_chain_score's count) and its bounds are known without the trace, so --E-cutoff (:904) and the decision (:905) come first, for every stitched read in every
+	// chain_traces mode; k_fast_chain_trace then writes the cells of the reads whose trace is wanted (1: the winners, 2: every read with a chained alignment) in place of
+	// k_edit_path and the host's walk over edlib's ops. Returns the number of reads traced.
+	uint64_t fastChainedAlignments()
+	{
+		std::vector<uint32_t> cand;
+		uint64_t cellsTotal = 0;
+		for (uint64_t r = 0; r < n; r++) {
+			ReadGlue& gl = glue[r];
+			const FastChainJob& job = fastChainJobs[r];
+			if (gl.longFailed || job.cells == 0 || gl.chainEditDistance < 0) continue;
+			const uint64_t readLen = R->offsets[r + 1] - R->offsets[r];
+			const uint32_t alnStart = job.x, alnEnd = std::min<uint64_t>(job.y, (uint64_t)job.x + job.cells - 1) + 1;   // :894-895 of the trace below
+			gl.hasChainAlignment = evalueModel.keeps(P->e_cutoff, hg.SizeInBP(), readLen, alnEnd - alnStart, (size_t)gl.chainEditDistance);
+			gl.chainWins = gl.hasChainAlignment && (gl.longSelected.empty() || gl.longEditDistance > gl.chainEditDistance);
+			if (!gl.hasChainAlignment || !(P->chain_traces >= 2 || (P->chain_traces == 1 && gl.chainWins))) continue;
+			gl.chainAlnStart = alnStart; gl.chainAlnEnd = alnEnd;   // (reported with the trace, as in the default mode)
+			cand.push_back((uint32_t)r);
+			cellsTotal += job.cells;
+		}
+		const size_t m = cand.size();
+		if (m == 0) return 0;
+		FastChainJob* hJobsT = st->hFastTraceJobs.reserve<FastChainJob>(m);
+		uint64_t at = 0;
+		for (size_t i = 0; i < m; i++) { hJobsT[i] = fastChainJobs[cand[i]]; hJobsT[i].traceOff = at; at += hJobsT[i].cells; }
+		// one block laid out like the result's four arrays: node ids, offsets, read positions (4 bytes a cell each), switches (1 byte)
+		const uint64_t T = cellsTotal, bytes = 13 * T;
+		FastChainJob* dJobsT = st->fastTraceJobs.reserve<FastChainJob>(m);
+		uint8_t* dTraceBlock = st->fastTrace.reserve<uint8_t>(bytes);
+		uint32_t* dWritten = st->fastWritten.reserve<uint32_t>(m);
+		uint8_t* hTraceBlock = st->hFastTrace.reserve<uint8_t>(bytes);
+		uint32_t* hWritten = st->hFastWritten.reserve<uint32_t>(m);
+		hipEvent_t timed[2] = { nullptr, nullptr };
+		if (sw.debugTimes) for (auto& e : timed) HIP_CHECK(hipEventCreate(&e));
+		HIP_CHECK(hipMemcpyAsync(dJobsT, hJobsT, m * sizeof(FastChainJob), hipMemcpyHostToDevice, stream));
+		if (timed[0]) HIP_CHECK(hipEventRecord(timed[0], stream));
+		launchFastChainTrace(stream, G->dev, dJobsT, (uint32_t)m, dStitchNodes, dChainAltNodes, (int32_t*)dTraceBlock, (uint32_t*)(dTraceBlock + 4 * T), (uint32_t*)(dTraceBlock + 8 * T), dTraceBlock + 12 * T, dWritten);
+		if (timed[1]) HIP_CHECK(hipEventRecord(timed[1], stream));
+		HIP_CHECK(hipMemcpyAsync(hWritten, dWritten, m * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+		HIP_CHECK(hipMemcpyAsync(hTraceBlock, dTraceBlock, bytes, hipMemcpyDeviceToHost, stream));
+		syncStream(stream);
+		if (timed[0]) {
+			float ms = 0;
+			HIP_CHECK(hipEventElapsedTime(&ms, timed[0], timed[1]));
+			for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
+			fprintf(stderr, "[gc times] fast mode: k_fast_chain_trace over %zu reads, %llu cells, %.3f ms on the device; no k_edit_path launch\n", m, (unsigned long long)T, ms);
+		}
+		for (size_t i = 0; i < m; i++) if (hWritten[i] != hJobsT[i].cells) throw std::runtime_error("internal: the fast-mode trace kernel and the stitched path disagree on a read's cell count");
+		const int32_t* tNode = (const int32_t*)hTraceBlock; const uint32_t* tOffset = (const uint32_t*)(hTraceBlock + 4 * T); const uint32_t* tSeqPos = (const uint32_t*)(hTraceBlock + 8 * T);
+		const uint8_t* tSwitch = hTraceBlock + 12 * T;
+		pool.run(m, [&](size_t i, size_t) {
+			ReadGlue& gl = glue[cand[i]];
+			const uint64_t b = hJobsT[i].traceOff, e = b + hJobsT[i].cells;
+			gl.chainTraceNode.assign(tNode + b, tNode + e); gl.chainTraceOffset.assign(tOffset + b, tOffset + e);
+			gl.chainTraceSeqPos.assign(tSeqPos + b, tSeqPos + e); gl.chainTraceSwitch.assign(tSwitch + b, tSwitch + e);
+		});
+		return m;
 	}
 
 	// ---------------- the final alignments encoded where their traces are (params->device_output; gc_output.hip): the GAF path / CIGAR text and the vg::Path bytes of

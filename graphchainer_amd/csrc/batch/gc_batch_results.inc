@@ -98,6 +98,32 @@
 	const unsigned long long* densePathOff() const { return (const unsigned long long*)hAnchorDense; }
 	const uint32_t* denseWords(int k) const { return (const uint32_t*)(hAnchorDense + 8 * denseAnchors) + (uint64_t)k * denseAnchors; }   // 0 x, 1 y, 2-4 first node / offset / seqPos, 5-7 last, 8 score, 9 the path words
 
+	// ---------------- gc_params::fast_mode: x of the chain's first anchor and y of its last (src/Aligner.cpp:836; the chain's, whichever piece of it is the longest)
+	void chainSpan(uint64_t r, uint32_t& x, uint32_t& y) const
+	{
+		const uint32_t* ids = chainOut + jobs[r].chainBegin;
+		const uint32_t first = ids[0], last = ids[chainLen[r] - 1];
+		if (deviceAnchors) {   // chain index = index among the read's dense anchors
+			const uint64_t a0 = hAnchorOff[2 * r];
+			x = denseWords(0)[a0 + first]; y = denseWords(1)[a0 + last];
+			return;
+		}
+		const ReadGlue& gl = glue[r];   // ... = index among the anchors the walk over the read's slots keeps
+		uint64_t slot = gl.slotBegin;
+		uint32_t kept = 0;
+		for (size_t f = 0; f < gl.nWindows; f++) {
+			const uint64_t F = gl.fragBegin + f;
+			const uint32_t nS = frags[F].seedEnd - frags[F].seedBegin;
+			if (fragStatus[F] == 1) break;
+			for (uint32_t k = 0; k < nS; k++) if (anchors[slot + k].valid) {
+				if (kept == first) x = anchors[slot + k].x;
+				if (kept == last) y = anchors[slot + k].y;
+				kept++;
+			}
+			slot += nS;
+		}
+	}
+
 	// ---------------- host stitching of what the kernel declined; NW distance of every stitched path against its read
 	void stitchAndChainDistances()
 	{
@@ -167,7 +193,7 @@
 				if (!onDevice && !sp.nodes.empty()) memcpy(hNodes + glue[r].stitchedBegin, sp.nodes.data(), sp.nodes.size() * sizeof(uint32_t));
 				if (sp.cells >= 0x7fffffffull) throw std::runtime_error("stitched path too long");
 				hJobsPS[r] = PathSeqJob { onDevice ? stitchInfo[r].start : ((1ull << 63) | glue[r].stitchedBegin), nCells, onDevice ? stitchInfo[r].len : (uint32_t)sp.nodes.size(), (uint32_t)sp.cells, sp.firstOffset, sp.lastOffset };
-				if (sp.cells) {
+				if (sp.cells && !P->fast_mode) {
 					uint32_t len = (uint32_t)(R->offsets[r + 1] - R->offsets[r]);
 					// first band: the length difference plus ~14 % of the shorter sequence (ONT-like error rates pass in one sweep) - widened to 20 %
 					// where that still fits the two-pairs-per-wave kernel: a wave's time follows the number of columns, not the band, so the wider
@@ -192,21 +218,65 @@
 			launchChainPathSeq(stream, G->dev, dJobsPS, (uint32_t)n, dStitchNodes, dNodes, dLetters, dLettersLen);
 			chainLetterJobs = hJobsPS;
 			dChainLetters = dLetters;
-			auto readLenOf = [R = R](uint32_t r) { return (uint32_t)(R->offsets[r + 1] - R->offsets[r]); };
-			launchEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, readLenOf, sw.debugTimes);
-			finishChainEditDistances = [=, &pairRead]() {   // waits for the kernels (they run beside the whole-read pass) and reruns the few pairs that need a wider band
-				finishEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, sw.debugTimes);
-				if (sw.debugEd) for (uint32_t i = 0; i < nPairs && i < 400; i++) {
-					const uint32_t r = pairRead[i];
-					fprintf(stderr, "[gc ed] read %u len %llu path %llu chain %u scoreSum %u onDevice %d distance %lld\n", r, (unsigned long long)(R->offsets[r + 1] - R->offsets[r]), (unsigned long long)glue[r].stitched.cells,
-						chainLen[r], deviceStitch ? stitchInfo[r].scoreSum : 0u, (int)glue[r].stitchedOnDevice, (long long)hOut[i]);
+			dChainAltNodes = dNodes;
+			if (P->fast_mode) {
+				// gc_params::fast_mode (src/Aligner.cpp:834-843): no NW distance of the chain. The score is the number of stitched cells whose letter is not the read's at
+				// min(y, x + j), counted by k_fast_chain_score from the letters just spelled; the pairs are not handed to launchEditDistances
+				FastChainJob* hJobsF = st->hFastJobs.reserve<FastChainJob>(n);
+				int64_t* hScore = st->hFastScore.reserve<int64_t>(n);
+				uint64_t nFast = 0;
+				for (uint64_t r = 0; r < n; r++) {
+					const PathSeqJob& pj = hJobsPS[r];
+					FastChainJob job { pj.srcOff, pj.outOff, R->offsets[r], 0, pj.count, pj.outCap, pj.firstOffset, pj.lastOffset, 0, 0 };
+					if (job.cells) {
+						chainSpan(r, job.x, job.y);
+						if (job.y >= R->offsets[r + 1] - R->offsets[r]) throw std::runtime_error("internal: a chain's last anchor ends beyond its read");   // (y = l + len - 1, :707)
+						nFast++;
+					}
+					hJobsF[r] = job;
 				}
-				for (uint32_t i = 0; i < nPairs; i++) {
-					ReadGlue& gl = glue[pairRead[i]];
-					gl.chainEditDistance = hOut[i];
-					if (hOut[i] < -1) { gl.chainEditDistance = -1; gl.capacityExceeded = true; }
-				}
-			};
+				FastChainJob* dJobsF = st->fastJobs.reserve<FastChainJob>(n);
+				int64_t* dScore = st->fastScore.reserve<int64_t>(n);
+				hipEvent_t timed[2] = { nullptr, nullptr };
+				if (sw.debugTimes) for (auto& e : timed) HIP_CHECK(hipEventCreate(&e));
+				if (n) HIP_CHECK(hipMemcpyAsync(dJobsF, hJobsF, n * sizeof(FastChainJob), hipMemcpyHostToDevice, stream));
+				if (timed[0]) HIP_CHECK(hipEventRecord(timed[0], stream));
+				launchFastChainScore(stream, dJobsF, (uint32_t)n, dLetters, dLettersLen, R->devBases, dScore);
+				if (timed[1]) HIP_CHECK(hipEventRecord(timed[1], stream));
+				if (n) HIP_CHECK(hipMemcpyAsync(hScore, dScore, n * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+				fastChainJobs = hJobsF;
+				finishChainEditDistances = [=]() {   // only collects the counts
+					syncStream(stream);
+					for (uint64_t r = 0; r < n; r++) {
+						if (!hJobsF[r].cells) continue;
+						ReadGlue& gl = glue[r];
+						gl.chainEditDistance = hScore[r];
+						if (hScore[r] < 0) { gl.chainEditDistance = -1; gl.capacityExceeded = true; }
+					}
+					if (timed[0]) {
+						float ms = 0;
+						HIP_CHECK(hipEventElapsedTime(&ms, timed[0], timed[1]));
+						for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
+						fprintf(stderr, "[gc times] fast mode: k_fast_chain_score over %llu stitched reads, %llu cells, %.3f ms on the device; no k_edit_distance launch for the chains\n", (unsigned long long)nFast, (unsigned long long)nCells, ms);
+					}
+				};
+			} else {
+				auto readLenOf = [R = R](uint32_t r) { return (uint32_t)(R->offsets[r + 1] - R->offsets[r]); };
+				launchEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, readLenOf, sw.debugTimes);
+				finishChainEditDistances = [=, &pairRead]() {   // waits for the kernels (they run beside the whole-read pass) and reruns the few pairs that need a wider band
+					finishEditDistances(st->edChainRun, stream, hPairs, hOut, nPairs, dPairs, dOut, R->devEdReads, R->devBases, R->devEqMasks, dLetters, dLettersLen, sw.debugTimes);
+					if (sw.debugEd) for (uint32_t i = 0; i < nPairs && i < 400; i++) {
+						const uint32_t r = pairRead[i];
+						fprintf(stderr, "[gc ed] read %u len %llu path %llu chain %u scoreSum %u onDevice %d distance %lld\n", r, (unsigned long long)(R->offsets[r + 1] - R->offsets[r]), (unsigned long long)glue[r].stitched.cells,
+							chainLen[r], deviceStitch ? stitchInfo[r].scoreSum : 0u, (int)glue[r].stitchedOnDevice, (long long)hOut[i]);
+					}
+					for (uint32_t i = 0; i < nPairs; i++) {
+						ReadGlue& gl = glue[pairRead[i]];
+						gl.chainEditDistance = hOut[i];
+						if (hOut[i] < -1) { gl.chainEditDistance = -1; gl.capacityExceeded = true; }
+					}
+				};
+			}
 		}
 		if (finishChainEditDistances) finishChainEditDistances();   // this thread would only wait for the whole-read pass otherwise
 		if (stitchNodesPending) {

@@ -127,6 +127,8 @@ struct BatchRun {
 	// stitchAndChainDistances()
 	const PathSeqJob* chainLetterJobs = nullptr;   // per read: where its stitched path's letters are in dChainLetters
 	const char* dChainLetters = nullptr;
+	const uint32_t* dChainAltNodes = nullptr;      // the node paths stitched on the host, uploaded for k_chain_pathseq (PathSeqJob::srcOff bit 63)
+	const FastChainJob* fastChainJobs = nullptr;   // gc_params::fast_mode, per read: its stitched piece and the chain's (x, y); cells == 0: none
 	// withoutChaining()
 	std::vector<uint32_t> zeroWords; std::vector<unsigned long long> zeroLongs; std::vector<uint4> zeroPerRead;
 	// joinWholeReadPass()
@@ -201,6 +203,7 @@ static int alignBatch(const gc::Switches& sw, const gc_graph* G, const gc_seeder
 	if (P->colinear_chaining == 0 && !P->long_pass) return fail(GC_ERR_INVALID, "colinear_chaining == 0 needs long_pass: without chaining the whole-read pass is all there is");
 	if (P->extra_heuristic != 0 && P->extra_heuristic != 1) return fail(GC_ERR_INVALID, "extra_heuristic must be 0 or 1");
 	if (P->selection_method < 0 || P->selection_method > GC_SELECT_ALL) return fail(GC_ERR_INVALID, "selection_method must be one of GC_SELECT_* (0..7)");
+	if (P->fast_mode != 0 && P->fast_mode != 1) return fail(GC_ERR_INVALID, "fast_mode must be 0 or 1");
 	if (std::isnan(P->seed_extend_density) || (P->seed_extend_density <= 0 && P->seed_extend_density != -1)) return fail(GC_ERR_INVALID, "seed_extend_density must be -1 (all seeds) or > 0 (src/AlignerMain.cpp:405)");
 	if (P->seed_extend_density != -1 && P->colinear_chaining == 1) return fail(GC_ERR_INVALID, "seed_extend_density must be -1 with colinear_chaining == 1: chaining tries all seeds (src/AlignerMain.cpp:204,449-453)");
 	{

@@ -427,6 +427,9 @@ int gc_set_device(int device)
 	return guarded([&]() { HIP_CHECK(hipSetDevice(device)); return (int)GC_OK; });
 }
 
+// fast_mode took the struct's tail padding: the other fields are where they were and the size is what it was
+static_assert(sizeof(gc_params) == 216 && offsetof(gc_params, fast_mode) == offsetof(gc_params, selection_method) + 4 && offsetof(gc_params, fast_mode) + 4 == sizeof(gc_params), "gc_params layout");
+
 void gc_params_default(gc_params* p)
 {
 	if (!p) return;
@@ -452,6 +455,7 @@ void gc_params_default(gc_params* p)
 	p->extra_heuristic = 0;         // off (src/AlignerMain.cpp:170,192)
 	p->colinear_chaining = 1;       // on; 0 is --no-colinear-chaining (src/AlignerMain.cpp:176,198-199)
 	p->selection_method = GC_SELECT_GREEDY_LENGTH;
+	p->fast_mode = 0;               // off (src/AlignerMain.cpp:180,195-196)
 }
 
 int gc_graph_create_from_gfa(const char* gfa_path, gc_graph** out)

@@ -588,6 +588,8 @@ struct gc_stream {
 	EditDistanceRun edChainRun;
 	DeviceBuffer edPathJobs, edPathOps, edPathLen, edPathScratch;   // alignment path of the chained alignment (gc_edpath.hip)
 	PinnedBuffer hEdPathJobs, hEdPathOps, hEdPathLen;
+	DeviceBuffer fastJobs, fastScore, fastTraceJobs, fastTrace, fastWritten;   // the chained alignment of gc_params::fast_mode (gc_fastchain.hip)
+	PinnedBuffer hFastJobs, hFastScore, hFastTraceJobs, hFastTrace, hFastWritten;
 	// whole-read decision (selection + edit distance of the best alignment)
 	struct LongDecision {
 		PinnedBuffer hJobs, hPairs, hOut;
@@ -622,6 +624,7 @@ struct gc_stream {
 		f("stitchSlotOf", stitchSlotOf.bytes); f("stitchRegions", stitchRegions.bytes); f("stitchNodes", stitchNodes.bytes); f("stitchInfo", stitchInfo.bytes); f("stitchCursor", stitchCursor.bytes); f("stitchSpill", stitchSpill.bytes);
 		f("anchorPerRead", anchorPerRead.bytes); f("anchorSlotEnd", anchorSlotEnd.bytes); f("anchorOff", anchorOff.bytes); f("anchorDense", anchorDense.bytes);
 		f("edPathJobs", edPathJobs.bytes); f("edPathOps", edPathOps.bytes); f("edPathLen", edPathLen.bytes); f("edPathScratch", edPathScratch.bytes); f("longSeeds", longSeeds.bytes);
+		f("fastJobs", fastJobs.bytes); f("fastScore", fastScore.bytes); f("fastTraceJobs", fastTraceJobs.bytes); f("fastTrace", fastTrace.bytes); f("fastWritten", fastWritten.bytes);
 		f("longJobs", longJobs.bytes); f("longAlns", longAlns.bytes); f("longResults", longResults.bytes); f("longScratch", longScratch.bytes); f("longCells", longCells.bytes);
 		f("longCursor", longCursor.bytes); f("longJobsFallback", longJobsFallback.bytes); f("longResultsFallback", longResultsFallback.bytes); f("longScratchFallback", longScratchFallback.bytes);
 		f("gluePerRead", gluePerRead.bytes); f("glueCursors", glueCursors.bytes); f("glueOut", glueOut.bytes); f("glueSeedCap", glueSeedCap.bytes); f("glueSeedOff", glueSeedOff.bytes);

@@ -338,6 +338,22 @@ uint32_t editPathGridBlocks(uint32_t nJobs);
 // ops: 0 match, 1 path letter alone, 2 read base alone, 3 mismatch; opsLen[i] = 0 when edlib would return no alignment
 void launchEditPath(hipStream_t stream, const EdPathJob* jobs, uint32_t nJobs, const char* letters, const char* bases, uint8_t* scratch, uint32_t maxQ, uint32_t maxT,
 	uint8_t* opsOut, uint32_t* opsLen);
+// ---- the chained alignment of gc_params::fast_mode (gc_fastchain.hip; src/Aligner.cpp:834-843,880-895): cell j of the stitched piece at read position min(y, x + j) ----
+struct FastChainJob {
+	uint64_t srcOff;              // the piece's first path node, as PathSeqJob::srcOff (bit 63: in altNodes)
+	uint64_t lettersOff;          // its letters as k_chain_pathseq spelled them (the score kernel reads these)
+	uint64_t readOff;             // the read's forward bases
+	uint64_t traceOff;            // the trace kernel's first cell in the four trace arrays
+	uint32_t count, cells;        // path nodes; cells on them (path_cells); 0: no stitched piece
+	uint32_t firstOffset, lastOffset;
+	uint32_t x, y;                // anchor_x of the chain's first anchor, anchor_y of its last (y < read length)
+};
+// outScore[r]: the cells of job r whose letter differs from the read's; -1 for a job without cells, -3 when lettersLen[r] is not the job's cell count
+void launchFastChainScore(hipStream_t stream, const FastChainJob* jobs, uint32_t nJobs, const char* letters, const uint32_t* lettersLen, const char* bases, int64_t* outScore);
+// the cells [traceOff, traceOff + cells) of the arrays in output coordinates (bigraph node id, offset in the original node, read position, next cell in another split node);
+// written[r]: the cells the job's nodes hold (the host compares it with `cells`; nothing is stored beyond traceOff + cells)
+void launchFastChainTrace(hipStream_t stream, const DGraph& g, const FastChainJob* jobs, uint32_t nJobs, const uint32_t* pathNodes, const uint32_t* altNodes,
+	int32_t* traceNode, uint32_t* traceOffset, uint32_t* traceSeqPos, uint8_t* traceSwitch, uint32_t* written);
 void launchLongOrder(hipStream_t stream, const uint32_t* workLen, const unsigned long long* workCount, uint32_t* order, uint32_t maxLen, uint32_t mode);
 void launchPublish(hipStream_t stream, const unsigned long long* src, unsigned long long* dst, uint32_t nWords);
 void launchZeroWords(hipStream_t stream, unsigned long long* dst, uint32_t nWords);   // nWords <= 64

@@ -117,6 +117,16 @@ typedef struct gc_params {
 	int32_t selection_method;   /* GC_SELECT_* below, the reference's SelectionMethod in its own order (src/AlignmentSelection.h:14-24). Read only when
 	                             *    colinear_chaining == 0; with chaining it has no effect: the whole-read side is always GreedyLength (src/Aligner.cpp:639) and
 	                             *    :904 selects among one alignment. Outside 0..7: GC_ERR_INVALID. */
+	int32_t fast_mode;          /* --fast-mode, fastMode (src/AlignerMain.cpp:48,195-196, src/Aligner.cpp:834-843): 0 (default) off, 1 on (anything else: GC_ERR_INVALID).
+	                             *    The chained alignment is made without edlib: its trace is the stitched piece itself, one cell per path base (path_cells of them),
+	                             *    cell j at read position min(y, x + j) with x = anchor_x of the CHAIN's first anchor (not of the longest piece's) and y = anchor_y of
+	                             *    its last. chain_edit_distance then holds the number of cells whose graph letter differs from the read letter at that position (letters
+	                             *    compared literally, IUPAC letters included), NOT an NW distance; chain_aln_start = x, chain_aln_end = min(y, x + path_cells - 1) + 1.
+	                             *    --E-cutoff and the decision (:904-905) use these numbers; chain_traces keeps its meaning. Neither k_edit_path nor an NW distance of
+	                             *    the chain runs: two small kernels (gc_fastchain.hip) count and write the cells. The whole-read side (long_*, long_edit_distance) is
+	                             *    untouched. Read only when colinear_chaining == 1 and stitch and edit_distances are set; no effect otherwise (the reference accepts
+	                             *    --fast-mode --no-colinear-chaining and never looks at the flag again). (Sits in what used to be padding: sizeof(gc_params) and the
+	                             *    layout of the other fields are unchanged.) */
 } gc_params;
 
 enum { GC_SELECT_GREEDY_LENGTH = 0, GC_SELECT_GREEDY_SCORE = 1, GC_SELECT_GREEDY_E = 2, GC_SELECT_SCHEDULE_INVERSE_E_SUM = 3, GC_SELECT_SCHEDULE_INVERSE_E_PRODUCT = 4,
@@ -279,7 +289,8 @@ typedef struct gc_result {
 	uint8_t*  chained_better;     /* [n_reads] 1: the chained alignment is the read's result, 0: the selected whole-read alignments are */
 	/* the chained alignment (chain_traces): its trace in output coordinates like long_trace_* (bigraph node id, offset in the original
 	 * node, read position, "next cell is in another split node"), one cell per op of edlib's alignment (src/Aligner.cpp:855-887);
-	 * alignmentStart / alignmentEnd (:894-895). Its alignmentScore is chain_edit_distance, its trace score 0 (never set, :739,891). */
+	 * alignmentStart / alignmentEnd (:894-895). Its alignmentScore is chain_edit_distance, its trace score 0 (never set, :739,891).
+	 * With gc_params::fast_mode: one cell per base of the stitched piece, and chain_edit_distance is the count of differing letters (see there). */
 	uint64_t* read_chain_trace_off; /* [n_reads+1] */
 	int32_t*  chain_trace_node; uint32_t* chain_trace_offset; uint32_t* chain_trace_seqpos; uint8_t* chain_trace_switch;
 	uint32_t* chain_aln_start; uint32_t* chain_aln_end;   /* [n_reads]; 0,0 where there is no chained alignment */
