@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = [
     "gc_params_default", "gc_graph_create_from_gfa", "gc_graph_create", "gc_graph_destroy", "gc_graph_num_nodes",
     "gc_graph_size_bp", "gc_graph_array", "gc_graph_trim_host", "gc_seeder_create", "gc_seeder_destroy", "gc_seeder_array",
     "gc_stream_create", "gc_stream_destroy", "gc_reads_upload", "gc_reads_destroy", "gc_align_batch",
-    "gc_seeds_upload", "gc_seeds_destroy", "gc_align_batch_seeded",
+    "gc_seeds_upload", "gc_seeds_destroy", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
 ]
@@ -31,6 +31,11 @@ class GcCapacities(C.Structure):
     """gc_capacities (include/graphchainer_amd.h): sizes of the device-side tables; 0 = automatic."""
     _fields_ = [("ext_max_items", C.c_int64), ("ext_max_pending", C.c_int64), ("ext_max_trace", C.c_int64), ("long_max_items", C.c_int64), ("long_column_store", C.c_int64),
                 ("long_cells_per_base", C.c_int64), ("long_scratch_bytes", C.c_int64), ("stitch_set_max", C.c_int64), ("stitch_bfs_cap", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+class GcParamsExt(C.Structure):
+    """gc_params_ext (include/graphchainer_amd.h): the options added after gc_params' layout was frozen."""
+    _fields_ = [("struct_size", C.c_uint32), ("x_drop", C.c_int32), ("precise_clipping", C.c_double)]
 
 
 class GcParams(C.Structure):
@@ -109,6 +114,10 @@ def load_library():
     lib.gc_align_batch_seeded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(GcParams), _P(_P(GcResult))]
     lib.gc_result_free.argtypes = [_P(GcResult)]
     lib.gc_params_default.argtypes = [_P(GcParams)]
+    lib.gc_params_ext_default.argtypes = [_P(GcParamsExt)]
+    lib.gc_params_ext_default.restype = None
+    lib.gc_align_batch_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(GcParams), _P(GcParamsExt), _P(_P(GcResult))]
+    lib.gc_test_max_x_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_int32, C.c_void_p]
     lib.gc_free.argtypes = [C.c_void_p]
     lib.gc_set_device.argtypes = [C.c_int]
     lib.gc_index_build.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_double, C.c_char_p]
@@ -182,6 +191,18 @@ def edit_path(a_list, b_list):
 
 GAM_DEVICE_HUFFMAN = 100   # GC_GAM_DEVICE_HUFFMAN: gam_level value that has the gzip members deflated on the device
 GAM_DEVICE_LZ = 101        # GC_GAM_DEVICE_LZ (r6): ... with LZ77 matches in front of the Huffman stage
+
+
+def max_x_scores(vp, vn, score_end, error_cost, cells=64):
+    """Test entry: WordSlice::maxXScoreFirstSlices of DP columns as the extension kernel computes it (gc_test_max_x_score)."""
+    lib = load_library()
+    vp = np.ascontiguousarray(vp, dtype=np.uint64)
+    vn = np.ascontiguousarray(vn, dtype=np.uint64)
+    score_end = np.ascontiguousarray(score_end, dtype=np.int32)
+    out = np.zeros(len(vp), dtype=np.int32)
+    _check(lib.gc_test_max_x_score(vp.ctypes.data, vn.ctypes.data, score_end.ctypes.data, len(vp), float(error_cost), int(cells), out.ctypes.data))
+    return out
+
 
 
 def std_sort_permutations(arrays, depth_limit=-1):
@@ -500,7 +521,7 @@ class BatchResult(dict):
 class Aligner:
     """Batched stand-in for the reference's per-read hot path (src/Aligner.cpp:601-922)."""
 
-    def __init__(self, graph, seeder=None, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1, force_global=False, seed_extend_density=-1.0, extra_heuristic=False, colinear_chaining=True, selection_method=0, fast_mode=False):
+    def __init__(self, graph, seeder=None, bandwidth=10, split_len=35, split_gap=35, colinear_gap=10000, seed_density=10.0, keep_traces=False, keep_seeds=False, long_pass=False, stitch=True, edit_distances=True, chain_traces=None, e_cutoff=-1.0, capacities=None, device_output=0, ramp_bandwidth=0, max_cells_per_slice=-1, force_global=False, seed_extend_density=-1.0, extra_heuristic=False, colinear_chaining=True, selection_method=0, fast_mode=False, precise_clipping=0.0, x_drop=0):
         """capacities: {field of gc_capacities: value} for the device-side tables (default: all automatic).
         seeder: the MinimizerSeeder, or None for a caller that brings its own seeds to every batch (align_batch(batch, seeds=SeedBatch(...))).
         device_output: gc_params::device_output - 1 / 2: the final alignments' GAF path and CIGAR text (= / X or M items), + 4: their vg::Path bytes, written
@@ -513,7 +534,10 @@ class Aligner:
         colinear_chaining=False: --no-colinear-chaining, plain GraphAligner - seeding and the whole-read pass alone (needs long_pass=True); the anchor, chain, path
         and chain-trace arrays come back empty, both edit distances -1, and long_index holds SelectAlignments(selection_method: one of SELECT_*).
         fast_mode: the reference's --fast-mode (gc_params::fast_mode): the chained alignment is the stitched path itself, cell j at read position min(y, x + j), and
-        chain_edit_distance counts its differing letters instead of an NW distance; no effect without chaining. An int other than 0 / 1 is refused by the library."""
+        chain_edit_distance counts its differing letters instead of an NW distance; no effect without chaining. An int other than 0 / 1 is refused by the library.
+        precise_clipping / x_drop: the reference's --precise-clipping / --X-drop (gc_params_ext; 0: off): alignments and anchors end at the cell with the best X score
+        for the identity cut-off instead of at the correctness trim, flatten_ties* are 0; an X-drop without a cut-off runs with 0.66. Values out of range are refused
+        by the library."""
         self.lib = load_library()
         self.graph = graph
         self.seeder = seeder
@@ -543,6 +567,10 @@ class Aligner:
         self.params.colinear_chaining = int(colinear_chaining)
         self.params.selection_method = int(selection_method)
         self.params.fast_mode = int(fast_mode)
+        self.params_ext = GcParamsExt()
+        self.lib.gc_params_ext_default(C.byref(self.params_ext))
+        self.params_ext.precise_clipping = float(precise_clipping)
+        self.params_ext.x_drop = int(x_drop)
         for name, value in (capacities or {}).items():
             if name not in dict(GcCapacities._fields_) or name == "reserved":
                 raise ValueError("no such capacity: " + name)
@@ -555,7 +583,11 @@ class Aligner:
         keep_traces or device_output) the dict also holds "gaf" (bytes: the reference's GAF lines) and "gaf_chained_skipped"; with other_formats also "json" (JSON
         lines) and "gam" (gzip members of framed vg::Alignment messages; gam_level: their zlib level, or GAM_DEVICE_HUFFMAN for the device's deflate)."""
         res = _P(GcResult)()
-        if seeds is not None:   # the caller's own hits in place of the minimizer seeder (gc_align_batch_seeded; seed_density does not apply)
+        ext_on = self.params_ext.precise_clipping != 0 or self.params_ext.x_drop != 0   # (with both off: the calls that take no block)
+        if ext_on and (seeds is not None or self.seeder is not None):
+            _check(self.lib.gc_align_batch_ext(self.graph.handle, None if seeds is not None else self.seeder.handle, self.stream, batch.handle, seeds.handle if seeds is not None else None,
+                                               C.byref(self.params), C.byref(self.params_ext), C.byref(res)))
+        elif seeds is not None:   # the caller's own hits in place of the minimizer seeder (gc_align_batch_seeded; seed_density does not apply)
             _check(self.lib.gc_align_batch_seeded(self.graph.handle, self.stream, batch.handle, seeds.handle, C.byref(self.params), C.byref(res)))
         elif self.seeder is None:
             raise ValueError("this Aligner has no seeder: pass seeds=SeedBatch(graph, batch, hits_per_read)")

@@ -48,7 +48,7 @@
 					// trace cells the two extensions of this seed may need: backward p rows, forward split_len - 1 - p (src/GraphAligner.h:499-511)
 					const uint32_t p = gl.seeds[k].seqPos - w.l, q = (uint32_t)P->split_len - 1 - p;
 					// (rows + 1 + score cells: the HMM keeps a one-slice extension only below a score of 24; under force_global the score reaches the rows)
-					budget += P->force_global ? (p ? 2 * p + 1 : 0) + (q ? 2 * q + 1 : 0) : (p ? p + 24 : 0) + (q ? q + 24 : 0);
+					budget += P->force_global || clip.on() ? (p ? 2 * p + 1 : 0) + (q ? 2 * q + 1 : 0) : (p ? p + 24 : 0) + (q ? q + 24 : 0);
 				}
 				fr.seedEnd = (uint32_t)slot;
 				windowSeeds[worker] = std::max(windowSeeds[worker], w.sr - w.sl);
@@ -103,6 +103,7 @@
 		if (P->ramp_bandwidth > P->bandwidth) cfg.bandwidth = P->ramp_bandwidth;
 		cfg.maxCells = P->max_cells_per_slice < 0 || P->max_cells_per_slice >= 0xffffffffll ? ~0u : (uint32_t)P->max_cells_per_slice;   // (no slice reaches 2^32 - 1 cells)
 		cfg.forceGlobal = P->force_global != 0;
+		clip.apply(cfg);   // precise clipping / the X-drop: every extension runs in k_extend_slab_clip (below)
 		cfg.maxSlices = 3;
 		cfg.maxItems = 72;
 		cfg.maxPending = 48;
@@ -117,7 +118,7 @@
 		dResults = st->results.reserve<ExtResult>(nWork);
 		// r6: fragments of up to 65 bases (one slice per extension) go through the lockstep kernel (gc_extend_frag.hip); what it declines and every longer fragment through the
 		// plain-layout kernel on per-lane slabs. GC_EXTEND_SLAB=1: the plain-layout kernel for everything, as up to r5 (A/B)
-		const bool fragKernel = P->split_len <= 65 && !sw.extendSlab;
+		const bool fragKernel = P->split_len <= 65 && !sw.extendSlab && !clip.on();   // (the lockstep kernel does not clip: a clipped batch takes the path of its declined items for everything)
 		uint8_t* dScratch = fragKernel ? nullptr : st->scratch.reserve<uint8_t>((uint64_t)lanes * slabBytes);
 		const uint32_t fragWaves = fragKernel ? extendFragWaves() : 0;
 		uint4* dFragItems = fragKernel ? st->fragItems.reserve<uint4>(extendFragScratchBytes(fragWaves) / sizeof(uint4)) : nullptr;

@@ -60,7 +60,9 @@
 			lcfg.maxPending = 96;
 			lcfg.forceGlobal = P->force_global != 0;
 			// (an extension's trace: rows + 1 + score cells. force_global keeps every slice, so the score reaches the rows)
-			lcfg.maxTrace = P->force_global ? (uint32_t)(2 * maxReadLen + 2 + 512) : (uint32_t)(maxReadLen + maxReadLen / 2 + 512);
+			// (precise clipping keeps slices the correctness trim would drop: the trace is bounded by the rows and the score as under force_global)
+			lcfg.maxTrace = P->force_global || clip.on() ? (uint32_t)(2 * maxReadLen + 2 + 512) : (uint32_t)(maxReadLen + maxReadLen / 2 + 512);
+			clip.apply(lcfg);   // precise clipping / the X-drop: the rounds launch k_long_extend<.., true, true>, the fallback k_long_pass<true, true>
 			// column store of the one-extension-per-wave kernel: the DP keeps every column (16 B) so that the backtrace loads its tiles' columns back instead of
 			// recomputing them (45 % of the kernel's column steps). ~2.1 columns per read row on cfg2; an extension that needs more than this room ends
 			// with EXT_OVERFLOW and its read goes to the plain-layout kernel, which recomputes. GC_TEST_LONG_MAX_COLS=0: no store (the r2 behaviour).
@@ -99,7 +101,7 @@
 			dRetryList = st->longRetryList.reserve<uint32_t>(workCapacity);   // work items whose band outgrew the register tables (per round)
 			dOrder = st->longOrder.reserve<uint32_t>(workCapacity);       // learns the round's work count (k_publish: no copy-engine transfer in the round loop)
 			roundTraceBudget = 0;
-			for (uint64_t r = 0; r < n; r++) { uint64_t len = R->offsets[r + 1] - R->offsets[r]; roundTraceBudget += 4 * ((P->force_global ? 2 * len + 2 : len + len / 2) + 1024); }   // up to four candidate seeds' worth per read (the speculation rule of the round loop keeps rounds within it); a seed's two traces: len + 1 + score cells
+			for (uint64_t r = 0; r < n; r++) { uint64_t len = R->offsets[r + 1] - R->offsets[r]; roundTraceBudget += 4 * ((P->force_global || clip.on() ? 2 * len + 2 : len + len / 2) + 1024); }   // up to four candidate seeds' worth per read (the speculation rule of the round loop keeps rounds within it); a seed's two traces: len + 1 + score cells
 			dRoundTrace = st->longRoundTrace.reserve<unsigned long long>(roundTraceBudget);
 			// extension scratch: one region per lane of a resident wave (persistent waves fetch work items)
 			// (bounded by a memory budget: 0.8 MB per lane for 10 kb reads, 2.4 MB for 50 kb reads; GC_TEST_LONG_SCRATCH_GB overrides the 48 GB)

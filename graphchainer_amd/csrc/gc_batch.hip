@@ -3,10 +3,19 @@
 
 extern "C" {
 
+// gc_params_ext as the batch runs with it: the cut-off the reference would run with (0.66 for an X-drop without one, src/AlignerMain.cpp:443-448) and its error cost in double
+struct ClipOptions {
+	double cutoff = 0;     // preciseClippingIdentityCutoff; 0: clipping off
+	double errorCost = 0;  // XscoreErrorCost = c / (1 - c) + 1 (src/GraphAlignerCommon.h:108)
+	int32_t xDrop = 0;     // Xdropcutoff
+	bool on() const { return cutoff != 0; }
+	void apply(ExtendConfig& cfg) const { if (on()) { cfg.setClipErrorCost(errorCost); cfg.xDrop = xDrop; } }
+};
+
 struct BatchRun {
 	// ---- the call
 	const gc::Switches sw;   // the GC_* switches as they were when the call began (host/gc_switches.hpp)
-	const gc_graph* const G; const gc_seeder* const S; const gc_seeds* const H; gc_stream* const st; const gc_reads* const R; const gc_params* const P; gc_result* const res;   // S: the minimizer index (gc_align_batch), or null and H: the caller's own hits (gc_align_batch_seeded)
+	const gc_graph* const G; const gc_seeder* const S; const gc_seeds* const H; gc_stream* const st; const gc_reads* const R; const gc_params* const P; const ClipOptions clip; gc_result* const res;   // S: the minimizer index (gc_align_batch), or null and H: the caller's own hits (gc_align_batch_seeded)
 	const double tCall, cpuCall;
 	double cpuJoined;
 	const uint64_t n;                        // reads in the batch
@@ -47,7 +56,7 @@ struct BatchRun {
 	uint64_t longScratchWords = 0;
 	bool shareLongScratch = false;
 	double longExtendUs = 0; uint32_t longRounds = 0;   // the rounds' extension kernels (event pairs) and how many rounds had work, reruns of the pass included
-	const gc::EValueModel evalueModel { 0.7 };   // src/Aligner.cpp:478-482 (precise clipping is out of scope)
+	const gc::EValueModel evalueModel { clip.on() ? clip.cutoff : 0.7 };   // src/Aligner.cpp:474-482: the clipping cut-off is the model's identity
 	struct DecisionPointers { EdPair* hPairs = nullptr; int64_t* hOut = nullptr; EdPair* dPairs = nullptr; int64_t* dOut = nullptr; char* dLetters = nullptr; uint32_t* dLettersLen = nullptr; } decisionPtr[2];
 	// ... the whole-read pass's own buffers and sizes (prepareWholeReadPass sets them; runLongRounds / growLongCells / longFallback / afterLongPass run on the pass thread)
 	LongJob* hJobs = nullptr;
@@ -135,8 +144,8 @@ struct BatchRun {
 	double tJoined = 0;
 	const LongCell* longCells = nullptr;   // keep_traces: the merged traces in pinned staging (a pageable destination made this copy 2-3 s per 10 k reads)
 
-	BatchRun(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result* res, double tCall, double cpuCall)
-		: sw(sw), G(G), S(S), H(H), st(st), R(R), P(P), res(res), tCall(tCall), cpuCall(cpuCall), cpuJoined(cpuCall), n(R->offsets.size() - 1), hg(G->host), pool(WorkerPool::batch()), glue(st->glue),
+	BatchRun(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, const ClipOptions& clip, gc_result* res, double tCall, double cpuCall)
+		: sw(sw), G(G), S(S), H(H), st(st), R(R), P(P), clip(clip), res(res), tCall(tCall), cpuCall(cpuCall), cpuJoined(cpuCall), n(R->offsets.size() - 1), hg(G->host), pool(WorkerPool::batch()), glue(st->glue),
 		  stream(st->stream) {}
 	~BatchRun() { if (longThread.joinable()) longThread.join(); }   // (an exception on the main thread must not leave the pass thread behind with dangling state)
 	BatchRun(const BatchRun&) = delete;
@@ -193,7 +202,25 @@ struct BatchRun {
 #include "batch/gc_batch_output.inc"   // the chained alignments' traces, the output encoders on the device, the flat result
 };
 
-static int alignBatch(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result** out)
+// The extension block's checks (src/AlignerMain.cpp:300-322,443-448; getSlices' assertion, ...Banded.h:504): host only, nothing but the two structs is read
+static int resolveExt(const gc_params* P, const gc_params_ext* X, ClipOptions& clip)
+{
+	clip = ClipOptions();
+	if (!X) return GC_OK;
+	if (X->struct_size < sizeof(gc_params_ext)) return fail(GC_ERR_INVALID, "gc_params_ext::struct_size is smaller than the struct (was it initialised with gc_params_ext_default?)");
+	if (X->struct_size > sizeof(gc_params_ext)) return fail(GC_ERR_INVALID, "gc_params_ext::struct_size is larger than this library knows: the caller's header is newer");
+	if (X->x_drop < 0) return fail(GC_ERR_INVALID, "gc_params_ext::x_drop must be 0 (off) or >= 1 (src/AlignerMain.cpp:316-322)");
+	const double c = X->precise_clipping;
+	if (std::isnan(c) || (c != 0 && !(c >= 0.001 && c <= 0.999))) return fail(GC_ERR_INVALID, "gc_params_ext::precise_clipping must be 0 (off) or in [0.001, 0.999] (src/AlignerMain.cpp:300-315)");
+	if (X->x_drop > 0 && P->force_global != 0) return fail(GC_ERR_INVALID, "gc_params_ext::x_drop cannot be combined with force_global (getSlices asserts, src/GraphAlignerBitvectorBanded.h:504)");
+	clip.cutoff = c;
+	clip.xDrop = X->x_drop;
+	if (clip.xDrop > 0 && clip.cutoff == 0) clip.cutoff = 0.66;   // the reference's default, not an override (src/AlignerMain.cpp:443-448)
+	if (clip.on()) clip.errorCost = clip.cutoff / (1.0 - clip.cutoff) + 1.0;
+	return GC_OK;
+}
+
+static int alignBatch(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, const ClipOptions& clip, gc_result** out)
 {
 	if (P->split_len < 16 || P->split_len > 64 || P->split_gap < 1) return fail(GC_ERR_INVALID, "split_len must be in [16,64] (one 64-row slice per fragment extension) and split_gap >= 1");
 	if (P->ramp_bandwidth < 0 || (P->ramp_bandwidth != 0 && P->ramp_bandwidth <= P->bandwidth)) return fail(GC_ERR_INVALID, "ramp_bandwidth must be 0 (off) or larger than bandwidth (src/AlignerMain.cpp:380-383)");
@@ -230,7 +257,7 @@ static int alignBatch(const gc::Switches& sw, const gc_graph* G, const gc_seeder
 		// (src/Aligner.cpp:904): with a cut-off set the traces are made whatever chain_traces says
 		gc_params effective = *P;
 		if (effective.chain_traces == 0 && effective.e_cutoff >= 0 && effective.stitch && effective.edit_distances) effective.chain_traces = 1;
-		BatchRun batch(sw, G, S, H, st, R, &effective, res, tCall, cpuCall);
+		BatchRun batch(sw, G, S, H, st, R, &effective, clip, res, tCall, cpuCall);
 		batch.run();
 		return (int)GC_OK;
 	});
@@ -241,21 +268,32 @@ static int alignBatch(const gc::Switches& sw, const gc_graph* G, const gc_seeder
 	return GC_OK;
 }
 
+int gc_align_batch_ext(const gc_graph* G, const gc_seeder* S, gc_stream* st, const gc_reads* R, const gc_seeds* H, const gc_params* P, const gc_params_ext* X, gc_result** out)
+{
+	if (!P || !out) return fail(GC_ERR_INVALID, "null argument");
+	ClipOptions clip;
+	if (int rc = resolveExt(P, X, clip)) return rc;
+	if ((S != nullptr) == (H != nullptr)) return fail(GC_ERR_INVALID, "gc_align_batch_ext takes a seeder or the caller's seeds, not both and not neither");
+	if (!G || !st || !R) return fail(GC_ERR_INVALID, "null argument");
+	gc::Switches sw = gc::Switches::fromEnvironment();
+	if (H) {
+		if (H->readOffsets != R->offsets) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds were uploaded for another read batch");
+		if (H->device != st->device) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds live on another device than the stream");
+		if (!sw.deviceGlue) return fail(GC_ERR_INVALID, "gc_align_batch_seeded needs the device seed glue (GC_DEVICE_GLUE=0 keeps the host glue, which only expands minimizer matches)");
+	}
+	return alignBatch(sw, G, S, H, st, R, P, clip, out);
+}
+
 int gc_align_batch(const gc_graph* G, const gc_seeder* S, gc_stream* st, const gc_reads* R, const gc_params* P, gc_result** out)
 {
 	if (!G || !S || !st || !R || !P || !out) return fail(GC_ERR_INVALID, "null argument");
-	return alignBatch(gc::Switches::fromEnvironment(), G, S, nullptr, st, R, P, out);
+	return gc_align_batch_ext(G, S, st, R, nullptr, P, nullptr, out);
 }
 
 int gc_align_batch_seeded(const gc_graph* G, gc_stream* st, const gc_reads* R, const gc_seeds* H, const gc_params* P, gc_result** out)
 {
 	if (!G || !st || !R || !H || !P || !out) return fail(GC_ERR_INVALID, "null argument");
-	if (H->readOffsets != R->offsets) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds were uploaded for another read batch");
-	if (H->device != st->device) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds live on another device than the stream");
-	const gc::Switches sw = gc::Switches::fromEnvironment();
-	if (!sw.deviceGlue) return fail(GC_ERR_INVALID, "gc_align_batch_seeded needs the device seed glue (GC_DEVICE_GLUE=0 keeps the host glue, which only expands minimizer matches)");
-	return alignBatch(sw, G, nullptr, H, st, R, P, out);
+	return gc_align_batch_ext(G, nullptr, st, R, H, P, nullptr, out);
 }
 
 } // extern "C"
-

@@ -402,6 +402,27 @@ int gc_std_sort_permutations(const uint32_t* keys, const uint64_t* offsets, uint
 	});
 }
 
+// Test entry: the plain-layout kernel's column maximum (clipMaxXScore, hip/gc_device.hpp) on the caller's columns
+int gc_test_max_x_score(const uint64_t* vp, const uint64_t* vn, const int32_t* score_end, uint64_t n, double error_cost, int32_t cells, int32_t* out)
+{
+	if (!out || ((!vp || !vn || !score_end) && n)) return fail(GC_ERR_INVALID, "null argument");
+	if (cells < 1 || cells > 64 || n >= 0xffffffffull) return fail(GC_ERR_INVALID, "gc_test_max_x_score: cells must be in [1, 64]");
+	return guarded([&]() {
+		requireDevice();
+		if (!n) return (int)GC_OK;
+		DeviceBuffer dVp, dVn, dScore, dOut;
+		uint64_t* a = dVp.reserve<uint64_t>(n); uint64_t* b = dVn.reserve<uint64_t>(n);
+		int32_t* c = dScore.reserve<int32_t>(n); int32_t* o = dOut.reserve<int32_t>(n);
+		HIP_CHECK(hipMemcpy(a, vp, n * sizeof(uint64_t), hipMemcpyHostToDevice));
+		HIP_CHECK(hipMemcpy(b, vn, n * sizeof(uint64_t), hipMemcpyHostToDevice));
+		HIP_CHECK(hipMemcpy(c, score_end, n * sizeof(int32_t), hipMemcpyHostToDevice));
+		launchTestMaxXScore(nullptr, a, b, c, (uint32_t)n, error_cost, cells, o);
+		HIP_CHECK(hipDeviceSynchronize());
+		HIP_CHECK(hipMemcpy(out, o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+		return (int)GC_OK;
+	});
+}
+
 int gc_device_count(void)
 {
 	int n = 0;
@@ -429,6 +450,15 @@ int gc_set_device(int device)
 
 // fast_mode took the struct's tail padding: the other fields are where they were and the size is what it was
 static_assert(sizeof(gc_params) == 216 && offsetof(gc_params, fast_mode) == offsetof(gc_params, selection_method) + 4 && offsetof(gc_params, fast_mode) + 4 == sizeof(gc_params), "gc_params layout");
+
+static_assert(sizeof(gc_params_ext) == 16 && offsetof(gc_params_ext, precise_clipping) == 8, "gc_params_ext layout");
+void gc_params_ext_default(gc_params_ext* e)
+{
+	if (!e) return;
+	e->struct_size = (uint32_t)sizeof(gc_params_ext);
+	e->x_drop = 0;               // off (src/AlignerMain.cpp: Xdropcutoff 0)
+	e->precise_clipping = 0.0;   // off
+}
 
 void gc_params_default(gc_params* p)
 {

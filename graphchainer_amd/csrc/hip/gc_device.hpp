@@ -166,6 +166,11 @@ struct SliceInfo {  // reference: DPSlice, src/GraphAlignerBitvectorCommon.h:138
 	int32_t j;                  // first read row of the slice (-64 for the initial slice)
 	uint32_t flags;             // bit0 currentlyCorrect, bit1 correctFromCorrect, bit2 falseFromCorrect, bit3 flatten tie, bit4 scoresNotValid (SLICE_NOT_VALID)
 	double correctLogOdds, falseLogOdds;
+	// Precise clipping (CLIP instantiations): the record's size is what every slab is laid out by, and the cell of the slice's minimum (minNode, minOffset) is read by the
+	// last-row start of the backtrace alone, which that mode does not have - its two words hold DPSlice::maxExactEndposNode / maxExactEndposScore instead. Only through these:
+	__device__ __forceinline__ void setClipScore(uint32_t node, int32_t x) { minNode = node; minOffset = (uint32_t)x; }
+	__device__ __forceinline__ int32_t clipScore() const { return (int32_t)minOffset; }
+	__device__ __forceinline__ uint32_t clipNode() const { return minNode; }
 };
 
 struct Pending {    // a node scheduled in the current slice with its incoming columns already folded
@@ -212,6 +217,13 @@ struct ExtendConfig {
 	// gc_params::force_global (forceGlobal, ...Banded.h:51,120,587-645): every slice is kept - no stop at a slice that is not correct-from-correct, no rewind of the ramp
 	// (so only slice 0 takes the ramp bandwidth, :544), no removeWronglyAlignedEnd. It changes the slice loop's decisions only, so it runs in the BAND instantiations too.
 	uint32_t forceGlobal = 0;
+	// gc_params_ext::precise_clipping / x_drop (preciseClipping, Xdropcutoff). Only the CLIP instantiation of extendSeedT reads them; the host launches it when clipping is on.
+	// The error cost E = c / (1 - c) + 1 (XscoreErrorCost, src/GraphAlignerCommon.h:108) is the host's double, bit for bit, in two 32-bit halves (an 8-byte member: see above)
+	uint32_t clipErrorCostLo = 0, clipErrorCostHi = 0;   // both 0: clipping off (E > 1 whenever it is on)
+	int32_t xDrop = 0;                                   // Xdropcutoff: 0 off (getViterbiSlices), >= 1 getXdropSlices
+	__host__ __device__ bool clipOn() const { return (clipErrorCostLo | clipErrorCostHi) != 0; }
+	__host__ __device__ double clipErrorCost() const { return __builtin_bit_cast(double, ((uint64_t)clipErrorCostHi << 32) | clipErrorCostLo); }
+	__host__ __device__ void setClipErrorCost(double e) { const uint64_t b = __builtin_bit_cast(uint64_t, e); clipErrorCostLo = (uint32_t)b; clipErrorCostHi = (uint32_t)(b >> 32); }
 	__host__ __device__ bool bandControls() const { return rampBandwidth != 0 || maxCells != ~0u || forceGlobal != 0; }
 };
 enum : uint32_t { SLICE_NOT_VALID = 16u };   // SliceInfo::flags: the slice reached maxCellsPerSlice (DPSlice::scoresNotValid, ...Banded.h:581-584)
@@ -348,13 +360,69 @@ __device__ inline int findItem(const uint32_t* itemNodes, const SliceInfo& sl, u
 	return -1;
 }
 
+// ---- precise clipping (gc_params_ext::precise_clipping): the X score of a cell is cells - score * E, truncated toward zero (ScoreType), E = XscoreErrorCost
+// (src/WordSlice.h:239-242). The product and the difference are each rounded to double, as the host compiler of the reference does them: a fused multiply-subtract rounds
+// once and gives another integer (E = 2.9411764705882355, cells 51, score 17: 1 against 0), so the two steps are spelled out.
+// (__dmul_rn / __dsub_rn are plain * and - in HIP and were contracted into one v_fma_f64 all the same: the pragma takes the contract flag off the two operations themselves)
+__device__ __forceinline__ int32_t clipXScore(int32_t cells, int32_t scoreHere, double errorCost)
+{
+#pragma clang fp contract(off)
+	const double product = (double)scoreHere * errorCost;
+	const double difference = (double)cells - product;
+	return (int32_t)difference;
+}
+// maxXScoreFirstSlices (src/WordSlice.h:223-232,313-336), the local-minima form as it is written there: the candidates are row 0 and the rows before a +1 delta
+__device__ inline int32_t clipMaxXScore(const WS& w, double errorCost, int cells)
+{
+	const int32_t scoreBeforeStart = wsBefore(w);
+	const uint64_t priorityCausedMinima = ~w.VP;
+	uint64_t possibleLocalMinima = w.VP & (priorityCausedMinima - w.VP);
+	possibleLocalMinima >>= 1;
+	possibleLocalMinima |= (1ull << 63) & (priorityCausedMinima | ~(priorityCausedMinima - w.VP)) & ~w.VP;
+	int32_t result = INT32_MIN;
+	possibleLocalMinima |= 1;
+	while (possibleLocalMinima != 0) {
+		GC_LOOP_TICK(2);
+		const uint64_t currentMinimumMask = possibleLocalMinima ^ (possibleLocalMinima - 1);
+		const int cellsHere = popc64(currentMinimumMask);
+		if (cellsHere > cells) break;
+		const int32_t scoreHere = scoreBeforeStart + popc64(w.VP & currentMinimumMask) - popc64(w.VN & currentMinimumMask);
+		const int32_t x = clipXScore(cellsHere, scoreHere, errorCost);
+		result = x > result ? x : result;
+		possibleLocalMinima &= ~currentMinimumMask;
+	}
+	return result;
+}
+// What getReverseTraceFromTableExactEndPos (...Common.h:353-379) looks for in the tile of the best slice's maxExactEndposNode: the cell that attains the slice's score
+struct ClipFind {
+	int32_t target;   // the slice's maxExactEndposScore - j
+	int cells;        // min(64, |seq| - j): rows inside the read
+	bool found; uint32_t column; int row; int32_t value;
+};
+__device__ inline void clipFindColumn(ClipFind& f, const WS& w, uint32_t column, double errorCost, uint32_t& status)
+{
+	const int32_t maxScore = clipMaxXScore(w, errorCost, f.cells);
+	if (maxScore > f.target) status = EXT_ASSERT;   // :358
+	if (maxScore != f.target) return;
+	for (int off = 63; off >= 0; off--) {
+		if (off >= f.cells) continue;   // :363
+		const int32_t scoreHere = clipXScore(off + 1, wsValue(w, off), errorCost);
+		if (scoreHere > f.target) status = EXT_ASSERT;   // :365
+		if (scoreHere == f.target && (!f.found || off > f.row)) { f.found = true; f.column = column; f.row = off; f.value = wsValue(w, off); }
+	}
+}
+
 // One (node, slice) tile: first column = `ws` (already merged over all incoming edges), then up to 63 Myers
 // steps. reference: src/GraphAlignerBitvectorCommon.h:1052-1167 for a node that is new in this slice.
 // If `columns` != nullptr every column is stored (backtrace recompute). If flatRows > 0 the minimum over
 // columns of the score at row flatRows-1 is tracked (fused flattenLastSliceEnd, ...Common.h:1210-1218).
+// CLIP (precise clipping): *maxX receives the maximum X score over the entry column and every later one (calculateNodeInner<PreciseClipping = true>, ...Common.h:971-975,
+// 1148-1151), or - with `find` - the recomputed columns are searched for the cell that attains the slice's score instead.
 struct TileResult { int32_t minScore; uint32_t minOffset; int32_t flatMin; uint32_t flatOffset; };
+template <bool CLIP = false>
 __device__ inline TileResult computeTile(const DGraph& g, uint32_t node, WS ws, bool prevExists, int32_t prevStartScore, uint64_t prevHP, uint64_t prevHN,
-	const Eq4& eq, NodeItem& out, WCol* columns, int flatRows, uint32_t& status, uint32_t colMask = 63, uint32_t colStride = 1, int lastColumn = 63)
+	const Eq4& eq, NodeItem& out, WCol* columns, int flatRows, uint32_t& status, uint32_t colMask = 63, uint32_t colStride = 1, int lastColumn = 63,
+	double errorCost = 0, int32_t* maxX = nullptr, ClipFind* find = nullptr)
 {
 	int nodeLength = g.nodeLength[node];
 	if (lastColumn + 1 < nodeLength) nodeLength = lastColumn + 1;   // (backtrace ring refill: the columns up to the one the walk stands on; `out`'s end column is then that column)
@@ -362,6 +430,7 @@ __device__ inline TileResult computeTile(const DGraph& g, uint32_t node, WS ws, 
 	TileResult r;
 	r.minScore = ws.score;   // (sic) taken before the merge with the row above, ...Common.h:968 vs :1052-1058
 	r.minOffset = 0;
+	if (CLIP && maxX) *maxX = clipMaxXScore(ws, errorCost, 64);   // (taken before the merge too, :973)
 	if (prevExists && wsBefore(ws) > prevStartScore) ws = wsMerge(ws, wsSource(prevStartScore));
 	int forceUntil = 0;
 	if (prevExists) {
@@ -390,6 +459,7 @@ __device__ inline TileResult computeTile(const DGraph& g, uint32_t node, WS ws, 
 	r.flatOffset = 0;
 	if (flatRows > 0) r.flatMin = ws.score - popc64(ws.VP & ~flatMask) + popc64(ws.VN & ~flatMask);
 	if (columns) columns[0] = WCol { ws.VP, ws.VN };   // ((0 & colMask) * colStride)
+	if (CLIP && find) clipFindColumn(*find, ws, 0, errorCost, status);   // (recalcNodeWordslice's column 0 is the stored start column)
 	uint64_t forceEq = prevExists ? ~0ull : ~1ull;
 	uint64_t HP = 0, HN = 0;
 	for (int pos = 1; pos < nodeLength; pos++) {
@@ -403,6 +473,8 @@ __device__ inline TileResult computeTile(const DGraph& g, uint32_t node, WS ws, 
 			if (f < r.flatMin) { r.flatMin = f; r.flatOffset = (uint32_t)pos; }
 		}
 		if (columns) columns[((uint32_t)pos & colMask) * colStride] = WCol { ws.VP, ws.VN };
+		if (CLIP && maxX) { const int32_t x = clipMaxXScore(ws, errorCost, 64); *maxX = x > *maxX ? x : *maxX; }
+		if (CLIP && find) clipFindColumn(*find, ws, (uint32_t)pos, errorCost, status);
 		HP |= hp << pos;
 		HN |= hn << pos;
 	}
@@ -545,7 +617,12 @@ struct EqFromBases {
 	__device__ __forceinline__ void rows(int len, int j, Eq4& eq) const { eqVector(seq, len, j, iupac, eq); }
 };
 // BAND: the band controls of cfg (ramp, cell limit); the default instantiation is the plain band.
-template <class EQS, bool BAND = false>
+// CLIP (with BAND only): precise clipping and the X-drop (gc_params_ext). Every slice records the maximum X score of its cells and the node that holds it - in the
+// slice record's minNode / minOffset, which only the last-row start of the backtrace reads and this mode does not have: no flattenLastSliceEnd (...Banded.h:414), no
+// removeWronglyAlignedEnd (:51,120), and the backtrace starts at the cell that attains the best slice's score (getReverseTraceFromTableExactEndPos, ...Common.h:321-383).
+// cfg.xDrop > 0 runs getXdropSlices (...Banded.h:703-830) in place of getViterbiSlices: the plain bandwidth, no stop, no ramp; a slice whose score falls more than
+// xDrop below the best so far is dropped and ends the loop.
+template <class EQS, bool BAND = false, bool CLIP = false>
 __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables& ct, const EQS& eqs, const ExtendConfig& cfg, const LaneScratch& sc,
 	int len, uint32_t startNode, uint32_t startOffset, uint32_t& nTrace, int32_t& score, ExtCounters& cnt)
 {
@@ -572,6 +649,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 		it.HP = nodeMask & ~upToOffset;
 		SliceInfo& s0 = sc.slices[0];
 		s0.minScore = 0; s0.minNode = startNode; s0.minOffset = startOffset;
+		if (CLIP) s0.setClipScore(startNode, 0);   // maxExactEndposScore = 0 and its node, ...Common.h:1259-1260
 		s0.first = 0; s0.count = 1; s0.bandwidth = 1; s0.j = -64;
 		s0.correctLogOdds = ct.initCorrect; s0.falseLogOdds = ct.initFalse;
 		s0.flags = 1;   // log(0.8) > log(0.2)
@@ -584,6 +662,10 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 	int rampUntil = 0, rampRedoIndex = -1;
 	const bool rampOn = BAND && cfg.rampBandwidth > cfg.bandwidth;
 	const bool keepAll = BAND && cfg.forceGlobal != 0;   // forceGlobal: the whole `if (!forceGlobal)` block of ...Banded.h:587-645 is skipped
+	static_assert(BAND || !CLIP, "CLIP is instantiated with BAND");
+	const double errorCost = CLIP ? cfg.clipErrorCost() : 0.0;
+	const bool xDropOn = CLIP && cfg.xDrop > 0;
+	int32_t bestXScore = 0;   // (getXdropSlices: the initial slice's)
 	for (int slice = 0; slice < numSlices; slice++) {
 		const SliceInfo prev = sc.slices[nSlices - 1];
 		int j = prev.j + 64;
@@ -591,9 +673,10 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 		int32_t previousQuitScore = prev.minScore + prev.bandwidth;
 		int32_t previousMinScore = prev.minScore;
 		int bandwidth = cfg.bandwidth;
-		if (BAND && rampOn && rampUntil >= slice) bandwidth = cfg.rampBandwidth;
+		if (BAND && rampOn && rampUntil >= slice && !xDropOn) bandwidth = cfg.rampBandwidth;   // (getXdropSlices: every slice at initialBandwidth, :733)
 		uint32_t cells = 0;   // (BAND) the slice's cellsProcessed: a node computed once (a DAG has no revisits, so no early leave) counts its length (...Common.h:1162)
-		int flatRows = (j + 64 > len) ? (len - j) : 0;   // last partial slice (...Banded.h:414)
+		int flatRows = (!CLIP && j + 64 > len) ? (len - j) : 0;   // last partial slice (...Banded.h:414: not under precise clipping)
+		int32_t sliceMaxX = INT32_MIN; uint32_t sliceMaxXNode = 0xffffffffu;   // (CLIP) the first strict maximum in pop order (:394-398)
 		// seed the queue from the previous slice's in-band nodes (...Banded.h:235-277; linearizable is all-false)
 		uint32_t nPending = 0;
 		for (uint32_t i = 0; i < prev.count; i++) {
@@ -618,9 +701,11 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			int prevIdx = findItem(sc.itemNodes, prev, p.node);
 			bool prevExists = prevIdx >= 0;
 			NodeItem& out = sc.items[nItems];
-			TileResult tr = computeTile(g, p.node, WS { p.VP, p.VN, p.score }, prevExists, prevExists ? sc.items[prevIdx].sScore : 0,
-				prevExists ? sc.items[prevIdx].HP : ~0ull, prevExists ? sc.items[prevIdx].HN : 0ull, eq, out, nullptr, flatRows, status);
+			int32_t tileMaxX = INT32_MIN;
+			TileResult tr = computeTile<CLIP>(g, p.node, WS { p.VP, p.VN, p.score }, prevExists, prevExists ? sc.items[prevIdx].sScore : 0,
+				prevExists ? sc.items[prevIdx].HP : ~0ull, prevExists ? sc.items[prevIdx].HN : 0ull, eq, out, nullptr, flatRows, status, 63, 1, 63, errorCost, CLIP ? &tileMaxX : nullptr);
 			if (status != EXT_OK) return status;
+			if (CLIP && tileMaxX > sliceMaxX) { sliceMaxX = tileMaxX; sliceMaxXNode = p.node; }
 			out.minScore = tr.minScore;
 			sc.itemNodes[nItems] = p.node;
 			nItems++;
@@ -653,6 +738,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 		const uint32_t flatTie = flatRows > 0 ? (flatOffset >> 31) << 3 : 0u;   // kept in the slice's flags (bit 3)
 		if (flatRows > 0) { cur.minScore = flatMin; cur.minNode = flatNode; cur.minOffset = flatOffset & 0x7fffffffu; }
 		if (cur.minScore < prev.minScore) return EXT_ASSERT;   // ...Banded.h:463
+		if (CLIP) cur.setClipScore(sliceMaxXNode, sliceMaxX + j);   // maxExactEndposNode / maxExactEndposScore (fillDPSlice adds slice.j, :456)
 		// correctness HMM (src/AlignmentCorrectnessEstimation.cpp:105-129): +, max, >= only
 		{
 			int mm = cur.minScore - prev.minScore;
@@ -670,6 +756,13 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 			if (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u))) rampRedoIndex = slice - 1;
 			if (cells >= cfg.maxCells) cur.flags |= SLICE_NOT_VALID;
 		}
+		if (xDropOn) {   // ...Banded.h:762-797: the slice loop of getXdropSlices
+			const int32_t x = cur.clipScore();
+			if (x > bestXScore) bestXScore = x;
+			if (x < bestXScore - cfg.xDrop) break;
+			sc.slices[nSlices++] = cur;
+			continue;
+		}
 		if (!keepAll && !(cur.flags & 2u)) break;   // !CorrectFromCorrect: stop, slice not kept (...Banded.h:589-607)
 		if (BAND && !keepAll && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
 			// ...Banded.h:608-644: not currently correct - redo from the snapshot with the ramp bandwidth up to this slice. (rampRedoIndex >= 0 here: the
@@ -683,7 +776,7 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 		sc.slices[nSlices++] = cur;
 	}
 	// removeWronglyAlignedEnd, ...Common.h:1231-1241 (not called with forceGlobal, ...Banded.h:51,120)
-	if (!keepAll) {
+	if (!keepAll && !CLIP) {
 		bool currentlyCorrect = (sc.slices[nSlices - 1].flags & 1u) != 0;
 		while (!currentlyCorrect) {
 			currentlyCorrect = (sc.slices[nSlices - 1].flags & 4u) != 0;
@@ -698,6 +791,31 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 
 	// ---- backtrace (getReverseTraceFromTable, ...Common.h:392-544)
 	Cell here { last.minNode, last.minOffset, (last.j + 63 < len - 1) ? last.j + 63 : len - 1 };
+	if (CLIP) {
+		// getReverseTraceFromTableExactEndPos: the slice with the first strict maximum of maxExactEndposScore from slice 1 on; its node's tile, recomputed, is searched for the
+		// cells that attain the score; the largest row wins, the first column at equal rows
+		uint32_t bestIndex = 1;
+		for (uint32_t k = 2; k < nSlices; k++) if (sc.slices[k].clipScore() > sc.slices[bestIndex].clipScore()) bestIndex = k;
+		const SliceInfo& bs = sc.slices[bestIndex];
+		const uint32_t bestNode = bs.clipNode();
+		const int bestItem = findItem(sc.itemNodes, bs, bestNode);
+		if (bestItem < 0) return EXT_ASSERT;
+		const NodeItem& it = sc.items[bestItem];
+		const int prevIdx = findItem(sc.itemNodes, sc.slices[bestIndex - 1], bestNode);
+		const bool prevExists = prevIdx >= 0;
+		eqs.rows(len, bs.j, eq);
+		ClipFind find { bs.clipScore() - bs.j, len - bs.j < 64 ? len - bs.j : 64, false, 0u, 0, 0 };
+		NodeItem scratch;
+		computeTile<true>(g, bestNode, itemStart(it), prevExists, prevExists ? sc.items[prevIdx].sScore : 0, prevExists ? sc.items[prevIdx].HP : ~0ull, prevExists ? sc.items[prevIdx].HN : 0ull,
+			eq, scratch, nullptr, 0, status, 63, 1, 63, errorCost, nullptr, &find);
+		if (scratch.eVP != it.eVP || scratch.eVN != it.eVN || scratch.eScore != it.eScore) status = EXT_ASSERT;   // sliceConsistency, :848-850
+		if (status != EXT_OK) return status;
+		cnt.recomputeTiles++;
+		cnt.columnSteps += g.nodeLength[bestNode];
+		if (!find.found) return EXT_ASSERT;   // :377-379
+		here = Cell { bestNode, find.column, bs.j + find.row };
+		score = find.value;   // startScore = getValue(bvOffset), :380
+	}
 	if (!pushTrace(sc, cfg, nTrace, here, false, status)) return status;
 	uint32_t curSlice = 0xffffffffu, curNode = 0xffffffffu;
 	int curItem = -1;
@@ -877,11 +995,11 @@ __device__ inline uint32_t extendSeedT(const DGraph& g, const CorrectnessTables&
 	return status;
 }
 
-template <bool BAND = false>
+template <bool BAND = false, bool CLIP = false>
 __device__ inline uint32_t extendSeed(const DGraph& g, const CorrectnessTables& ct, const uint8_t* iupac, const ExtendConfig& cfg, const LaneScratch& sc,
 	const char* seq, int len, uint32_t startNode, uint32_t startOffset, uint32_t& nTrace, int32_t& score, ExtCounters& cnt)
 {
-	return extendSeedT<EqFromBases, BAND>(g, ct, EqFromBases { seq, iupac }, cfg, sc, len, startNode, startOffset, nTrace, score, cnt);
+	return extendSeedT<EqFromBases, BAND, CLIP>(g, ct, EqFromBases { seq, iupac }, cfg, sc, len, startNode, startOffset, nTrace, score, cnt);
 }
 
 } // namespace gcdev

@@ -272,6 +272,10 @@ struct WaveScratch {
 __host__ __device__ inline uint64_t waveScratchWords(uint32_t maxSlices, uint32_t maxItems, uint32_t maxTrace, uint32_t maxCols = 0) { return (uint64_t)maxSlices * 4 + (uint64_t)maxItems * 8 + 2ull * maxTrace + 2ull * maxCols + WAVE_SPILL_WORDS; }
 
 struct WSlice { int32_t minScore; uint32_t minNode, minOffset, first, count; int32_t bandwidth; int32_t j; uint32_t flags; };
+// (CLIP) the slice's maxExactEndposScore / maxExactEndposNode live where the cell of the minimum does without clipping - see SliceInfo's accessors, gc_device.hpp
+__device__ __forceinline__ void setClipScore(WSlice& s, uint32_t node, int32_t x) { s.minNode = node; s.minOffset = (uint32_t)x; }
+__device__ __forceinline__ int32_t clipScore(const WSlice& s) { return (int32_t)s.minOffset; }
+__device__ __forceinline__ uint32_t clipNode(const WSlice& s) { return s.minNode; }
 
 __device__ __forceinline__ void storeSlice(const WaveScratch& ws, uint32_t s, const WSlice& x)
 {
@@ -361,9 +365,34 @@ __device__ __forceinline__ WS wsMergeWave(const WS& a, const WS& b)
 // instead of running the column loop a second time (one extension per wave with a column store, WaveScratch::maxCols).
 // What the preamble leaves for the caller of MODE 2 / the stored-column backtrace: the repaired carries of the row above.
 struct TilePreamble { uint64_t prevHP, prevHN, forceEq; int forceUntil; };
-template <int MODE, typename LANE_TABLES>
+// Precise clipping: WordSlice::maxXScore of a column (see clipMaxXScore, gc_device.hpp). One extension per wave: the column is uniform, so lane r takes row r - its value from
+// two masked popcounts, as the column minimum of the slice loop does - computes (ScoreType)((r + 1) - value * E) and the wave takes the maximum; that is the reference's
+// cell-by-cell form (src/WordSlice.h:264-272), which equals the local-minima form over all 64 rows (tests/test_precise_model.py holds the two against each other).
+// Lanes holding different extensions run the local-minima form.
+template <bool ROWS_IN_LANES>
+__device__ __forceinline__ int32_t clipMaxXScoreWave(const WS& w, double errorCost)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	if (ROWS_IN_LANES) {
+		const uint64_t upTo = ~(~1ull << threadIdx.x);   // bits 0..r
+		const int32_t value = wsBefore(w) + popc64(w.VP & upTo) - popc64(w.VN & upTo);
+		int32_t x = clipXScore((int32_t)threadIdx.x + 1, value, errorCost);
+		auto higher = [](int32_t a, int32_t b) { return a > b ? a : b; };
+		x = higher(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x111, 0xf, 0xf, false));
+		x = higher(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x112, 0xf, 0xf, false));
+		x = higher(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x114, 0xf, 0xf, false));
+		x = higher(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x118, 0xf, 0xf, false));
+		x = higher(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x142, 0xa, 0xf, false));
+		x = higher(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x143, 0xc, 0xf, false));
+		return (int32_t)GC_READLANE(x, 63);
+	}
+#endif
+	return clipMaxXScore(w, errorCost, 64);
+}
+// CLIP: *maxX receives the maximum X score of the entry column (before the merges, ...Common.h:973) and of every later column (:1148-1151); the column loop is the C++ form.
+template <int MODE, bool CLIP = false, typename LANE_TABLES>
 __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t node, WS ws, bool prevExists, int32_t prevStartScore, uint64_t prevHP, uint64_t prevHN,
-	const Eq4& eq, NodeItem& out, const LANE_TABLES& tables, int flatRows, uint32_t& status, TilePreamble* preambleOnly = nullptr)
+	const Eq4& eq, NodeItem& out, const LANE_TABLES& tables, int flatRows, uint32_t& status, TilePreamble* preambleOnly = nullptr, double errorCost = 0, int32_t* maxX = nullptr)
 {
 	constexpr bool COLUMNS = MODE == 1;
 	int nodeLength = g.nodeLength[node];
@@ -371,6 +400,7 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 	TileResult r;
 	r.minScore = ws.score;   // (sic) before the merge with the row above, ...Common.h:968 vs :1052-1058
 	r.minOffset = 0;
+	if (CLIP && maxX) *maxX = clipMaxXScoreWave<LANE_TABLES::eqInLanes>(ws, errorCost);
 #if defined(__HIP_DEVICE_COMPILE__)
 	if (prevExists && wsBefore(ws) > prevStartScore) ws = LANE_TABLES::eqInLanes ? wsMergeWave(ws, wsSource(prevStartScore)) : wsMerge(ws, wsSource(prevStartScore));
 #else
@@ -412,7 +442,7 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 	// and the forced-first-row flag fetched with one s_bfe_u64 each on a running field descriptor, loop-invariant masks folded into the four
 	// match masks, and the bottom row's horizontal deltas parked in lane `pos` of a VGPR (one v_writelane per column, two ballots per tile)
 	// instead of two 64-bit shift-or pairs. Not taken for IUPAC nodes and for the read's last slice (row-limited minimum).
-	if (LANE_TABLES::eqInLanes && !seq.ambiguous && flatRows <= 0) {
+	if (!CLIP && LANE_TABLES::eqInLanes && !seq.ambiguous && flatRows <= 0) {
 		const uint64_t eA = gcUniform64(eq.a & forceEq), eC = gcUniform64(eq.c & forceEq), eG = gcUniform64(eq.g & forceEq), eT = gcUniform64(eq.t & forceEq);
 		const uint64_t forced = gcUniform64(forceUntil >= 63 ? ~0ull : ((2ull << forceUntil) - 1));   // columns 1..forceUntil: first row forced
 		prevHP = gcUniform64(prevHP); prevHN = gcUniform64(prevHN);
@@ -480,6 +510,7 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 			if (f < r.flatMin) { r.flatMin = f; r.flatOffset = (uint32_t)pos; }
 		}
 		if (MODE != 0) tables.colSet((uint32_t)pos, ws);
+		if (CLIP && maxX) { const int32_t x = clipMaxXScoreWave<LANE_TABLES::eqInLanes>(ws, errorCost); *maxX = x > *maxX ? x : *maxX; }
 		HP |= hp << pos;
 		HN |= hn << pos;
 	}
@@ -493,10 +524,14 @@ __device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t nod
 // BAND: the band controls (gc_params::ramp_bandwidth / max_cells_per_slice) as extendSeedT<.., true> has them. The ramp's rewind and the cell limit's break run here; an
 // extension that keeps a slice flagged scoresNotValid answers EXT_OVERFLOW (its read goes to the plain-layout fallback, whose backtrace has the flagged rules).
 // forceGlobal (gc_params::force_global, BAND only): every slice is kept - no stop, no snapshot or rewind (slice 0 alone takes the ramp bandwidth), no removeWronglyAlignedEnd.
-template <bool REGCOLS, bool BAND = false>
+// CLIP (with BAND only): precise clipping and the X-drop, as extendSeedT<.., true, true> has them - the slice's maximum X score and its node travel in the slice record's
+// clipScore / clipNode; no flatten, no end trim, getXdropSlices with xDrop > 0, the backtrace's start from getReverseTraceFromTableExactEndPos. Capacities and retries as for BAND.
+template <bool REGCOLS, bool BAND = false, bool CLIP = false>
 __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const CorrectnessTables& ct, const EqSource& eqSrc, int bandwidthCfg, lds_u32* lds, const WaveScratch& wsx,
-	int len, uint32_t startNode, uint32_t startOffset, uint32_t which, uint32_t& nTrace, int32_t& score, ExtCounters& cnt, int rampBandwidth = 0, uint32_t maxCells = ~0u, bool forceGlobal = false)
+	int len, uint32_t startNode, uint32_t startOffset, uint32_t which, uint32_t& nTrace, int32_t& score, ExtCounters& cnt, int rampBandwidth = 0, uint32_t maxCells = ~0u, bool forceGlobal = false,
+	double errorCost = 0, int32_t xDrop = 0)
 {
+	static_assert(BAND || !CLIP, "CLIP is instantiated with BAND");
 	const LaneLdsT<REGCOLS> L { lds, wsx.lane, wsx.lanes, wsx.spillBase(), {}, wsx.regCap < 64 ? wsx.regCap : 64u, { 0, 0, 0, 0, 0 }, 0, 0 };
 	uint32_t status = EXT_OK;
 	nTrace = 0;
@@ -524,6 +559,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		L.pSet(0, 0, startNode, it.sScore, 0, it.HP, it.HN);
 		WSlice s0;
 		s0.minScore = 0; s0.minNode = startNode; s0.minOffset = startOffset; s0.first = 0; s0.count = 1; s0.bandwidth = 1; s0.j = -64; s0.flags = 1;
+		if (CLIP) setClipScore(s0, startNode, 0);   // ...Common.h:1259-1260
 		storeSlice(wsx, 0, s0);
 	}
 	uint32_t nItems = 1, nSlices = 1;
@@ -540,16 +576,19 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 	const bool keepAll = BAND && forceGlobal;   // the `if (!forceGlobal)` block of ...Banded.h:587-645 is skipped
 	double snapCorrect = 0, snapFalse = 0;
 	uint32_t snapCols = 0;
+	const bool xDropOn = CLIP && xDrop > 0;
+	int32_t bestXScore = 0;   // (getXdropSlices: the initial slice's)
 	Eq4 eq;
 	for (int slice = 0; slice < numSlices; slice++) {
 		int j = prevJ + 64;
 		eqVectorBits(eqSrc, len, j, eq);
 		int32_t previousQuitScore = prevMinScore + prevBandwidth;
 		int bandwidth = bandwidthCfg;
-		if (BAND && rampOn && rampUntil >= slice) bandwidth = rampBandwidth;
+		if (BAND && rampOn && rampUntil >= slice && !xDropOn) bandwidth = rampBandwidth;   // (getXdropSlices: initialBandwidth throughout, ...Banded.h:733)
 		const uint32_t sliceCols = nCols;   // (BAND) the column-store cursor behind the previous slice's items
 		uint32_t cells = 0;                 // (BAND) cellsProcessed: on a DAG a node is computed once per slice and counts its length (...Common.h:1162)
-		int flatRows = (j + 64 > len) ? (len - j) : 0;
+		int flatRows = (!CLIP && j + 64 > len) ? (len - j) : 0;   // (...Banded.h:414: no flattenLastSliceEnd under precise clipping)
+		int32_t sliceMaxX = INT32_MIN; uint32_t sliceMaxXNode = 0xffffffffu;   // (CLIP) first strict maximum in pop order, :394-398
 		const int cb = REGCOLS ? 1 : (buf ^ 1);   // table buffer `cb` = current slice
 		auto prevFind = [&](uint32_t node) __attribute__((always_inline)) -> int { return L.find((uint32_t)(REGCOLS ? 0 : buf), nPrev, node); };
 		uint32_t nPending = 0;
@@ -624,10 +663,12 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			GC_MARK(1);   // pop + previous-slice lookup
 			const uint32_t tileLength = g.nodeLength[pnode];
 			if (storeCols && nCols + tileLength - 1 > wsx.maxCols) return EXT_OVERFLOW;
-			TileResult tr = storeCols ? computeTileW<2>(g, pnode, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status)
-				: computeTileW<0>(g, pnode, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status);
+			int32_t tileMaxX = INT32_MIN;
+			TileResult tr = storeCols ? computeTileW<2, CLIP>(g, pnode, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status, nullptr, errorCost, CLIP ? &tileMaxX : nullptr)
+				: computeTileW<0, CLIP>(g, pnode, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status, nullptr, errorCost, CLIP ? &tileMaxX : nullptr);
 			GC_MARK(2);   // tile columns
 			if (status != EXT_OK) return status;
+			if (CLIP && tileMaxX > sliceMaxX) { sliceMaxX = tileMaxX; sliceMaxXNode = pnode; }
 			out.minScore = tr.minScore;
 			if (storeCols) {
 				// columns 1 .. length-1 (VP, VN; column c sits in lane c) go to the column store in one coalesced 16 B-per-lane store; the item record
@@ -697,6 +738,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		const uint32_t flatTie = flatRows > 0 ? (flatOffset >> 31) << 3 : 0u;
 		if (flatRows > 0) { cur.minScore = flatMin; cur.minNode = flatNode; cur.minOffset = flatOffset & 0x7fffffffu; }
 		if (cur.minScore < prevMinScore) return EXT_ASSERT;
+		if (CLIP) setClipScore(cur, sliceMaxXNode, sliceMaxX + j);   // fillDPSlice adds slice.j, ...Banded.h:456
 		double curCorrect, curFalse;
 		{
 			int mm = cur.minScore - prevMinScore;
@@ -710,7 +752,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			cur.flags = (curCorrect > curFalse ? 1u : 0u) | (cfc ? 2u : 0u) | (ffc ? 4u : 0u) | flatTie;
 		}
 		if (BAND) {
-			if (!keepAll && (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u)))) {   // ...Banded.h:572-576: the previous slice is the snapshot (never returned to with forceGlobal)
+			if (!keepAll && !xDropOn && (rampUntil == slice - 1 || (rampUntil < slice && (cur.flags & 1u) && (cur.flags & 4u)))) {   // ...Banded.h:572-576: the previous slice is the snapshot (never returned to with forceGlobal)
 				if (nPrev > wsx.maxTrace) return EXT_OVERFLOW;
 				rampRedoIndex = slice - 1;
 				snapCorrect = prevCorrect; snapFalse = prevFalse; snapCols = sliceCols;
@@ -718,8 +760,13 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			}
 			if (cells >= maxCells) cur.flags |= SLICE_NOT_VALID;   // ...Banded.h:581-584 (>=)
 		}
-		if (!keepAll && !(cur.flags & 2u)) break;
-		if (BAND && !keepAll && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
+		if (xDropOn) {   // ...Banded.h:762-797: kept unless its score fell more than xDrop below the best so far
+			const int32_t x = clipScore(cur);
+			if (x > bestXScore) bestXScore = x;
+			if (x < bestXScore - xDrop) break;
+		}
+		if (!xDropOn && !keepAll && !(cur.flags & 2u)) break;
+		if (BAND && !xDropOn && !keepAll && rampOn && !(cur.flags & 1u) && rampUntil < slice) {
 			// ...Banded.h:608-644: redo from the snapshot with the ramp bandwidth up to this slice - truncate the slice and item stacks and the column store to it, and reload
 			// the previous-slice table (entry e = item first + e) and the correctness state (rampRedoIndex >= 0: the snapshot is taken at slice rampUntil + 1 at the latest)
 			rampUntil = slice;
@@ -744,7 +791,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 	}
 	GC_MARK(5);   // slice epilogue (HMM, slice record)
 	// removeWronglyAlignedEnd (not called with forceGlobal, ...Banded.h:51,120)
-	if (!keepAll) {
+	if (!keepAll && !CLIP) {
 		bool currentlyCorrect = (loadSlice(wsx, nSlices - 1).flags & 1u) != 0;
 		while (!currentlyCorrect) {
 			currentlyCorrect = (loadSlice(wsx, nSlices - 1).flags & 4u) != 0;
@@ -801,6 +848,33 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		return true;
 	};
 	Cell here { last.minNode, last.minOffset, (last.j + 63 < len - 1) ? last.j + 63 : len - 1 };
+	if (CLIP) {
+		// getReverseTraceFromTableExactEndPos (...Common.h:321-383): the slice with the first strict maximum from slice 1 on; its node's tile is recomputed once by the plain
+		// core's tile function, which searches the columns for the cell that attains the score (once per extension: no wave form of it)
+		uint32_t bestIndex = 1;
+		WSlice bs = loadSlice(wsx, 1);
+		for (uint32_t k = 2; k < nSlices; k++) { const WSlice t = loadSlice(wsx, k); if (clipScore(t) > clipScore(bs)) { bs = t; bestIndex = k; } }
+		const uint32_t bestNode = clipNode(bs);
+		const int bestItem = findItemW(wsx, bs, bestNode);
+		if (bestItem < 0) return EXT_ASSERT;
+		const NodeItem it = loadItem(wsx, (uint32_t)bestItem);
+		const int prevIdx = findItemW(wsx, loadSlice(wsx, bestIndex - 1), bestNode);
+		const bool prevExists = prevIdx >= 0;
+		NodeItem pit {};
+		if (prevExists) pit = loadItem(wsx, (uint32_t)prevIdx);
+		eqVectorBits(eqSrc, len, bs.j, eq);
+		ClipFind find { clipScore(bs) - bs.j, len - bs.j < 64 ? len - bs.j : 64, false, 0u, 0, 0 };
+		NodeItem scratch;
+		computeTile<true>(g, bestNode, itemStart(it), prevExists, prevExists ? pit.sScore : 0, prevExists ? pit.HP : ~0ull, prevExists ? pit.HN : 0ull,
+			eq, scratch, nullptr, 0, status, 63, 1, 63, errorCost, nullptr, &find);
+		if (scratch.eVP != it.eVP || scratch.eVN != it.eVN || scratch.eScore != it.eScore) status = EXT_ASSERT;   // sliceConsistency, :848-850
+		if (status != EXT_OK) return status;
+		cnt.recomputeTiles++;
+		cnt.columnSteps += g.nodeLength[bestNode];
+		if (!find.found) return EXT_ASSERT;   // :377-379
+		here = Cell { bestNode, find.column, bs.j + find.row };
+		score = find.value;   // startScore = getValue(bvOffset), :380
+	}
 	if (!pushTraceW(here, false)) return status;
 	uint32_t curSliceIdx = 0xffffffffu, curNode = 0xffffffffu;
 	WSlice cs = last, ps = last;

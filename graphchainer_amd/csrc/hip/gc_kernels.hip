@@ -158,7 +158,7 @@ __device__ __forceinline__ LaneScratch laneScratch(uint8_t* slab, const ExtendCo
 // 4 waves per SIMD (<= 128 VGPRs; the kernel wanted 131 and ran 3): it waits on memory 56 % of the time, so the extra wave
 // pays for the 4 spilled registers: 34.2 -> 29.0 ms alone on cfg2 (5 or 6 waves spill 57 / 196 registers and lose).
 #define GC_EXTEND_SLAB_PARAMS DGraph g, const CorrectnessTables* __restrict__ ct, const uint8_t* __restrict__ iupac, ExtendConfig cfg, 	const ExtItem* __restrict__ work, uint32_t nWork, const char* __restrict__ bases, ExtResult* __restrict__ results, 	uint8_t* __restrict__ scratch, uint64_t slabBytes, PoolCell* __restrict__ tracePool, unsigned long long* __restrict__ traceCursor, uint64_t traceCapacity, 	unsigned long long* __restrict__ counters, uint32_t retryStatus, ExtSelection sel
-template <bool BAND>
+template <bool BAND, bool CLIP = false>
 __device__ __forceinline__ void extendSlabBody(GC_EXTEND_SLAB_PARAMS)
 {
 #if defined(GC_EXTEND_PRIO) && GC_EXTEND_PRIO
@@ -182,7 +182,7 @@ __device__ __forceinline__ void extendSlabBody(GC_EXTEND_SLAB_PARAMS)
 		ExtItem it = work[w];
 		uint32_t nTrace = 0;
 		int32_t score = 0;
-		uint32_t status = extendSeed<BAND>(g, *ct, iupac, cfg, sc, bases + it.seqOff, (int)it.seqLen, it.node, it.offset, nTrace, score, cnt);
+		uint32_t status = extendSeed<BAND, CLIP>(g, *ct, iupac, cfg, sc, bases + it.seqOff, (int)it.seqLen, it.node, it.offset, nTrace, score, cnt);
 		ExtResult res;
 		res.status = status;
 		res.score = score;
@@ -221,6 +221,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_extend_slab_band(GC_EXTEND_SLAB_PARAMS)
 {
 	extendSlabBody<true>(g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
+}
+// the same with precise clipping / the X-drop (gc_params_ext): every fragment extension of a clipped batch - the lockstep kernel does not clip
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_extend_slab_clip(GC_EXTEND_SLAB_PARAMS)
+{
+	extendSlabBody<true, true>(g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
 }
 // =====================================================================================================
 // K3b - fragment post-pass: merges the two one-way traces of every seed, replays the reference's serial
@@ -892,7 +897,7 @@ __device__ inline uint32_t endToEndScore(LongAln* mine, uint32_t nAln, uint32_t 
 	return contiguousEnd == readLen ? minGoodness : current;
 }
 
-template <bool BAND>   // BAND: the band controls of cfg (extendSeedT<.., true>)
+template <bool BAND, bool CLIP = false>   // BAND: the band controls of cfg (extendSeedT<.., true>); CLIP: precise clipping / the X-drop (extendSeedT<.., true, true>)
 __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTables* __restrict__ ct, const uint8_t* __restrict__ iupac, ExtendConfig cfg,
 	const LongJob* __restrict__ jobs, uint32_t nReads, const LongSeed* __restrict__ seeds, const char* __restrict__ bases, uint64_t rcBase,
 	uint32_t minClusterSize, uint32_t extraHeuristic, uint8_t* __restrict__ scratch, uint64_t slabBytes,
@@ -948,11 +953,11 @@ __global__ void __launch_bounds__(64) k_long_pass(DGraph g, const CorrectnessTab
 			if (p > 0) {
 				uint32_t twinNode, twinOffset;
 				twinOf(g, sd.node, sd.offset, twinNode, twinOffset);
-				stB = extendSeed<BAND>(g, *ct, iupac, cfg, ls.sc, bases + rcBase + job.readOff + (uint64_t)(L - p), p, twinNode, twinOffset, nB, scoreB, cnt);
+				stB = extendSeed<BAND, CLIP>(g, *ct, iupac, cfg, ls.sc, bases + rcBase + job.readOff + (uint64_t)(L - p), p, twinNode, twinOffset, nB, scoreB, cnt);
 				ties += cnt.flattenTie;
 				if (stB == EXT_OK) for (uint32_t i = 0; i < nB; i++) ls.traceB[i] = ls.sc.trace[i];
 			}
-			if (p < L - 1 && stB != EXT_ASSERT) { stF = extendSeed<BAND>(g, *ct, iupac, cfg, ls.sc, bases + job.readOff + (uint64_t)(p + 1), L - 1 - p, sd.node, sd.offset, nF, scoreF, cnt); ties += cnt.flattenTie; }   // (a throwing backward extension ends getAlignmentFromSeed before the forward one runs)
+			if (p < L - 1 && stB != EXT_ASSERT) { stF = extendSeed<BAND, CLIP>(g, *ct, iupac, cfg, ls.sc, bases + job.readOff + (uint64_t)(p + 1), L - 1 - p, sd.node, sd.offset, nF, scoreF, cnt); ties += cnt.flattenTie; }   // (a throwing backward extension ends getAlignmentFromSeed before the forward one runs)
 			if (stB == EXT_ASSERT || stF == EXT_ASSERT) { status = 1; break; }
 			if (stB == EXT_OVERFLOW || stF == EXT_OVERFLOW) { status = 2; break; }
 			bool hasB = stB == EXT_OK, hasF = stF == EXT_OK;
@@ -1138,7 +1143,7 @@ __global__ void __launch_bounds__(64) k_long_select(DGraph g, const LongJob* __r
 #ifndef GC_LONG_MIN_WAVES
 #define GC_LONG_MIN_WAVES 1
 #endif
-template <int LANES, bool PERSISTENT, bool BAND = false>   // BAND: the band controls of cfg (extendSeedWave<.., true>)
+template <int LANES, bool PERSISTENT, bool BAND = false, bool CLIP = false>   // BAND: the band controls of cfg (extendSeedWave<.., true>); CLIP: precise clipping / the X-drop (extendSeedWave<.., true, true>)
 #ifndef GC_LONG_WAVES_ONE
 #define GC_LONG_WAVES_ONE 5   // waves per SIMD the one-extension-per-wave instantiation is compiled for. 8: 64 VGPRs, 35 of them spilled to 112 B of scratch per lane; 7: 72 / 80 B; 6: 80 / 48 B;
                               // 5 (and 4): 87 VGPRs, no scratch. The kernel is bound by the CU's scalar unit, not by latency: all five measure the same, so the build without scratch is kept
@@ -1188,7 +1193,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES =
 			uint32_t nTrace = 0;
 			int32_t score = 0;
 			EqSource eqSrc { masks + it.maskOff, it.maskWords, it.startBit };
-			if (BAND) res.status = extendSeedWave<LANES == 1, true>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt,
+			if (CLIP) res.status = extendSeedWave<LANES == 1, true, true>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt,
+				cfg.rampBandwidth, cfg.maxCells, cfg.forceGlobal != 0, cfg.clipErrorCost(), cfg.xDrop);
+			else if (BAND) res.status = extendSeedWave<LANES == 1, true>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt,
 				cfg.rampBandwidth, cfg.maxCells, cfg.forceGlobal != 0);
 			else res.status = extendSeedWave<LANES == 1>(g, *ct, eqSrc, cfg.bandwidth, (lds_u32*)&lds.w[0][0], wsx, (int)it.seqLen, it.node, it.offset, 0, nTrace, score, cnt);
 			res.score = score;
@@ -1416,7 +1423,8 @@ void launchExtend(hipStream_t stream, const DGraph& g, const CorrectnessTables* 
 	if (nWork == 0) return;
 	const uint32_t upper = sel.mode == 1 ? 2 * sel.nFrags : nWork;   // (a device-side list holds at most nWork items; waves beyond its count leave at once)
 	uint32_t lanes = retryStatus ? retryLanes : extendGridLanes(upper);
-	if (cfg.bandControls()) hipLaunchKernelGGL(k_extend_slab_band, dim3(lanes / 64), dim3(64), 0, stream, g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
+	if (cfg.clipOn()) hipLaunchKernelGGL(k_extend_slab_clip, dim3(lanes / 64), dim3(64), 0, stream, g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
+	else if (cfg.bandControls()) hipLaunchKernelGGL(k_extend_slab_band, dim3(lanes / 64), dim3(64), 0, stream, g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
 	else hipLaunchKernelGGL(k_extend_slab, dim3(lanes / 64), dim3(64), 0, stream, g, ct, iupac, cfg, work, nWork, bases, results, scratch, slabBytes, tracePool, traceCursor, traceCapacity, counters, retryStatus, sel);
 }
 
@@ -1495,9 +1503,11 @@ void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 	const bool persistent = nWorkOnDevice || (uint64_t)blocks * lanes < nWork;
 	// the band controls (gc_params::ramp_bandwidth / max_cells_per_slice) run in their own instantiation: the default one is compiled as before
 	const bool band = cfg.bandControls();
-#define GC_LAUNCH_ONE(N, P, B) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_extend<N, P, B>), dim3(blocks), dim3(64), 0, stream, g, ct, masks, cfg, work, order, nWork, scratch, words, tracePool, traceCursor, traceCapacity, results, counters, nextSlot, retryStatus, nWorkOnDevice, capListOut, capCountOut)
-#define GC_LAUNCH_TEAM(N) do { if (band) { if (persistent) GC_LAUNCH_ONE(N, true, true); else GC_LAUNCH_ONE(N, false, true); } \
-	else if (persistent) GC_LAUNCH_ONE(N, true, false); else GC_LAUNCH_ONE(N, false, false); } while (0)
+	const bool clip = cfg.clipOn();   // precise clipping / the X-drop: an instantiation of its own, with the band controls
+#define GC_LAUNCH_ONE(N, P, B, C) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_extend<N, P, B, C>), dim3(blocks), dim3(64), 0, stream, g, ct, masks, cfg, work, order, nWork, scratch, words, tracePool, traceCursor, traceCapacity, results, counters, nextSlot, retryStatus, nWorkOnDevice, capListOut, capCountOut)
+#define GC_LAUNCH_TEAM(N) do { if (clip) { if (persistent) GC_LAUNCH_ONE(N, true, true, true); else GC_LAUNCH_ONE(N, false, true, true); } \
+	else if (band) { if (persistent) GC_LAUNCH_ONE(N, true, true, false); else GC_LAUNCH_ONE(N, false, true, false); } \
+	else if (persistent) GC_LAUNCH_ONE(N, true, false, false); else GC_LAUNCH_ONE(N, false, false, false); } while (0)
 	switch (lanes) {
 		case 1: GC_LAUNCH_TEAM(1); break;
 		case 2: GC_LAUNCH_TEAM(2); break;
@@ -1576,6 +1586,17 @@ void launchLongFinish(hipStream_t stream, uint32_t nReads, const LongState* stat
 	if (nReads) hipLaunchKernelGGL(k_long_finish, dim3((nReads + 255) / 256), dim3(256), 0, stream, nReads, state, results);
 }
 
+// test entry (gc_test_max_x_score): one column per thread through the extension core's column maximum
+__global__ void __launch_bounds__(64) k_test_max_x_score(const uint64_t* __restrict__ vp, const uint64_t* __restrict__ vn, const int32_t* __restrict__ scoreEnd, uint32_t n, double errorCost, int cells, int32_t* __restrict__ out)
+{
+	const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+	if (i < n) out[i] = clipMaxXScore(WS { vp[i], vn[i], scoreEnd[i] }, errorCost, cells);
+}
+void launchTestMaxXScore(hipStream_t stream, const uint64_t* vp, const uint64_t* vn, const int32_t* scoreEnd, uint32_t n, double errorCost, int cells, int32_t* out)
+{
+	if (n) hipLaunchKernelGGL(k_test_max_x_score, dim3((n + 63) / 64), dim3(64), 0, stream, vp, vn, scoreEnd, n, errorCost, cells, out);
+}
+
 uint64_t longSlabBytes(const ExtendConfig& cfg) { return (extendSlabBytes(cfg) + sizeof(TraceCell) * (uint64_t)cfg.maxTrace + 63) & ~63ull; }
 
 void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables* ct, const uint8_t* iupac, const ExtendConfig& cfg, const LongJob* jobs, uint32_t nReads,
@@ -1584,7 +1605,10 @@ void launchLongPass(hipStream_t stream, const DGraph& g, const CorrectnessTables
 {
 	if (nReads == 0) return;
 	uint32_t blocks = (nReads + 63) / 64;
-	if (cfg.bandControls())
+	if (cfg.clipOn())
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_long_pass<true, true>), dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, extraHeuristic, scratch, slabBytes,
+			cellPool, cellCursor, cellCapacity, alns, results, counters);
+	else if (cfg.bandControls())
 		hipLaunchKernelGGL(k_long_pass<true>, dim3(blocks), dim3(64), 0, stream, g, ct, iupac, cfg, jobs, nReads, seeds, bases, rcBase, minClusterSize, extraHeuristic, scratch, slabBytes,
 			cellPool, cellCursor, cellCapacity, alns, results, counters);
 	else

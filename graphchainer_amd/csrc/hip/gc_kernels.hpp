@@ -183,6 +183,7 @@ void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* rea
 	uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st, uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed,
 	ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors, bool forceGlobal = false);
 // test entry: arrays of (key << 32 | index) elements sorted by key with the wave-cooperative replay of std::sort (gc_stdsort_wave.hpp); scratch: 3 words per element + 64 per array
+void launchTestMaxXScore(hipStream_t stream, const uint64_t* vp, const uint64_t* vn, const int32_t* scoreEnd, uint32_t n, double errorCost, int cells, int32_t* out);   // test entry (gc_test_max_x_score)
 void launchTestStdSort(hipStream_t stream, unsigned long long* elems, const uint64_t* off, uint32_t nArrays, uint32_t* scratch, long depthLimit);
 
 // the read batch as the fragment extension kernel sees it: per read and strand four match-mask bit vectors (gc_reads.hip)

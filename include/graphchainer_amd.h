@@ -342,6 +342,39 @@ void gc_result_free(gc_result* r);
  * (GC_DEVICE_GLUE=0: GC_ERR_INVALID). */
 int gc_align_batch_seeded(const gc_graph* g, gc_stream* st, const gc_reads* reads, const gc_seeds* seeds, const gc_params* params, gc_result** out);
 
+/* Extension block of gc_params, whose layout is frozen: options added after it, starting with the reference's --precise-clipping and --X-drop.
+ *
+ * precise_clipping is preciseClippingIdentityCutoff c, the caller's double bit for bit; the error cost E = c / (1 - c) + 1 (XscoreErrorCost, src/GraphAlignerCommon.h:108) is
+ * computed from it in double. With it on, in BOTH extension passes:
+ *  - every DP column's maximum X score is taken - max over the column's local minima of (ScoreType)(cells - score * E), a double expression (a rounded product, a rounded
+ *    difference) truncated toward zero, over all 64 rows (calculateNodeInner<PreciseClipping = true>, src/GraphAlignerBitvectorCommon.h:971-975,1148-1151; WordSlice::maxXScore,
+ *    src/WordSlice.h:223-242,313-336); a slice keeps the first strict maximum in node-pop order with its node (calculateSlice, src/GraphAlignerBitvectorBanded.h:394-398) plus
+ *    the slice's first row (fillDPSlice, :456); the initial slice has 0 at the seed's node (...Common.h:1259-1260);
+ *  - flattenLastSliceEnd is not called (...Banded.h:414) and removeWronglyAlignedEnd is not called (:51,120); the slice loop (getViterbiSlices) is otherwise unchanged;
+ *  - the backtrace starts where getReverseTraceFromTableExactEndPos (...Common.h:321-383) puts it: the slice with the first strict maximum from slice 1 on, its node's tile
+ *    recomputed, the largest row inside the read that attains the score (the first column at equal rows); the trace's score is that cell's value; the walk is unchanged.
+ *    The assertions at :358,365,377-379 fail the read (failed_assertion), as every assertion of the reference does here;
+ *  - the E-value model's identity is c instead of 0.7 (src/Aligner.cpp:474-482): e_cutoff, the alignment selection and the chained alignment's test use it.
+ * x_drop is Xdropcutoff: with it on the slice loop is getXdropSlices (...Banded.h:703-830) - every slice at the initial bandwidth, no correctness stop, no ramp, no rewind;
+ * the best X score starts at the initial slice's 0; a slice whose score is below best - x_drop is dropped and ends the loop (the first slice dropped: the extension fails);
+ * scoresNotValid is set with >= (:768). x_drop > 0 with precise_clipping == 0 runs with c = 0.66 (src/AlignerMain.cpp:443-448; the reference's default, a caller's value is
+ * never overridden). x_drop > 0 with gc_params::force_global: GC_ERR_INVALID (getSlices asserts, :504). Ranges: src/AlignerMain.cpp:300-322.
+ *
+ * What the mode changes in a result: alignments and anchors may end before the read's (fragment's) end, and flatten_ties / flatten_ties_long are 0 - the one rule this
+ * library defines instead of reproducing (the order of tied minima in flattenLastSliceEnd) is never reached, so a clipped result follows from the reference's sources alone.
+ * The fragment pass runs every extension in the plain-layout kernel (the lockstep kernel does not clip); the whole-read pass keeps its rounds, in the clipping
+ * instantiation of its one-extension-per-wave kernel. */
+typedef struct gc_params_ext {
+	uint32_t struct_size;        /* sizeof(gc_params_ext) of the caller's header; a larger value than the library knows: GC_ERR_INVALID */
+	int32_t  x_drop;             /* --X-drop, Xdropcutoff: 0 (default) off, >= 1 on; < 0: GC_ERR_INVALID */
+	double   precise_clipping;   /* --precise-clipping, preciseClippingIdentityCutoff: 0 (default) off; else in [0.001, 0.999]; anything else, NaN included: GC_ERR_INVALID */
+} gc_params_ext;
+void gc_params_ext_default(gc_params_ext* e);
+/* gc_align_batch (seeder given, seeds NULL) or gc_align_batch_seeded (seeder NULL, seeds given) with the extension block; both or neither: GC_ERR_INVALID. ext == NULL: the
+ * defaults - exactly those two calls. The block and the parameters are checked on the host before anything else is looked at, so an invalid combination is refused
+ * with or without a device. */
+int gc_align_batch_ext(const gc_graph* g, const gc_seeder* s, gc_stream* st, const gc_reads* reads, const gc_seeds* seeds, const gc_params* params, const gc_params_ext* ext, gc_result** out);
+
 /* gc_result_free keeps the large arrays of freed results (trace cells, output text: up to 24 GB in all) for the next batch's result - fresh memory of that size is
  * mapped and zero-filled page by page every batch otherwise; gc_reads_destroy and the device deflate keep their device / pinned blocks the same way (up to 24 GB and 4 GB per cache).
  * gc_result_cache_trim gives everything that is held back to the allocator (e.g. when a host stops aligning). */
@@ -431,6 +464,10 @@ int gc_gzip_streams_lz(const uint8_t* bytes, const uint64_t* offsets, uint64_t n
  * Array s = keys[offsets[s] .. offsets[s + 1]); perm_out[offsets[s] + i] = index inside its array of the element that ends at place i. depth_limit < 0: the reference's
  * 2 floor(log2 n); a small value forces introsort's heapsort path. */
 int gc_std_sort_permutations(const uint32_t* keys, const uint64_t* offsets, uint64_t n_arrays, int64_t depth_limit, uint32_t* perm_out);
+
+/* Test entry (no counterpart in the reference): the extension kernels' maximum X score (the local-minima form) of n DP columns (vp, vn, score_end: WordSlice's VP, VN, scoreEnd) over their
+ * first `cells` rows (1..64) with the error cost given as a double - WordSlice::maxXScoreFirstSlices on the device, where a fused multiply-subtract would round differently. */
+int gc_test_max_x_score(const uint64_t* vp, const uint64_t* vn, const int32_t* score_end, uint64_t n, double error_cost, int32_t cells, int32_t* out);
 
 int gc_device_count(void);
 int gc_set_device(int device);

@@ -50,6 +50,7 @@ struct Binding {
 	gc_graph* graph = nullptr;
 	gc_seeder* seeder = nullptr;
 	gc_params params {};
+	gc_params_ext ext { (uint32_t)sizeof(gc_params_ext), 0, 0.0 };   // --precise-clipping / --X-drop (off unless bind() was given a block)
 	std::vector<int64_t> nodeIDs, nodeOffset;   // split node -> bigraph node id, offset in the original node
 	size_t minimizerLength = 15;                // the seeder's k: SeedHit::matchLen (src/MinimizerSeeder.cpp:549)
 };
@@ -68,10 +69,13 @@ inline std::vector<int64_t> graphArray(const gc_graph* g, const char* name)
 // turns on what the replay needs (whole-read pass, traces, seeds). The band controls -B / -C go in params.ramp_bandwidth and
 // params.max_cells_per_slice (src/AlignerMain.cpp:248-249), --global-alignment in params.force_global (:299), --seeds-extend-density / --extra-heuristic in
 // params.seed_extend_density / extra_heuristic (:217,247; a density other than -1 needs params.colinear_chaining = 0); AlignOneWay then accepts exactly those values.
-inline void bind(gc_graph* graph, gc_seeder* seeder, gc_params params)
+// --precise-clipping / --X-drop (src/AlignerMain.cpp:300-322) go in `ext` (gc_params_ext: precise_clipping, x_drop); without the argument both are off.
+inline void bind(gc_graph* graph, gc_seeder* seeder, gc_params params, const gc_params_ext* ext = nullptr)
 {
 	Binding& b = binding();
 	b.graph = graph; b.seeder = seeder;
+	gc_params_ext_default(&b.ext);
+	if (ext) b.ext = *ext;
 	params.long_pass = 1; params.keep_traces = 1; params.keep_seeds = 1; params.stitch = 1; params.edit_distances = 1;
 	b.params = params;
 	b.nodeIDs = graphArray(graph, "nodeIDs"); b.nodeOffset = graphArray(graph, "nodeOffset");
@@ -96,7 +100,7 @@ public:
 		if (!stream && gc_stream_create(&stream) != GC_OK) throw std::runtime_error(gc_last_error());
 		const uint64_t off[2] = { 0, sequence.size() };
 		if (gc_reads_upload(sequence.data(), off, 1, &reads) != GC_OK) throw std::runtime_error(gc_last_error());
-		if (gc_align_batch(b.graph, b.seeder, stream, reads, &b.params, &result) != GC_OK) throw std::runtime_error(gc_last_error());
+		if (gc_align_batch_ext(b.graph, b.seeder, stream, reads, nullptr, &b.params, &b.ext, &result) != GC_OK) throw std::runtime_error(gc_last_error());
 		current = sequence;
 		return *result;
 	}
@@ -209,12 +213,19 @@ inline void OrderSeeds(const AlignmentGraph&, std::vector<SeedHit>&) {}
 // starts at `offset` (src/Aligner.cpp:691): `sequence` is then the fragment, and the read it belongs to is the one getSeeds saw last.
 inline AlignmentResult AlignOneWay(const AlignmentGraph&, const std::string& /*seq_id*/, const std::string& sequence, size_t initialBandwidth, size_t rampBandwidth, size_t maxCellsPerSlice, bool /*quietMode*/,
 	bool /*sloppyOptimizations: implied by l < 0, as at src/Aligner.cpp:565,684*/, const std::vector<SeedHit>&, Common::AlignerGraphsizedState&, bool /*lowMemory*/, bool forceGlobal, bool preciseClipping,
-	size_t /*minClusterSize: fixed at bind() time*/, double seedExtendDensity, bool nondeterministicOptimizations, double /*preciseClippingIdentityCutoff*/, int Xdropcutoff,
+	size_t /*minClusterSize: fixed at bind() time*/, double seedExtendDensity, bool nondeterministicOptimizations, double preciseClippingIdentityCutoff, int Xdropcutoff,
 	long long l = -1, long long /*r*/ = -1, long long offset = 0, const std::string* wholeRead = nullptr)
 {
-	// Options of this signature the kernels do not implement are refused, not ignored: a caller that asks for them would silently get the default behaviour otherwise.
-	// (--precise-clipping / X-drop: src/GraphAlignerBitvectorBanded.h:61-68,703-.)
-	if (preciseClipping || Xdropcutoff > 0) throw std::invalid_argument("gcshim::AlignOneWay: --precise-clipping / X-drop are not built (DESIGN.md section 9)");
+	// --precise-clipping / X-drop (src/GraphAlignerBitvectorBanded.h:61-68,703-): the replayed batch ran with the gc_params_ext given to bind(), and a call must ask for the same -
+	// the rule forceGlobal follows below. An X-drop bound without a cut-off runs with 0.66, as the reference's front end sets it (src/AlignerMain.cpp:443-448); the cut-off is
+	// compared as the double it is, and read only when preciseClipping says there is one.
+	{
+		const gc_params_ext& e = binding().ext;
+		const double boundCutoff = e.precise_clipping != 0 ? e.precise_clipping : (e.x_drop > 0 ? 0.66 : 0.0);
+		if (preciseClipping != (boundCutoff != 0) || (preciseClipping && preciseClippingIdentityCutoff != boundCutoff))
+			throw std::invalid_argument("gcshim::AlignOneWay: preciseClipping / preciseClippingIdentityCutoff differ from the precise_clipping given to gcshim::bind()");
+		if ((Xdropcutoff > 0 ? Xdropcutoff : 0) != (int)e.x_drop) throw std::invalid_argument("gcshim::AlignOneWay: Xdropcutoff differs from the x_drop given to gcshim::bind()");
+	}
 	// The replayed batch ran with the band controls and the forced global alignment (forceGlobal, src/GraphAlignerBitvectorBanded.h:587) given to bind(): a call must ask for the same ones. The reference turns the ramp on only when it is wider than
 	// the band (src/GraphAlignerBitvectorBanded.h:544), and SIZE_MAX cells per slice is its "unlimited" (src/AlignerMain.cpp:149), the -1 of gc_params.
 	const gc_params& bound = binding().params;
