@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = [
     "gc_params_default", "gc_graph_create_from_gfa", "gc_graph_create", "gc_graph_destroy", "gc_graph_num_nodes",
     "gc_graph_size_bp", "gc_graph_array", "gc_graph_trim_host", "gc_seeder_create", "gc_seeder_destroy", "gc_seeder_array",
     "gc_stream_create", "gc_stream_destroy", "gc_reads_upload", "gc_reads_destroy", "gc_align_batch",
-    "gc_seeds_upload", "gc_seeds_destroy", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
+    "gc_seeds_upload", "gc_seeds_destroy", "gc_seeds_hits", "gc_seeds_kernel_ms", "gc_mxm_index_create", "gc_mxm_index_destroy", "gc_mxm_index_array", "gc_seeds_mxm", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
 ]
@@ -111,6 +111,13 @@ def load_library():
     lib.gc_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(GcParams), _P(_P(GcResult))]
     lib.gc_seeds_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_void_p)]
     lib.gc_seeds_destroy.argtypes = [C.c_void_p]
+    lib.gc_seeds_hits.argtypes = [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_uint64)]
+    lib.gc_seeds_kernel_ms.argtypes = [C.c_void_p]
+    lib.gc_seeds_kernel_ms.restype = C.c_double
+    lib.gc_mxm_index_create.argtypes = [C.c_void_p, _P(C.c_void_p)]
+    lib.gc_mxm_index_destroy.argtypes = [C.c_void_p]
+    lib.gc_mxm_index_array.argtypes = [C.c_void_p, C.c_char_p, _P(_P(C.c_int64)), _P(C.c_uint64)]
+    lib.gc_seeds_mxm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, _P(C.c_void_p)]
     lib.gc_align_batch_seeded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(GcParams), _P(_P(GcResult))]
     lib.gc_result_free.argtypes = [_P(GcResult)]
     lib.gc_params_default.argtypes = [_P(GcParams)]
@@ -464,12 +471,81 @@ class SeedBatch:
                 per_read.append(np.array([tuple(int(x) for x in h) for h in hits], dtype=SEED_HIT_DTYPE))
         self.offsets = np.zeros(len(per_read) + 1, dtype=np.uint64)
         self.offsets[1:] = np.cumsum([len(h) for h in per_read], dtype=np.uint64) if per_read else []
-        self.hits = np.concatenate(per_read) if per_read else np.zeros(0, dtype=SEED_HIT_DTYPE)
-        _check(self.lib.gc_seeds_upload(graph.handle, batch.handle, self.hits.ctypes.data if len(self.hits) else None, self.offsets.ctypes.data, len(per_read), C.byref(self.handle)))
+        flat = np.concatenate(per_read) if per_read else np.zeros(0, dtype=SEED_HIT_DTYPE)
+        _check(self.lib.gc_seeds_upload(graph.handle, batch.handle, flat.ctypes.data if len(flat) else None, self.offsets.ctypes.data, len(per_read), C.byref(self.handle)))
+
+    @classmethod
+    def _adopt(cls, handle):
+        """A SeedBatch around a gc_seeds the library made itself (MxmIndex.seeds)."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.handle = handle
+        return self
+
+    def hits(self):
+        """The raw records as they lie in HBM (gc_seeds_hits): per read a SEED_HIT_DTYPE array - what was uploaded, or what the device seeder found, in its defined order."""
+        ptr, off, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(self.lib.gc_seeds_hits(self.handle, C.byref(ptr), C.byref(off), C.byref(n)))
+        try:
+            offsets = np.ctypeslib.as_array(C.cast(off, _P(C.c_uint64)), shape=(n.value + 1,)).copy()
+            total = int(offsets[-1])
+            flat = np.frombuffer(C.string_at(ptr.value, total * SEED_HIT_DTYPE.itemsize), dtype=SEED_HIT_DTYPE).copy() if total else np.zeros(0, dtype=SEED_HIT_DTYPE)
+        finally:
+            self.lib.gc_free(ptr)
+            self.lib.gc_free(off)
+        return [flat[int(offsets[r]):int(offsets[r + 1])] for r in range(n.value)]
+
+    @property
+    def kernel_ms(self):
+        """Device milliseconds of the seeder that made these hits (0 for uploaded ones)."""
+        return float(self.lib.gc_seeds_kernel_ms(self.handle))
 
     def close(self):
         if self.handle:
             self.lib.gc_seeds_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MXM_MUM, MXM_MEM = 1, 2   # GC_MXM_MUM / GC_MXM_MEM
+
+
+class MxmIndex:
+    """The MUM / MEM seeder's index of a graph's forward segments, resident in HBM (gc_mxm_index_create): suffix array, packed text, segment table, prefix table.
+    seeds() is the reference's --seeds-mum-count / --seeds-mem-count N with --seeds-mxm-length L: index.seeds(batch, "mum" | "mem", count=N (None or -1: all), min_len=L)."""
+
+    def __init__(self, graph):
+        self.lib = load_library()
+        self.graph = graph           # the index belongs to the graph: keep it alive
+        self.handle = C.c_void_p()
+        _check(self.lib.gc_mxm_index_create(graph.handle, C.byref(self.handle)))
+
+    def array(self, name):
+        """'sa', 'node_start', 'node_id', 'bytes', 'build_us', 'prefix_len' (gc_mxm_index_array)."""
+        return _fetch_array(self.lib.gc_mxm_index_array, self.handle, name)
+
+    def seeds(self, batch, mode="mem", count=None, min_len=20, graph=None):
+        """The batch's MUM / MEM seeds, found and resolved on the device: a SeedBatch for Aligner.align_batch(batch, seeds=...). graph: the graph to resolve against, the index's own
+        unless given (another one is refused)."""
+        modes = {"mum": MXM_MUM, "mem": MXM_MEM}
+        mode = modes.get(mode, mode)
+        if not isinstance(mode, int):
+            raise ValueError("mode is 'mum' or 'mem'")
+        max_count = 0xFFFFFFFFFFFFFFFF if count is None or count == -1 else int(count)
+        if max_count < 0 or min_len < 0:
+            raise ValueError("count and min_len cannot be negative")
+        handle = C.c_void_p()
+        _check(self.lib.gc_seeds_mxm((graph or self.graph).handle, self.handle, batch.handle, mode, max_count, int(min_len), C.byref(handle)))
+        return SeedBatch._adopt(handle)
+
+    def close(self):
+        if self.handle:
+            self.lib.gc_mxm_index_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -1021,6 +1021,7 @@ int gc_seeds_upload(const gc_graph* G, const gc_reads* R, const gc_seed_hit* hit
 		H->dev = SeedHitArrays { arrays, arrays + nHits, arrays + 2 * nHits, arrays + 3 * nHits, arrays + 4 * nHits };
 		unsigned long long* dBad = (unsigned long long*)(D + oBad);
 		SeedHit* dHits = (SeedHit*)(D + oHits);   // (the raw records stay in the block's tail: 24 B per hit beside the 20 B the glue reads)
+		H->devHits = dHits;
 		hipStream_t q = threadStream(H->device);
 		unsigned long long bad = ~0ull;
 		HIP_CHECK(hipMemcpyAsync(H->devReadHitOff, off32.data(), (n_reads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, q));
@@ -1044,6 +1045,184 @@ int gc_seeds_upload(const gc_graph* G, const gc_reads* R, const gc_seed_hit* hit
 	return GC_OK;
 }
 void gc_seeds_destroy(gc_seeds* s) { delete s; }
+
+int gc_seeds_hits(const gc_seeds* s, gc_seed_hit** hits, uint64_t** read_hit_off, uint64_t* n_reads)
+{
+	if (!s || !hits || !read_hit_off || !n_reads) return fail(GC_ERR_INVALID, "null argument");
+	*hits = nullptr; *read_hit_off = nullptr;
+	const uint64_t n = s->readOffsets.size() - 1;
+	std::vector<uint32_t> off32(n + 1);
+	gc_seed_hit* h = mallocArray<gc_seed_hit>(s->nHits);
+	uint64_t* off = mallocArray<uint64_t>(n + 1);
+	int rc = guarded([&]() {
+		requireDevice();
+		HIP_CHECK(hipMemcpy(off32.data(), s->devReadHitOff, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		if (s->nHits) HIP_CHECK(hipMemcpy(h, s->devHits, s->nHits * sizeof(gc_seed_hit), hipMemcpyDeviceToHost));
+		return (int)GC_OK;
+	});
+	if (rc != GC_OK) { free(h); free(off); return rc; }
+	for (uint64_t r = 0; r <= n; r++) off[r] = off32[r];
+	*hits = h; *read_hit_off = off; *n_reads = n;
+	return GC_OK;
+}
+double gc_seeds_kernel_ms(const gc_seeds* s) { return s ? s->kernelMs : 0; }
+
+// ---- the MUM / MEM seeder (the reference's MummerSeeder, src/MummerSeeder.cpp) ---------------
+int gc_mxm_index_create(const gc_graph* G, gc_mxm_index** out)
+{
+	if (!G || !out) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	// the forward original segments, from what the graph holds: bigraph id 2 * nodeID, its split nodes in offset order (64-letter chunks)
+	const size_t nB = G->hOrigSize.size();
+	uint64_t letters = 0;
+	std::vector<uint32_t> ids;
+	for (size_t id = 0; id < nB; id += 2) if (G->hLookupOff[id + 1] > G->hLookupOff[id]) { ids.push_back((uint32_t)id); letters += (uint64_t)G->hOrigSize[id] + 1; }
+	if (letters >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_mxm_index_create: a text of 2^32 - 16 letters or more (the segments and one separator each) does not fit the index's 32-bit positions");
+	gc_mxm_index* X = new gc_mxm_index();
+	int rc = guarded([&]() {
+		requireDevice();
+		HIP_CHECK(hipGetDevice(&X->device));
+		X->graph = G;
+		const auto t0 = std::chrono::steady_clock::now();
+		const uint32_t n = (uint32_t)letters;
+		std::vector<uint8_t> codes(n, 0);
+		X->nodeStart.resize(ids.size() + 1);
+		X->nodeId.resize(ids.size());
+		uint32_t at = 0;
+		for (size_t k = 0; k < ids.size(); k++) { X->nodeStart[k] = at; X->nodeId[k] = (int32_t)(ids[k] / 2); at += G->hOrigSize[ids[k]] + 1; }
+		X->nodeStart[ids.size()] = n;
+		const gc::AlignmentGraph& g = G->host;
+		WorkerPool::instance().run(ids.size(), [&](size_t k, size_t) {
+			uint8_t* dst = codes.data() + X->nodeStart[k];
+			for (uint32_t e = G->hLookupOff[ids[k]]; e < G->hLookupOff[ids[k] + 1]; e++) {
+				const uint32_t node = G->hLookup[e];
+				const size_t len = g.nodeLength[node], off = g.nodeOffset[node];
+				for (size_t j = 0; j < len; j++) dst[off + j] = gc::mxmRefCode(g.NodeSequences(node, j));
+			}
+		});
+		auto parallelFor = [](size_t count, const std::function<void(size_t)>& body) { WorkerPool::instance().run(count, [&](size_t i, size_t) { body(i); }); };
+		const std::vector<uint32_t> sa = gc::mxmSuffixArray(codes.data(), n, parallelFor);
+		std::vector<uint64_t> packed, invalid;
+		gc::mxmPackText(codes.data(), n, packed, invalid);
+		X->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+		auto up = [&](const auto& v) { auto* d = uploadVector(v); X->allocations.push_back((void*)d); X->deviceBytes += std::max<size_t>(v.size(), 1) * sizeof(v[0]); return d; };
+		MxmIndexView& d = X->dev;
+		d.n = n; d.nNodes = (uint32_t)ids.size(); d.prefixLen = gc::MXM_PREFIX_LEN;
+		d.sa = up(sa); d.packed = up(packed); d.invalid = up(invalid); d.nodeStart = up(X->nodeStart); d.nodeId = up(X->nodeId);
+		uint32_t* table = nullptr;
+		const size_t tableBytes = ((size_t)2 << (2 * d.prefixLen)) * sizeof(uint32_t);
+		HIP_CHECK(hipMalloc((void**)&table, tableBytes));
+		X->allocations.push_back(table);
+		X->deviceBytes += tableBytes;
+		d.prefix = table;
+		hipStream_t q = threadStream(X->device);
+		HIP_CHECK(hipMemsetAsync(table, 0, tableBytes, q));
+		launchMxmPrefixTable(q, d, table);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipStreamSynchronize(q));
+		return (int)GC_OK;
+	});
+	if (rc != GC_OK) { delete X; return rc; }
+	*out = X;
+	return GC_OK;
+}
+void gc_mxm_index_destroy(gc_mxm_index* x) { delete x; }
+
+int gc_mxm_index_array(const gc_mxm_index* X, const char* name, int64_t** out, uint64_t* count)
+{
+	if (!X || !name || !out || !count) return fail(GC_ERR_INVALID, "null argument");
+	const std::string nm = name;
+	std::vector<int64_t> v;
+	if (nm == "node_start") v.assign(X->nodeStart.begin(), X->nodeStart.end());
+	else if (nm == "node_id") v.assign(X->nodeId.begin(), X->nodeId.end());
+	else if (nm == "bytes") v.push_back((int64_t)X->deviceBytes);
+	else if (nm == "build_us") v.push_back((int64_t)(X->buildSeconds * 1e6));
+	else if (nm == "prefix_len") v.push_back((int64_t)X->dev.prefixLen);
+	else if (nm == "sa") {
+		std::vector<uint32_t> sa(X->dev.n);
+		int rc = guarded([&]() { requireDevice(); if (X->dev.n) HIP_CHECK(hipMemcpy(sa.data(), X->dev.sa, (size_t)X->dev.n * 4, hipMemcpyDeviceToHost)); return (int)GC_OK; });
+		if (rc != GC_OK) return rc;
+		v.assign(sa.begin(), sa.end());
+	}
+	else return fail(GC_ERR_INVALID, "unknown index array " + nm);
+	*out = mallocArray<int64_t>(v.size());
+	memcpy(*out, v.data(), v.size() * sizeof(int64_t));
+	*count = v.size();
+	return GC_OK;
+}
+
+int gc_seeds_mxm(const gc_graph* G, const gc_mxm_index* X, const gc_reads* R, int32_t mode, uint64_t max_count, uint32_t min_len, gc_seeds** out)
+{
+	// host checks first: a malformed call is GC_ERR_INVALID whether or not a device is present
+	if (!G || !X || !R || !out) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	if (mode != GC_MXM_MUM && mode != GC_MXM_MEM) return fail(GC_ERR_INVALID, "gc_seeds_mxm: mode is neither GC_MXM_MUM nor GC_MXM_MEM");
+	if (min_len < 2) return fail(GC_ERR_INVALID, "gc_seeds_mxm: min_len must be at least 2");
+	if (max_count == 0) return fail(GC_ERR_INVALID, "gc_seeds_mxm: max_count must be at least 1 (UINT64_MAX: all)");
+	if (X->graph != G) return fail(GC_ERR_INVALID, "gc_seeds_mxm: the index was built from another graph");
+	const uint64_t nReads = R->offsets.size() - 1;
+	// a read's tiles: 64 query positions of one strand each, forward strand first; none for a read shorter than min_len or with a letter outside the alphabet
+	std::vector<uint32_t> tileOff(nReads + 1, 0);
+	uint64_t tiles = 0;
+	for (uint64_t r = 0; r < nReads; r++) {
+		const uint64_t len = R->offsets[r + 1] - R->offsets[r];
+		// (a hit's match_len and raw_goodness are at most the read's length, and match_len + read length + raw_goodness must stay below 2^32 as at upload)
+		if (len >= 0x40000000ull) return fail(GC_ERR_INVALID, "gc_seeds_mxm: read " + std::to_string(r) + " has 2^30 letters or more");
+		tileOff[r] = (uint32_t)tiles;
+		if (len >= min_len && !R->invalid[r]) tiles += 2 * ((len - min_len + 1 + 63) / 64);
+		if (tiles >= 0x7ffffff0ull) return fail(GC_ERR_INVALID, "gc_seeds_mxm: too many query positions in one batch; split the batch");
+	}
+	tileOff[nReads] = (uint32_t)tiles;
+	gc_seeds* H = new gc_seeds();
+	int rc = guarded([&]() {
+		requireDevice();
+		HIP_CHECK(hipGetDevice(&H->device));
+		H->readOffsets = R->offsets;
+		hipStream_t q = threadStream(H->device);
+		DeviceBuffer dTileOff;
+		uint32_t* pTileOff = dTileOff.reserve<uint32_t>(nReads + 1);
+		HIP_CHECK(hipMemcpyAsync(pTileOff, tileOff.data(), (nReads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+		hipEvent_t e0 = nullptr, e1 = nullptr;
+		struct Events { hipEvent_t &a, &b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events { e0, e1 };
+		HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+		HIP_CHECK(hipEventRecord(e0, q));
+		MxmSeedRun run;
+		struct Drain { hipStream_t q; ~Drain() { (void)hipStreamSynchronize(q); } } drain { q };   // (before `run` frees its scratch and dTileOff goes: nothing of this call may still be running)
+		HIP_CHECK(run.candidates(q, X->dev, R->devBases, R->devOffsets, pTileOff, (uint32_t)nReads, (uint32_t)tiles, mode, min_len));
+		if (run.nCandidates > 0x7fffffffull) return fail(GC_ERR_INVALID, "gc_seeds_mxm: 2^31 matches or more in one batch; split the batch");
+		uint64_t nHits = 0;
+		HIP_CHECK(run.select(q, (uint32_t)nReads, max_count, nHits));
+		H->nHits = nHits;
+		size_t at = 0;
+		auto part = [&](size_t bytes) { const size_t here = at; at += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return here; };
+		const size_t oOff = part((nReads + 1) * sizeof(uint32_t)), oArrays = part(5 * nHits * sizeof(uint32_t)), oBad = part(sizeof(unsigned long long)), oHits = part(nHits * sizeof(SeedHit));   // (gc_seeds_upload's layout)
+		HIP_CHECK(hipMalloc(&H->block, at));
+		char* D = (char*)H->block;
+		H->devReadHitOff = (uint32_t*)(D + oOff);
+		uint32_t* arrays = (uint32_t*)(D + oArrays);
+		H->dev = SeedHitArrays { arrays, arrays + nHits, arrays + 2 * nHits, arrays + 3 * nHits, arrays + 4 * nHits };
+		unsigned long long* dBad = (unsigned long long*)(D + oBad);
+		H->devHits = (SeedHit*)(D + oHits);
+		unsigned long long bad = ~0ull;
+		HIP_CHECK(hipMemcpyAsync(dBad, &bad, sizeof(bad), hipMemcpyHostToDevice, q));
+		HIP_CHECK(hipMemsetAsync(H->devReadHitOff, 0, (nReads + 1) * sizeof(uint32_t), q));
+		HIP_CHECK(run.write(q, (uint32_t)nReads, nHits, H->devHits, H->devReadHitOff));
+		const SeedLookup lookup { G->dev.origSize, G->dev.lookupOff, G->dev.lookup, G->dev.nodeOffset, (uint32_t)G->hOrigSize.size() };
+		launchSeedResolve(q, lookup, H->devHits, nHits, H->devReadHitOff, (uint32_t)nReads, R->devOffsets, H->dev, dBad);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipEventRecord(e1, q));
+		HIP_CHECK(hipMemcpyAsync(&bad, dBad, sizeof(bad), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		float ms = 0;
+		HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+		H->kernelMs = ms;
+		if (bad != ~0ull) throw std::runtime_error("gc_seeds_mxm: a match does not resolve to a position of the graph (hit " + std::to_string(bad >> 2) + ")");   // (the index and the graph disagree: a bug, not an input)
+		return (int)GC_OK;
+	});
+	if (rc != GC_OK) { delete H; return rc; }
+	*out = H;
+	return GC_OK;
+}
 
 // ---- the batch pipeline -----------------------------------------------------------------------------------
 

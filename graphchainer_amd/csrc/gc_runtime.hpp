@@ -15,6 +15,8 @@
 #include "host/gc_correctness.hpp"
 #include "host/gc_selection.hpp"
 #include "host/gc_switches.hpp"
+#include "host/gc_mxm_build.hpp"
+#include "hip/gc_mxm_core.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -506,7 +508,22 @@ struct gc_seeds {
 	uint32_t* devReadHitOff = nullptr;     // [n+1] the caller's read_hit_off: where a read's seeds begin in every per-seed array of the batch
 	SeedHitArrays dev {};                  // [nHits] each, carved from one allocation
 	void* block = nullptr;
+	SeedHit* devHits = nullptr;            // [nHits] the raw records in the block's tail, as uploaded or as gc_seeds_mxm wrote them (gc_seeds_hits)
+	double kernelMs = 0;                   // gc_seeds_mxm: device time from the first kernel to the last
 	~gc_seeds() { if (block) (void)hipFree(block); }
+};
+
+// the MUM / MEM index of a graph's forward segments (gc_mxm_index_create): suffix array, packed text, segment table and prefix table in HBM; read-only, shared by streams
+struct gc_mxm_index {
+	const gc_graph* graph = nullptr;       // the graph it was built from: gc_seeds_mxm refuses another
+	int device = 0;
+	std::vector<uint32_t> nodeStart;       // host copies of the two small tables
+	std::vector<int32_t> nodeId;
+	MxmIndexView dev {};
+	uint64_t deviceBytes = 0;
+	double buildSeconds = 0;               // text and suffix array on the host
+	std::vector<void*> allocations;
+	~gc_mxm_index() { for (void* p : allocations) (void)hipFree(p); }
 };
 
 struct StitchedPath { std::vector<uint32_t> nodes; uint32_t firstOffset = 0, lastOffset = 0; uint64_t cells = 0; };

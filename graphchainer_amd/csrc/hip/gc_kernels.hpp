@@ -182,6 +182,24 @@ void launchSeedResolve(hipStream_t stream, const SeedLookup& lookup, const SeedH
 void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* readOff, uint32_t nReads, const uint8_t* invalidRead, const SeedHitArrays& hits, const uint32_t* readSeedOff, const uint32_t* winCapOff,
 	uint32_t splitLen, uint32_t splitGap, bool longPass, const GlueStaging& st, uint32_t* perRead /* 6 x (nReads + 1) words of scratch */, LongSeed* longSeeds, FragSeed* readSeeds, Fragment* frags, uint32_t* fragFirstSeed,
 	ReadChainJob* jobs, GlueRead* out, unsigned long long* cursors, bool forceGlobal = false);
+// ---- the MUM / MEM seeder (gc_mxm_index_create, gc_seeds_mxm; gc_mxm.hip, per-position logic in gc_mxm_core.hpp) ----
+struct MxmIndexView;
+void launchMxmPrefixTable(hipStream_t stream, const MxmIndexView& ix, uint32_t* table /* [2 << (2 * prefixLen)], zeroed */);
+// One batch through the seeder, in the three steps between which the host sizes what comes next: candidates (count, scan, fill, the defined order), select (the `count` longest per
+// read -> nFinal), write (the final records and their 32-bit read offsets into the gc_seeds block). Each waits for the stream where it reads a total back; the destructor frees the scratch.
+struct MxmSeedRun {
+	uint64_t nCandidates = 0;   // after candidates(): every MEM / MUM of the batch; more than 2^31 - 1 and nothing further was done
+	hipError_t candidates(hipStream_t q, const MxmIndexView& ix, const char* bases, const uint64_t* readOff, const uint32_t* tileOff /* [nReads + 1], device */, uint32_t nReads, uint32_t nTiles, int32_t mode, uint32_t minLen);
+	hipError_t select(hipStream_t q, uint32_t nReads, uint64_t maxCount, uint64_t& nFinal);
+	hipError_t write(hipStream_t q, uint32_t nReads, uint64_t nFinal, SeedHit* out, uint32_t* readHitOff);
+	~MxmSeedRun();
+private:
+	void *tiles = nullptr, *work = nullptr, *sortTmp = nullptr, *ranges = nullptr;
+	size_t workBytes = 0;
+	SeedHit* cand = nullptr;
+	uint64_t *sortedOuter = nullptr, *keptOff = nullptr;
+	uint32_t *order = nullptr, *candOff = nullptr;
+};
 // test entry: arrays of (key << 32 | index) elements sorted by key with the wave-cooperative replay of std::sort (gc_stdsort_wave.hpp); scratch: 3 words per element + 64 per array
 void launchTestMaxXScore(hipStream_t stream, const uint64_t* vp, const uint64_t* vn, const int32_t* scoreEnd, uint32_t n, double errorCost, int cells, int32_t* out);   // test entry (gc_test_max_x_score)
 void launchTestStdSort(hipStream_t stream, unsigned long long* elems, const uint64_t* off, uint32_t nArrays, uint32_t* scratch, long depthLimit);

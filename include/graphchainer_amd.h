@@ -233,6 +233,39 @@ typedef struct gc_seed_hit {
  * are accepted here and set the read's failed_assertion in the batch. */
 int gc_seeds_upload(const gc_graph* g, const gc_reads* reads, const gc_seed_hit* hits, const uint64_t* read_hit_off /* [n_reads+1] */, uint64_t n_reads, gc_seeds** out);
 void gc_seeds_destroy(gc_seeds* s);
+/* The raw records of a gc_seeds, read back from HBM: hits[read_hit_off[i] .. read_hit_off[i+1]) are read i's, as uploaded or as gc_seeds_mxm found them. Both arrays are
+ * malloc'd (free with gc_free). */
+int gc_seeds_hits(const gc_seeds* s, gc_seed_hit** hits, uint64_t** read_hit_off /* [n_reads+1] */, uint64_t* n_reads);
+/* Device milliseconds gc_seeds_mxm spent between its first kernel and its last (0 for uploaded seeds). */
+double gc_seeds_kernel_ms(const gc_seeds* s);
+
+/* ---- MUM / MEM seeds on the device (replaces MummerSeeder, src/MummerSeeder.cpp; --seeds-mum-count / --seeds-mem-count / --seeds-mxm-length) ---------- */
+/* The index: every original segment of g in forward orientation, in ascending node id, each followed by a separator - letters a, c, g, t (u) in either case, anything else a
+ * separator - with its full suffix array (separator < a < c < g < t; built on the host by prefix doubling on the library's worker threads), the text packed 2 bits per letter
+ * plus a mask, the segment start table and a table from the first 12 letters to a suffix-array interval. In HBM: about 4.3 bytes per text letter plus 4^12 x 8 bytes. 32-bit
+ * positions: a text of 2^32 - 16 letters or more is GC_ERR_INVALID. The graph may come from gc_graph_create_from_gfa, gc_graph_create or the index cache; the index is not
+ * stored in the cache, and it is not built on the device. Read-only, may be shared by streams; it belongs to g, which must outlive it. */
+typedef struct gc_mxm_index gc_mxm_index;
+int gc_mxm_index_create(const gc_graph* g, gc_mxm_index** out);
+void gc_mxm_index_destroy(gc_mxm_index* x);
+/* name in {"sa","node_start","node_id","bytes","build_us","prefix_len"}: the suffix array (text positions), the text position of every segment's first letter (plus the
+ * text's length), the segments' node ids, the index's bytes in HBM, the host build time, the table's letters; a malloc'd int64 array (free with gc_free). */
+int gc_mxm_index_array(const gc_mxm_index* x, const char* name, int64_t** out, uint64_t* count);
+
+#define GC_MXM_MUM 1
+#define GC_MXM_MEM 2
+/* The seeds MummerSeeder::getMumSeeds / getMemSeeds return for every read of the batch, found on the device and resolved there (as gc_seeds_upload resolves): a gc_seeds bound
+ * to `reads` and `g` that gc_align_batch_seeded / gc_align_batch_ext take unchanged.
+ * A MEM is (p, i, l): l >= min_len, T[p..p+l) == q[i..i+l) over a, c, g, t, and neither side can be extended (i == 0, p == 0 or T[p-1] != q[i-1]; the same at p+l, i+l); the
+ * separator and a read letter outside a, c, g, t (u) equal nothing, so a match never leaves a segment. A MUM is mummer's MAM: a MEM whose matched string occurs once in the text
+ * (forward segments only; the forward read and its reverse complement are separate queries; uniqueness in the query is not required). A reverse-strand match becomes
+ * node_offset = node length - offset - l, seq_pos = read length - i - l, reverse = 1; every hit has raw_goodness = match_len = l.
+ * max_count: the longest that many matches of a read over both strands are kept, UINT64_MAX: all. The order of a read's hits, and so which of the equal-length matches at the
+ * cut-off stay, is this library's own (the reference's follows mummer's emission order through a priority queue and an unstable sort): match_len descending, forward strand
+ * before reverse, query position in the searched orientation ascending, text position ascending.
+ * A read with a letter outside the IUPAC alphabet (flagged at upload) gets no hits. GC_ERR_INVALID, checked on the host before a device is needed: a null pointer, another mode,
+ * min_len < 2, max_count == 0, an index built from another graph; from the device: 2^31 matches or more in the batch before the cut (split the batch). */
+int gc_seeds_mxm(const gc_graph* g, const gc_mxm_index* x, const gc_reads* reads, int32_t mode, uint64_t max_count, uint32_t min_len, gc_seeds** out);
 
 /* ---- the hot path ---------------------------------------------------------------------------------- */
 
