@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = [
     "gc_params_default", "gc_graph_create_from_gfa", "gc_graph_create", "gc_graph_destroy", "gc_graph_num_nodes",
     "gc_graph_size_bp", "gc_graph_array", "gc_graph_trim_host", "gc_seeder_create", "gc_seeder_destroy", "gc_seeder_array",
     "gc_stream_create", "gc_stream_destroy", "gc_reads_upload", "gc_reads_destroy", "gc_align_batch",
-    "gc_seeds_upload", "gc_seeds_destroy", "gc_seeds_hits", "gc_seeds_kernel_ms", "gc_mxm_index_create", "gc_mxm_index_destroy", "gc_mxm_index_array", "gc_seeds_mxm", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
+    "gc_seeds_upload", "gc_seeds_destroy", "gc_seeds_hits", "gc_seeds_kernel_ms", "gc_mxm_index_create", "gc_mxm_options_default", "gc_mxm_index_open", "gc_mxm_cache_check", "gc_mxm_index_destroy", "gc_mxm_index_array", "gc_seeds_mxm", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
 ]
@@ -115,6 +115,10 @@ def load_library():
     lib.gc_seeds_kernel_ms.argtypes = [C.c_void_p]
     lib.gc_seeds_kernel_ms.restype = C.c_double
     lib.gc_mxm_index_create.argtypes = [C.c_void_p, _P(C.c_void_p)]
+    lib.gc_mxm_options_default.argtypes = [_P(GcMxmOptions)]
+    lib.gc_mxm_options_default.restype = None
+    lib.gc_mxm_index_open.argtypes = [C.c_void_p, _P(GcMxmOptions), _P(C.c_void_p)]
+    lib.gc_mxm_cache_check.argtypes = [C.c_char_p, _P(C.c_uint64)]
     lib.gc_mxm_index_destroy.argtypes = [C.c_void_p]
     lib.gc_mxm_index_array.argtypes = [C.c_void_p, C.c_char_p, _P(_P(C.c_int64)), _P(C.c_uint64)]
     lib.gc_seeds_mxm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, _P(C.c_void_p)]
@@ -513,20 +517,43 @@ class SeedBatch:
 
 
 MXM_MUM, MXM_MEM = 1, 2   # GC_MXM_MUM / GC_MXM_MEM
+MXM_BUILDS = {"host": 0, "device": 1}   # GC_MXM_BUILD_HOST / GC_MXM_BUILD_DEVICE
+
+
+class GcMxmOptions(C.Structure):
+    _fields_ = [("build", C.c_int32), ("reserved", C.c_int32), ("cache_prefix", C.c_char_p)]
+
+
+def mxm_cache_check(prefix):
+    """Verifies <prefix>.gcmxm on the host (gc_mxm_cache_check; no GPU needed): dict of version, text_letters, segments, file_bytes, text_fingerprint. A file that is missing,
+    damaged, truncated or of another version raises."""
+    info = (C.c_uint64 * 5)()
+    _check(load_library().gc_mxm_cache_check(os.fsencode(prefix), info))
+    return dict(zip(("version", "text_letters", "segments", "file_bytes", "text_fingerprint"), (int(x) for x in info)))
 
 
 class MxmIndex:
-    """The MUM / MEM seeder's index of a graph's forward segments, resident in HBM (gc_mxm_index_create): suffix array, packed text, segment table, prefix table.
+    """The MUM / MEM seeder's index of a graph's forward segments, resident in HBM (gc_mxm_index_open): suffix array, packed text, segment table, prefix table.
+    build: "host" (default) or "device" - who builds the suffix array, the same array either way. cache_prefix: the reference's --seeds-mxm-cache-prefix - <prefix>.gcmxm is
+    loaded if it exists, else the index is built and saved there. With neither argument this is gc_mxm_index_create.
     seeds() is the reference's --seeds-mum-count / --seeds-mem-count N with --seeds-mxm-length L: index.seeds(batch, "mum" | "mem", count=N (None or -1: all), min_len=L)."""
 
-    def __init__(self, graph):
+    def __init__(self, graph, build="host", cache_prefix=None):
         self.lib = load_library()
         self.graph = graph           # the index belongs to the graph: keep it alive
         self.handle = C.c_void_p()
-        _check(self.lib.gc_mxm_index_create(graph.handle, C.byref(self.handle)))
+        options = GcMxmOptions()
+        self.lib.gc_mxm_options_default(C.byref(options))
+        mode = MXM_BUILDS.get(build, build)
+        if not isinstance(mode, int):
+            raise ValueError("build is 'host' or 'device'")
+        options.build = mode
+        options.cache_prefix = os.fsencode(cache_prefix) if cache_prefix else None
+        _check(self.lib.gc_mxm_index_open(graph.handle, C.byref(options), C.byref(self.handle)))
 
     def array(self, name):
-        """'sa', 'node_start', 'node_id', 'bytes', 'build_us', 'prefix_len' (gc_mxm_index_array)."""
+        """'sa', 'node_start', 'node_id', 'bytes', 'build_us', 'prefix_len', 'build_mode' (0 host, 1 device, 2 loaded from the cache), 'build_rounds', 'build_scratch_bytes',
+        'cache_save_us', 'sa_us' (gc_mxm_index_array)."""
         return _fetch_array(self.lib.gc_mxm_index_array, self.handle, name)
 
     def seeds(self, batch, mode="mem", count=None, min_len=20, graph=None):

@@ -1068,18 +1068,23 @@ int gc_seeds_hits(const gc_seeds* s, gc_seed_hit** hits, uint64_t** read_hit_off
 double gc_seeds_kernel_ms(const gc_seeds* s) { return s ? s->kernelMs : 0; }
 
 // ---- the MUM / MEM seeder (the reference's MummerSeeder, src/MummerSeeder.cpp) ---------------
-int gc_mxm_index_create(const gc_graph* G, gc_mxm_index** out)
+// what gc_mxm_index_create and gc_mxm_index_open share. `who`: the entry point's name for the messages; cachePrefix empty: no cache
+static int mxmIndexOpen(const char* who, const gc_graph* G, int32_t build, const std::string& cachePrefix, gc_mxm_index** out)
 {
-	if (!G || !out) return fail(GC_ERR_INVALID, "null argument");
-	*out = nullptr;
 	// the forward original segments, from what the graph holds: bigraph id 2 * nodeID, its split nodes in offset order (64-letter chunks)
 	const size_t nB = G->hOrigSize.size();
 	uint64_t letters = 0;
 	std::vector<uint32_t> ids;
 	for (size_t id = 0; id < nB; id += 2) if (G->hLookupOff[id + 1] > G->hLookupOff[id]) { ids.push_back((uint32_t)id); letters += (uint64_t)G->hOrigSize[id] + 1; }
-	if (letters >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_mxm_index_create: a text of 2^32 - 16 letters or more (the segments and one separator each) does not fit the index's 32-bit positions");
+	if (letters >= 0xfffffff0ull) return fail(GC_ERR_INVALID, std::string(who) + ": a text of 2^32 - 16 letters or more (the segments and one separator each) does not fit the index's 32-bit positions");
+	const std::string cachePath = cachePrefix.empty() ? std::string() : gc::mxmCachePath(cachePrefix);
+	const bool load = !cachePath.empty() && gc::mxmCacheExists(cachePath);
+	// (a host check, before a device is needed; nothing falls back to the host build by itself)
+	if (!load && build == GC_MXM_BUILD_DEVICE && !gc::mxmDeviceBuildTakes(letters))
+		return fail(GC_ERR_INVALID, std::string(who) + ": the device build takes a text of fewer than 2^31 - 1 letters (hipCUB counts in int) and this one has " + std::to_string(letters) + "; build it on the host (GC_MXM_BUILD_HOST)");
 	gc_mxm_index* X = new gc_mxm_index();
 	int rc = guarded([&]() {
+		try {
 		requireDevice();
 		HIP_CHECK(hipGetDevice(&X->device));
 		X->graph = G;
@@ -1100,30 +1105,116 @@ int gc_mxm_index_create(const gc_graph* G, gc_mxm_index** out)
 				for (size_t j = 0; j < len; j++) dst[off + j] = gc::mxmRefCode(g.NodeSequences(node, j));
 			}
 		});
-		auto parallelFor = [](size_t count, const std::function<void(size_t)>& body) { WorkerPool::instance().run(count, [&](size_t i, size_t) { body(i); }); };
-		const std::vector<uint32_t> sa = gc::mxmSuffixArray(codes.data(), n, parallelFor);
-		std::vector<uint64_t> packed, invalid;
-		gc::mxmPackText(codes.data(), n, packed, invalid);
-		X->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-		auto up = [&](const auto& v) { auto* d = uploadVector(v); X->allocations.push_back((void*)d); X->deviceBytes += std::max<size_t>(v.size(), 1) * sizeof(v[0]); return d; };
+		const uint64_t fingerprint = cachePath.empty() ? 0 : gc::mxmTextFingerprint(codes.data(), n);
+		hipStream_t q = threadStream(X->device);
 		MxmIndexView& d = X->dev;
 		d.n = n; d.nNodes = (uint32_t)ids.size(); d.prefixLen = gc::MXM_PREFIX_LEN;
-		d.sa = up(sa); d.packed = up(packed); d.invalid = up(invalid); d.nodeStart = up(X->nodeStart); d.nodeId = up(X->nodeId);
+		auto upRaw = [&](const auto* src, size_t count) {
+			std::remove_const_t<std::remove_pointer_t<decltype(src)>>* p = nullptr;
+			const size_t bytes = std::max<size_t>(count, 1) * sizeof(*src);
+			HIP_CHECK(hipMalloc((void**)&p, bytes));
+			X->allocations.push_back((void*)p);
+			X->deviceBytes += bytes;
+			if (count) HIP_CHECK(hipMemcpy(p, src, count * sizeof(*src), hipMemcpyHostToDevice));
+			return p;
+		};
+		auto up = [&](const auto& v) { return upRaw(v.data(), v.size()); };
+		if (load) {
+			gc::MxmCacheFile file;
+			gc::mxmCacheLoad(cachePath, file, &fingerprint);
+			// (the fingerprint covers every letter and separator, so the segment starts agree; the node ids are compared on their own)
+			if (file.info.n != n || file.info.segments != ids.size() || memcmp(file.nodeStart, X->nodeStart.data(), (ids.size() + 1) * 4) != 0 || memcmp(file.nodeId, X->nodeId.data(), ids.size() * 4) != 0)
+				throw gc::MxmCacheError("MUM / MEM index cache " + cachePath + ": segment table mismatch (the cache was built from another graph)");
+			X->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+			X->buildMode = 2;
+			d.sa = upRaw(file.sa, n); d.packed = upRaw(file.packed, file.packedWords); d.invalid = upRaw(file.invalid, file.invalidWords);
+		} else {
+			std::vector<uint32_t> sa;
+			std::vector<uint64_t> packed, invalid;
+			const auto tSa = std::chrono::steady_clock::now();
+			if (build == GC_MXM_BUILD_DEVICE) {
+				uint32_t* dSa = nullptr;
+				HIP_CHECK(hipMalloc((void**)&dSa, std::max<size_t>(n, 1) * sizeof(uint32_t)));
+				X->allocations.push_back(dSa);
+				X->deviceBytes += std::max<size_t>(n, 1) * sizeof(uint32_t);
+				MxmSaBuild info;
+				HIP_CHECK(launchMxmSuffixArray(q, codes.data(), n, dSa, info));
+				X->saSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tSa).count();
+				gc::mxmPackText(codes.data(), n, packed, invalid);
+				X->buildRounds = info.rounds; X->buildScratchBytes = info.scratchBytes; X->buildMode = 1;
+				d.sa = dSa;
+			} else {
+				auto parallelFor = [](size_t count, const std::function<void(size_t)>& body) { WorkerPool::instance().run(count, [&](size_t i, size_t) { body(i); }); };
+				sa = gc::mxmSuffixArray(codes.data(), n, parallelFor, &X->buildRounds);
+				X->saSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tSa).count();
+				gc::mxmPackText(codes.data(), n, packed, invalid);
+			}
+			X->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+			if (build != GC_MXM_BUILD_DEVICE) d.sa = up(sa);
+			d.packed = up(packed); d.invalid = up(invalid);
+			if (!cachePath.empty()) {
+				const auto t1 = std::chrono::steady_clock::now();
+				if (build == GC_MXM_BUILD_DEVICE) { sa.resize(n); if (n) HIP_CHECK(hipMemcpy(sa.data(), d.sa, (size_t)n * 4, hipMemcpyDeviceToHost)); }
+				gc::mxmCacheSave(cachePath, X->nodeStart, X->nodeId, packed, invalid, sa.data(), n, fingerprint);
+				X->cacheSaveSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+			}
+		}
+		d.nodeStart = up(X->nodeStart); d.nodeId = up(X->nodeId);
 		uint32_t* table = nullptr;
 		const size_t tableBytes = ((size_t)2 << (2 * d.prefixLen)) * sizeof(uint32_t);
 		HIP_CHECK(hipMalloc((void**)&table, tableBytes));
 		X->allocations.push_back(table);
 		X->deviceBytes += tableBytes;
 		d.prefix = table;
-		hipStream_t q = threadStream(X->device);
 		HIP_CHECK(hipMemsetAsync(table, 0, tableBytes, q));
 		launchMxmPrefixTable(q, d, table);
 		HIP_CHECK(hipGetLastError());
 		HIP_CHECK(hipStreamSynchronize(q));
 		return (int)GC_OK;
+		} catch (const gc::MxmCacheError& e) {
+			return fail(GC_ERR_GRAPH, e.what());   // (a cache that cannot be used or written: never used half, never overwritten)
+		}
 	});
 	if (rc != GC_OK) { delete X; return rc; }
 	*out = X;
+	return GC_OK;
+}
+
+int gc_mxm_index_create(const gc_graph* G, gc_mxm_index** out)
+{
+	if (!G || !out) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	return mxmIndexOpen("gc_mxm_index_create", G, GC_MXM_BUILD_HOST, std::string(), out);
+}
+
+void gc_mxm_options_default(gc_mxm_options* o)
+{
+	if (!o) return;
+	o->build = GC_MXM_BUILD_HOST; o->reserved = 0; o->cache_prefix = nullptr;
+}
+
+int gc_mxm_index_open(const gc_graph* G, const gc_mxm_options* o, gc_mxm_index** out)
+{
+	// host checks first: a malformed call is GC_ERR_INVALID whether or not a device is present
+	if (!G || !o || !out) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	if (o->build != GC_MXM_BUILD_HOST && o->build != GC_MXM_BUILD_DEVICE) return fail(GC_ERR_INVALID, "gc_mxm_index_open: build is neither GC_MXM_BUILD_HOST nor GC_MXM_BUILD_DEVICE");
+	if (o->reserved != 0) return fail(GC_ERR_INVALID, "gc_mxm_index_open: reserved must be 0");
+	return mxmIndexOpen("gc_mxm_index_open", G, o->build, o->cache_prefix ? std::string(o->cache_prefix) : std::string(), out);
+}
+
+int gc_mxm_cache_check(const char* cache_prefix, uint64_t* info)
+{
+	if (!cache_prefix || !*cache_prefix) return fail(GC_ERR_INVALID, "gc_mxm_cache_check: no cache prefix");
+	const std::string path = gc::mxmCachePath(cache_prefix);
+	try {
+		gc::MxmCacheFile file;
+		gc::mxmCacheLoad(path, file);
+		if (gc::mxmCacheTextFingerprint(file) != file.info.fingerprint) throw gc::MxmCacheError("MUM / MEM index cache " + path + ": the stored text does not have the stored fingerprint");
+		if (info) { info[0] = file.info.version; info[1] = file.info.n; info[2] = file.info.segments; info[3] = file.info.fileBytes; info[4] = file.info.fingerprint; }
+	} catch (const std::exception& e) {
+		return fail(GC_ERR_GRAPH, e.what());
+	}
 	return GC_OK;
 }
 void gc_mxm_index_destroy(gc_mxm_index* x) { delete x; }
@@ -1138,6 +1229,11 @@ int gc_mxm_index_array(const gc_mxm_index* X, const char* name, int64_t** out, u
 	else if (nm == "bytes") v.push_back((int64_t)X->deviceBytes);
 	else if (nm == "build_us") v.push_back((int64_t)(X->buildSeconds * 1e6));
 	else if (nm == "prefix_len") v.push_back((int64_t)X->dev.prefixLen);
+	else if (nm == "sa_us") v.push_back((int64_t)(X->saSeconds * 1e6));
+	else if (nm == "build_mode") v.push_back((int64_t)X->buildMode);
+	else if (nm == "build_rounds") v.push_back((int64_t)X->buildRounds);
+	else if (nm == "build_scratch_bytes") v.push_back((int64_t)X->buildScratchBytes);
+	else if (nm == "cache_save_us") v.push_back((int64_t)(X->cacheSaveSeconds * 1e6));
 	else if (nm == "sa") {
 		std::vector<uint32_t> sa(X->dev.n);
 		int rc = guarded([&]() { requireDevice(); if (X->dev.n) HIP_CHECK(hipMemcpy(sa.data(), X->dev.sa, (size_t)X->dev.n * 4, hipMemcpyDeviceToHost)); return (int)GC_OK; });

@@ -16,6 +16,7 @@
 #include "host/gc_selection.hpp"
 #include "host/gc_switches.hpp"
 #include "host/gc_mxm_build.hpp"
+#include "host/gc_mxm_cache.hpp"
 #include "hip/gc_mxm_core.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -521,7 +522,12 @@ struct gc_mxm_index {
 	std::vector<int32_t> nodeId;
 	MxmIndexView dev {};
 	uint64_t deviceBytes = 0;
-	double buildSeconds = 0;               // text and suffix array on the host
+	double buildSeconds = 0;               // text and suffix array: built on the host or the device, or read from the cache file and verified
+	double saSeconds = 0;                  // of buildSeconds, the suffix array alone (0 when loaded)
+	int buildMode = 0;                     // 0 host build, 1 device build, 2 loaded from the cache (gc_mxm_index_open)
+	uint32_t buildRounds = 0;              // doubling rounds after the first sort (0 when loaded)
+	uint64_t buildScratchBytes = 0;        // what a device build allocated beside the SA, freed again
+	double cacheSaveSeconds = 0;           // writing <prefix>.gcmxm after a build (0: nothing written)
 	std::vector<void*> allocations;
 	~gc_mxm_index() { for (void* p : allocations) (void)hipFree(p); }
 };

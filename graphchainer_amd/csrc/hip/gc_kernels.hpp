@@ -185,6 +185,10 @@ void launchSeedGlueHits(hipStream_t stream, const DGraph& g, const uint64_t* rea
 // ---- the MUM / MEM seeder (gc_mxm_index_create, gc_seeds_mxm; gc_mxm.hip, per-position logic in gc_mxm_core.hpp) ----
 struct MxmIndexView;
 void launchMxmPrefixTable(hipStream_t stream, const MxmIndexView& ix, uint32_t* table /* [2 << (2 * prefixLen)], zeroed */);
+// The index's suffix array built on the device (gc_mxm_sa.hip): hostCodes [n] (0 separator, 1..4 = a c g t) are uploaded, sa [n] (device) is filled with the host builder's order.
+// n below 2^31 - 1 (hipCUB counts in int; the caller refuses more by name). Waits for the stream once per doubling round; its scratch is gone when it returns.
+struct MxmSaBuild { uint32_t rounds = 0; uint64_t scratchBytes = 0; };   // doubling rounds after the first sort; every byte the build allocated beside the SA
+hipError_t launchMxmSuffixArray(hipStream_t stream, const uint8_t* hostCodes, uint32_t n, uint32_t* sa, MxmSaBuild& info);
 // One batch through the seeder, in the three steps between which the host sizes what comes next: candidates (count, scan, fill, the defined order), select (the `count` longest per
 // read -> nFinal), write (the final records and their 32-bit read offsets into the gc_seeds block). Each waits for the stream where it reads a total back; the destructor frees the scratch.
 struct MxmSeedRun {

@@ -18,6 +18,11 @@ namespace gc {
 // letters of the direct-address table in front of the suffix array: 4^12 intervals of 8 bytes = 128 MiB, and what is left of a 20-letter window's search is a handful of steps
 inline constexpr uint32_t MXM_PREFIX_LEN = 12;
 
+// the device build of the suffix array (hip/gc_mxm_sa.hip) counts its items in int, as hipCUB does: it takes a text of fewer letters than this, the host build any text the
+// index's 32-bit positions hold
+inline constexpr uint64_t MXM_DEVICE_BUILD_MAX = 0x7fffffffull;
+inline bool mxmDeviceBuildTakes(uint64_t letters) { return letters < MXM_DEVICE_BUILD_MAX; }
+
 struct MxmText {
 	std::vector<uint8_t> codes;        // 0 separator, 1..4 = a c g t
 	std::vector<uint32_t> nodeStart;   // [segments + 1]; the last entry is the text's length
@@ -42,11 +47,13 @@ inline void mxmAppendSegment(MxmText& t, int32_t nodeId, const char* letters, si
 }
 inline void mxmFinishText(MxmText& t) { t.nodeStart.push_back((uint32_t)t.codes.size()); }
 
-// parallelFor(n, body): runs body(i) for i in [0, n), on as many threads as the caller has (the library passes its worker pool, a test a plain loop)
+// parallelFor(n, body): runs body(i) for i in [0, n), on as many threads as the caller has (the library passes its worker pool, a test a plain loop); rounds: the doubling
+// rounds it took after the first sort, when asked for
 template <class ParallelFor>
-std::vector<uint32_t> mxmSuffixArray(const uint8_t* codes, uint32_t n, ParallelFor&& parallelFor)
+std::vector<uint32_t> mxmSuffixArray(const uint8_t* codes, uint32_t n, ParallelFor&& parallelFor, uint32_t* rounds = nullptr)
 {
 	std::vector<uint32_t> sa(n);
+	if (rounds) *rounds = 0;
 	if (!n) return sa;
 	constexpr uint32_t K = 21;   // letters of the first key: 3 bits each (0 beyond the text, separator 1, letters 2..5)
 	std::vector<uint64_t> key(n);
@@ -84,6 +91,7 @@ std::vector<uint32_t> mxmSuffixArray(const uint8_t* codes, uint32_t n, ParallelF
 	// members' (after every group has been sorted: the new ranks are staged in `fresh`), so groups are independent within a round.
 	std::vector<uint32_t> fresh;
 	for (uint64_t h = K; !groups.empty(); h *= 2) {
+		if (rounds) ++*rounds;
 		auto second = [&](uint32_t i) -> int64_t { return (uint64_t)i + h < n ? (int64_t)rank[i + h] : -1; };
 		parallelFor(groups.size(), [&](size_t g) {
 			std::sort(sa.begin() + groups[g].first, sa.begin() + groups[g].second, [&](uint32_t x, uint32_t y) { return second(x) < second(y); });

@@ -244,13 +244,44 @@ double gc_seeds_kernel_ms(const gc_seeds* s);
  * separator - with its full suffix array (separator < a < c < g < t; built on the host by prefix doubling on the library's worker threads), the text packed 2 bits per letter
  * plus a mask, the segment start table and a table from the first 12 letters to a suffix-array interval. In HBM: about 4.3 bytes per text letter plus 4^12 x 8 bytes. 32-bit
  * positions: a text of 2^32 - 16 letters or more is GC_ERR_INVALID. The graph may come from gc_graph_create_from_gfa, gc_graph_create or the index cache; the index is not
- * stored in the cache, and it is not built on the device. Read-only, may be shared by streams; it belongs to g, which must outlive it. */
+ * stored in the gc_index_* cache, and this call builds it on the host every time (gc_mxm_index_open: the device build and a file of its own). Read-only, may be shared by
+ * streams; it belongs to g, which must outlive it. */
 typedef struct gc_mxm_index gc_mxm_index;
 int gc_mxm_index_create(const gc_graph* g, gc_mxm_index** out);
 void gc_mxm_index_destroy(gc_mxm_index* x);
-/* name in {"sa","node_start","node_id","bytes","build_us","prefix_len"}: the suffix array (text positions), the text position of every segment's first letter (plus the
- * text's length), the segments' node ids, the index's bytes in HBM, the host build time, the table's letters; a malloc'd int64 array (free with gc_free). */
+/* name in {"sa","node_start","node_id","bytes","build_us","prefix_len","build_mode","build_rounds","build_scratch_bytes","cache_save_us","sa_us"}: the suffix array (text positions), the
+ * text position of every segment's first letter (plus the text's length), the segments' node ids, the index's bytes in HBM, the time to produce text and suffix array (a build, or
+ * a file read plus verification), the table's letters, how the suffix array came to be (0 host build, 1 device build, 2 loaded from the cache), the doubling rounds of the build
+ * after its first sort (0 when loaded), the peak device scratch of a device build (else 0), the time spent writing the cache file (0: none written), of build_us the suffix array alone (0 when loaded); a malloc'd int64 array (free
+ * with gc_free). */
 int gc_mxm_index_array(const gc_mxm_index* x, const char* name, int64_t** out, uint64_t* count);
+
+/* gc_mxm_index_create with a choice of builder and the reference's --seeds-mxm-cache-prefix (src/AlignerMain.cpp:87,227, src/MummerSeeder.cpp:65-89,137-161: load the index if
+ * the cache exists, else build it and save it). gc_mxm_options_default: host build, no cache - what gc_mxm_index_create does.
+ *   build          GC_MXM_BUILD_HOST: prefix doubling on the library's worker threads. GC_MXM_BUILD_DEVICE: the same algorithm on the GPU (radix sort of a 21-letter key, then
+ *                  doubling rounds over the tied suffixes only); the suffix array is the host's element for element. Its scratch, freed before the call returns, is 29 bytes
+ *                  per text letter plus 8 per letter still tied after the first sort. It takes a text of fewer than 2^31 - 1 letters (hipCUB counts in int): a longer one is
+ *                  GC_ERR_INVALID, checked on the host - build that one with GC_MXM_BUILD_HOST; nothing falls back by itself.
+ *   cache_prefix   NULL or "": no file. Else the file is <prefix>.gcmxm - ONE file in a private format of this library (csrc/host/gc_mxm_cache.hpp), not the reference's
+ *                  <prefix>.aux (a boost text archive) and mummer's <prefix>_index files, which cannot be written or read without those libraries. If the file exists it is
+ *                  loaded and nothing is built (`build` is not looked at); otherwise the index is built by `build` and saved, through a temporary name in the same directory
+ *                  and a rename. The file holds the segment table, the packed text, the raw suffix array (4 bytes per letter), an FNV-1a-64 fingerprint of the text and a
+ *                  checksum; the prefix table is rebuilt on the device. A load verifies magic, version, sizes, checksum, tables, suffix-array bounds and the fingerprint and
+ *                  segment table against g: any mismatch is GC_ERR_GRAPH with the file and the failure in gc_last_error, and the file is neither used nor overwritten (delete
+ *                  it to rebuild). A file that cannot be written is GC_ERR_GRAPH too.
+ * GC_ERR_INVALID before a device is needed: a null pointer, another build value, reserved != 0.
+ * gc_mxm_cache_check: host only, as gc_index_check is - verifies <prefix>.gcmxm (all of the above but the comparison with a graph; the stored text against its fingerprint
+ * instead) and fills info[5] = { version, text letters, segments, file bytes, text fingerprint }; info may be NULL. */
+#define GC_MXM_BUILD_HOST   0
+#define GC_MXM_BUILD_DEVICE 1
+typedef struct gc_mxm_options {
+	int32_t build;              /* GC_MXM_BUILD_*; anything else: GC_ERR_INVALID */
+	int32_t reserved;           /* must be 0 */
+	const char* cache_prefix;   /* --seeds-mxm-cache-prefix; NULL or "": no cache */
+} gc_mxm_options;
+void gc_mxm_options_default(gc_mxm_options* o);
+int gc_mxm_index_open(const gc_graph* g, const gc_mxm_options* o, gc_mxm_index** out);
+int gc_mxm_cache_check(const char* cache_prefix, uint64_t* info /* [5] or NULL */);
 
 #define GC_MXM_MUM 1
 #define GC_MXM_MEM 2
