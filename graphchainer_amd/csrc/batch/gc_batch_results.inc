@@ -202,6 +202,10 @@
 					uint32_t firstBand = (longer - shorter) + std::max<uint32_t>(64, shorter / 7);
 					const uint32_t halfLimit = editDistanceMaxK(0);
 					if (firstBand < halfLimit) firstBand = std::max(firstBand, std::min<uint32_t>(halfLimit - 1, (longer - shorter) + shorter / 5));
+					// three pairs per wave where the length difference plus 10 % of the shorter sequence fit the band a team of 21 lanes holds (launchEditDistances widens the band to all of it):
+					// with column groups that band is 1 441, and cfg2's chain pairs (distances 1 100-1 300) pass it in one sweep
+					const uint32_t thirdLimit = editDistanceTeamMaxK(3);
+					if (len <= 65536 && (longer - shorter) + shorter / 10 < thirdLimit) firstBand = thirdLimit - 1;
 					hPairs[nPairs++] = EdPair { nCells, cells, (uint32_t)r, (uint32_t)r, firstBand };
 					pairRead.push_back((uint32_t)r);
 				}

@@ -48,7 +48,7 @@ int gc_edit_distance(const char* a, const uint64_t* a_off, const char* b, const 
 		HIP_CHECK(hipMemcpy(pr, reads.data(), n_pairs * sizeof(EdRead), hipMemcpyHostToDevice));
 		EditDistanceRun run;
 		auto readLenOf = [&](uint32_t r) { return reads[r].len; };
-		launchEditDistances(run, nullptr, pairs.data(), out, (uint32_t)n_pairs, pp, po, pr, pb, pm, pa, nullptr, readLenOf, sw.debugTimes, sw.edFirstK.has_value());   // (the test hook's band picks the kernel class as a whole-read pair's own bound does)
+		launchEditDistances(run, nullptr, pairs.data(), out, (uint32_t)n_pairs, pp, po, pr, pb, pm, pa, nullptr, readLenOf, sw.debugTimes);
 		finishEditDistances(run, nullptr, pairs.data(), out, (uint32_t)n_pairs, pp, po, pr, pb, pm, pa, nullptr, sw.debugTimes);
 		return (int)GC_OK;
 	});

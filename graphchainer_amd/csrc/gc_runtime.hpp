@@ -978,7 +978,7 @@ inline uint32_t editDistanceUnit(uint32_t k, uint32_t readLen)
 inline void createStream(hipStream_t* q) { HIP_CHECK(hipStreamCreateWithFlags(q, hipStreamNonBlocking)); }
 
 inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair* hPairs, int64_t* hOut, uint32_t nPairs, EdPair* dPairs, int64_t* dOut, const EdRead* dReads, const char* dBases,
-	const uint64_t* dEqMasks, const char* dLetters, const uint32_t* dLettersLen, const std::function<uint32_t(uint32_t)>& readLen, bool debugTimes, bool kIsBound = false)
+	const uint64_t* dEqMasks, const char* dLetters, const uint32_t* dLettersLen, const std::function<uint32_t(uint32_t)>& readLen, bool debugTimes)
 {
 	if (!nPairs) return;
 	if (!run.ready) HIP_CHECK(hipEventCreateWithFlags(&run.ready, hipEventDisableTiming));
@@ -997,11 +997,11 @@ inline void launchEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 		c += 2;                                                               // classes 2..6: one pair per wave, units of 1..16 blocks
 		if (unit == 1 && hPairs[i].k < editDistanceMaxK(0) && len <= 131072) {   // class 1: two pairs per wave (small first band)
 			c = 1;
-			// class 0 (r4): three pairs per wave, bands below 1290 - for pairs whose k is a bound (a whole-read pair's k comes from the alignment itself: one sweep, always enough).
-			// A chain pair's k is a guess; tried there whenever length difference + 10 % of the shorter sequence fit, 45 % of cfg2's chain pairs (distances 1 100-1 300) came back
-			// for a second sweep and the two kernels together took 352 ms per nine batches against 311 (`gpurun_out/r4_ring`): chain pairs stay with two per wave
-			if (kIsBound && len <= 65536 && hPairs[i].k < editDistanceTeamMaxK(3)) c = 0;
-			// a sweep of these kernels takes columns + units steps whatever the band, as long as the band fits the team's lanes - so the first guess may as well be the widest band that
+			// class 0 (r4): three pairs per wave, bands up to what a team of 21 lanes holds (1 441 with groups of 8 columns). A whole-read pair's k comes from the alignment itself:
+			// one sweep, always enough. A chain pair's k is a guess: at the r4 limit of 1 289, 45 % of cfg2's chain pairs (distances 1 100-1 300) came back for a second sweep and
+			// they stayed with two per wave; at 1 441, 0.7 % come back and the caller sends them here (gc_batch_results.inc)
+			if (len <= 65536 && hPairs[i].k < editDistanceTeamMaxK(3)) c = 0;
+			// a sweep of these kernels takes column groups + units steps whatever the band, as long as the band fits the team's lanes - so the first guess may as well be the widest band that
 			// does (any k >= the distance gives the distance): a chain pair whose guess (length difference + 14 %) was a little short used to pay a failed sweep here, a second
 			// failed sweep with the same guess in the one-pair-per-wave kernel and a third with the doubled band (r3)
 			hPairs[i].k = c == 0 ? editDistanceTeamMaxK(3) - 1 : std::max(hPairs[i].k, editDistanceMaxK(0) - 1);

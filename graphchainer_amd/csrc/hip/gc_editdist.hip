@@ -8,15 +8,18 @@
 //
 // k_edit_distance: one wave per (path, read) pair. Rows = read bases, 64 per 64-bit word ("block"), columns = path
 // letters. Lane l owns the units l, l+64, l+128, ... (unit = G consecutive blocks = 64G rows) and the wave sweeps the
-// matrix as a skewed wavefront: at step t unit B works on column t - B, so the horizontal delta leaving unit B-1
-// at column j is exactly what unit B needs one step later (one cross-lane shuffle per step). Only the cells with
-// Ukkonen's corridor are computed (the diagonals d = row - column with |d| + |(n - m) - d| <= k, about k of them): unit B is active
-// for columns [64G*B - reachRight, 64G*B + 64G - 1 + reachLeft], enters
-// with all-+1 vertical deltas below its upper neighbour and gets +1 as incoming horizontal delta when it is the top
-// of the band. Band values are upper bounds and exact along every path of cost <= k, so a result <= k is the edit
-// distance; otherwise k doubles and the pass repeats. k < 4000*G keeps a lane's consecutive units disjoint in time
-// (no limit when the read has at most 64 units, i.e. up to 4096*G rows); the host escalates G = 1, 2, 4, 8, 16.
+// matrix as a skewed wavefront of column groups: at step t unit B works on the C columns of group t - B, so what unit B-1
+// publishes after a group - its bottom row's score and the group's C horizontal deltas - is exactly what unit B needs one
+// step later (two cross-lane shuffles per step). The step itself - corridor, windows, the C Myers columns, the final cell,
+// the letter ring's refill rule - is gc_editdist_core.hpp, shared by the three kernels here and compiled for the host by
+// tests/ed_host. Only the cells within Ukkonen's corridor are computed (the diagonals d = row - column with
+// |d| + |(n - m) - d| <= k, about k of them, widened to whole groups); a unit enters with all-+1 vertical deltas below its
+// upper neighbour and gets +1 as incoming horizontal delta when it is the top of the band. Band values are upper bounds
+// and exact along every path of cost <= k, so a result <= k is the edit distance; otherwise k doubles and the pass
+// repeats. k < 4000*G keeps a lane's consecutive units disjoint in time (edMaxBand; no limit when the read has at most
+// 64 units, i.e. up to 4096*G rows); the host escalates G = 1, 2, 4, 8, 16.
 #include "gc_kernels.hpp"
+#include "gc_editdist_core.hpp"
 #include <hip/hip_runtime.h>
 
 namespace gcdev {
@@ -128,16 +131,28 @@ __global__ void __launch_bounds__(64) k_chain_pathseq(DGraph g, const PathSeqJob
 
 #define ED_RING 8192u
 
+// the refill of a letter ring at the steps that are a multiple of PERIOD (gc_editdist_core.hpp): lane `first` of `stride` loads its share of the columns up to `end`
+template <uint32_t RB, uint32_t C>
+__device__ __forceinline__ void refillRing(uint8_t* ring, uint32_t ringMask, const EdBand& bd, const char* path, uint32_t tNext, uint32_t& loadedEnd, uint32_t first, uint32_t stride)
+{
+	const uint32_t end = edRingEnd<RB, C>(bd, tNext);
+	if (end > loadedEnd) { edRingFill(ring, ringMask, path, bd.m, loadedEnd, end, first, stride); loadedEnd = end; }
+}
+
+// (waves per SIMD as before the column groups for units of 1, 2 and 4 words; units of 8 and 16 words - a few single-wave pairs of reads beyond 65 536 bases - keep their
+// 96 and 192 registers of state out of scratch instead)
 template <int G>
-__global__ void __launch_bounds__(64) k_edit_distance(const EdPair* __restrict__ pairs, uint32_t nPairs, const EdRead* __restrict__ reads, const char* __restrict__ bases,
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G >= 8 ? 1 : G >= 4 ? 3 : G >= 2 ? 4 : 5))) k_edit_distance(const EdPair* __restrict__ pairs, uint32_t nPairs, const EdRead* __restrict__ reads, const char* __restrict__ bases,
 	const uint64_t* __restrict__ eqMasks, const char* __restrict__ letters, const uint32_t* __restrict__ lettersLen, int64_t* __restrict__ outDistance)
 {
 	GC_RAISE_ED_PRIO();
-	__shared__ uint8_t ring[ED_RING];
+	__shared__ __attribute__((aligned(8))) uint8_t ring[ED_RING];
 	__shared__ int32_t resultSlot;
 	const uint32_t lane = threadIdx.x;
-	constexpr uint32_t RB = 64u * G;                 // rows per unit
+	constexpr uint32_t C = edColsOfUnit(G), RB = 64u * G;   // columns per step, rows per unit
 	constexpr uint32_t K_MAX = 4000u * G;             // the corridor is about k diagonals wide: a lane's consecutive units (64 units = 4096 G rows apart) stay disjoint in time
+	constexpr uint32_t PERIOD = ED_RING / (2 * C);
+	static_assert(K_MAX - 1 <= edMaxBand(RB, 64, C), "a lane's consecutive units must stay disjoint in time");
 	for (uint32_t pi = blockIdx.x; pi < nPairs; pi += gridDim.x) {
 		const EdPair pair = pairs[pi];
 		const EdRead rd = reads[pair.read];
@@ -145,123 +160,38 @@ __global__ void __launch_bounds__(64) k_edit_distance(const EdPair* __restrict__
 		const uint32_t m = lettersLen ? lettersLen[pair.lenIndex] : pair.m;
 		if (m == 0xffffffffu) { if (lane == 0) outDistance[pi] = -3; continue; }   // path letters overflowed their slot
 		if (n == 0 || m == 0) { if (lane == 0) outDistance[pi] = (int64_t)(n + m); continue; }
-		const char* path = letters + pair.lettersOff;
-		const uint64_t* masks = eqMasks + rd.eqOff;
-		const uint32_t nU = (n + RB - 1) / RB;
+		const EdSource src { eqMasks + rd.eqOff, rd.words, letters + pair.lettersOff, bases + rd.readOff, n, m };
 		const uint32_t diff = n > m ? n - m : m - n;
 		const uint32_t cap = n > m ? n : m;
 		uint32_t k = pair.k > diff ? pair.k : diff;
 		if (k < 1) k = 1;
 		if (k > cap) k = cap;
 		int64_t answer = -2;                         // -2: this G cannot hold the band, the host retries with a larger one
-		// the letter ring is refilled every 1024 steps up to column t + 2048, so it holds the columns from t + 2048 - ED_RING on; unit B reads
-		// column t' - B for t' < t + 1024: every unit's column is still there iff nU - 1 + 2048 <= ED_RING - 1 (larger pairs: the next unit size)
-		if (nU + 2048 <= ED_RING) while (true) {
-			if (k >= K_MAX && nU > 64) break;   // (with at most one unit per lane there is nothing to keep disjoint: any band width works)
+		while (true) {
+			const EdBand bd = edBand<RB>(n, m, k);
+			if (!edLanesHold(k, K_MAX, bd.nU, 64)) break;
+			if (!edRingHolds<RB, C>(bd, ED_RING, PERIOD)) break;
 			// ---- one banded pass
-			uint64_t VP[G], VN[G], eqA[G], eqC[G], eqG[G], eqT[G];
+			EdUnit<G> u;
 			uint32_t B = lane;                       // current unit of this lane
-			int32_t score = 0;
 			bool fresh = true;                       // unit state not initialised yet
-			uint32_t pack = 0;                       // published (score << 2) | (hout + 1)
+			EdPub pub { 0, 0 };
 			uint32_t loadedEnd = 0;
-			// per-unit step window, refreshed when the lane moves to its next unit
-			uint32_t tBegin = 0xffffffffu, tEnd = 0xffffffffu, tHinEnd = 0, finalStep = 0xffffffffu;
-			const uint32_t lastUnit = (n - 1) / RB;
-			// Ukkonen's corridor: a path of cost <= k from (0,0) to (n-1,m-1) spends at least |row - column| to get where it is and at least
-			// |(n - m) - (row - column)| to get home, so it only visits diagonals with |d| + |(n - m) - d| <= k: from min(0, n-m) - a to
-			// max(0, n-m) + a with a = (k - |n-m|) / 2 - about k diagonals, half of the symmetric |row - column| <= k
-			const uint32_t slack = (k - diff) / 2;
-			const uint64_t reachRight = (uint64_t)(n > m ? n - m : 0) + slack;   // row - column at most this: columns from rowBase - reachRight
-			const uint64_t reachLeft = (uint64_t)(m > n ? m - n : 0) + slack;    // column - row at most this: columns to row + reachLeft
-			auto enterUnit = [&](uint32_t b) {
-				B = b;
-				fresh = true;
-				if (b >= nU) { tBegin = 0xffffffffu; tEnd = 0xffffffffu; return; }
-				const uint64_t rowBase = (uint64_t)RB * b;
-				const uint64_t c0 = rowBase > reachRight ? rowBase - reachRight : 0;
-				const uint64_t c1 = rowBase + RB - 1 + reachLeft;
-				const uint64_t lastCol = c1 < m - 1 ? c1 : m - 1;
-				tBegin = c0 > lastCol ? 0xffffffffu : (uint32_t)(c0 + b);          // (a unit below the band at every column never runs)
-				tEnd = (uint32_t)(lastCol + b);
-				tHinEnd = b > 0 ? (uint32_t)(rowBase - 1 + reachLeft + b) : 0;      // last step whose column the upper neighbour also computes
-				finalStep = b == lastUnit ? m - 1 + b : 0xffffffffu;
-			};
-			enterUnit(lane);
+			EdWindow w = edWindow<RB, C>(bd, B);      // per-unit step window, refreshed when the lane moves to its next unit
 			if (lane == 0) resultSlot = -1;
-			const uint32_t steps = m + nU - 1;
+			const uint32_t steps = (m - 1) / C + bd.nU;
 			for (uint32_t t = 0; t < steps; t++) {
-				if ((t & 1023u) == 0) {
-					uint32_t end = t + 2048 < m ? t + 2048 : m;
-					for (uint32_t c = loadedEnd + lane; c < end; c += 64) {
-						const uint8_t ch = (uint8_t)path[c];
-						ring[c & (ED_RING - 1)] = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
-					}
-					loadedEnd = end > loadedEnd ? end : loadedEnd;
+				if ((t & (PERIOD - 1)) == 0) {
+					refillRing<RB, C>(ring, ED_RING - 1, bd, src.path, t + PERIOD, loadedEnd, lane, 64);
 					__syncthreads();
 				}
-				const uint32_t nbPack = __shfl(pack, (lane + 63) & 63);
-				if (B < nU && t > tEnd) { do enterUnit(B + 64); while (B < nU && t > tEnd); }
-				if (t < tBegin) continue;
-				const uint32_t j = t - B;
-				if (fresh) {
-					fresh = false;
-					const uint32_t wordBase = (RB / 64) * B;
-					for (int q = 0; q < G; q++) {
-						VP[q] = ~0ull; VN[q] = 0;
-						const uint32_t w = wordBase + q;
-						const bool in = w < rd.words;
-						eqA[q] = in ? masks[w] : 0ull;
-						eqC[q] = in ? masks[rd.words + w] : 0ull;
-						eqG[q] = in ? masks[2ull * rd.words + w] : 0ull;
-						eqT[q] = in ? masks[3ull * rd.words + w] : 0ull;
-					}
-					if (j == 0) score = (int32_t)(RB * (B + 1));
-					else score = (int32_t)(nbPack >> 2) - ((int32_t)(nbPack & 3u) - 1) + (int32_t)RB;   // below the upper neighbour's previous column, all +1
-				}
-				const uint32_t code = ring[j & (ED_RING - 1)];
-				int hin = 1;                         // top of the band (and row -1 of the matrix): +1 per column
-				if (B > 0 && t <= tHinEnd) hin = (int)(nbPack & 3u) - 1;
-				uint64_t hinP = hin > 0 ? 1 : 0, hinN = hin < 0 ? 1 : 0;
-				for (int q = 0; q < G; q++) {
-					uint64_t Eq;
-					if (code < 4) {
-						const uint64_t lo = (code & 1) ? eqC[q] : eqA[q], hi = (code & 1) ? eqT[q] : eqG[q];
-						Eq = (code & 2) ? hi : lo;
-					} else {                         // any other letter: compare the 64 read bases of this block directly
-						Eq = 0;
-						const uint8_t letter = (uint8_t)path[j];
-						const uint64_t row0 = (uint64_t)RB * B + 64ull * q;
-						for (uint32_t i = 0; i < 64 && row0 + i < n; i++) if ((uint8_t)bases[rd.readOff + row0 + i] == letter) Eq |= 1ull << i;
-					}
-					const uint64_t vp = VP[q], vn = VN[q];
-					const uint64_t Xv = Eq | vn;
-					Eq |= hinN;
-					const uint64_t Xh = (((Eq & vp) + vp) ^ vp) | Eq;
-					uint64_t Ph = vn | ~(Xh | vp);
-					uint64_t Mh = vp & Xh;
-					const uint64_t outP = Ph >> 63, outN = Mh >> 63;
-					Ph = (Ph << 1) | hinP;
-					Mh = (Mh << 1) | hinN;
-					VP[q] = Mh | ~(Xv | Ph);
-					VN[q] = Ph & Xv;
-					hinP = outP; hinN = outN;
-				}
-				const int hout = (int)hinP - (int)hinN;
-				score += hout;
-				pack = ((uint32_t)score << 2) | (uint32_t)(hout + 1);
-				if (t == finalStep) {                // the cell (n-1, m-1): subtract the deltas of the padding rows below it
-					int32_t d = score;
-					for (int q = 0; q < G; q++) {
-						const uint64_t row0 = (uint64_t)RB * B + 64ull * q;
-						uint64_t pad = 0;
-						if (row0 >= n) pad = ~0ull;
-						else if (row0 + 64 > n) pad = ~0ull << (n - row0);
-						d -= __popcll(VP[q] & pad);
-						d += __popcll(VN[q] & pad);
-					}
-					resultSlot = d;
-				}
+				EdPub nb;
+				nb.score = __shfl(pub.score, (lane + 63) & 63);
+				nb.bits = (uint32_t)__shfl((int)pub.bits, (lane + 63) & 63);
+				if (B < bd.nU && t > w.tEnd) { do { B += 64; w = edWindow<RB, C>(bd, B); fresh = true; } while (B < bd.nU && t > w.tEnd); }
+				if (t < w.tBegin) continue;
+				int32_t d;
+				if (edStep<C, G>(u, fresh, w, src, B, t, nb, ring, ED_RING - 1, pub, d)) resultSlot = d;
 			}
 			__syncthreads();
 			const int32_t d = resultSlot;
@@ -275,26 +205,24 @@ __global__ void __launch_bounds__(64) k_edit_distance(const EdPair* __restrict__
 }
 
 // Several pairs per wave (unit of one block): the corridor of a 10 kb pair is 16-23 units wide, so a wave with one pair keeps a third of its
-// lanes busy and its time is set by the number of steps (columns + units), not by the band. The wave is cut into teams of TEAM lanes - 32: two
-// pairs, bands up to k = 1900; 21: three pairs (one lane idles), bands up to k = 1290, which a 10 kb read's whole-read pair and most chain pairs
-// fit (r4) - and every team sweeps its own pair: lane l of a team owns the units l, l + TEAM, ... (a lane's consecutive units are disjoint in
-// time while k < 65 TEAM - 63), the neighbour shuffle stays inside the team, each team has its own letter ring and result slot, and the teams
+// lanes busy and its time is set by the number of steps (column groups + units), not by the band. The wave is cut into teams of TEAM lanes - 32: two
+// pairs, bands up to k = 1900; 21: three pairs (one lane idles), bands up to k = 1441, which a 10 kb read's whole-read pair and nearly all chain pairs
+// fit - and every team sweeps its own pair: lane l of a team owns the units l, l + TEAM, ... (a lane's consecutive units are disjoint in
+// time while k <= edMaxBand(64, TEAM, C)), the neighbour shuffle stays inside the team, each team has its own letter ring and result slot, and the teams
 // step together (a team that is done, or has a shorter pair, idles). Same arithmetic as k_edit_distance<1>; a pair whose band would outgrow the
 // team answers -2 and is rerun by the host with the wider kernels.
-#define ED_HALF_KMAX 1900u
-#define ED_THIRD_KMAX 1290u
+// (waves per SIMD as before the column groups, 5 and 4: the registers that costs are pair constants, spilled where a unit is entered and where a letter is no ACGT)
 template <uint32_t TEAM, uint32_t RING>
-__global__ void __launch_bounds__(64) k_edit_distance_team(const EdPair* __restrict__ pairs, uint32_t nPairs, const EdRead* __restrict__ reads, const char* __restrict__ bases,
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TEAM >= 32 ? 4 : 5))) k_edit_distance_team(const EdPair* __restrict__ pairs, uint32_t nPairs, const EdRead* __restrict__ reads, const char* __restrict__ bases,
 	const uint64_t* __restrict__ eqMasks, const char* __restrict__ letters, const uint32_t* __restrict__ lettersLen, int64_t* __restrict__ outDistance)
 {
 	GC_RAISE_ED_PRIO();
-	constexpr uint32_t PAIRS = 64u / TEAM, KMAX = TEAM >= 32 ? ED_HALF_KMAX : ED_THIRD_KMAX, AHEAD = RING / 2, PERIOD = RING / 4;
-	static_assert(KMAX < 65 * TEAM - 63, "a lane's consecutive units must stay disjoint in time");
-	__shared__ uint8_t ringAll[(PAIRS + 1) * RING];   // (+ 1: the lanes beyond the last whole team address a ring of their own and never touch it)
+	constexpr uint32_t C = ED_COLS, RB = 64u, PAIRS = 64u / TEAM, KMAX = TEAM >= 32 ? ED_HALF_KMAX : ED_THIRD_KMAX, PERIOD = RING / (2 * C);
+	static_assert(KMAX - 1 <= edMaxBand(RB, TEAM, C), "a lane's consecutive units must stay disjoint in time");
+	__shared__ __attribute__((aligned(8))) uint8_t ringAll[(PAIRS + 1) * RING];   // (+ 1: the lanes beyond the last whole team address a ring of their own and never touch it)
 	__shared__ int32_t resultSlot[PAIRS + 1];
 	const uint32_t lane = threadIdx.x, half = lane / TEAM, l = lane - half * TEAM;
 	uint8_t* ring = ringAll + half * RING;
-	constexpr uint32_t RB = 64u;
 	for (uint32_t base = blockIdx.x * PAIRS; base < nPairs; base += gridDim.x * PAIRS) {
 		const uint32_t pi = base + half;
 		const bool valid = half < PAIRS && pi < nPairs;
@@ -311,112 +239,40 @@ __global__ void __launch_bounds__(64) k_edit_distance_team(const EdPair* __restr
 		bool more = valid;
 		if (valid && m == 0xffffffffu) { answer = -3; more = false; }            // path letters overflowed their slot
 		else if (valid && (n == 0 || m == 0)) { answer = (int64_t)(n + m); more = false; }
-		const char* path = letters + pair.lettersOff;
-		const uint64_t* masks = eqMasks + rd.eqOff;
-		const uint32_t nU = (n + RB - 1) / RB;
+		const EdSource src { eqMasks + rd.eqOff, rd.words, letters + pair.lettersOff, bases + rd.readOff, n, m };
 		const uint32_t diff = n > m ? n - m : m - n;
 		const uint32_t cap = n > m ? n : m;
 		uint32_t k = pair.k > diff ? pair.k : diff;
 		if (k < 1) k = 1;
 		if (k > cap) k = cap;
-		if (more && !(nU + AHEAD <= RING)) more = false;                       // the ring must still hold column t - (nU - 1) when it is refilled up to t + AHEAD (-2: the wider kernels take it)
 		while (__any(more)) {
-			if (more && k >= KMAX && nU > TEAM) more = false;                    // -2
+			EdBand bd = edBand<RB>(n, m, k);
+			if (more && !(edLanesHold(k, KMAX, bd.nU, TEAM) && edRingHolds<RB, C>(bd, RING, PERIOD))) more = false;   // -2: the wider kernels take it
+			if (!more) bd.nU = 0;                                                 // (no unit, no window, no step)
 			// ---- one banded pass of every half that still has one to do
-			uint64_t VP = ~0ull, VN = 0, eqA = 0, eqC = 0, eqG = 0, eqT = 0;
+			EdUnit<1> u;
 			uint32_t B = l;
-			int32_t score = 0;
 			bool fresh = true;
-			uint32_t pack = 0, loadedEnd = 0;
-			uint32_t tBegin = 0xffffffffu, tEnd = 0xffffffffu, tHinEnd = 0, finalStep = 0xffffffffu;
-			const uint32_t lastUnit = n ? (n - 1) / RB : 0;
-			const uint32_t slack = more ? (k - diff) / 2 : 0;
-			const uint64_t reachRight = (uint64_t)(n > m ? n - m : 0) + slack;
-			const uint64_t reachLeft = (uint64_t)(m > n ? m - n : 0) + slack;
-			auto enterUnit = [&](uint32_t b) {
-				B = b;
-				fresh = true;
-				if (!more || b >= nU) { tBegin = 0xffffffffu; tEnd = 0xffffffffu; return; }
-				const uint64_t rowBase = (uint64_t)RB * b;
-				const uint64_t c0 = rowBase > reachRight ? rowBase - reachRight : 0;
-				const uint64_t c1 = rowBase + RB - 1 + reachLeft;
-				const uint64_t lastCol = c1 < m - 1 ? c1 : m - 1;
-				tBegin = c0 > lastCol ? 0xffffffffu : (uint32_t)(c0 + b);
-				tEnd = (uint32_t)(lastCol + b);
-				tHinEnd = b > 0 ? (uint32_t)(rowBase - 1 + reachLeft + b) : 0;
-				finalStep = b == lastUnit ? m - 1 + b : 0xffffffffu;
-			};
-			enterUnit(l);
+			EdPub pub { 0, 0 };
+			uint32_t loadedEnd = 0;
+			EdWindow w = edWindow<RB, C>(bd, B);
 			if (l == 0 && half < PAIRS) resultSlot[half] = -1;
-			const uint32_t steps = more ? m + nU - 1 : 0;
+			const uint32_t steps = more ? (m - 1) / C + bd.nU : 0;
 			uint32_t allSteps = steps;
 			for (int d = 32; d >= 1; d >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)allSteps, d); allSteps = other > allSteps ? other : allSteps; }
 			const int neighbour = (int)(half * TEAM + (l + TEAM - 1) % TEAM);
 			for (uint32_t t = 0; t < allSteps; t++) {
 				if ((t & (PERIOD - 1)) == 0) {
-					if (more) {
-						const uint32_t end = t + AHEAD < m ? t + AHEAD : m;
-						for (uint32_t c = loadedEnd + l; c < end; c += TEAM) {
-							const uint8_t ch = (uint8_t)path[c];
-							ring[c & (RING - 1)] = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
-						}
-						loadedEnd = end > loadedEnd ? end : loadedEnd;
-					}
+					if (more) refillRing<RB, C>(ring, RING - 1, bd, src.path, t + PERIOD, loadedEnd, l, TEAM);
 					__syncthreads();
 				}
-				const uint32_t nbPack = (uint32_t)__shfl((int)pack, neighbour);
-				if (B < nU && t > tEnd) { do enterUnit(B + TEAM); while (B < nU && t > tEnd); }
-				if (t < tBegin || t >= steps) continue;
-				const uint32_t j = t - B;
-				if (fresh) {
-					fresh = false;
-					const uint32_t w = B;
-					const bool in = w < rd.words;
-					VP = ~0ull; VN = 0;
-					eqA = in ? masks[w] : 0ull;
-					eqC = in ? masks[rd.words + w] : 0ull;
-					eqG = in ? masks[2ull * rd.words + w] : 0ull;
-					eqT = in ? masks[3ull * rd.words + w] : 0ull;
-					if (j == 0) score = (int32_t)(RB * (B + 1));
-					else score = (int32_t)(nbPack >> 2) - ((int32_t)(nbPack & 3u) - 1) + (int32_t)RB;
-				}
-				const uint32_t code = ring[j & (RING - 1)];
-				int hin = 1;
-				if (B > 0 && t <= tHinEnd) hin = (int)(nbPack & 3u) - 1;
-				uint64_t hinP = hin > 0 ? 1 : 0, hinN = hin < 0 ? 1 : 0;
-				uint64_t Eq;
-				if (code < 4) {
-					const uint64_t lo = (code & 1) ? eqC : eqA, hi = (code & 1) ? eqT : eqG;
-					Eq = (code & 2) ? hi : lo;
-				} else {
-					Eq = 0;
-					const uint8_t letter = (uint8_t)path[j];
-					const uint64_t row0 = (uint64_t)RB * B;
-					for (uint32_t i = 0; i < 64 && row0 + i < n; i++) if ((uint8_t)bases[rd.readOff + row0 + i] == letter) Eq |= 1ull << i;
-				}
-				const uint64_t Xv = Eq | VN;
-				Eq |= hinN;
-				const uint64_t Xh = (((Eq & VP) + VP) ^ VP) | Eq;
-				uint64_t Ph = VN | ~(Xh | VP);
-				uint64_t Mh = VP & Xh;
-				const uint64_t outP = Ph >> 63, outN = Mh >> 63;
-				Ph = (Ph << 1) | hinP;
-				Mh = (Mh << 1) | hinN;
-				VP = Mh | ~(Xv | Ph);
-				VN = Ph & Xv;
-				const int hout = (int)outP - (int)outN;
-				score += hout;
-				pack = ((uint32_t)score << 2) | (uint32_t)(hout + 1);
-				if (t == finalStep) {
-					int32_t d = score;
-					const uint64_t row0 = (uint64_t)RB * B;
-					uint64_t pad = 0;
-					if (row0 >= n) pad = ~0ull;
-					else if (row0 + 64 > n) pad = ~0ull << (n - row0);
-					d -= __popcll(VP & pad);
-					d += __popcll(VN & pad);
-					resultSlot[half] = d;
-				}
+				EdPub nb;
+				nb.score = __shfl(pub.score, neighbour);
+				nb.bits = (uint32_t)__shfl((int)pub.bits, neighbour);
+				if (B < bd.nU && t > w.tEnd) { do { B += TEAM; w = edWindow<RB, C>(bd, B); fresh = true; } while (B < bd.nU && t > w.tEnd); }
+				if (t < w.tBegin) continue;
+				int32_t d;
+				if (edStep<C, 1>(u, fresh, w, src, B, t, nb, ring, RING - 1, pub, d)) resultSlot[half] = d;
 			}
 			__syncthreads();
 			const int32_t d = resultSlot[half];
@@ -431,17 +287,21 @@ __global__ void __launch_bounds__(64) k_edit_distance_team(const EdPair* __restr
 	}
 }
 
-// The whole matrix by one WORKGROUP (r4): thread B owns the 64 rows of block B for every column, the threads sweep the matrix as one skewed wavefront (block B is on column t - B at
-// step t) and hand the horizontal delta of their bottom row to the next thread through LDS, one barrier per step. For the pairs whose band would cover most of the matrix anyway - a
+// The whole matrix by one WORKGROUP (r4): thread B owns the 64 rows of block B for every column group, the threads sweep the matrix as one skewed wavefront (block B is on group t - B
+// at step t) and hand the group's horizontal deltas of their bottom row to the next thread through LDS, one barrier per step. For the pairs whose band would cover most of the matrix anyway - a
 // chain whose path spells a fraction of its read (distance >= the length difference), a whole-read alignment of a sliver of its read: the banded kernels give such a pair ONE wave
 // with up to sixteen blocks per lane and step (config 5: a 50 000 x 1 000 pair held its stream for 385 ms; cfg2: ~800 pairs per batch in k_edit_distance<4>, 11.8 ms alone). Here a
-// pair takes columns + blocks steps of one block each: ~1 ms for the former, and every pair of the latter kind gets its own three waves. No band, no retry: the result is exact.
+// pair takes column groups + blocks steps of one block each, and every pair of the latter kind gets its own waves. No band, no retry: the result is exact.
 #define ED_BLOCK_THREADS 1024u
+#define ED_BLOCK_RING 16384u
 __global__ void __launch_bounds__(ED_BLOCK_THREADS) k_edit_distance_block(const EdPair* __restrict__ pairs, uint32_t nPairs, const EdRead* __restrict__ reads, const char* __restrict__ bases,
 	const uint64_t* __restrict__ eqMasks, const char* __restrict__ letters, const uint32_t* __restrict__ lettersLen, int64_t* __restrict__ outDistance)
 {
 	GC_RAISE_ED_PRIO();
-	__shared__ int8_t hand[2][ED_BLOCK_THREADS];   // the horizontal delta leaving block B's bottom row at the column it has just computed, double-buffered by step parity
+	constexpr uint32_t C = ED_COLS, PERIOD = ED_BLOCK_RING / (2 * C);
+	static_assert((PERIOD + ED_BLOCK_THREADS - 1) * C <= ED_BLOCK_RING, "the ring holds the group of the last block when it is refilled for the first");
+	__shared__ __attribute__((aligned(8))) uint8_t ring[ED_BLOCK_RING];
+	__shared__ uint32_t hand[2][ED_BLOCK_THREADS];   // the horizontal deltas leaving block B's bottom row in the group it has just computed, double-buffered by step parity
 	__shared__ int32_t resultSlot;
 	const uint32_t B = threadIdx.x;
 	for (uint32_t pi = blockIdx.x; pi < nPairs; pi += gridDim.x) {
@@ -453,53 +313,30 @@ __global__ void __launch_bounds__(ED_BLOCK_THREADS) k_edit_distance_block(const 
 		if (n == 0 || m == 0) { if (B == 0) outDistance[pi] = (int64_t)(n + m); continue; }
 		const uint32_t nU = (n + 63u) / 64u;
 		if (nU > blockDim.x) { if (B == 0) outDistance[pi] = -2; continue; }       // (the host sends only pairs that fit: -2 = the banded kernels take it)
-		const char* path = letters + pair.lettersOff;
-		const uint64_t* masks = eqMasks + rd.eqOff;
-		const bool mine = B < nU;
-		const bool in = mine && B < rd.words;
-		const uint64_t eqA = in ? masks[B] : 0ull, eqC = in ? masks[rd.words + B] : 0ull, eqG = in ? masks[2ull * rd.words + B] : 0ull, eqT = in ? masks[3ull * rd.words + B] : 0ull;
-		uint64_t VP = ~0ull, VN = 0;
-		int32_t score = (int32_t)(64u * (B + 1));                                  // the bottom row of the block in the column before the first: D[i][-1] = i + 1
-		const uint32_t lastUnit = (n - 1) / 64u;
-		const uint32_t steps = m + nU - 1;
+		const EdSource src { eqMasks + rd.eqOff, rd.words, letters + pair.lettersOff, bases + rd.readOff, n, m };
+		const EdBand bd = edBand<64>(n, m, n > m ? n : m);
+		const EdWindow w = edWindowFull<C>(bd, B);
+		const uint32_t mPad = (m + C - 1) / C * C;
+		EdUnit<1> u;
+		edEnter<1>(u, src, B < nU ? B : 0);
+		u.score = (int32_t)(64u * (B + 1));                                        // every block starts on column 0: D[i][-1] = i + 1
+		bool fresh = false;
+		EdPub pub { 0, 0 };
+		uint32_t loadedEnd = 0;
+		const uint32_t steps = (m - 1) / C + nU;
 		if (B == 0) resultSlot = -1;
-		__syncthreads();
-		uint8_t chNext = mine && B == 0 ? (uint8_t)path[0] : 0;                      // the letter of the NEXT step is fetched a step ahead: its latency hides behind this step's work and barrier
 		for (uint32_t t = 0; t < steps; t++) {
-			const uint32_t j = t - B;
-			const uint8_t ch = chNext;
-			if (mine && t + 1 >= B && j + 1 < m) chNext = (uint8_t)path[j + 1];
-			if (mine && t >= B && j < m) {
-				const int hin = B > 0 ? (int)hand[(t + 1) & 1][B - 1] : 1;              // (the row above the matrix climbs by one per column)
-				uint64_t Eq;
-				if (ch == 'A') Eq = eqA; else if (ch == 'C') Eq = eqC; else if (ch == 'G') Eq = eqG; else if (ch == 'T') Eq = eqT;
-				else {
-					Eq = 0;
-					const uint64_t row0 = 64ull * B;
-					for (uint32_t i = 0; i < 64 && row0 + i < n; i++) if ((uint8_t)bases[rd.readOff + row0 + i] == ch) Eq |= 1ull << i;
-				}
-				const uint64_t hinP = hin > 0 ? 1 : 0, hinN = hin < 0 ? 1 : 0;
-				const uint64_t Xv = Eq | VN;
-				Eq |= hinN;
-				const uint64_t Xh = (((Eq & VP) + VP) ^ VP) | Eq;
-				uint64_t Ph = VN | ~(Xh | VP);
-				uint64_t Mh = VP & Xh;
-				const int hout = (int)(Ph >> 63) - (int)(Mh >> 63);
-				Ph = (Ph << 1) | hinP;
-				Mh = (Mh << 1) | hinN;
-				VP = Mh | ~(Xv | Ph);
-				VN = Ph & Xv;
-				score += hout;
-				hand[t & 1][B] = (int8_t)hout;
-				if (B == lastUnit && j == m - 1) {
-					int32_t d = score;
-					const uint64_t row0 = 64ull * B;
-					uint64_t pad = 0;
-					if (row0 + 64 > n) pad = ~0ull << (n - row0);                        // rows of the block beyond the read: step back up to row n - 1
-					d -= __popcll(VP & pad);
-					d += __popcll(VN & pad);
-					resultSlot = d;
-				}
+			if ((t & (PERIOD - 1)) == 0) {           // (the barrier that ended the step before keeps these writes behind its reads)
+				const uint64_t want = (uint64_t)(t + PERIOD) * C;
+				const uint32_t end = want < mPad ? (uint32_t)want : mPad;
+				if (end > loadedEnd) { edRingFill(ring, ED_BLOCK_RING - 1, src.path, m, loadedEnd, end, B, blockDim.x); loadedEnd = end; }
+				__syncthreads();
+			}
+			if (t >= w.tBegin && t <= w.tEnd) {
+				EdPub nb { 0, B > 0 ? hand[(t + 1) & 1][B - 1] : 0u };   // (every block starts on group 0: the neighbour's score is never asked for)
+				int32_t d;
+				if (edStep<C, 1>(u, fresh, w, src, B, t, nb, ring, ED_BLOCK_RING - 1, pub, d)) resultSlot = d;
+				hand[t & 1][B] = pub.bits;
 			}
 			__syncthreads();
 		}
