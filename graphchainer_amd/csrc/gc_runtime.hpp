@@ -1093,7 +1093,7 @@ inline void finishEditDistances(EditDistanceRun& run, hipStream_t stream, EdPair
 		todo.swap(next);
 		todo.insert(todo.end(), later.begin(), later.end());
 	}
-	// still -2: the band is too wide for the NW kernel (a read longer than 65536 bases more than 32256 edits away from its path); the caller flags the read
+	// still -2: the band is too wide for the NW kernel (a read longer than 65536 bases 64000 or more edits away from its path: k_edit_distance<16> ends on the widest band its lanes hold); the caller flags the read
 	// back to the caller's order
 	run.grouped.assign(hOut, hOut + nPairs);
 	for (uint32_t i = 0; i < nPairs; i++) hOut[run.perm[i]] = run.grouped[i];

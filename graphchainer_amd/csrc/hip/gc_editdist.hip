@@ -198,7 +198,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G >= 8 
 			__syncthreads();
 			if (d >= 0 && (uint32_t)d <= k) { answer = d; break; }
 			if (k >= cap) { answer = d; break; }    // the band already covers the whole matrix
+			const uint32_t failedK = k;
 			k = k * 2 < cap ? k * 2 : cap;
+			// no kernel is wider than the unit of 16 words: before it gives a pair up, it tries the widest band its lanes hold (a read of 65 700 bases 32 020 edits from its
+			// path, first band 32 000: twice that is beyond the lanes, 63 999 is not)
+			if (G == 16 && failedK < K_MAX - 1 && !edLanesHold(k, K_MAX, bd.nU, 64)) k = K_MAX - 1;
 		}
 		if (lane == 0) outDistance[pi] = answer;
 	}

@@ -16,10 +16,13 @@
 //     alone) is taken whenever it is tight, else LEFT (EDLIB_EDOP_DELETE, a target letter alone), else the diagonal
 //     (match when the scores are equal, mismatch otherwise).
 // edlib computes its columns inside an Ukkonen band of half-width `bestScore`; the cells a tight move or an optimal split
-// can touch lie on optimal paths, where band values are exact, so the result does not depend on the band's bookkeeping: the
+// can touch lie on optimal paths, where band values are exact, so the result does not depend on how wide the band is: the
 // restatement uses a plain |row - column| <= bestScore band for the Hirschberg columns (as edlib's CPU cost is what the CPU
-// baseline times) and whole columns for the small traced-back leaves. edlibAlign itself returns no alignment when either string
-// is empty (:133-152).
+// baseline times) and whole columns for the small traced-back leaves. It does depend on the band's bookkeeping in one place:
+// every row of the band at a half's LAST column must be read out, its top row included. With nearly identical strings
+// (bestScore of a few units, so a band a few blocks wide) the optimal split sits on that row; a band narrowed once more after
+// the last column loses it, no split is found and the pair gets no alignment where edlib gives one (lastColumn below;
+// tests/edit_path_cases.py holds such pairs). edlibAlign itself returns no alignment when either string is empty (:133-152).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -91,8 +94,10 @@ inline std::vector<int32_t> lastColumn(const unsigned char* query, size_t Q, con
 			score[last] = score[last - 1] - hout + 64 + newHout;
 			hout = newHout;
 		}
+		// the band's top moves down for the NEXT column; after the last one it stays, or the read-out below would drop the block with the band's
+		// top row of this column - the row an optimal split sits on when the strings are nearly identical
 		const long long lowRow = (long long)j + 1 - band;
-		if (lowRow > 0) first = std::max(first, (size_t)std::min<long long>((long long)last, lowRow / 64));
+		if (lowRow > 0 && j + 1 < T) first = std::max(first, (size_t)std::min<long long>((long long)last, lowRow / 64));
 	}
 	for (size_t b = first; b <= last; b++) {
 		int32_t v = score[b];

@@ -1,6 +1,7 @@
 // The unit step of the edit-distance kernels (csrc/hip/gc_editdist_core.hpp) on the host: the core driven unit by unit (every unit a lane of its own), as the lanes of a
 // team of 21 and of 32 (a lane moves through the units l, l + TEAM, ...), and over the whole matrix as the workgroup kernel drives it, each with the letter ring the kernels
-// keep and its refill rule, against a plain DP held here. A sweep is ONE banded pass, as the kernels run it before they double k.
+// keep and its refill rule, against a plain DP held here. A sweep is ONE banded pass, as the kernels run it before they double k. The units of 2, 8 and 16 words run with
+// the columns per step that k_edit_distance<G> gives them (edColsOfUnit) as well, on one lane per unit and on two or three lanes.
 #include "gc_editdist_core.hpp"
 
 #include <algorithm>
@@ -166,6 +167,16 @@ static void checkPair(const std::string& read, const std::string& path, uint32_t
 	if (wide) {
 		verdict(sweep<C, 2>(read, path, kAsked, 0, 0, 8192, BANDED), "units of two words");
 		verdict(sweep<C, 4>(read, path, kAsked, 3, edMaxBand(256, 3, C) + 1, 8192, BANDED), "units of four words, three lanes");
+		// the wide units with the columns per step k_edit_distance<G> gives them (edColsOfUnit), a lane moving through several units
+		if constexpr (C == edColsOfUnit(2)) verdict(sweep<C, 2>(read, path, kAsked, 3, edMaxBand(128, 3, C) + 1, 8192, BANDED), "units of two words at their own columns, three lanes");
+		if constexpr (C == edColsOfUnit(8)) {
+			verdict(sweep<C, 8>(read, path, kAsked, 0, 0, 8192, BANDED), "units of eight words");
+			verdict(sweep<C, 8>(read, path, kAsked, 2, edMaxBand(512, 2, C) + 1, 8192, BANDED), "units of eight words, two lanes");
+		}
+		if constexpr (C == edColsOfUnit(16)) {
+			verdict(sweep<C, 16>(read, path, kAsked, 0, 0, 8192, BANDED), "units of sixteen words");
+			verdict(sweep<C, 16>(read, path, kAsked, 2, edMaxBand(1024, 2, C) + 1, 8192, BANDED), "units of sixteen words, two lanes");
+		}
 	}
 }
 
@@ -251,13 +262,40 @@ static void checkRings(uint64_t seed)
 	}
 }
 
+// Pairs whose optimal path runs along the corridor's edge: X + S against S + Y with |X| = |Y| = s (the path leaves the main diagonal at once, follows the diagonal s away from
+// it and comes back in the last s columns: both edges of the corridor at k = d) and X + S against S (the overhang: one edge), with k one below, at and one above the
+// distance, both orders. A mutated pair stays near the main diagonal, where a corridor one diagonal too narrow costs nothing.
+struct EdgePair { std::string a, b; uint32_t d; };
+static std::vector<EdgePair> edgePairs(uint64_t seed)
+{
+	Rng r(seed + 77);
+	std::vector<EdgePair> out;
+	for (uint32_t len : { 200u, 700u, 2049u, 5000u }) for (uint32_t s : { 1u, 31u, 64u, 65u, 300u }) {
+		const std::string S = randomSeq(r, len, false), X = randomSeq(r, s, false), Y = randomSeq(r, s, false);
+		out.push_back({ X + S, S + Y, 0 });
+		out.push_back({ X + S, S, 0 });
+	}
+	for (EdgePair& p : out) p.d = plainDistance(p.a, p.b);
+	return out;
+}
+template <uint32_t C>
+static void checkEdges(const std::vector<EdgePair>& pairs)
+{
+	for (const EdgePair& p : pairs) for (uint32_t k : { p.d - 1, p.d, p.d + 1 }) {
+		checkPair<C>(p.a, p.b, p.d, k, true);
+		checkPair<C>(p.b, p.a, p.d, k, true);
+	}
+}
+
 int main(int argc, char** argv)
 {
 	const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
 	static_assert(edMaxBand(64, 21, 1) == 1301 && edMaxBand(64, 21, 8) == 1441 && edMaxBand(64, 32, 8) == 2233, "the band a team holds");
 	checkColumns<1>(seed); checkColumns<2>(seed); checkColumns<4>(seed); checkColumns<8>(seed);
 	checkLimits<1>(seed); checkLimits<4>(seed); checkLimits<8>(seed);
-	checkRings<4>(seed); checkRings<8>(seed);
+	checkRings<1>(seed); checkRings<4>(seed); checkRings<8>(seed);
+	const std::vector<EdgePair> edges = edgePairs(seed);
+	checkEdges<1>(edges); checkEdges<2>(edges); checkEdges<4>(edges); checkEdges<8>(edges);
 	if (failures) { printf("FAILED: %ld checks of %ld sweeps\n", failures, sweeps); return 1; }
 	printf("OK %ld sweeps\n", sweeps);
 	return 0;

@@ -1,7 +1,8 @@
 """The edit-distance kernels step through the matrix a group of C columns at a time (csrc/hip/gc_editdist_core.hpp): gca.edit_distance against the oracle's plain DP, both
 orders, at the smallest shapes where the groups can go wrong - one past each letter ring, the lengths from which a lane takes a second unit, either side of the bands at which
 a pair changes kernel, the workgroup kernel with a ragged last group, and matrices smaller than a group or a word. tests/test_edit_distance_host.py drives the same core
-on the host; this file is about the kernels around it (rings in LDS, the shuffle between lanes, the hand-over through LDS, the rerun path)."""
+on the host; this file is about the kernels around it (rings in LDS, the shuffle between lanes, the hand-over through LDS, the rerun path). It stays with the team kernels,
+k_edit_distance<1> and the workgroup kernel; the units of 2 to 16 words are launched by tests/test_edit_distance_wide_units_gpu.py."""
 import ctypes as C
 import os
 import random

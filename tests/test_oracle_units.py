@@ -304,6 +304,31 @@ def test_edit_path_matches_edlib_op_for_op():
     assert n > 200 and hirschberg >= 15
 
 
+def test_edit_path_edges_match_edlib_op_for_op():
+    """oracle/edlib_path.hpp against the real edlib on tests/edit_path_cases.py: nearly identical strings above the 1 MB limit (the optimal split on the edge of a band a few
+    blocks wide - where the restatement once narrowed the band after the last column and answered "no alignment"), either side of the limit, tall thin leaves, column counts at
+    1 023 .. 8 194 and letters outside ACGT. Same distance, same op count, same ops; and every pair, none of which has an empty side, gets an alignment."""
+    from edit_path_cases import assert_is_alignment, edit_path_cases, is_split
+    from oracle.binding import oracle_edit_path
+    cases = edit_path_cases()
+    want = reference("edit_path_edges")
+    assert len(want) == len(cases)
+    blocks = {}
+    wrong = []
+    for (name, q, t), w in zip(cases, want):
+        got_d, got_ops = oracle_edit_path(q, t)
+        want_d, want_len = (int(x) for x in w[:16].view(np.int64))
+        if got_d != want_d or len(got_ops) != want_len or not np.array_equal(edit_path_record(got_d, got_ops), w):
+            wrong.append((name, len(q), len(t), got_d, want_d, len(got_ops), want_len))
+            continue
+        assert_is_alignment(q, t, want_d, got_ops, name)
+        blocks.setdefault(name.split("/")[0], []).append(is_split(q, t))
+    assert not wrong, f"{len(wrong)} of {len(cases)} (name, Q, T, distance, edlib's, ops, edlib's): {wrong[:12]}"
+    assert {b: len(v) for b, v in blocks.items()} == {"near": 96, "limit": 8, "strips": 3, "rings": 14, "letters": 4}
+    assert all(blocks["near"]) and blocks["strips"] == [False, False, True] and all(blocks["rings"]) and all(blocks["letters"])   # (10 000 x 500: halves of 250 columns)
+    assert blocks["limit"] == [False, True] * 4
+
+
 def evalue_cases():
     rng = random.Random(7)
     cases = []
@@ -333,4 +358,10 @@ RECORDED = {
     "edit_distance": lambda ref: np.array([ref.lib.ref_edit_distance(a, len(a), b, len(b)) for a, b in edit_distance_cases()], dtype=np.int64),
     "edit_path": lambda ref: np.array([edit_path_record(*ref.edit_path(q, t)) for q, t in _path_cases(random.Random(2024))]),
     "evalue": lambda ref: np.array([ref.evalue(*c) for c in evalue_cases()]).view(np.uint64),
+    "edit_path_edges": lambda ref: _edit_path_edges(ref),
 }
+
+
+def _edit_path_edges(ref):
+    from edit_path_cases import edit_path_cases
+    return np.array([edit_path_record(*ref.edit_path(q, t)) for _, q, t in edit_path_cases()])
