@@ -55,8 +55,54 @@ struct DGraph {
 	// seed clustering (orderSeedsByChaining, src/GraphAligner.h:245-262): chain of every split node and its approximate position on it
 	const uint32_t* chainNumber;      // [n]
 	const uint64_t* chainApproxPos;   // [n]
-	const NodeRec* nodeRec;           // [n] (r6) the per-node record of the fragment extension kernel
+	const NodeRec* nodeRec;           // [n] (r6) the per-node record of the fragment and whole-read extension kernels
 };
+
+// A read of graph data that no kernel ever writes, through the constant address space: where the address is wave-uniform (the one-extension-per-wave kernel) the
+// device compiles it to a scalar-cache load, which waits neither for a vector load nor for the wave's own stores; where it is per lane, to the vector load it was.
+// What makes this right: the graph arrays and the node records are written only before any aligning kernel is launched (uploadGraph, which ends with a device
+// synchronise after k_build_node_rec), and the scalar cache is invalidated at every kernel start. Nothing that a kernel writes may ever be read through gcK.
+template <typename T> __device__ __forceinline__ T gcK(const T* p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	return *(const __attribute__((address_space(4))) T*)(unsigned long long)p;
+#else
+	return *p;
+#endif
+}
+// the whole record of a node, one 32-byte read (the records are 32-byte aligned: hipMalloc'ed, 32 bytes each)
+__device__ __forceinline__ NodeRec gcNodeRec(const DGraph& g, uint32_t node)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	typedef uint32_t Words8 __attribute__((ext_vector_type(8)));
+	static_assert(sizeof(NodeRec) == sizeof(Words8), "NodeRec is eight words");
+	const Words8 w = gcK((const Words8*)(g.nodeRec + node));
+	NodeRec r;
+	r.comp = w[0]; r.outOff = w[1]; r.inOff = w[2]; r.meta = w[3];
+	r.w0 = (uint64_t)w[4] | ((uint64_t)w[5] << 32); r.w1 = (uint64_t)w[6] | ((uint64_t)w[7] << 32);
+	return r;
+#else
+	return g.nodeRec[node];
+#endif
+}
+__device__ __forceinline__ uint32_t recLength(const NodeRec& r) { return r.meta & 127u; }   // 1..64
+__device__ __forceinline__ uint32_t recRank(const NodeRec& r) { return r.comp; }
+__device__ __forceinline__ uint32_t gcNodeLength(const DGraph& g, uint32_t node) { return gcK(&g.nodeRec[node].meta) & 127u; }   // where only the length of a node is asked
+// The CSR ranges: begin from the record, end = begin + degree unless the 8-bit degree field is saturated (255: or more) - then from the CSR array's next entry.
+// (there is no record n, so the end never comes from nodeRec[node + 1])
+struct EdgeRange { uint32_t begin, end; };
+__device__ __forceinline__ EdgeRange recOutRange(const DGraph& g, uint32_t node, const NodeRec& r)
+{
+	const uint32_t deg = (r.meta >> 8) & 255u;
+	return EdgeRange { r.outOff, deg < 255u ? r.outOff + deg : gcK(g.outOff + node + 1) };
+}
+__device__ __forceinline__ EdgeRange recInRange(const DGraph& g, uint32_t node, const NodeRec& r)
+{
+	const uint32_t deg = (r.meta >> 16) & 255u;
+	return EdgeRange { r.inOff, deg < 255u ? r.inOff + deg : gcK(g.inOff + node + 1) };
+}
+__device__ __forceinline__ uint32_t gcOutAdj(const DGraph& g, uint32_t e) { return gcK(g.outAdj + e); }
+__device__ __forceinline__ uint32_t gcInAdj(const DGraph& g, uint32_t e) { return gcK(g.inAdj + e); }
 
 struct WS {   // one DP column over 64 read rows (reference: src/WordSlice.h:150-166)
 	uint64_t VP, VN;
@@ -332,6 +378,21 @@ __device__ __forceinline__ NodeSeq loadNodeSeq(const DGraph& g, uint32_t node)
 	} else {
 		const uint64_t* p = g.ambSeq + 4 * (size_t)(node - g.firstAmbiguous);
 		s.w0 = p[0]; s.w1 = p[1]; s.w2 = p[2]; s.w3 = p[3];
+		s.ambiguous = true;
+	}
+	return s;
+}
+// the same from the node's record (gcNodeRec): the two code words lie in it unless the node is ambiguous; then the four one-hot words come from ambSeq through gcK
+__device__ __forceinline__ NodeSeq recNodeSeq(const DGraph& g, uint32_t node, const NodeRec& r)
+{
+	NodeSeq s;
+	if (!(r.meta & NODEREC_SLOW)) {
+		s.w0 = r.w0; s.w1 = r.w1;
+		s.w2 = s.w3 = 0;
+		s.ambiguous = false;
+	} else {
+		const uint64_t* p = g.ambSeq + 4 * (size_t)(node - g.firstAmbiguous);
+		s.w0 = gcK(p); s.w1 = gcK(p + 1); s.w2 = gcK(p + 2); s.w3 = gcK(p + 3);
 		s.ambiguous = true;
 	}
 	return s;

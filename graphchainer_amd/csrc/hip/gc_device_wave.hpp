@@ -14,6 +14,8 @@
 // in HBM, interleaved across the lanes of the team at 8-byte granularity (word w of lane l at base[w*lanes + l]).
 // A slice that needs more nodes than the tables hold ends the extension with EXT_LDS_CAP (see k_long_extend's retry and
 // the plain-layout fallback k_long_pass).
+// The graph is read through the per-node record and the constant address space (gc_device.hpp: gcNodeRec, gcK and the accessors beside them): scalar-cache loads in the
+// one-extension-per-wave kernel, which wait for no vector load and no store of the wave. What the extension itself wrote - items, slices, columns, trace - is read with plain loads.
 #pragma once
 #include "gc_device.hpp"
 #include "gc_column_asm.hpp"
@@ -391,12 +393,12 @@ __device__ __forceinline__ int32_t clipMaxXScoreWave(const WS& w, double errorCo
 }
 // CLIP: *maxX receives the maximum X score of the entry column (before the merges, ...Common.h:973) and of every later column (:1148-1151); the column loop is the C++ form.
 template <int MODE, bool CLIP = false, typename LANE_TABLES>
-__device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t node, WS ws, bool prevExists, int32_t prevStartScore, uint64_t prevHP, uint64_t prevHN,
+__device__ __forceinline__ TileResult computeTileW(const DGraph& g, uint32_t node, const NodeRec& rec, WS ws, bool prevExists, int32_t prevStartScore, uint64_t prevHP, uint64_t prevHN,
 	const Eq4& eq, NodeItem& out, const LANE_TABLES& tables, int flatRows, uint32_t& status, TilePreamble* preambleOnly = nullptr, double errorCost = 0, int32_t* maxX = nullptr)
 {
 	constexpr bool COLUMNS = MODE == 1;
-	int nodeLength = g.nodeLength[node];
-	NodeSeq seq = loadNodeSeq(g, node);
+	int nodeLength = (int)recLength(rec);   // rec: the node's record, read by the caller (gcNodeRec)
+	NodeSeq seq = recNodeSeq(g, node, rec);
 	TileResult r;
 	r.minScore = ws.score;   // (sic) before the merge with the row above, ...Common.h:968 vs :1052-1058
 	r.minOffset = 0;
@@ -544,7 +546,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 	int buf = 0;   // table buffer `buf` = previous slice (LDS tables swap roles every slice; register tables rotate instead and stay 0/1)
 	uint32_t nPrev = 1;
 	{
-		int nl = g.nodeLength[startNode];
+		int nl = (int)gcNodeLength(g, startNode);
 		NodeItem it;
 		it.node = startNode;
 		it.sVP = it.sVN = it.eVP = it.eVN = 0;
@@ -593,6 +595,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		auto prevFind = [&](uint32_t node) __attribute__((always_inline)) -> int { return L.find((uint32_t)(REGCOLS ? 0 : buf), nPrev, node); };
 		uint32_t nPending = 0;
 		auto pushEdge = [&](uint32_t target, WS incoming, bool skipFirst) __attribute__((always_inline)) {
+			const NodeRec trec = gcNodeRec(g, target);   // the target's first letter and its rank: one read
 			int found = L.find(2u, nPending, target);
 			uint32_t slot = found >= 0 ? (uint32_t)found : nPending;
 			WS add = incoming;
@@ -607,7 +610,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 					else if (prevStart > before) { hinP = 1; hinN = 0; }
 					else { hinP = 0; hinN = 0; }
 				} else { hinP = 1; hinN = 0; }
-				NodeSeq nseq = loadNodeSeq(g, target);
+				NodeSeq nseq = recNodeSeq(g, target, trec);
 				uint64_t hp, hn;
 #if defined(__HIP_DEVICE_COMPILE__)
 				uint64_t eqFirst;
@@ -626,7 +629,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			}
 			if (slot == nPending) {
 				if (nPending >= L.maxEntries()) { status = EXT_LDS_CAP; return; }
-				L.qSet(slot, target, g.componentNumber[target], add);
+				L.qSet(slot, target, recRank(trec), add);
 				nPending++;
 			} else {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -661,11 +664,12 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			typename LaneLdsT<REGCOLS>::Entry pe { 0, 0, 0, ~0ull, 0ull };
 			if (prevExists) pe = L.get((uint32_t)buf, (uint32_t)pi);
 			GC_MARK(1);   // pop + previous-slice lookup
-			const uint32_t tileLength = g.nodeLength[pnode];
+			const NodeRec prec = gcNodeRec(g, pnode);   // the popped node's record, once per tile: length, letters, out-edge range
+			const uint32_t tileLength = recLength(prec);
 			if (storeCols && nCols + tileLength - 1 > wsx.maxCols) return EXT_OVERFLOW;
 			int32_t tileMaxX = INT32_MIN;
-			TileResult tr = storeCols ? computeTileW<2, CLIP>(g, pnode, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status, nullptr, errorCost, CLIP ? &tileMaxX : nullptr)
-				: computeTileW<0, CLIP>(g, pnode, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status, nullptr, errorCost, CLIP ? &tileMaxX : nullptr);
+			TileResult tr = storeCols ? computeTileW<2, CLIP>(g, pnode, prec, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status, nullptr, errorCost, CLIP ? &tileMaxX : nullptr)
+				: computeTileW<0, CLIP>(g, pnode, prec, pws, prevExists, (int32_t)pe.w1, pe.a, pe.b, eq, out, L, flatRows, status, nullptr, errorCost, CLIP ? &tileMaxX : nullptr);
 			GC_MARK(2);   // tile columns
 			if (status != EXT_OK) return status;
 			if (CLIP && tileMaxX > sliceMaxX) { sliceMaxX = tileMaxX; sliceMaxXNode = pnode; }
@@ -688,8 +692,8 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			nItems++;
 			cur.count++;
 			cnt.dpTiles++;
-			cnt.columnSteps += g.nodeLength[pnode];
-			if (flatRows > 0) { cnt.recomputeTiles++; cnt.columnSteps += g.nodeLength[pnode]; }
+			cnt.columnSteps += tileLength;
+			if (flatRows > 0) { cnt.recomputeTiles++; cnt.columnSteps += tileLength; }
 			if (tr.minScore > previousQuitScore + bandwidth + 128) return EXT_ASSERT;
 			currentMin = tr.minScore < currentMin ? tr.minScore : currentMin;
 			if (tr.minScore < cur.minScore) { cur.minScore = tr.minScore; cur.minNode = pnode; cur.minOffset = tr.minOffset; }
@@ -722,8 +726,9 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			if (newEndMin < prevMinScore) return EXT_ASSERT;
 			if (newEndMin <= currentMin + bandwidth) {
 				GC_MARK(3);   // item store + bookkeeping
-				for (uint32_t e = g.outOff[pnode]; e < g.outOff[pnode + 1]; e++) {
-					pushEdge(g.outAdj[e], newEnd, false);
+				const EdgeRange outs = recOutRange(g, pnode, prec);
+				for (uint32_t e = outs.begin; e < outs.end; e++) {
+					pushEdge(gcOutAdj(g, e), newEnd, false);
 					if (status != EXT_OK) return status;
 				}
 				GC_MARK(4);   // out-edge pushes
@@ -870,7 +875,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		if (scratch.eVP != it.eVP || scratch.eVN != it.eVN || scratch.eScore != it.eScore) status = EXT_ASSERT;   // sliceConsistency, :848-850
 		if (status != EXT_OK) return status;
 		cnt.recomputeTiles++;
-		cnt.columnSteps += g.nodeLength[bestNode];
+		cnt.columnSteps += gcNodeLength(g, bestNode);
 		if (!find.found) return EXT_ASSERT;   // :377-379
 		here = Cell { bestNode, find.column, bs.j + find.row };
 		score = find.value;   // startScore = getValue(bvOffset), :380
@@ -917,40 +922,42 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		int32_t quitScore = cs.minScore + cs.bandwidth;
 		int32_t previousQuitScore = ps.minScore + ps.bandwidth;
 		int32_t scoreHere = wsValue(itemStart(curIt), 0);
-		uint32_t inBegin = g.inOff[curNode], inEnd = g.inOff[curNode + 1];
+		const NodeRec crec = gcNodeRec(g, curNode);
+		const EdgeRange ins = recInRange(g, curNode, crec);
+		const uint32_t inBegin = ins.begin, inEnd = ins.end;
 		if (scoreHere > quitScore) {
 			int32_t smallest = scoreHere + 1;
 			out = Cell { 0, 0, 0 };
 			nodeSwitch = false;
 			if (prevItExists) { smallest = prevIt.sScore; out = Cell { curNode, 0, j - 1 }; }
 			for (uint32_t e = inBegin; e < inEnd; e++) {
-				uint32_t nb = g.inAdj[e];
+				uint32_t nb = gcInAdj(g, e);
 				int p = findPrev(nb);
-				if (p >= 0) { NodeItem pn = loadItem(wsx, (uint32_t)p); if (pn.eScore <= smallest) { smallest = pn.eScore; out = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, j - 1 }; nodeSwitch = true; } }
+				if (p >= 0) { NodeItem pn = loadItem(wsx, (uint32_t)p); if (pn.eScore <= smallest) { smallest = pn.eScore; out = Cell { nb, gcNodeLength(g, nb) - 1, j - 1 }; nodeSwitch = true; } }
 				int c = findCur(nb);
 				if (c >= 0 && nb != curNode) {
 					int32_t v = wsValue(itemEnd(loadItem(wsx, (uint32_t)c)), 0);
-					if (v < smallest) { smallest = v; out = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, j }; nodeSwitch = true; }
+					if (v < smallest) { smallest = v; out = Cell { nb, gcNodeLength(g, nb) - 1, j }; nodeSwitch = true; }
 				}
 			}
 			return true;
 		}
-		NodeSeq nseq = loadNodeSeq(g, curNode);
+		NodeSeq nseq = recNodeSeq(g, curNode, crec);
 		int eqBit = (int)(eqOfColumn(eq, nseq, 0) & 1);
 		if (prevItExists && prevIt.sScore == scoreHere - 1) { out = Cell { curNode, 0, j - 1 }; nodeSwitch = false; return true; }
 		Cell bestInvalid { 0xffffffffu, 0xffffffffu, -1 };
 		int32_t bestInvalidScore = scoreHere + 1;
 		for (uint32_t e = inBegin; e < inEnd; e++) {
-			uint32_t nb = g.inAdj[e];
+			uint32_t nb = gcInAdj(g, e);
 			int c = findCur(nb);
-			if (c >= 0 && wsValue(itemEnd(loadItem(wsx, (uint32_t)c)), 0) == scoreHere - 1) { out = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, j }; nodeSwitch = true; return true; }
+			if (c >= 0 && wsValue(itemEnd(loadItem(wsx, (uint32_t)c)), 0) == scoreHere - 1) { out = Cell { nb, gcNodeLength(g, nb) - 1, j }; nodeSwitch = true; return true; }
 			int p = findPrev(nb);
 			if (p >= 0) {
 				int32_t cornerScore = loadItem(wsx, (uint32_t)p).eScore;
 				if (cornerScore > previousQuitScore) {
-					if (cornerScore < bestInvalidScore) { bestInvalidScore = cornerScore; bestInvalid = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, j - 1 }; }
+					if (cornerScore < bestInvalidScore) { bestInvalidScore = cornerScore; bestInvalid = Cell { nb, gcNodeLength(g, nb) - 1, j - 1 }; }
 				} else if (cornerScore == scoreHere - (eqBit ? 0 : 1)) {
-					out = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, j - 1 }; nodeSwitch = true; return true;
+					out = Cell { nb, gcNodeLength(g, nb) - 1, j - 1 }; nodeSwitch = true; return true;
 				}
 			}
 		}
@@ -974,6 +981,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			if (prevItExists) prevIt = loadItem(wsx, (uint32_t)pi);
 			GC_MARK(7);   // backtrace: item lookups + loads
 			NodeItem scratchItem;
+			const NodeRec curRec = gcNodeRec(g, curNode);
 #if defined(__HIP_DEVICE_COMPILE__)
 			if (storeCols) {
 				// The DP kept this tile's columns: load them back (column c into lane c; column 0 is the item's start column), rebuild the column
@@ -981,9 +989,9 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				// the tile's column loop is not run a second time (45 % of the kernel's column steps were these recomputes). The preamble (merge with
 				// the row above, first-row repair) is redone because the masks need its carries.
 				TilePreamble pre;
-				computeTileW<1>(g, curNode, itemStart(curIt), prevItExists, prevItExists ? prevIt.sScore : 0, prevItExists ? prevIt.HP : ~0ull, prevItExists ? prevIt.HN : 0ull,
+				computeTileW<1>(g, curNode, curRec, itemStart(curIt), prevItExists, prevItExists ? prevIt.sScore : 0, prevItExists ? prevIt.HP : ~0ull, prevItExists ? prevIt.HN : 0ull,
 					eq, scratchItem, L, 0, status, &pre);
-				const uint32_t tileLength = g.nodeLength[curNode];
+				const uint32_t tileLength = recLength(curRec);
 				const uint32_t c = threadIdx.x;
 				unsigned long long vp = curIt.sVP, vn = curIt.sVN;
 				if (c >= 1 && c < tileLength) {
@@ -993,17 +1001,17 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				L.cr[0] = (uint32_t)vp; L.cr[1] = (uint32_t)(vp >> 32); L.cr[2] = (uint32_t)vn; L.cr[3] = (uint32_t)(vn >> 32);
 				const uint64_t upToC = (c >= 63 ? ~0ull : ((2ull << c) - 1)) & ~1ull;   // bits 1..c
 				L.cr[4] = (uint32_t)(curIt.sScore + popc64(curIt.HP & upToC) - popc64(curIt.HN & upToC));
-				const NodeSeq seq = loadNodeSeq(g, curNode);
+				const NodeSeq seq = recNodeSeq(g, curNode, curRec);
 				L.walkMasks = false;
 				if (!seq.ambiguous) L.setWalkMasks(seq.w0, seq.w1, eq, pre.forceEq, pre.prevHN);
 			} else
 #endif
 			{
-				computeTileW<1>(g, curNode, itemStart(curIt), prevItExists, prevItExists ? prevIt.sScore : 0, prevItExists ? prevIt.HP : ~0ull, prevItExists ? prevIt.HN : 0ull,
+				computeTileW<1>(g, curNode, curRec, itemStart(curIt), prevItExists, prevItExists ? prevIt.sScore : 0, prevItExists ? prevIt.HP : ~0ull, prevItExists ? prevIt.HN : 0ull,
 					eq, scratchItem, L, 0, status);
 				if (scratchItem.eVP != curIt.eVP || scratchItem.eVN != curIt.eVN || scratchItem.eScore != curIt.eScore) status = EXT_ASSERT;
 			}
-			cnt.recomputeTiles++; cnt.backtraceTiles++; cnt.columnSteps += g.nodeLength[curNode];   // (the reference's units: it does recompute)
+			cnt.recomputeTiles++; cnt.backtraceTiles++; cnt.columnSteps += recLength(curRec);   // (the reference's units: it does recompute)
 			if (status != EXT_OK) return status;
 			GC_MARK(8);   // backtrace: column recompute
 		}
@@ -1044,7 +1052,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			if (scoreHere > quitScore || scoreDiagonal > previousQuitScore || scoreUp > previousQuitScore) {
 				nxt = scoreDiagonal < scoreUp ? Cell { curNode, off - 1, here.seqPos - 1 } : Cell { curNode, off, here.seqPos - 1 };
 			} else {
-				NodeSeq nseq = loadNodeSeq(g, curNode);
+				NodeSeq nseq = recNodeSeq(g, curNode, gcNodeRec(g, curNode));
 				int eqBit = (int)(eqOfColumn(eq, nseq, (int)off) & 1);
 				if (scoreUp == scoreHere - 1) nxt = Cell { curNode, off, here.seqPos - 1 };
 				else if (scoreDiagonal == scoreHere - (eqBit ? 0 : 1)) nxt = Cell { curNode, off - 1, here.seqPos - 1 };
@@ -1070,7 +1078,9 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 				here = nxt;
 				continue;
 			}
-			NodeSeq nseq = loadNodeSeq(g, curNode);
+			const NodeRec crec = gcNodeRec(g, curNode);
+			const EdgeRange ins = recInRange(g, curNode, crec);
+			NodeSeq nseq = recNodeSeq(g, curNode, crec);
 			int eqBit = (int)((eqOfColumn(eq, nseq, 0) >> offset) & 1);
 			int32_t scoreHere = wsValue(start, offset);
 			int32_t quitScore = cs.minScore + cs.bandwidth;
@@ -1079,23 +1089,23 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			if (scoreHere > quitScore) {
 				int32_t smallest = wsValue(start, offset - 1);
 				nxt = Cell { curNode, 0, sp - 1 };
-				for (uint32_t e = g.inOff[curNode]; e < g.inOff[curNode + 1]; e++) {
-					uint32_t nb = g.inAdj[e];
+				for (uint32_t e = ins.begin; e < ins.end; e++) {
+					uint32_t nb = gcInAdj(g, e);
 					int c = findCur(nb);
 					if (c < 0) continue;
 					WS ne = itemEnd(loadItem(wsx, (uint32_t)c));
-					if (wsValue(ne, offset - 1) <= smallest) { smallest = wsValue(ne, offset - 1); nxt = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, sp - 1 }; sw = true; }
-					if (wsValue(ne, offset) < smallest && nb != curNode) { smallest = wsValue(ne, offset); nxt = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, sp }; sw = true; }
+					if (wsValue(ne, offset - 1) <= smallest) { smallest = wsValue(ne, offset - 1); nxt = Cell { nb, gcNodeLength(g, nb) - 1, sp - 1 }; sw = true; }
+					if (wsValue(ne, offset) < smallest && nb != curNode) { smallest = wsValue(ne, offset); nxt = Cell { nb, gcNodeLength(g, nb) - 1, sp }; sw = true; }
 				}
 				found = true;
 			} else {
-				for (uint32_t e = g.inOff[curNode]; e < g.inOff[curNode + 1] && !found; e++) {
-					uint32_t nb = g.inAdj[e];
+				for (uint32_t e = ins.begin; e < ins.end && !found; e++) {
+					uint32_t nb = gcInAdj(g, e);
 					int c = findCur(nb);
 					if (c < 0) continue;
 					WS ne = itemEnd(loadItem(wsx, (uint32_t)c));
-					if (wsValue(ne, offset) == scoreHere - 1) { nxt = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, sp }; sw = true; found = true; }
-					else if (wsValue(ne, offset - 1) == scoreHere - (eqBit ? 0 : 1)) { nxt = Cell { nb, (uint32_t)g.nodeLength[nb] - 1, sp - 1 }; sw = true; found = true; }
+					if (wsValue(ne, offset) == scoreHere - 1) { nxt = Cell { nb, gcNodeLength(g, nb) - 1, sp }; sw = true; found = true; }
+					else if (wsValue(ne, offset - 1) == scoreHere - (eqBit ? 0 : 1)) { nxt = Cell { nb, gcNodeLength(g, nb) - 1, sp - 1 }; sw = true; found = true; }
 				}
 			}
 			if (!found) return EXT_ASSERT;
@@ -1164,7 +1174,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 			// scalar instructions per cell. Same comparisons on the same values as the loop below (src/GraphAlignerBitvectorCommon.h:555-708).
 			uint32_t hori = here.offset;
 			int vert = row;
-			const NodeSeq nseq = loadNodeSeq(g, curNode);
+			const NodeSeq nseq = recNodeSeq(g, curNode, gcNodeRec(g, curNode));
 			const uint32_t laneRow = threadIdx.x;
 			const uint64_t above = ~1ull << laneRow;   // rows below this lane's row in the word (bits > r)
 			auto rowValues = [&](const WS& c) __attribute__((always_inline)) -> int32_t { return c.score - popc64(c.VP & above) + popc64(c.VN & above); };
@@ -1198,7 +1208,7 @@ __device__ __forceinline__ uint32_t extendSeedWave(const DGraph& g, const Correc
 		{
 			uint32_t hori = here.offset;
 			int vert = row;
-			NodeSeq nseq = loadNodeSeq(g, curNode);
+			NodeSeq nseq = recNodeSeq(g, curNode, gcNodeRec(g, curNode));
 			// Values are tracked incrementally: a step up changes a column's value by its vertical delta bit, so the two
 			// columns are re-read (and one value recomputed from popcounts) only when the walk moves one column left.
 			WS ch = L.col(hori), cl = L.col(hori - 1);
