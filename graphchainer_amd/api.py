@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "gc_seeds_upload", "gc_seeds_destroy", "gc_seeds_hits", "gc_seeds_kernel_ms", "gc_mxm_index_create", "gc_mxm_options_default", "gc_mxm_index_open", "gc_mxm_cache_check", "gc_mxm_index_destroy", "gc_mxm_index_array", "gc_seeds_mxm", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
+    "gc_reads_parse", "gc_fastx_table_free",
 ]
 
 
@@ -443,6 +444,37 @@ class ReadBatch:
         self.handle = C.c_void_p()
         _check(self.lib.gc_reads_upload(blob, self.offsets.ctypes.data, len(bs), C.byref(self.handle)))
 
+    @classmethod
+    def from_text(cls, data, fmt, final=True):
+        """FASTA / FASTQ text parsed on the device (gc_reads_parse): -> (batch, ids, consumed). fmt: "fasta" / "fastq" (or GC_FASTX_*). The batch is what ReadBatch(list of
+        the reads) is - blob, offsets, lengths and the same device object - and ids are the header lines behind their first byte, as bytes. final=False: data is a chunk
+        from the middle of a file; only records whose end it holds are returned and `consumed` is where the next chunk must begin (0: bring more)."""
+        lib = load_library()
+        code = FASTX_FORMATS.get(fmt, fmt)
+        if not isinstance(code, int):
+            raise ValueError("fmt is 'fasta' or 'fastq'")
+        data = bytes(data) if not isinstance(data, bytes) else data
+        lib.gc_reads_parse.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_uint32, _P(C.c_void_p), _P(_P(GcFastxTable))]
+        lib.gc_fastx_table_free.argtypes = [_P(GcFastxTable)]
+        lib.gc_fastx_table_free.restype = None
+        handle, table = C.c_void_p(), _P(GcFastxTable)()
+        _check(lib.gc_reads_parse(data, len(data), code, FASTX_FINAL if final else 0, C.byref(handle), C.byref(table)))
+        try:
+            t = table.contents
+            n = int(t.n_reads)
+            self = cls.__new__(cls)
+            self.lib, self.handle = lib, handle
+            self.offsets = np.ctypeslib.as_array(t.offsets, shape=(n + 1,)).copy()
+            self.lengths = np.diff(self.offsets)
+            self.blob = C.string_at(t.bases, int(self.offsets[n]))
+            name_off = np.ctypeslib.as_array(t.name_off, shape=(n + 1,))
+            names = C.string_at(t.names, int(name_off[n]))
+            ids = [names[int(name_off[i]):int(name_off[i + 1]) - 1] for i in range(n)]
+            self.kernel_ms = float(t.kernel_ms)
+            return self, ids, int(t.consumed)
+        finally:
+            lib.gc_fastx_table_free(table)
+
     def close(self):
         if self.handle:
             self.lib.gc_reads_destroy(self.handle)
@@ -453,6 +485,88 @@ class ReadBatch:
             self.close()
         except Exception:
             pass
+
+
+FASTX_FASTA, FASTX_FASTQ, FASTX_FINAL = 1, 2, 1   # GC_FASTX_FASTA / GC_FASTX_FASTQ / GC_FASTX_FINAL
+FASTX_FORMATS = {"fasta": FASTX_FASTA, "fastq": FASTX_FASTQ}
+
+
+class GcFastxTable(C.Structure):
+    """gc_fastx_table (include/graphchainer_amd.h): what gc_reads_parse hands back in host memory."""
+    _fields_ = [("n_reads", C.c_uint64), ("consumed", C.c_uint64), ("offsets", _P(C.c_uint64)), ("bases", _P(C.c_char)), ("name_off", _P(C.c_uint64)), ("names", _P(C.c_char)),
+                ("kernel_ms", C.c_double)]
+
+
+def fastx_file_format(path):
+    """FastQ::streamFastqFromFile's choice by file name (src/fastqloader.h:98-139): ("fasta" | "fastq" | None, gzipped). None: the reference reads nothing from such a
+    file and reports nothing."""
+    name = os.fsdecode(path)
+    gz = len(name) > 3 and name.endswith(".gz")
+    if gz:
+        name = name[:-3]
+    fastq = (len(name) > 6 and name.endswith(".fastq")) or (len(name) > 3 and name.endswith(".fq"))
+    fasta = (len(name) > 6 and name.endswith(".fasta")) or (len(name) > 3 and name.endswith(".fa"))
+    return ("fasta" if fasta else "fastq" if fastq else None), gz
+
+
+def _file_chunks(path, gz, size):
+    """The file's bytes in pieces of about `size`; a .gz is inflated piece by piece, concatenated members included (as zstr does)."""
+    with open(path, "rb") as f:
+        if not gz:
+            while True:
+                piece = f.read(size)
+                if not piece:
+                    return
+                yield piece
+        import zlib
+        inflate = zlib.decompressobj(47)   # gzip or zlib header, by itself
+        raw, started = b"", False   # started: inside a member
+        while True:
+            if not raw:
+                raw = f.read(max(size // 4, 1 << 16))
+                if not raw:
+                    if started:
+                        raise EOFError(f"{os.fsdecode(path)}: the file ends inside a gzip member")
+                    return
+            started = True
+            piece = inflate.decompress(raw, size)
+            raw = inflate.unconsumed_tail
+            if inflate.eof:               # the member ended: another may follow
+                raw = inflate.unused_data
+                inflate = zlib.decompressobj(47)
+                started = False
+            if piece:
+                yield piece
+
+
+def read_files(paths, batch_bytes=100 << 20):
+    """Generator of (batch, ids) over read files, the reference's way (src/Aligner.cpp:167-187): the format by the file name (fastx_file_format; a file of another name
+    gives nothing), .gz inflated on the host with zlib, about batch_bytes of file text per batch. A record cut by the end of a chunk is carried over to the next one, a
+    record longer than the chunk makes the chunk grow; files are never joined - the end of each file is parsed as the end of a file."""
+    batch_bytes = max(int(batch_bytes), 1)
+    for path in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths):
+        fmt, gz = fastx_file_format(path)
+        if fmt is None:
+            continue
+        held = b""
+        pieces = _file_chunks(path, gz, batch_bytes)
+        nxt = next(pieces, None)
+        while nxt is not None:
+            held += nxt
+            nxt = next(pieces, None)
+            if nxt is None:
+                break                      # `held` runs to the end of the file
+            batch, ids, consumed = ReadBatch.from_text(held, fmt, final=False)
+            held = held[consumed:]
+            if ids:
+                yield batch, ids
+            else:
+                batch.close()              # no complete record yet: the chunk grows
+        batch, ids, _ = ReadBatch.from_text(held, fmt, final=True)
+        if ids:
+            yield batch, ids
+        else:
+            batch.close()
 
 
 # gc_seed_hit (include/graphchainer_amd.h): SeedHit as a seeder hands it over, src/GraphAlignerWrapper.h:14

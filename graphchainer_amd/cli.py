@@ -1,0 +1,451 @@
+"""The command line: `python -m graphchainer_amd -g graph.gfa -f reads.fq.gz -a out.gaf`, the reference's GraphChainer binary over this library.
+
+resolve(argv) -> Config turns a command line into what a run needs - the reference's option names, short forms, defaults, checks and messages
+(src/AlignerMain.cpp:35-112,138-464) - and touches neither the library nor a device. main(argv) runs it: one stream, one batch of file text at a time
+(api.read_files: the reads are parsed on the device; the alignments are encoded on the device for the writers chosen), records written in input order, every output
+file through a temporary name and a rename.
+
+Accepted and without effect: -t / --threads (checked >= 1), --high-memory, --verbose, --short-verbose (the progress text and the closing statistics are not
+reproduced), and --greedy-E / --greedy-score, which the reference declares and never reads. --try-all-seeds (and --all-alignments, which sets it) does what it does
+in the reference: it overrides --seeds-extend-density to -1 with a warning (src/AlignerMain.cpp:449-453); the whole-read call itself never tries all seeds
+(src/Aligner.cpp:565, with and without chaining). Refused with one line and exit status 1, before anything is loaded: the options in REFUSED and a .vg graph.
+"""
+import math
+import os
+import re
+import sys
+import time
+from dataclasses import dataclass, field
+
+VERSION = "graphchainer_amd 1.0"
+UNLIMITED = (1 << 64) - 1          # what the reference's size_t options hold after "-1"
+
+# name -> (short form, value type or None for a switch, takes several values)
+OPTIONS = {
+    "graph": ("g", "string", False), "reads": ("f", "string", True), "alignments-out": ("a", "string", False),
+    "sampling-step": (None, "long", False), "colinear-split-len": (None, "long", False), "colinear-split-gap": (None, "long", False), "colinear-gap": (None, "long", False),
+    "fast-mode": (None, None, False),
+    "help": ("h", None, False), "version": (None, None, False), "threads": ("t", "size", False), "verbose": (None, None, False), "short-verbose": (None, None, False),
+    "E-cutoff": (None, "double", False), "all-alignments": (None, None, False), "extra-heuristic": (None, None, False), "try-all-seeds": (None, None, False),
+    "global-alignment": (None, None, False), "optimal-alignment": (None, None, False), "X-drop": (None, "int", False), "precise-clipping": (None, "double", False),
+    "cigar-match-mismatch": (None, None, False), "generate-path": (None, None, False), "generate-path-seed": (None, "long", False), "graph-statistics": (None, None, False),
+    "seeds-clustersize": (None, "size", False), "seeds-extend-density": (None, "double", False), "seeds-minimizer-length": (None, "size", False),
+    "seeds-minimizer-windowsize": (None, "size", False), "seeds-minimizer-density": (None, "double", False), "seeds-minimizer-ignore-frequent": (None, "double", False),
+    "seeds-mum-count": (None, "size", False), "seeds-mem-count": (None, "size", False), "seeds-mxm-length": (None, "size", False), "seeds-mxm-cache-prefix": (None, "string", False),
+    "seeds-file": ("s", "string", True), "seedless-DP": (None, None, False), "DP-restart-stride": (None, "size", False),
+    "bandwidth": ("b", "size", False), "ramp-bandwidth": ("B", "size", False), "tangle-effort": ("C", "size", False), "high-memory": (None, None, False),
+    "schedule-inverse-E-sum": (None, None, False), "schedule-inverse-E-product": (None, None, False), "schedule-score": (None, None, False), "schedule-length": (None, None, False),
+    "greedy-length": (None, None, False), "greedy-E": (None, None, False), "greedy-score": (None, None, False), "no-colinear-chaining": (None, None, False),
+    # this build's own
+    "batch-bytes": (None, "size", False), "device": (None, "size", False), "index-cache": (None, "string", False),
+}
+REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "seeds-file", "generate-path", "generate-path-seed", "graph-statistics")
+SELECT = {"greedy-length": 0, "schedule-inverse-E-sum": 3, "schedule-inverse-E-product": 4, "schedule-score": 5, "schedule-length": 6, "all-alignments": 7}   # GC_SELECT_*
+
+HELP = """Mandatory parameters:
+  -g [ --graph ] arg                    input graph (.gfa)
+  -f [ --reads ] arg                    input reads (fasta or fastq, uncompressed or gzipped)
+  -a [ --alignments-out ] arg           output alignment file (.gaf/.gam/.json), may be given several times
+
+Colinear chaining parameters:
+  --sampling-step arg                   Sampling step factor, an integer (default 1); sets --colinear-split-gap = ceil(arg * --colinear-split-len)
+  --colinear-split-len arg              length of the fragments the read is split into [default 35]
+  --colinear-split-gap arg              distance between consecutive fragments [default 35]
+  --colinear-gap arg                    split the chain's path where consecutive anchors are further apart [default 10000]
+  --fast-mode                           skip the edit distance computation after chaining (output the path instead of an alignment)
+  --no-colinear-chaining                align as GraphAligner does, without chaining
+  --greedy-length, --schedule-inverse-E-sum, --schedule-inverse-E-product, --schedule-score, --schedule-length
+                                        how --no-colinear-chaining selects the alignments it writes (one at most)
+
+General parameters:
+  -h [ --help ]                         help message
+  --version                             print version
+  --E-cutoff arg                        discard alignments with E-value > arg
+  --all-alignments                      return all alignments (the chaining default)
+  --extra-heuristic                     use heuristics to discard more seed hits
+  --try-all-seeds                       overrides --seeds-extend-density to -1 (the chaining default)
+  --global-alignment                    force the read to be aligned end-to-end even if the alignment score is poor
+  --X-drop arg                          X-drop heuristic to end alignment with score cutoff arg (int)
+  --precise-clipping arg                clip the alignment ends with arg as the identity cutoff (float)
+  --cigar-match-mismatch                M for matches and mismatches in the cigar string instead of = and X
+
+Seeding parameters:
+  --seeds-clustersize arg               discard seed clusters with fewer than arg seeds
+  --seeds-extend-density arg            extend up to approximately the best (arg * sequence length) seeds (-1 for all)
+  --seeds-minimizer-length arg          k-mer length for minimizer seeding [15]
+  --seeds-minimizer-windowsize arg      window size for minimizer seeding [20]
+  --seeds-minimizer-density arg         keep approximately (arg * sequence length) least common minimizers (-1 for all) [10]
+  --seeds-minimizer-ignore-frequent arg ignore arg most frequent fraction of minimizers [0.001]
+  --seeds-mum-count arg                 arg longest maximal unique matches fully contained in a node (-1 for all)
+  --seeds-mem-count arg                 arg longest maximal exact matches fully contained in a node (-1 for all)
+  --seeds-mxm-length arg                minimum length for maximal unique / exact matches [20]
+  --seeds-mxm-cache-prefix arg          store the mum/mem seeding index on disk for reuse, or reuse it if it exists
+
+Extension parameters:
+  -b [ --bandwidth ] arg                alignment bandwidth [10]
+  -B [ --ramp-bandwidth ] arg           ramp bandwidth
+  -C [ --tangle-effort ] arg            tangle effort limit (-1 for unlimited)
+
+This build's own:
+  --batch-bytes arg                     bytes of read file text per batch [100 MB]
+  --device arg                          GPU to run on [0]
+  --index-cache arg                     load the graph and minimizer index from this file if it exists, else build them and save them there.
+                                        An existing file wins: it is checked for the minimizer length and window only, not against -g or
+                                        --seeds-minimizer-ignore-frequent
+
+Accepted and without effect: -t [ --threads ] arg (must be >= 1), --high-memory, --verbose, --short-verbose, --greedy-E, --greedy-score.
+Not supported by this build: --optimal-alignment, --seedless-DP, --DP-restart-stride, -s [ --seeds-file ], --generate-path, --generate-path-seed,
+--graph-statistics, a .vg graph.
+"""
+
+
+class CliExit(Exception):
+    """The command line ends here: status and what goes to stderr (and to stdout for --version)."""
+
+    def __init__(self, status, stderr="", stdout=""):
+        super().__init__(stderr)
+        self.status, self.stderr, self.stdout = status, stderr, stdout
+
+
+@dataclass
+class Config:
+    graph: str = ""
+    reads: list = field(default_factory=list)
+    outputs: dict = field(default_factory=dict)          # "gaf" / "json" / "gam" -> path (the last one given of each kind, as the reference keeps it)
+    aligner: dict = field(default_factory=dict)          # keyword arguments of api.Aligner
+    min_cluster_size: int = 1                            # gc_params::min_cluster_size
+    seeder: dict = field(default_factory=dict)           # {"kind": "minimizer", "length", "window", "keep_fraction"} or {"kind": "mxm", "mode", "count", "min_len", "cache_prefix"}
+    cigar_match_mismatch: bool = False
+    threads: int = 1
+    batch_bytes: int = 100 << 20
+    device: int = 0
+    index_cache: str = ""
+    warnings: list = field(default_factory=list)         # what the reference prints and goes on
+
+
+def _convert(name, kind, text):
+    bad = CliExit(1, f"the argument ('{text}') for option '--{name}' is invalid\nrun with option -h for help\n")
+    if kind == "string":
+        return text
+    if kind in ("long", "int", "size"):
+        if not re.fullmatch(r"[+-]?[0-9]+", text):
+            raise bad
+        value = int(text)
+        if kind == "size":                     # the reference's size_t: a minus sign wraps, as its lexical_cast does
+            if abs(value) > UNLIMITED:
+                raise bad
+            return value % (1 << 64)
+        limit = 1 << (63 if kind == "long" else 31)
+        if not -limit <= value < limit:
+            raise bad
+        return value
+    if not re.fullmatch(r"[+-]?(([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)?|inf(inity)?|nan)", text, flags=re.I):
+        raise bad
+    return float(text)
+
+
+def parse(argv):
+    """boost::program_options as the reference sets it up: --name arg, --name=arg, -n arg, -narg, unambiguous prefixes of long names; -f and -s take every token up to
+    the next option. -> {name: [values]} (a switch: [])."""
+    shorts = {short: name for name, (short, _, _) in OPTIONS.items() if short}
+
+    def fail(text):
+        raise CliExit(1, text + "\nrun with option -h for help\n")
+
+    seen, i = {}, 0
+    while i < len(argv):
+        token = argv[i]
+        i += 1
+        attached = None
+        if token.startswith("--") and len(token) > 2:
+            key, eq, value = token[2:].partition("=")
+            if key not in OPTIONS:
+                guesses = [n for n in OPTIONS if n.startswith(key)]
+                if len(guesses) > 1:
+                    fail(f"option '--{key}' is ambiguous and matches " + ", ".join(f"'--{g}'" for g in sorted(guesses)))
+                if not guesses:
+                    fail(f"unrecognised option '--{key}'")
+                key = guesses[0]
+            name, shown = key, "--" + key
+            if eq:
+                attached = value
+        elif token.startswith("-") and len(token) > 1 and token != "--":
+            if token[1] not in shorts:
+                fail(f"unrecognised option '{token}'")
+            name, shown = shorts[token[1]], "--" + shorts[token[1]]
+            if len(token) > 2:
+                attached = token[2:]
+        else:
+            fail("too many positional options have been specified on the command line")
+        _, kind, several = OPTIONS[name]
+        if kind is None:
+            if attached is not None:
+                fail(f"option '{shown}' does not take any arguments")
+            seen.setdefault(name, [])
+            continue
+        values = []
+        if attached is not None:
+            values.append(attached)
+        elif i < len(argv):
+            values.append(argv[i])
+            i += 1
+        else:
+            fail(f"the required argument for option '{shown}' is missing")
+        if several:
+            while i < len(argv) and not (argv[i].startswith("-") and len(argv[i]) > 1):
+                values.append(argv[i])
+                i += 1
+        if name in seen and not several and name != "alignments-out":
+            fail(f"option '{shown}' cannot be specified more than once")
+        seen.setdefault(name, []).extend(_convert(name, kind, v) for v in values)
+    return seen
+
+
+def resolve(argv):
+    """Command line -> Config, or CliExit. Neither the library nor a device is touched."""
+    vm = parse(list(argv))
+    if "help" in vm:
+        raise CliExit(0, HELP)
+    if "version" in vm:
+        raise CliExit(0, "", "Version " + VERSION + "\n")
+    for name in REFUSED:
+        if name in vm:
+            raise CliExit(1, f"--{name} is not supported by this build\nrun with option -h for help\n")
+    last = lambda name, default: vm[name][-1] if name in vm else default   # noqa: E731
+    graph = last("graph", "")
+    if len(graph) >= 3 and graph.endswith(".vg"):
+        raise CliExit(1, f"a .vg graph ({graph}) is not supported by this build: give a .gfa\nrun with option -h for help\n")
+    chaining = "no-colinear-chaining" not in vm
+
+    cfg = Config()
+    errors, messages = [], []          # messages: warnings and errors in the order of the reference's checks, as it prints them
+
+    def warning(text):
+        cfg.warnings.append(text)
+        messages.append(text)
+
+    def error(text):
+        errors.append(text)
+        messages.append(text)
+
+    # GraphAligner's vg presets (:186-193), then the chaining defaults (:201-209)
+    minimizer_density, minimizer_length, minimizer_window, extend_density, discard_fraction, bandwidth = 10.0, 15, 20, -1.0, 0.001, 10
+    selection, try_all = (SELECT["all-alignments"], True) if chaining else (SELECT["greedy-length"], False)
+    colinear_gap, split_len, split_gap, sampling_step = 10000, 35, 35, 1
+
+    cfg.graph, cfg.reads = graph, list(vm.get("reads", []))
+    outputs = list(vm.get("alignments-out", []))
+    cfg.threads = last("threads", 1)
+    bandwidth = last("bandwidth", bandwidth)
+    extend_density = last("seeds-extend-density", extend_density)
+    discard_fraction = last("seeds-minimizer-ignore-frequent", discard_fraction)
+    cfg.min_cluster_size = last("seeds-clustersize", 1)
+    minimizer_density = last("seeds-minimizer-density", minimizer_density)
+    minimizer_length = last("seeds-minimizer-length", minimizer_length)
+    minimizer_window = last("seeds-minimizer-windowsize", minimizer_window)
+    mxm_length, mem_count, mum_count = last("seeds-mxm-length", 20), last("seeds-mem-count", 0), last("seeds-mum-count", 0)
+    cache_prefix = last("seeds-mxm-cache-prefix", "")
+    colinear_gap, split_len, split_gap = last("colinear-gap", colinear_gap), last("colinear-split-len", split_len), last("colinear-split-gap", split_gap)
+    sampling_step = last("sampling-step", sampling_step)
+    if sampling_step != 1:
+        if "colinear-split-gap" in vm:
+            warning("WARNING: --sampling-step and --colinear-split-gap are both set! --colinear-split-gap will be ignored, and set to (--sampling-step * --colinear-split-len)")
+        split_gap = math.ceil(sampling_step * split_len)
+    ramp, max_cells = last("ramp-bandwidth", 0), last("tangle-effort", UNLIMITED)
+    if "try-all-seeds" in vm:
+        try_all = True
+    cfg.cigar_match_mismatch = "cigar-match-mismatch" in vm
+    methods = 0
+    for name in ("all-alignments", "greedy-length", "schedule-inverse-E-sum", "schedule-inverse-E-product", "schedule-score", "schedule-length"):
+        if name in vm:
+            selection = SELECT[name]
+            methods += 1
+            if name == "all-alignments":
+                try_all = True
+    e_cutoff = last("E-cutoff", -1.0)
+    precise, cutoff = False, 0.5
+    if "precise-clipping" in vm:
+        precise, cutoff = True, vm["precise-clipping"][-1]
+        if cutoff < 0.001 or cutoff > 0.999 or cutoff != cutoff:
+            error("precise clipping identity cutoff must be between 0.001 and 0.999")
+        if 0.001 <= cutoff < 0.501:
+            warning("Warning: precise clipping identity cutoff set below 0.501. Output will almost certainly contain spurious alignments.")
+    x_drop = 0
+    if "X-drop" in vm:
+        x_drop = vm["X-drop"][-1]
+        if x_drop < 1:
+            error("X-drop score cutoff must be > 1")
+    if cfg.graph == "":
+        error("graph file must be given")
+    if not cfg.reads:
+        error("read file must be given")
+    if not outputs:
+        error("alignments-out must be given")
+    for path in outputs:
+        if len(path) >= 4 and path.endswith(".gam"):
+            cfg.outputs["gam"] = path
+        elif len(path) >= 5 and path.endswith(".json"):
+            cfg.outputs["json"] = path
+        elif len(path) >= 4 and path.endswith(".gaf"):
+            cfg.outputs["gaf"] = path
+        else:
+            error(f"unknown output alignment format ({path}), must be either .gaf, .gam or .json")
+    if cfg.threads < 1:
+        error("number of threads must be >= 1")
+    if bandwidth < 1:
+        error("default bandwidth must be >= 1")
+    if ramp != 0 and ramp <= bandwidth:
+        error("ramp bandwidth must be higher than default bandwidth")
+    if mxm_length < 2:
+        error("mum/mem minimum length must be >= 2")
+    if minimizer_length >= 32:
+        error("Maximum minimizer length is 31")
+    if discard_fraction < 0 or discard_fraction >= 1:
+        error("Minimizer discard fraction must be 0 <= x < 1")
+    if minimizer_density < 0 and minimizer_density != -1:
+        error("Minimizer density can't be negative")
+    if extend_density <= 0 and extend_density != -1:
+        error("Seed extension density can't be negative")
+    picked = (1 if mum_count != 0 else 0) + (1 if mem_count != 0 else 0) + (1 if minimizer_density != 0 else 0)
+    if picked == 0:
+        error("pick a seeding method")
+    if picked > 1:
+        error("pick only one seeding method")
+    if x_drop > 0 and not precise:
+        warning("--X-drop is set but --precise-clipping is not, using default value of --precise-clipping .66")
+        precise, cutoff = True, 0.66
+    if try_all and "seeds-extend-density" in vm and vm["seeds-extend-density"][-1] != -1:
+        warning("WARNING: --try-all-seeds and --seeds-extend-density are both set! --seeds-extend-density will be ignored")
+        extend_density = -1.0
+    if methods > 1:
+        error("pick only one method for selecting outputted alignments")
+    # what the library's fields can hold (the reference's are size_t and long long)
+    for name, value, limit in (("bandwidth", bandwidth, 1 << 31), ("ramp-bandwidth", ramp, 1 << 31), ("colinear-split-len", split_len, 1 << 31), ("colinear-split-gap", split_gap, 1 << 31),
+                               ("seeds-clustersize", cfg.min_cluster_size, 1 << 31), ("seeds-mxm-length", mxm_length, 1 << 32), ("seeds-minimizer-windowsize", minimizer_window, 1 << 31),
+                               ("device", last("device", 0), 1 << 31), ("tangle-effort", 0 if max_cells == UNLIMITED else max_cells, 1 << 63)):
+        if not -limit <= value < limit:
+            error(f"--{name} {value} is beyond what this build can hold")
+    if errors:
+        raise CliExit(1, "".join(line + "\n" for line in messages) + "run with option -h for help\n")
+
+    if minimizer_density != 0:
+        cfg.seeder = {"kind": "minimizer", "length": minimizer_length, "window": minimizer_window, "keep_fraction": 1 - discard_fraction}   # src/Aligner.cpp:1162
+    else:
+        count = mum_count if mum_count != 0 else mem_count
+        cfg.seeder = {"kind": "mxm", "mode": "mum" if mum_count != 0 else "mem", "count": -1 if count == UNLIMITED else count, "min_len": mxm_length, "cache_prefix": cache_prefix}
+    cfg.aligner = dict(
+        bandwidth=bandwidth, ramp_bandwidth=ramp, max_cells_per_slice=-1 if max_cells == UNLIMITED else max_cells,
+        split_len=split_len, split_gap=split_gap, colinear_gap=colinear_gap, seed_density=float(minimizer_density),
+        e_cutoff=float(e_cutoff), force_global="global-alignment" in vm, seed_extend_density=float(extend_density), extra_heuristic="extra-heuristic" in vm,
+        colinear_chaining=chaining, selection_method=selection, fast_mode="fast-mode" in vm,
+        precise_clipping=float(cutoff) if precise else 0.0, x_drop=x_drop)
+    cfg.batch_bytes = max(1, last("batch-bytes", 100 << 20))
+    cfg.device = last("device", 0)
+    cfg.index_cache = last("index-cache", "")
+    return cfg
+
+
+class _Outputs:
+    """Every output file is written under a temporary name beside it and renamed when the run is complete; a run that fails leaves no file."""
+
+    def __init__(self, paths):
+        self.paths, self.files = dict(paths), {}
+
+    def __enter__(self):
+        try:
+            for fmt, path in self.paths.items():
+                self.files[fmt] = open(f"{path}.tmp{os.getpid()}", "wb")
+        except BaseException as e:         # (a later file could not be opened: the earlier ones are closed and removed)
+            self.__exit__(type(e), e, None)
+            raise
+        return self
+
+    def write(self, fmt, data):
+        self.files[fmt].write(data)
+
+    def __exit__(self, kind, value, trace):
+        for fmt, f in self.files.items():
+            f.close()
+            if kind is None:
+                os.replace(f.name, self.paths[fmt])
+            elif os.path.exists(f.name):
+                os.unlink(f.name)
+        return False
+
+
+def run(cfg, stderr=sys.stderr):
+    """Aligns cfg.reads to cfg.graph and writes cfg.outputs. Returns the counts it reports."""
+    import numpy as np
+
+    from . import api
+    api.set_device(cfg.device)
+    seeder = index = None
+    minimizer = cfg.seeder["kind"] == "minimizer"
+    if cfg.index_cache and os.path.exists(cfg.index_cache):
+        info = api.check_index_cache(cfg.index_cache)
+        if minimizer and (not info["has_seeder"] or (info["k"], info["w"]) != (cfg.seeder["length"], cfg.seeder["window"])):
+            raise RuntimeError(f"{cfg.index_cache} holds no minimizer index of length {cfg.seeder['length']} and window {cfg.seeder['window']}")
+        graph, cached = api.load_index_cache(cfg.index_cache)
+        seeder = cached if minimizer else None
+    else:
+        graph = api.AlignmentGraph(cfg.graph)
+        if minimizer:
+            seeder = api.MinimizerSeeder(graph, cfg.seeder["length"], cfg.seeder["window"], cfg.seeder["keep_fraction"])
+        if cfg.index_cache:
+            api.save_index_cache(graph, seeder, cfg.index_cache)
+    if not minimizer:
+        index = api.MxmIndex(graph, cache_prefix=cfg.seeder["cache_prefix"] or None)
+    # what the chosen writers need: the whole-read pass and the two edit distances that pick the winner, and the final alignments encoded on the device, where their traces
+    # are - the GAF pieces (= / X items, or M items with --cigar-match-mismatch) for a .gaf, the vg::Path bytes for a .json or .gam; no trace comes down (keep_traces=0)
+    formats = tuple(f for f in ("gaf", "json", "gam") if f in cfg.outputs)
+    device_output = ((2 if cfg.cigar_match_mismatch else 1) if "gaf" in formats else 0) | (4 if "json" in formats or "gam" in formats else 0)
+    aligner = api.Aligner(graph, seeder, long_pass=True, edit_distances=True, keep_traces=0, device_output=device_output, **cfg.aligner)
+    aligner.params.min_cluster_size = cfg.min_cluster_size
+    counts = {"reads": 0, "flagged": 0, "failed_assertion": 0, "capacity_exceeded": 0, "batches": 0, "seconds": 0.0}   # seconds: reading, aligning and writing, setup left out
+    started = time.time()
+    with _Outputs(cfg.outputs) as outputs:
+        for batch, ids in api.read_files(cfg.reads, cfg.batch_bytes):
+            try:
+                seeds = index.seeds(batch, cfg.seeder["mode"], count=cfg.seeder["count"], min_len=cfg.seeder["min_len"]) if index is not None else None
+                try:
+                    out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
+                finally:
+                    if seeds is not None:
+                        seeds.close()
+                for f in formats:
+                    outputs.write(f, out[f])
+                failed, capacity = np.asarray(out["failed_assertion"]) != 0, np.asarray(out["capacity_exceeded"]) != 0
+                counts["reads"] += len(ids)
+                counts["batches"] += 1
+                counts["failed_assertion"] += int(failed.sum())
+                counts["capacity_exceeded"] += int(capacity.sum())
+                counts["flagged"] += int((failed | capacity).sum())
+                del out
+            finally:
+                batch.close()
+    counts["seconds"] = time.time() - started
+    if counts["flagged"]:
+        print(f"{counts['flagged']} of {counts['reads']} reads were flagged and have no alignment written: {counts['failed_assertion']} failed an assertion "
+              f"(a letter outside the nucleotide alphabet among them), {counts['capacity_exceeded']} exceeded a capacity", file=stderr)
+    return counts
+
+
+def main(argv=None):
+    try:
+        cfg = resolve(sys.argv[1:] if argv is None else argv)
+    except CliExit as e:
+        sys.stdout.write(e.stdout)
+        sys.stderr.write(e.stderr)
+        return e.status
+    for line in cfg.warnings:
+        print(line, file=sys.stderr)
+    import zlib
+    try:
+        run(cfg)
+    except zlib.error as e:
+        print(f"a gzipped read file could not be inflated: {e}", file=sys.stderr)
+        return 1
+    except (RuntimeError, OSError, EOFError) as e:
+        print(f"{e}", file=sys.stderr)
+        return 1
+    return 0

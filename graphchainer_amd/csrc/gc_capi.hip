@@ -2,6 +2,7 @@
 #include "gc_runtime.hpp"
 #include "host/gc_stageclock.hpp"
 #include "hip/gc_seedhits_core.hpp"
+#include "hip/gc_fastx_core.hpp"
 #include <malloc.h>
 
 extern "C" {
@@ -976,6 +977,192 @@ int gc_reads_upload(const char* bases, const uint64_t* offsets, uint64_t n, gc_r
 	return GC_OK;
 }
 void gc_reads_destroy(gc_reads* r) { delete r; }
+
+// FASTA / FASTQ text -> the read batch gc_reads_upload builds from the same reads, and the host's table of them. The text goes up once; lines, roles, records, the
+// compacted bases and the ids are made on the device (hip/gc_fastx.hip); the per-read layout needs the lengths on the host, so the offsets come down before the gather.
+int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flags, gc_reads** reads, gc_fastx_table** table)
+{
+	// host checks first: a malformed call is GC_ERR_INVALID whether or not a device is present
+	if (!reads || !table || (!text && len)) return fail(GC_ERR_INVALID, "null argument");
+	*reads = nullptr; *table = nullptr;
+	if (format != GC_FASTX_FASTA && format != GC_FASTX_FASTQ) return fail(GC_ERR_INVALID, "gc_reads_parse: format is GC_FASTX_FASTA or GC_FASTX_FASTQ");
+	if (flags & ~(uint32_t)GC_FASTX_FINAL) return fail(GC_ERR_INVALID, "gc_reads_parse: unknown flag bits");
+	if (len >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_reads_parse: the loader uses 32-bit positions: split the text into chunks below 2^32 - 16 bytes");
+	static_assert(GC_FASTX_FASTA == gcdev::FX_FASTA && GC_FASTX_FASTQ == gcdev::FX_FASTQ && GC_FASTX_FINAL == gcdev::FX_FINAL, "the header's constants are the kernels'");
+	gc_reads* R = new gc_reads();
+	gc_fastx_table* T = nullptr;
+	hipStream_t uploadStream = nullptr;
+	int rc = guarded([&]() {
+		requireDevice();
+		using namespace gcdev;
+		HIP_CHECK(hipGetDevice(&R->device));
+		const int device = R->device;
+		hipStream_t q = threadStream(device);
+		uploadStream = q;
+		const uint32_t L = (uint32_t)len;
+		const bool final = (flags & GC_FASTX_FINAL) != 0;
+		auto round = [](size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; };
+		// blocks of this call: the text and its tables on the device, one pinned block for what goes up and comes down; all from the read batches' caches
+		struct Held { BlockCache* cache; void* p = nullptr; size_t bytes = 0; int device; hipStream_t q;
+			~Held() { if (p) { (void)hipStreamSynchronize(q); cache->put(p, bytes, device); } } };   // (waits: a copy or kernel of a failed call may still use the block)
+		Held textBlock { &g_readDeviceBlocks, nullptr, 0, device, q }, tableBlock { &g_readDeviceBlocks, nullptr, 0, device, q }, pinned { &g_readPinnedBlocks, nullptr, 0, device, q },
+			small { &g_readPinnedBlocks, nullptr, 0, device, q };
+		struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
+		HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+		double kernelMs = 0;
+		auto addSegment = [&]() { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b)); kernelMs += ms; };   // (after the synchronize that follows the segment)
+
+		// ---- 1: the text goes up, its newlines are counted (the line tables are sized by the count) ----
+		// pinned: text [L] | counts. The text's part is used again at the end for the bases and ids coming down: a line gives bytes to one of them at most, so both fit
+		const size_t hMeta = round(L), pinnedBytes = hMeta + round(FX_META_WORDS * sizeof(uint32_t));
+		pinned.p = g_readPinnedBlocks.get(pinnedBytes, device, pinned.bytes);
+		char* H = (char*)pinned.p;
+		uint32_t* hostMeta = (uint32_t*)(H + hMeta);
+		textBlock.p = g_readDeviceBlocks.get(pinnedBytes, device, textBlock.bytes);
+		char* devText = (char*)textBlock.p;
+		uint32_t* devMeta = (uint32_t*)(devText + hMeta);
+		if (L) { memcpy(H, text, L); HIP_CHECK(hipMemcpyAsync(devText, H, L, hipMemcpyHostToDevice, q)); }
+		HIP_CHECK(hipEventRecord(ev.a, q));
+		HIP_CHECK(fxCountNewlines(q, devText, L, devMeta));
+		HIP_CHECK(hipEventRecord(ev.b, q));
+		HIP_CHECK(hipMemcpyAsync(hostMeta, devMeta, FX_META_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		addSegment();
+
+		FxView v {};
+		v.text = devText; v.len = L; v.format = format; v.final = final ? 1u : 0u;
+		v.nNewlines = hostMeta[FX_META_NEWLINES];
+		if (v.nNewlines > L) throw std::runtime_error("gc_reads_parse: more newlines than bytes");
+		v.nLines = v.nNewlines + (final && L && text[L - 1] != '\n' ? 1u : 0u);
+
+		// ---- 2: line table, roles, destinations; the counts come down ----
+		// device: per line, then per record (at most one per line), then the ids (every id with its NUL is as long as its header line: at most L bytes in all), then the scans' scratch
+		const size_t lines = v.nLines;
+		size_t at = 0;
+		auto part = [&](size_t bytes) { const size_t here = at; at += round(bytes); return here; };
+		const size_t oLineEnd = part(lines * 4), oMap = part(lines), oScanned = part(lines), oHdr = part(lines * 4), oRecIdx = part(lines * 4), oContrib = part((lines + 1) * 4),
+			oDest = part((lines + 1) * 4), oRecLine = part(lines * 4), oReadOff = part((lines + 1) * 8), oNameLen = part((lines + 1) * 4), oNameOff = part((lines + 1) * 4),
+			oNames = part((size_t)L + 1);
+		FxTables t {};
+		t.tempBytes = fxScanTempBytes(L, v.nLines);
+		const size_t oTemp = part(t.tempBytes);
+		tableBlock.p = g_readDeviceBlocks.get(at, device, tableBlock.bytes);
+		char* D = (char*)tableBlock.p;
+		t.lineEnd = (uint32_t*)(D + oLineEnd); t.map = (uint8_t*)(D + oMap); t.scanned = (uint8_t*)(D + oScanned); t.hdr = (uint32_t*)(D + oHdr); t.recIdx = (uint32_t*)(D + oRecIdx);
+		t.contrib = (uint32_t*)(D + oContrib); t.dest = (uint32_t*)(D + oDest); t.recLine = (uint32_t*)(D + oRecLine); t.meta = devMeta; t.temp = D + oTemp;
+		v.lineEnd = t.lineEnd;
+		uint32_t nHeaders = 0, nRecords = 0, total = 0, consumed = final ? L : 0;
+		if (v.nLines) {
+			HIP_CHECK(hipEventRecord(ev.a, q));
+			HIP_CHECK(fxBuildTables(q, v, t));
+			HIP_CHECK(hipEventRecord(ev.b, q));
+			HIP_CHECK(hipMemcpyAsync(hostMeta, devMeta, FX_META_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+			HIP_CHECK(hipStreamSynchronize(q));
+			addSegment();
+			if (v.nNewlines && hostMeta[FX_META_SELECTED] != v.nNewlines) throw std::runtime_error("gc_reads_parse: the line table disagrees with the newline count");
+			nHeaders = hostMeta[FX_META_HEADERS]; nRecords = hostMeta[FX_META_RECORDS]; total = hostMeta[FX_META_BASES]; consumed = hostMeta[FX_META_CONSUMED];
+			if (nRecords > nHeaders || nHeaders > v.nLines || total > L || consumed > L) throw std::runtime_error("gc_reads_parse: the record table is out of range");
+		}
+		const uint64_t n = nRecords;
+
+		// ---- 3: read offsets and id offsets, down to the host for the per-read layout ----
+		// a second, small pinned block: offsets | id offsets | invalid flags | the four layout arrays that go up
+		size_t sat = 0;
+		auto spart = [&](size_t bytes) { const size_t here = sat; sat += round(bytes); return here; };
+		const size_t sOff = spart((n + 1) * 8), sNameOff = spart((n + 1) * 4), sInvalid = spart(n), sMaskOff = spart(n * 8), sMaskWords = spart(n * 4), sEqOff = spart(n * 8), sEdReads = spart(n * sizeof(EdRead));
+		small.p = g_readPinnedBlocks.get(sat, device, small.bytes);
+		char* S = (char*)small.p;
+		uint64_t* hostOff = (uint64_t*)(S + sOff);
+		uint32_t* hostNameOff = (uint32_t*)(S + sNameOff);
+		hostOff[0] = 0; hostNameOff[0] = 0;
+		if (v.nLines) {
+			HIP_CHECK(hipEventRecord(ev.a, q));
+			HIP_CHECK(fxBuildRecords(q, v, t, nHeaders, nRecords, (uint64_t*)(D + oReadOff), (uint32_t*)(D + oNameLen), (uint32_t*)(D + oNameOff)));
+			HIP_CHECK(fxWriteNames(q, v, t, nRecords, (const uint32_t*)(D + oNameOff), D + oNames));
+			HIP_CHECK(hipEventRecord(ev.b, q));
+			HIP_CHECK(hipMemcpyAsync(hostOff, D + oReadOff, (n + 1) * 8, hipMemcpyDeviceToHost, q));
+			HIP_CHECK(hipMemcpyAsync(hostNameOff, D + oNameOff, (n + 1) * 4, hipMemcpyDeviceToHost, q));
+			HIP_CHECK(hipStreamSynchronize(q));
+			addSegment();
+		}
+		const uint64_t namesBytes = hostNameOff[n];
+		if (hostOff[n] != total || namesBytes + total > L) throw std::runtime_error("gc_reads_parse: the read offsets disagree with the base count");
+		for (uint64_t r = 0; r < n; r++) if (hostOff[r + 1] < hostOff[r] || hostNameOff[r + 1] <= hostNameOff[r]) throw std::runtime_error("gc_reads_parse: offsets decrease");
+
+		// ---- 4: the read batch, laid out as gc_reads_upload lays it out; the gather writes the bases where the upload's copy would have put them ----
+		R->offsets.assign(hostOff, hostOff + n + 1);
+		R->totalBases = total;
+		R->maskOff.assign(n, 0);
+		R->maskWords.assign(n, 0);
+		uint64_t* hMaskOff = (uint64_t*)(S + sMaskOff); uint32_t* hMaskWords = (uint32_t*)(S + sMaskWords); uint64_t* hEqOff = (uint64_t*)(S + sEqOff); EdRead* hEdReads = (EdRead*)(S + sEdReads);
+		uint64_t totalWords = 0, eqWords = 0;
+		for (uint64_t r = 0; r < n; r++) {
+			R->maskOff[r] = hMaskOff[r] = totalWords;
+			R->maskWords[r] = hMaskWords[r] = (uint32_t)((hostOff[r + 1] - hostOff[r] + 63) / 64 + 1);
+			totalWords += 8ull * hMaskWords[r];
+			hEdReads[r] = EdRead { hostOff[r], eqWords, (uint32_t)(hostOff[r + 1] - hostOff[r]), hMaskWords[r] };
+			hEqOff[r] = eqWords;
+			eqWords += 4ull * hMaskWords[r];
+		}
+		size_t rat = 0;
+		auto rpart = [&](size_t bytes) { const size_t here = rat; rat += round(bytes); return here; };
+		const uint64_t total64 = total;
+		const size_t oBases = rpart(2 * total64), oOffsets = rpart((n + 1) * sizeof(uint64_t)), oMasks = rpart(totalWords * sizeof(uint64_t)), oEqMasks = rpart(eqWords * sizeof(uint64_t)),
+			oEdReads = rpart(n * sizeof(EdRead)), oPacked = rpart(((total64 >> 5) + 1) * sizeof(uint64_t)), oInvalid = rpart(((total64 >> 6) + 1) * sizeof(uint64_t)), oChunkRead = rpart(((total64 >> 6) + 1) * sizeof(uint32_t)),
+			oMaskOff = rpart(n * sizeof(uint64_t)), oMaskWords = rpart(n * sizeof(uint32_t)), oEqOff = rpart(n * sizeof(uint64_t)), oReadInvalid = rpart(n);
+		R->deviceBlock = g_readDeviceBlocks.get(rat, device, R->deviceBlockBytes);
+		char* B = (char*)R->deviceBlock;
+		R->devBases = B + oBases; R->devOffsets = (uint64_t*)(B + oOffsets); R->devMasks = (uint64_t*)(B + oMasks); R->devEqMasks = (uint64_t*)(B + oEqMasks); R->devEdReads = (EdRead*)(B + oEdReads);
+		R->devPacked = (uint64_t*)(B + oPacked); R->devInvalid = (uint64_t*)(B + oInvalid); R->devChunkRead = (uint32_t*)(B + oChunkRead); R->devReadInvalid = (uint8_t*)(B + oReadInvalid);
+		uint64_t* pMaskOff = (uint64_t*)(B + oMaskOff);
+		uint32_t* pMaskWords = (uint32_t*)(B + oMaskWords);
+		uint64_t* pEqOff = (uint64_t*)(B + oEqOff);
+		R->devMaskOff = pMaskOff; R->devMaskWords = pMaskWords;
+		HIP_CHECK(hipMemcpyAsync(R->devOffsets, hostOff, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, q));
+		if (n) {
+			HIP_CHECK(hipMemcpyAsync(pMaskOff, hMaskOff, n * sizeof(uint64_t), hipMemcpyHostToDevice, q));
+			HIP_CHECK(hipMemcpyAsync(pMaskWords, hMaskWords, n * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+			HIP_CHECK(hipMemcpyAsync(pEqOff, hEqOff, n * sizeof(uint64_t), hipMemcpyHostToDevice, q));
+			HIP_CHECK(hipMemcpyAsync(R->devEdReads, hEdReads, n * sizeof(EdRead), hipMemcpyHostToDevice, q));
+		}
+		HIP_CHECK(hipEventRecord(ev.a, q));
+		if (v.nLines) HIP_CHECK(fxGatherBases(q, v, t, total, R->devBases));
+		launchPackReads(q, R->devOffsets, (uint32_t)n, total, R->devBases, pMaskOff, pMaskWords, R->devMasks, pEqOff, R->devEqMasks, R->devReadInvalid, R->devPacked, R->devInvalid, R->devChunkRead);
+		HIP_CHECK(hipEventRecord(ev.b, q));
+		R->invalid.assign(n, 0);
+		if (n) HIP_CHECK(hipMemcpyAsync(S + sInvalid, R->devReadInvalid, n, hipMemcpyDeviceToHost, q));
+		if (total) HIP_CHECK(hipMemcpyAsync(H, R->devBases, total, hipMemcpyDeviceToHost, q));
+		if (namesBytes) HIP_CHECK(hipMemcpyAsync(H + total, D + oNames, namesBytes, hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		addSegment();
+		if (n) memcpy(R->invalid.data(), S + sInvalid, n);
+
+		// ---- the host's table: one allocation, the struct | offsets | name_off | bases | names ----
+		const size_t tHead = (sizeof(gc_fastx_table) + 15) & ~(size_t)15, tArr = (n + 1) * sizeof(uint64_t);
+		char* mem = (char*)malloc(tHead + 2 * tArr + total + namesBytes + 2);
+		if (!mem) throw std::runtime_error("gc_reads_parse: out of host memory");
+		T = (gc_fastx_table*)mem;
+		T->n_reads = n; T->consumed = consumed; T->kernel_ms = kernelMs;
+		T->offsets = (uint64_t*)(mem + tHead); T->name_off = (uint64_t*)(mem + tHead + tArr); T->bases = mem + tHead + 2 * tArr; T->names = T->bases + total + 1;
+		memcpy(T->offsets, hostOff, tArr);
+		for (uint64_t r = 0; r <= n; r++) T->name_off[r] = hostNameOff[r];
+		if (total) memcpy(T->bases, H, total);
+		T->bases[total] = 0;
+		if (namesBytes) memcpy(T->names, H + total, namesBytes);
+		T->names[namesBytes] = 0;
+		return (int)GC_OK;
+	});
+	if (rc != GC_OK) {
+		if (uploadStream) (void)hipStreamSynchronize(uploadStream);
+		delete R;
+		free(T);
+		return rc;
+	}
+	*reads = R;
+	*table = T;
+	return GC_OK;
+}
+void gc_fastx_table_free(gc_fastx_table* t) { free(t); }
 
 // ---- seed hits from the host's own seeder -------------------------------------------------------------------
 int gc_seeds_upload(const gc_graph* G, const gc_reads* R, const gc_seed_hit* hits, const uint64_t* read_hit_off, uint64_t n_reads, gc_seeds** out)

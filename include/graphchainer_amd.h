@@ -211,6 +211,31 @@ void gc_stream_destroy(gc_stream* st);
 int gc_reads_upload(const char* bases, const uint64_t* offsets, uint64_t n, gc_reads** out);
 void gc_reads_destroy(gc_reads* r);
 
+/* FASTA / FASTQ text to a read batch, parsed on the device: the reads FastQ::streamFastqFromFile (src/fastqloader.h, as the reader thread calls it, src/Aligner.cpp:167-187)
+ * yields for the same bytes, as the gc_reads that gc_reads_upload builds from them, plus a table in HOST memory of what the output writers need beside a result.
+ * format: GC_FASTX_FASTA / GC_FASTX_FASTQ (the caller looks at the file name as the reference does; a .gz is inflated by the caller). The read's id is its whole header
+ * line behind the first byte; read letters are not looked at here (gc_reads_upload's rules hold: a letter outside IUPAC flags the read in the result).
+ * flags: GC_FASTX_FINAL - the text runs to the end of the file: the reference's end-of-file rules apply and consumed == len. Without it the text is a chunk
+ * from the middle of a file: only lines that end in '\n' count, a record whose end is not yet known (a FASTQ record without its fourth line; the last FASTA record, whose
+ * next header has not been seen) is left out, and consumed is the byte where the caller's next chunk must begin - 0 with n_reads 0 when the chunk holds no complete
+ * record: the caller then brings more. A text of length 0 is valid and gives an empty batch.
+ * GC_ERR_INVALID, checked before a device is needed: a null pointer, another format, unknown flag bits, len of 2^32 - 16 or more (the loader uses 32-bit positions: split
+ * the file). Free the table with the function below, the reads as any read batch. */
+#define GC_FASTX_FASTA 1
+#define GC_FASTX_FASTQ 2
+#define GC_FASTX_FINAL 1u
+typedef struct gc_fastx_table {
+	uint64_t n_reads;
+	uint64_t consumed;
+	uint64_t* offsets;       /* [n_reads + 1] read i = bases[offsets[i] .. offsets[i+1]): the arrays the output writers take */
+	char* bases;             /* the compacted reads */
+	uint64_t* name_off;      /* [n_reads + 1] id i = names + name_off[i], NUL-terminated */
+	char* names;
+	double kernel_ms;        /* device time of the loader's kernels and the packing kernels, copies and waits left out */
+} gc_fastx_table;
+int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flags, gc_reads** reads, gc_fastx_table** table);
+void gc_fastx_table_free(gc_fastx_table* t);
+
 /* ---- seed hits from the host's own seeder ----------------------------------------------------------- */
 /* SeedHit as a seeder hands it over (src/GraphAlignerWrapper.h:14): what Seeder::getSeeds returns whether the hits come from minimizers, MUM / MEM matches or a
  * seeds file (src/Aligner.cpp:87-108), before OrderSeeds. */
