@@ -75,11 +75,8 @@
 			dLongAlns = st->longAlns.reserve<LongAln>(alnSlots);
 			LongReadResult* dLongResults = st->longResults.reserve<LongReadResult>(n);
 			dLongCells = st->longCells.reserve<LongCell>(cellBudget, true);
-			// the rounds are serial (select -> extend -> merge, the host decides when to stop) and have a stream of their own beside the pass's stream
-			if (!st->roundStream) {
-				createStream(&st->roundStream);
-				for (auto& e : st->roundEvents) HIP_CHECK(hipEventCreate(&e));
-			}
+			// the rounds are serial (select -> extend -> merge, the host decides when to stop) and have a stream of their own beside the pass's stream: the token slot's
+			// (longTokenTake sets passRounds); what comes before the token - init and the first round's select - runs on the pass's stream
 			// cursors: [0] cell pool, [8..15] counters (+ [16..31] profiling stamps), the round loop's at [32..35]: work count, round trace cursor, next work slot, length of the retry list
 			cursorWords = 32 + 8 * 16;
 			dLongCursor = st->longCursor.reserve<unsigned long long>(cursorWords);
@@ -192,8 +189,8 @@
 	{
 		if (n == 0) return;
 		unsigned long long* dLongScratch = nullptr;   // (set when the token is taken - before the first extension launch)
-		hipStream_t q = st->roundStream;
-		hipEvent_t* ring = st->roundEvents;
+		hipStream_t q = ls;                           // until the token is taken: the pass's own stream; from then on the round stream of the token slot the pass holds (passRounds)
+		hipEvent_t* ring = nullptr;
 		// the rounds' extension time: read a ring slot's pair before the slot is reused (its round is complete by then: every round's
 		// work count has been awaited since) and what is left after the last round
 		auto collect = [&](int slot) { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ring[2 * slot], ring[2 * slot + 1])); longExtendUs += (double)ms * 1000.0; };
@@ -202,6 +199,7 @@
 		volatile unsigned long long* hCursor = hLongSmall + 32;
 		double dbgWaitUs = 0;
 		const double dbgT0 = nowUs();
+		// what comes before the token - init, the first round's select, order and publish - runs on the pass's own stream, beside the pass that holds the token now
 		launchLongInit(q, dLongJobs, (uint32_t)n, dLongState);
 		uint32_t lastWork = 0xffffffffu;
 
@@ -226,8 +224,11 @@
 			uint32_t nWorkItems = (uint32_t)hCursor[0];
 			if (nWorkItems == 0) break;
 			if (!dLongScratch) {
+				// (the host has just waited for the pass's own stream: everything queued there is complete, so no event links it to the token's stream)
 				longTokenTake();
 				dLongScratch = shareLongScratch ? longScratchOfToken : dLongScratchOwn;
+				q = passRounds->q;
+				ring = passRounds->ring;
 			}
 			uint32_t team = longExtendTeamSize(nWorkItems, sw.testLongTeam.value_or(0));
 			uint32_t blocks = std::min<uint32_t>((nWorkItems + team - 1) / team, (uint32_t)std::max<uint64_t>(1, (scratchLanes - 64) / team));
@@ -251,20 +252,22 @@
 			launchLongMerge(q, G->dev, dLongJobs, (uint32_t)n, dLongSeeds, dCandSeed, dLongWorkResults, dRoundTrace, dLongState, dLongAlns, dLongCells, dLongCursor, cellBudget, (uint32_t)P->extra_heuristic);
 			lastWork = nWorkItems;
 			// no wait here: the next round's select / order / publish queue up right behind the merge, and the only host round trip per
-			// round is the work count above (with a second wait after the merge the stream drained twice per round, and each refill
-			// waited behind whatever other batches had queued on the device)
+			// round is the work count above (with a second wait after the merge the stream drained twice per round)
 			timedRounds++;
 			longRounds++;
 		}
-		// (the last round's count has come down: every extension kernel of the pass is complete, the scratch is free)
+		// (the last round's count has come down: every extension kernel of the pass is complete, the scratch is free and the token's stream is empty)
+		const double dbgT1 = nowUs();
+		if (ring) for (int k = std::max(0, timedRounds - LONG_EVENT_RING); k < timedRounds; k++) collect(k % LONG_EVENT_RING);   // (before the release: the ring goes to the next pass with the token)
 		longTokenDrop();
 		// the per-read results go straight into pinned host memory (the kernel writes them across PCIe): a copy-engine transfer here queued behind
-		// the other batch's bulk downloads for 30-50 ms while this pass still held the device's whole-read token
-		launchLongFinish(q, (uint32_t)n, dLongState, hLongResults);
-		const double dbgT1 = nowUs();
-		syncStream(q);
-		if (sw.debugTimes) fprintf(stderr, "[gc times] whole-read rounds: %.1f ms in all, %.1f ms waiting for the rounds' work counts, %.1f ms in the last wait, %d rounds\n", (nowUs() - dbgT0) / 1e3, dbgWaitUs / 1e3, (nowUs() - dbgT1) / 1e3, timedRounds);
-		for (int k = std::max(0, timedRounds - LONG_EVENT_RING); k < timedRounds; k++) collect(k % LONG_EVENT_RING);
+		// the other batch's bulk downloads for 30-50 ms while this pass still held the device's whole-read token. On the pass's own stream: the token's is the next pass's now
+		launchLongFinish(ls, (uint32_t)n, dLongState, hLongResults);
+		syncStream(ls);
+		if (sw.debugTimes) {
+			const char* hwq = getenv("GPU_MAX_HW_QUEUES");
+			fprintf(stderr, "[gc times] whole-read rounds: %.1f ms in all, %.1f ms waiting for the rounds' work counts, %.1f ms in the last wait, %d rounds, GPU_MAX_HW_QUEUES=%s\n", (nowUs() - dbgT0) / 1e3, dbgWaitUs / 1e3, (nowUs() - dbgT1) / 1e3, timedRounds, hwq ? hwq : "unset");
+		}
 	}
 
 	uint64_t longFallback()   // reads whose band did not fit the wave layout's tables are rerun with the plain-layout kernel; returns how many
@@ -484,6 +487,10 @@
 								longScratchOfToken = g_longScratch[device & 15].buffer[0].reserve<unsigned long long>(longScratchWords);
 							}
 						}
+						// the round loop's stream: the one of the token slot this pass now holds (every pass of the device that holds the slot runs its rounds there, one at a time);
+						// without a token the gc_stream's own
+						passRounds = token.owns_lock() ? &g_longScratch[device & 15].rounds[token.slot] : &st->ownRounds;
+						passRounds->ensure(token.owns_lock());
 						held = true;
 						if (sw.debugTimes) fprintf(stderr, "[gc token] stream %p pass began %.1f asked %.1f got %.1f (call began %.1f)\n", (void*)st, tTokenAsk / 1e3, tAsk / 1e3, nowUs() / 1e3, tCall / 1e3);
 						if (longWallBeginUs == 0.0) longWallBeginUs = nowUs();   // (whole_read_pass_wall: from the pass's first take of the token - a pool rerun takes it again - to its last release)
@@ -491,6 +498,7 @@
 					longTokenDrop = [&]() {
 						if (!held) return;
 						held = false;
+						passRounds = nullptr;   // (the slot's stream goes to the next pass with the token)
 						longWallEndUs = nowUs();
 						if (sw.debugTimes) fprintf(stderr, "[gc token] stream %p released %.1f\n", (void*)st, nowUs() / 1e3);
 						token.unlock();   // the next batch's pass may start; what follows is this batch's own tail
@@ -507,7 +515,8 @@
 					longError = std::current_exception();
 					longTokenTake = nullptr; longTokenDrop = nullptr;   // (they refer to this thread's locals)
 					// the token is released when this lambda returns: a kernel of this pass may still be writing to the shared scratch
-					if (st->roundStream) (void)hipStreamSynchronize(st->roundStream);
+					if (passRounds && passRounds->q) (void)hipStreamSynchronize(passRounds->q);   // (still set: the pass failed between take and drop)
+					passRounds = nullptr;
 					(void)hipStreamSynchronize(st->longStream);
 				}
 			});

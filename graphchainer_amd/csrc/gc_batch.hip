@@ -53,6 +53,7 @@ struct BatchRun {
 	// init / select / order / publish and the host's wait for the work count (each a launch that queues among the other batches' kernels), and its k_long_finish at the
 	// end, no longer sit between two passes' extension kernels
 	std::function<void()> longTokenTake, longTokenDrop;   // (set by the pass thread for its round loop)
+	RoundStream* passRounds = nullptr;   // between take and drop: the round loop's stream and events - the token slot's, or the gc_stream's own without a token (GC_LONG_TOKEN=0)
 	uint64_t longScratchWords = 0;
 	bool shareLongScratch = false;
 	double longExtendUs = 0; uint32_t longRounds = 0;   // the rounds' extension kernels (event pairs) and how many rounds had work, reruns of the pass included

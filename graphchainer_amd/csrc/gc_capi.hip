@@ -887,7 +887,7 @@ void gc_stream_destroy(gc_stream* st)
 			TokenHold alone;
 			alone.lock(g_longPassToken[st->device & 15], 1, true);   // (every slot free and nobody beside: as a pass that fills the chip waits)
 			int current = 0;
-			if (hipGetDevice(&current) == hipSuccess) { (void)hipSetDevice(st->device); for (auto& b : shared.buffer) b.release(); (void)hipSetDevice(current); }
+			if (hipGetDevice(&current) == hipSuccess) { (void)hipSetDevice(st->device); for (auto& b : shared.buffer) b.release(); for (auto& r : shared.rounds) r.release(); (void)hipSetDevice(current); }
 		}
 	}
 	delete st;

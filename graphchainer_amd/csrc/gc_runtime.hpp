@@ -47,7 +47,12 @@ struct DeviceError : std::runtime_error { using std::runtime_error::runtime_erro
 // twice that: on 4 queues the whole-read pass's rounds wait behind the other batch's k_extend / k_chain / k_stitch (kernel trace: 60 ms of
 // foreign kernels between two rounds). 16 queues: 228 -> 209 ms per batch on cfg2; 32 oversubscribe the command processor (290 ms).
 // The HIP runtime reads the variable at its first call and it configures the whole process, so it is the HOST's to set (bench.py and the
-// scripts set GPU_MAX_HW_QUEUES=16 before anything touches HIP); the library only says so, once, when a second stream is created without it.
+// scripts set GPU_MAX_HW_QUEUES=16 before anything touches HIP - unless the host has preset it: a box that presets 4 keeps 4); the library only says so, once, when a
+// second stream is created without it.
+// The whole-read pass's critical path does not count on the setting. Dispatches of streams that share a hardware queue run in submission order, one after the other, so
+// whatever the other batches' streams put on the pass's queue while it ran executed inside it (profiles/passgap_timeline_parent.txt: 20 ms per pass on 4 queues, in front
+// of the round's extension, while the host fetched its work count). Queueing the rounds ahead of the count only moved those dispatches. The remedy is a
+// queue nobody shares: the rounds of every gc_stream run on the one stream of the token slot, created at the highest stream priority (RoundStream below).
 inline void noteHardwareQueues(int streamsAlive)
 {
 	static std::atomic<bool> said { false };
@@ -151,7 +156,35 @@ inline int longTokenCount(std::optional<int> tokensOverride, uint64_t nReads, ui
 // The pass's extension scratch (up to 48 GB: one region per resident wave) is only touched while the token is held, so the gc_streams of a device share ONE
 // (r3: 85 -> 37 GB per stream for 10 k x 10 kb batches, which is what lets five batches be in flight on a 288 GB device instead of three). It belongs to the
 // token: reserved (grown) by the pass that holds it, freed when the device's last gc_stream goes.
-struct SharedLongScratch { DeviceBuffer buffer[LONG_TOKENS_MAX]; int streams = 0; };
+// The round loop's stream belongs to the token as well: one pass per token slot runs its rounds at a time, so the slot has ONE stream (and event ring) that every pass
+// holding it uses in turn - not one per gc_stream, four of which sat idle among five batches' sixty-odd streams. Created by the slot's first pass, destroyed with the scratch.
+// GC_LONG_TOKEN=0 (no token, passes overlap) keeps one per gc_stream (gc_stream::ownRounds).
+inline constexpr int LONG_EVENT_RING = 8;
+struct RoundStream {
+	hipStream_t q = nullptr;
+	hipEvent_t ring[2 * LONG_EVENT_RING] {};   // (begin, end) pairs around the rounds' extension launches
+	// ofToken: the slot's stream is created at the device's highest stream priority. HIP keeps the hardware queues of each priority apart, so the pass's rounds - the step's
+	// critical path, one pass per slot at a time - get a queue that the dozens of default-priority streams of the batches in flight do not share, however few queues the host
+	// was granted (GPU_MAX_HW_QUEUES); on a shared queue every foreign dispatch submitted during the pass ran inside it, one after the other. That HIP does so is what the
+	// kernel traces show, not a documented promise: in profiles/passgap_timeline.txt every dispatch of the token's stream is on queue id 5, which no other stream's dispatch uses.
+	// r3 tried priorities on the five per-stream round streams and lost; this is one stream, used only while the token is held. Without a token: default priority.
+	void ensure(bool ofToken)
+	{
+		if (q) return;
+		for (auto& e : ring) if (!e) HIP_CHECK(hipEventCreate(&e));
+		int least = 0, greatest = 0;
+		if (ofToken) HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+		if (ofToken && greatest != least) HIP_CHECK(hipStreamCreateWithPriority(&q, hipStreamNonBlocking, greatest));
+		else HIP_CHECK(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+	}
+	void release()
+	{
+		for (auto& e : ring) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+		if (q) (void)hipStreamDestroy(q);
+		q = nullptr;
+	}
+};
+struct SharedLongScratch { DeviceBuffer buffer[LONG_TOKENS_MAX]; RoundStream rounds[LONG_TOKENS_MAX]; int streams = 0; };
 inline SharedLongScratch g_longScratch[16];
 inline std::mutex g_longScratchCount;
 
@@ -588,7 +621,6 @@ struct EditDistanceRun {
 	~EditDistanceRun() { for (auto& q : streams) if (q) (void)hipStreamDestroy(q); if (ready) (void)hipEventDestroy(ready); }
 };
 
-inline constexpr int LONG_EVENT_RING = 8;
 struct gc_stream {
 	std::vector<ReadGlue> glue;   // per-read host records of the batch in flight (storage reused)
 	int device = 0;             // the device the stream was created on; gc_align_batch selects it for the calling thread
@@ -626,8 +658,8 @@ struct gc_stream {
 	uint64_t batchesDone = 0;                 // batches this stream has finished (a second whole-read token is only taken from the second batch on: the first sizes the stream's buffers)
 	bool poolsRerun = false;                  // the last batch ran its fragment pipeline again with larger pools: the next one gives back what that overshot
 	double traceCellsPerSlot = 0, pathWordsPerSlot = 0;   // what this stream's batches have used of the fragment pipeline's trace pool / anchor path pool per anchor slot (0: no batch yet)
-	hipStream_t roundStream = nullptr;       // the round loop of the whole-read pass (created by the stream's first pass; longStream carries the pass's uploads, reruns and decision)
-	hipEvent_t roundEvents[2 * LONG_EVENT_RING] {};   // a ring of (begin, end) pairs around the rounds' extension launches
+	RoundStream ownRounds;                   // the round loop's stream WITHOUT the token (GC_LONG_TOKEN=0; created by the stream's first such pass). With it the rounds run on the token slot's stream
+	                                         // (SharedLongScratch::rounds); longStream carries the pass's uploads, its first select, reruns and decision
 	DeviceBuffer longSeeds, longJobs, longAlns, longResults, longScratch, longCells, longCursor, longJobsFallback, longResultsFallback, longScratchFallback;
 	DeviceBuffer gluePerRead, glueCursors, glueOut, glueSeedCap, glueSeedOff, glueWinCapOff, glueU32[8], glueSort, gluePos, glueWin;   // seed glue on the device (gc_seedglue.hip)
 	PinnedBuffer hGlueOut, hGlueWinCapOff, hGlueSmall;
@@ -662,8 +694,7 @@ struct gc_stream {
 		for (auto& e : ev) if (e) (void)hipEventDestroy(e);
 		for (auto& e : fragEv) if (e) (void)hipEventDestroy(e);
 		for (auto& e : longEv) if (e) (void)hipEventDestroy(e);
-		for (auto& e : roundEvents) if (e) (void)hipEventDestroy(e);
-		if (roundStream) (void)hipStreamDestroy(roundStream);
+		ownRounds.release();
 		if (stream) (void)hipStreamDestroy(stream);
 		if (longStream) (void)hipStreamDestroy(longStream);
 	}
