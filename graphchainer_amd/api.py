@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
     "gc_reads_parse", "gc_fastx_table_free",
+    "gc_seed_store_open", "gc_seed_store_from_memory", "gc_seed_store_info", "gc_seed_store_destroy", "gc_seeds_from_store",
 ]
 
 
@@ -621,6 +622,64 @@ class SeedBatch:
     def close(self):
         if self.handle:
             self.lib.gc_seeds_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GcSeedStoreStats(C.Structure):
+    """gc_seed_store_stats (include/graphchainer_amd.h)."""
+    _fields_ = [("messages", C.c_uint64), ("seeds", C.c_uint64), ("distinct_hashes", C.c_uint64), ("hbm_bytes", C.c_uint64), ("host_ms", C.c_double), ("device_ms", C.c_double),
+                ("inflate_ms", C.c_double), ("frame_ms", C.c_double), ("upload_ms", C.c_double), ("decode_ms", C.c_double), ("sort_ms", C.c_double)]
+
+
+class SeedStore:
+    """The seeds of the reference's -s / --seeds-file files, decoded on the device and resident in HBM (gc_seed_store_open): SeedStore(paths) reads GAM files (gzip or zlib, in
+    the order given), SeedStore(streams=[bytes, ...]) takes streams that are inflated already. seeds(graph, batch, ids) joins a read batch's names - the ids ReadBatch.from_text
+    or read_files returned - to their seeds on the device: a SeedBatch for Aligner.align_batch(batch, seeds=...). Read-only; may be shared by aligners."""
+
+    def __init__(self, paths=None, streams=None):
+        if (paths is None) == (streams is None):
+            raise ValueError("give paths or streams")
+        self.lib = lib = load_library()
+        lib.gc_seed_store_open.argtypes = [_P(C.c_char_p), C.c_uint32, _P(C.c_void_p)]
+        lib.gc_seed_store_from_memory.argtypes = [_P(C.c_void_p), C.c_void_p, C.c_uint32, _P(C.c_void_p)]
+        lib.gc_seed_store_info.argtypes = [C.c_void_p, _P(GcSeedStoreStats)]
+        lib.gc_seed_store_destroy.argtypes = [C.c_void_p]
+        lib.gc_seed_store_destroy.restype = None
+        lib.gc_seeds_from_store.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, _P(C.c_void_p)]
+        self.handle = C.c_void_p()
+        if paths is not None:
+            paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+            array = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+            _check(lib.gc_seed_store_open(array, len(paths), C.byref(self.handle)))
+        else:
+            streams = [bytes(s) for s in streams]
+            buffers = [C.create_string_buffer(s, max(len(s), 1)) for s in streams]
+            array = (C.c_void_p * max(len(streams), 1))(*[C.cast(b, C.c_void_p) for b in buffers])
+            lens = np.array([len(s) for s in streams] + [0], dtype=np.uint64)
+            _check(lib.gc_seed_store_from_memory(array, lens.ctypes.data, len(streams), C.byref(self.handle)))
+
+    def seeds(self, graph, batch, ids):
+        names = b"".join((i if isinstance(i, bytes) else i.encode()) + b"\0" for i in ids)
+        name_off = np.zeros(len(ids) + 1, dtype=np.uint64)
+        name_off[1:] = np.cumsum([len(i if isinstance(i, bytes) else i.encode()) + 1 for i in ids], dtype=np.uint64) if len(ids) else []
+        handle = C.c_void_p()
+        _check(self.lib.gc_seeds_from_store(graph.handle, self.handle, batch.handle, names, name_off.ctypes.data, len(ids), C.byref(handle)))
+        return SeedBatch._adopt(handle)
+
+    def info(self):
+        stats = GcSeedStoreStats()
+        _check(self.lib.gc_seed_store_info(self.handle, C.byref(stats)))
+        return {name: getattr(stats, name) for name, _ in GcSeedStoreStats._fields_}
+
+    def close(self):
+        if self.handle:
+            self.lib.gc_seed_store_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -39,7 +39,7 @@ OPTIONS = {
     # this build's own
     "batch-bytes": (None, "size", False), "device": (None, "size", False), "index-cache": (None, "string", False),
 }
-REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "seeds-file", "generate-path", "generate-path-seed", "graph-statistics")
+REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "generate-path", "generate-path-seed", "graph-statistics")
 SELECT = {"greedy-length": 0, "schedule-inverse-E-sum": 3, "schedule-inverse-E-product": 4, "schedule-score": 5, "schedule-length": 6, "all-alignments": 7}   # GC_SELECT_*
 
 HELP = """Mandatory parameters:
@@ -80,6 +80,7 @@ Seeding parameters:
   --seeds-mem-count arg                 arg longest maximal exact matches fully contained in a node (-1 for all)
   --seeds-mxm-length arg                minimum length for maximal unique / exact matches [20]
   --seeds-mxm-cache-prefix arg          store the mum/mem seeding index on disk for reuse, or reuse it if it exists
+  -s [ --seeds-file ] arg               external seeds (.gam)
 
 Extension parameters:
   -b [ --bandwidth ] arg                alignment bandwidth [10]
@@ -94,7 +95,7 @@ This build's own:
                                         --seeds-minimizer-ignore-frequent
 
 Accepted and without effect: -t [ --threads ] arg (must be >= 1), --high-memory, --verbose, --short-verbose, --greedy-E, --greedy-score.
-Not supported by this build: --optimal-alignment, --seedless-DP, --DP-restart-stride, -s [ --seeds-file ], --generate-path, --generate-path-seed,
+Not supported by this build: --optimal-alignment, --seedless-DP, --DP-restart-stride, --generate-path, --generate-path-seed,
 --graph-statistics, a .vg graph.
 """
 
@@ -114,7 +115,7 @@ class Config:
     outputs: dict = field(default_factory=dict)          # "gaf" / "json" / "gam" -> path (the last one given of each kind, as the reference keeps it)
     aligner: dict = field(default_factory=dict)          # keyword arguments of api.Aligner
     min_cluster_size: int = 1                            # gc_params::min_cluster_size
-    seeder: dict = field(default_factory=dict)           # {"kind": "minimizer", "length", "window", "keep_fraction"} or {"kind": "mxm", "mode", "count", "min_len", "cache_prefix"}
+    seeder: dict = field(default_factory=dict)           # {"kind": "minimizer", "length", "window", "keep_fraction"}, {"kind": "mxm", "mode", "count", "min_len", "cache_prefix"} or {"kind": "file", "paths"}
     cigar_match_mismatch: bool = False
     threads: int = 1
     batch_bytes: int = 100 << 20
@@ -245,6 +246,7 @@ def resolve(argv):
     minimizer_window = last("seeds-minimizer-windowsize", minimizer_window)
     mxm_length, mem_count, mum_count = last("seeds-mxm-length", 20), last("seeds-mem-count", 0), last("seeds-mum-count", 0)
     cache_prefix = last("seeds-mxm-cache-prefix", "")
+    seed_files = list(vm.get("seeds-file", []))
     colinear_gap, split_len, split_gap = last("colinear-gap", colinear_gap), last("colinear-split-len", split_len), last("colinear-split-gap", split_gap)
     sampling_step = last("sampling-step", sampling_step)
     if sampling_step != 1:
@@ -306,7 +308,7 @@ def resolve(argv):
         error("Minimizer density can't be negative")
     if extend_density <= 0 and extend_density != -1:
         error("Seed extension density can't be negative")
-    picked = (1 if mum_count != 0 else 0) + (1 if mem_count != 0 else 0) + (1 if minimizer_density != 0 else 0)
+    picked = (1 if mum_count != 0 else 0) + (1 if mem_count != 0 else 0) + (1 if minimizer_density != 0 else 0) + (1 if seed_files else 0)   # src/AlignerMain.cpp:407-410
     if picked == 0:
         error("pick a seeding method")
     if picked > 1:
@@ -328,7 +330,9 @@ def resolve(argv):
     if errors:
         raise CliExit(1, "".join(line + "\n" for line in messages) + "run with option -h for help\n")
 
-    if minimizer_density != 0:
+    if seed_files:
+        cfg.seeder = {"kind": "file", "paths": seed_files}
+    elif minimizer_density != 0:
         cfg.seeder = {"kind": "minimizer", "length": minimizer_length, "window": minimizer_window, "keep_fraction": 1 - discard_fraction}   # src/Aligner.cpp:1162
     else:
         count = mum_count if mum_count != 0 else mem_count
@@ -378,8 +382,11 @@ def run(cfg, stderr=sys.stderr):
     import numpy as np
 
     from . import api
+    from_file = cfg.seeder["kind"] == "file"
+    if from_file and not all(os.path.exists(p) for p in cfg.seeder["paths"]):
+        raise CliExit(0, "No seeds file exists\n")            # src/Aligner.cpp:1185-1186: said, and the run ends with status 0 and no output
     api.set_device(cfg.device)
-    seeder = index = None
+    seeder = index = store = None
     minimizer = cfg.seeder["kind"] == "minimizer"
     if cfg.index_cache and os.path.exists(cfg.index_cache):
         info = api.check_index_cache(cfg.index_cache)
@@ -393,7 +400,9 @@ def run(cfg, stderr=sys.stderr):
             seeder = api.MinimizerSeeder(graph, cfg.seeder["length"], cfg.seeder["window"], cfg.seeder["keep_fraction"])
         if cfg.index_cache:
             api.save_index_cache(graph, seeder, cfg.index_cache)
-    if not minimizer:
+    if from_file:
+        store = api.SeedStore(cfg.seeder["paths"])             # every file, in command-line order, before any read is aligned (src/Aligner.cpp:1169-1190)
+    elif not minimizer:
         index = api.MxmIndex(graph, cache_prefix=cfg.seeder["cache_prefix"] or None)
     # what the chosen writers need: the whole-read pass and the two edit distances that pick the winner, and the final alignments encoded on the device, where their traces
     # are - the GAF pieces (= / X items, or M items with --cigar-match-mismatch) for a .gaf, the vg::Path bytes for a .json or .gam; no trace comes down (keep_traces=0)
@@ -406,7 +415,10 @@ def run(cfg, stderr=sys.stderr):
     with _Outputs(cfg.outputs) as outputs:
         for batch, ids in api.read_files(cfg.reads, cfg.batch_bytes):
             try:
-                seeds = index.seeds(batch, cfg.seeder["mode"], count=cfg.seeder["count"], min_len=cfg.seeder["min_len"]) if index is not None else None
+                if store is not None:
+                    seeds = store.seeds(graph, batch, ids)
+                else:
+                    seeds = index.seeds(batch, cfg.seeder["mode"], count=cfg.seeder["count"], min_len=cfg.seeder["min_len"]) if index is not None else None
                 try:
                     out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
                 finally:
@@ -442,6 +454,9 @@ def main(argv=None):
     import zlib
     try:
         run(cfg)
+    except CliExit as e:
+        sys.stderr.write(e.stderr)
+        return e.status
     except zlib.error as e:
         print(f"a gzipped read file could not be inflated: {e}", file=sys.stderr)
         return 1

@@ -3,7 +3,9 @@
 #include "host/gc_stageclock.hpp"
 #include "hip/gc_seedhits_core.hpp"
 #include "hip/gc_fastx_core.hpp"
+#include "host/gc_seedfile_frame.hpp"
 #include <malloc.h>
+#include <zlib.h>
 
 extern "C" {
 
@@ -1500,6 +1502,348 @@ int gc_seeds_mxm(const gc_graph* G, const gc_mxm_index* X, const gc_reads* R, in
 		HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
 		H->kernelMs = ms;
 		if (bad != ~0ull) throw std::runtime_error("gc_seeds_mxm: a match does not resolve to a position of the graph (hit " + std::to_string(bad >> 2) + ")");   // (the index and the graph disagree: a bug, not an input)
+		return (int)GC_OK;
+	});
+	if (rc != GC_OK) { delete H; return rc; }
+	*out = H;
+	return GC_OK;
+}
+
+// ---- seeds from GAM files (the reference's -s: src/Aligner.cpp:1169-1190, src/stream.hpp:81-123) --------------------
+} // extern "C"
+
+namespace {
+
+struct SeedFileInvalid : std::runtime_error { using std::runtime_error::runtime_error; };
+struct SeedFileUnreadable : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// a device array that grows by doubling and keeps what it holds
+struct SeedStoreArray {
+	void* p = nullptr;
+	size_t cap = 0;
+	void ensure(size_t used, size_t need, hipStream_t q)
+	{
+		if (need <= cap) return;
+		const size_t want = std::max(need + 256, cap * 2);
+		void* grown = nullptr;
+		HIP_CHECK(hipMalloc(&grown, want));
+		hipError_t e = used ? hipMemcpyAsync(grown, p, used, hipMemcpyDeviceToDevice, q) : hipSuccess;
+		if (e == hipSuccess) e = hipStreamSynchronize(q);
+		if (e != hipSuccess) { (void)hipFree(grown); HIP_CHECK(e); }
+		if (p) (void)hipFree(p);
+		p = grown; cap = want;
+	}
+	// the doubling's head room goes back before the store keeps the array
+	void fit(size_t used, hipStream_t q)
+	{
+		if (!p || cap <= used + used / 16 + 4096) return;
+		SeedStoreArray exact;
+		exact.ensure(0, used, q);
+		HIP_CHECK(hipMemcpyAsync(exact.p, p, used, hipMemcpyDeviceToDevice, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		std::swap(p, exact.p); std::swap(cap, exact.cap);
+	}
+	void* handOver(gc_seed_store& S) { void* r = p; if (r) { S.allocations.push_back(r); S.deviceBytes += cap; } p = nullptr; cap = 0; return r; }
+	~SeedStoreArray() { if (p) (void)hipFree(p); }
+};
+
+double msSince(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// pieces in, a gc_seed_store out: every piece is uploaded, decoded into the growing arrays and dropped
+struct SeedStoreBuilder {
+	gc_seed_store& S;
+	hipStream_t q;
+	gc::Switches sw = gc::Switches::fromEnvironment();
+	SeedStoreArray hits, hash, nameOff, nameLen, pool;
+	DeviceBuffer piece, msgOff, nameStart, local, temp, flags;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	uint64_t n = 0, poolUsed = 0;
+	unsigned long long* dBad = nullptr;
+	std::vector<uint64_t> fileFirst;   // the first message of every file among all messages
+	double sinkMs = 0;
+
+	SeedStoreBuilder(gc_seed_store& store, hipStream_t stream) : S(store), q(stream)
+	{
+		HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+		dBad = flags.reserve<unsigned long long>(2);
+		const unsigned long long none = ~0ull;
+		HIP_CHECK(hipMemcpyAsync(dBad, &none, sizeof(none), hipMemcpyHostToDevice, q));
+		HIP_CHECK(hipMemsetAsync(dBad + 1, 0, sizeof(unsigned long long), q));
+		HIP_CHECK(hipStreamSynchronize(q));
+	}
+	~SeedStoreBuilder() { (void)hipStreamSynchronize(q); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+
+	void addPiece(const uint8_t* bytes, size_t len, const uint32_t* off, uint32_t count)
+	{
+		const auto t0 = std::chrono::steady_clock::now();
+		if (n + count >= 0x7fffffffull) throw SeedFileInvalid("2^31 - 1 messages or more");
+		uint8_t* dPiece = piece.reserve<uint8_t>(len + 16);   // (k_sf_decode stages whole 16-byte words)
+		uint32_t* dOff = msgOff.reserve<uint32_t>((size_t)count + 1);
+		HIP_CHECK(hipMemcpyAsync(dPiece, bytes, len, hipMemcpyHostToDevice, q));
+		HIP_CHECK(hipMemcpyAsync(dOff, off, ((size_t)count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+		hits.ensure(n * sizeof(SeedHit), (n + count) * sizeof(SeedHit), q);
+		hash.ensure(n * 8, (n + count) * 8, q);
+		nameOff.ensure(n * 8, (n + count) * 8, q);
+		nameLen.ensure(n * 4, (n + count) * 4, q);
+		uint32_t* dStart = nameStart.reserve<uint32_t>(count);
+		uint32_t* dLocal = local.reserve<uint32_t>(count);
+		const size_t tempBytes = sfTempBytes(count, 0);
+		void* dTemp = temp.reserve<char>(tempBytes);
+		HIP_CHECK(hipStreamSynchronize(q));
+		S.uploadMs += msSince(t0);
+		uint32_t* lens = (uint32_t*)nameLen.p + n;
+		HIP_CHECK(hipEventRecord(e0, q));
+		HIP_CHECK(sfDecodePiece(q, dPiece, dOff, count, n, sw.testSeedfileHashBits, (SeedHit*)hits.p + n, (uint64_t*)hash.p + n, dStart, lens, dBad));
+		HIP_CHECK(sfScanNameLengths(q, dTemp, tempBytes, lens, count, dLocal));
+		uint32_t last[2] = { 0, 0 };
+		HIP_CHECK(hipMemcpyAsync(&last[0], dLocal + (count - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipMemcpyAsync(&last[1], lens + (count - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		const uint64_t total = (uint64_t)last[0] + last[1];   // (the names lie inside the piece: at most its bytes)
+		pool.ensure(poolUsed, poolUsed + total, q);
+		HIP_CHECK(sfCopyNames(q, dPiece, dOff, dStart, lens, dLocal, count, poolUsed, (uint8_t*)pool.p, (uint64_t*)nameOff.p + n));
+		HIP_CHECK(hipEventRecord(e1, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		float ms = 0;
+		HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+		S.decodeMs += ms;
+		poolUsed += total;
+		n += count;
+		sinkMs += msSince(t0);
+	}
+
+	// after every file: the first message the device refused, by file and index
+	void check()
+	{
+		unsigned long long bad = ~0ull;
+		HIP_CHECK(hipMemcpyAsync(&bad, dBad, sizeof(bad), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		if (bad == ~0ull) return;
+		const uint64_t i = bad >> 2;
+		const size_t f = (size_t)(std::upper_bound(fileFirst.begin(), fileFirst.end(), i) - fileFirst.begin()) - 1;
+		const char* what[] = { "", "has no mapping", "has a mapping without an edit", "does not parse as a vg::Alignment" };
+		throw SeedFileInvalid("file " + std::to_string(f) + " message " + std::to_string(i - fileFirst[f]) + " " + what[bad & 3]);
+	}
+
+	void oneStream(uint32_t index, const std::function<void(gc::SeedFileFramer&)>& feed)
+	{
+		fileFirst.push_back(n);
+		gc::SeedFileFramer framer(sw.testSeedfilePiece, [&](const uint8_t* bytes, size_t len, const uint32_t* off, uint32_t count, uint64_t) { addPiece(bytes, len, off, count); });
+		try {
+			feed(framer);
+			framer.finish();
+		} catch (const gc::SeedFileError& e) {
+			throw SeedFileInvalid("file " + std::to_string(index) + ": " + e.what());
+		} catch (const SeedFileInvalid& e) {
+			throw SeedFileInvalid("file " + std::to_string(index) + ": " + e.what());
+		}
+		S.messages += framer.messages();
+		S.seeds += framer.seeds();
+		check();
+	}
+
+	void finish()
+	{
+		if (n) {
+			SeedStoreArray sorted, order;
+			sorted.ensure(0, n * 8, q);
+			order.ensure(0, n * 4, q);
+			const size_t tempBytes = sfTempBytes((uint32_t)n, 0);
+			void* dTemp = temp.reserve<char>(tempBytes);
+			uint32_t* dIota = local.reserve<uint32_t>(n);
+			HIP_CHECK(hipEventRecord(e0, q));
+			HIP_CHECK(sfSortStore(q, dTemp, tempBytes, (const uint64_t*)hash.p, (uint32_t)n, (uint64_t*)sorted.p, (uint32_t*)order.p, dIota, (uint32_t*)(dBad + 1)));
+			HIP_CHECK(hipEventRecord(e1, q));
+			uint32_t distinct = 0;
+			HIP_CHECK(hipMemcpyAsync(&distinct, dBad + 1, sizeof(distinct), hipMemcpyDeviceToHost, q));
+			HIP_CHECK(hipStreamSynchronize(q));
+			float ms = 0;
+			HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+			S.sortMs = ms;
+			S.distinct = distinct;
+			S.dev.sortedHash = (const uint64_t*)sorted.handOver(S);
+			S.dev.order = (const uint32_t*)order.handOver(S);
+		}
+		hits.fit(n * sizeof(SeedHit), q); nameOff.fit(n * 8, q); nameLen.fit(n * 4, q); pool.fit(poolUsed, q);
+		S.dev.hits = (const SeedHit*)hits.handOver(S);
+		S.dev.nameOff = (const uint64_t*)nameOff.handOver(S);
+		S.dev.nameLen = (const uint32_t*)nameLen.handOver(S);
+		S.dev.namePool = (const uint8_t*)pool.handOver(S);
+		S.dev.n = (uint32_t)n;
+		S.dev.hashBits = sw.testSeedfileHashBits;
+	}
+};
+
+// the file's inflated bytes into the framer: gzip or zlib by the header, concatenated members read through (as api._file_chunks reads a read file)
+void seedFileInflate(const char* path, gc::SeedFileFramer& framer, SeedStoreBuilder& B)
+{
+	FILE* f = fopen(path, "rb");
+	if (!f) throw SeedFileUnreadable(std::string("cannot open seeds file ") + path);
+	struct Close { FILE* f; ~Close() { fclose(f); } } close { f };
+	z_stream z;
+	memset(&z, 0, sizeof(z));
+	if (inflateInit2(&z, 47) != Z_OK) throw std::runtime_error("zlib: inflateInit2 failed");
+	struct End { z_stream* z; ~End() { inflateEnd(z); } } end { &z };
+	std::vector<uint8_t> in(1 << 20), out(4 << 20);
+	bool inMember = false;
+	for (;;) {
+		const size_t got = fread(in.data(), 1, in.size(), f);
+		if (!got) break;
+		z.next_in = in.data(); z.avail_in = (uInt)got;
+		while (z.avail_in) {
+			z.next_out = out.data(); z.avail_out = (uInt)out.size();
+			const auto t0 = std::chrono::steady_clock::now();
+			const int rc = inflate(&z, Z_NO_FLUSH);
+			B.S.inflateMs += msSince(t0);
+			const size_t produced = out.size() - z.avail_out;
+			if (rc != Z_OK && rc != Z_STREAM_END && !(rc == Z_BUF_ERROR && produced)) throw SeedFileInvalid(std::string("the stream is neither gzip nor zlib, or is damaged (") + (z.msg ? z.msg : "zlib error") + ")");
+			inMember = rc != Z_STREAM_END;
+			if (produced) {
+				const auto t1 = std::chrono::steady_clock::now();
+				const double sinkBefore = B.sinkMs;
+				framer.push(out.data(), produced);
+				B.S.frameMs += msSince(t1) - (B.sinkMs - sinkBefore);
+			}
+			if (rc == Z_STREAM_END && inflateReset(&z) != Z_OK) throw std::runtime_error("zlib: inflateReset failed");
+		}
+	}
+	if (inMember) throw SeedFileInvalid("the file ends inside a compressed member");
+}
+
+int seedStoreMake(uint32_t n, const std::function<void(uint32_t, gc::SeedFileFramer&, SeedStoreBuilder&)>& feed, gc_seed_store** out)
+{
+	gc_seed_store* S = new gc_seed_store();
+	int rc = guarded([&]() {
+		try {
+			requireDevice();
+			HIP_CHECK(hipGetDevice(&S->device));
+			SeedStoreBuilder B(*S, threadStream(S->device));
+			for (uint32_t i = 0; i < n; i++) B.oneStream(i, [&](gc::SeedFileFramer& framer) { feed(i, framer, B); });
+			B.finish();
+			return (int)GC_OK;
+		} catch (const SeedFileInvalid& e) {
+			return fail(GC_ERR_INVALID, std::string("seeds file: ") + e.what());
+		} catch (const SeedFileUnreadable& e) {
+			return fail(GC_ERR_GRAPH, e.what());
+		}
+	});
+	if (rc != GC_OK) { delete S; return rc; }
+	*out = S;
+	return GC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int gc_seed_store_open(const char* const* paths, uint32_t n_paths, gc_seed_store** out)
+{
+	if (!out || (n_paths && !paths)) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	for (uint32_t i = 0; i < n_paths; i++) if (!paths[i]) return fail(GC_ERR_INVALID, "null argument");
+	return seedStoreMake(n_paths, [&](uint32_t i, gc::SeedFileFramer& framer, SeedStoreBuilder& B) { seedFileInflate(paths[i], framer, B); }, out);
+}
+
+int gc_seed_store_from_memory(const void* const* streams, const uint64_t* lens, uint32_t n, gc_seed_store** out)
+{
+	if (!out || (n && (!streams || !lens))) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	for (uint32_t i = 0; i < n; i++) if (!streams[i] && lens[i]) return fail(GC_ERR_INVALID, "null argument");
+	return seedStoreMake(n, [&](uint32_t i, gc::SeedFileFramer& framer, SeedStoreBuilder& B) {
+		const auto t0 = std::chrono::steady_clock::now();
+		const double sinkBefore = B.sinkMs;
+		if (lens[i]) framer.push((const uint8_t*)streams[i], lens[i]);
+		B.S.frameMs += msSince(t0) - (B.sinkMs - sinkBefore);
+	}, out);
+}
+
+int gc_seed_store_info(const gc_seed_store* s, gc_seed_store_stats* o)
+{
+	if (!s || !o) return fail(GC_ERR_INVALID, "null argument");
+	o->messages = s->messages; o->seeds = s->seeds; o->distinct_hashes = s->distinct; o->hbm_bytes = s->deviceBytes;
+	o->inflate_ms = s->inflateMs; o->frame_ms = s->frameMs; o->upload_ms = s->uploadMs; o->decode_ms = s->decodeMs; o->sort_ms = s->sortMs;
+	o->host_ms = s->inflateMs + s->frameMs; o->device_ms = s->decodeMs + s->sortMs;
+	return GC_OK;
+}
+void gc_seed_store_destroy(gc_seed_store* s) { delete s; }
+
+int gc_seeds_from_store(const gc_graph* G, const gc_seed_store* S, const gc_reads* R, const char* names, const uint64_t* name_off, uint64_t n_reads, gc_seeds** out)
+{
+	// host checks first: a malformed call is GC_ERR_INVALID whether or not a device is present
+	if (!G || !S || !R || !name_off || !out) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	if (n_reads != R->offsets.size() - 1) return fail(GC_ERR_INVALID, "gc_seeds_from_store: n_reads differs from the read batch's");
+	if (n_reads >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_seeds_from_store: too many reads");
+	if (name_off[0] != 0) return fail(GC_ERR_INVALID, "gc_seeds_from_store: name_off must start at 0");
+	for (uint64_t r = 0; r < n_reads; r++) if (name_off[r + 1] <= name_off[r]) return fail(GC_ERR_INVALID, "gc_seeds_from_store: read " + std::to_string(r) + " has no name and terminator byte in name_off");
+	const uint64_t nameBytes = name_off[n_reads];
+	if (nameBytes && !names) return fail(GC_ERR_INVALID, "null argument");
+	gc_seeds* H = new gc_seeds();
+	int rc = guarded([&]() {
+		requireDevice();
+		HIP_CHECK(hipGetDevice(&H->device));
+		H->readOffsets = R->offsets;
+		hipStream_t q = threadStream(H->device);
+		struct Drain { hipStream_t q; ~Drain() { (void)hipStreamSynchronize(q); } };
+		DeviceBuffer dNames, dNameOff, dFirst, dCount, dOff64, dTemp;
+		Drain drain { q };   // (before the buffers above go: nothing of this call may still be running)
+		uint8_t* pNames = dNames.reserve<uint8_t>(nameBytes);
+		uint64_t* pNameOff = dNameOff.reserve<uint64_t>(n_reads + 1);
+		uint32_t* pFirst = dFirst.reserve<uint32_t>(n_reads);
+		uint64_t* pCount = dCount.reserve<uint64_t>(n_reads + 1);
+		uint64_t* pOff64 = dOff64.reserve<uint64_t>(n_reads + 1);
+		const size_t tempBytes = sfTempBytes(0, (uint32_t)n_reads);
+		void* pTemp = dTemp.reserve<char>(tempBytes);
+		if (nameBytes) HIP_CHECK(hipMemcpyAsync(pNames, names, nameBytes, hipMemcpyHostToDevice, q));
+		HIP_CHECK(hipMemcpyAsync(pNameOff, name_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, q));
+		hipEvent_t e0 = nullptr, e1 = nullptr;
+		struct Events { hipEvent_t &a, &b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events { e0, e1 };
+		HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+		HIP_CHECK(hipEventRecord(e0, q));
+		HIP_CHECK(sfJoinCount(q, S->dev, pNames, pNameOff, (uint32_t)n_reads, pFirst, pCount));
+		HIP_CHECK(sfJoinScan(q, pTemp, tempBytes, pCount, (uint32_t)n_reads, pOff64));
+		uint64_t nHits = 0;
+		HIP_CHECK(hipMemcpyAsync(&nHits, pOff64 + n_reads, sizeof(nHits), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		if (nHits >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_seeds_from_store: 2^32 hits or more; split the batch");
+		H->nHits = nHits;
+		size_t at = 0;
+		auto part = [&](size_t bytes) { const size_t here = at; at += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return here; };
+		const size_t oOff = part((n_reads + 1) * sizeof(uint32_t)), oArrays = part(5 * nHits * sizeof(uint32_t)), oBad = part(3 * sizeof(unsigned long long)), oHits = part(nHits * sizeof(SeedHit));   // (gc_seeds_upload's layout)
+		HIP_CHECK(hipMalloc(&H->block, at));
+		char* D = (char*)H->block;
+		H->devReadHitOff = (uint32_t*)(D + oOff);
+		uint32_t* arrays = (uint32_t*)(D + oArrays);
+		H->dev = SeedHitArrays { arrays, arrays + nHits, arrays + 2 * nHits, arrays + 3 * nHits, arrays + 4 * nHits };
+		unsigned long long* dBad = (unsigned long long*)(D + oBad);   // resolve, match_len, raw_goodness
+		H->devHits = (SeedHit*)(D + oHits);
+		unsigned long long bad[3] = { ~0ull, ~0ull, ~0ull };
+		HIP_CHECK(hipMemcpyAsync(dBad, bad, sizeof(bad), hipMemcpyHostToDevice, q));
+		HIP_CHECK(sfJoinGather(q, S->dev, pNames, pNameOff, (uint32_t)n_reads, pFirst, pOff64, R->devOffsets, H->devHits, H->devReadHitOff, dBad + 1, dBad + 2));
+		const SeedLookup lookup { G->dev.origSize, G->dev.lookupOff, G->dev.lookup, G->dev.nodeOffset, (uint32_t)G->hOrigSize.size() };
+		launchSeedResolve(q, lookup, H->devHits, nHits, H->devReadHitOff, (uint32_t)n_reads, R->devOffsets, H->dev, dBad);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipEventRecord(e1, q));
+		HIP_CHECK(hipMemcpyAsync(bad, dBad, sizeof(bad), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		float ms = 0;
+		HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+		H->kernelMs = ms;
+		// gc_seeds_upload's order: its host checks read by read (a read's match_len before its raw_goodness), then the device's
+		if (bad[1] != ~0ull || bad[2] != ~0ull) {
+			const bool len = bad[1] != ~0ull && (bad[2] == ~0ull || (bad[1] >> 32) <= (bad[2] >> 32));
+			const unsigned long long b = len ? bad[1] : bad[2];
+			return fail(GC_ERR_INVALID, "gc_seeds_from_store: read " + std::to_string(b >> 32) + " hit " + std::to_string(b & 0xffffffffull) + ": " +
+				(len ? "match_len of 2^31 or more" : "raw_goodness too large for the 32-bit seed goodness (match_len + read length + raw_goodness must stay below 2^32)"));
+		}
+		if (bad[0] != ~0ull) {
+			const uint64_t i = bad[0] >> 2;
+			std::vector<uint32_t> off32(n_reads + 1);
+			HIP_CHECK(hipMemcpy(off32.data(), H->devReadHitOff, (n_reads + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+			const uint64_t r = (uint64_t)(std::upper_bound(off32.begin(), off32.end(), (uint32_t)i) - off32.begin()) - 1;
+			const char* what[] = { "", "no such node in the graph", "node_offset is not inside the original node", "seq_pos is not inside the read" };
+			return fail(GC_ERR_INVALID, "gc_seeds_from_store: read " + std::to_string(r) + " hit " + std::to_string(i - off32[r]) + ": " + what[bad[0] & 3]);
+		}
 		return (int)GC_OK;
 	});
 	if (rc != GC_OK) { delete H; return rc; }

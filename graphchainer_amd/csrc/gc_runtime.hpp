@@ -18,6 +18,7 @@
 #include "host/gc_mxm_build.hpp"
 #include "host/gc_mxm_cache.hpp"
 #include "hip/gc_mxm_core.hpp"
+#include "hip/gc_seedfile_core.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -545,6 +546,16 @@ struct gc_seeds {
 	SeedHit* devHits = nullptr;            // [nHits] the raw records in the block's tail, as uploaded or as gc_seeds_mxm wrote them (gc_seeds_hits)
 	double kernelMs = 0;                   // gc_seeds_mxm: device time from the first kernel to the last
 	~gc_seeds() { if (block) (void)hipFree(block); }
+};
+
+// the seeds of the -s files (gc_seed_store_open), decoded and sorted by name hash in HBM: read-only, shared by streams
+struct gc_seed_store {
+	int device = 0;
+	SfStoreView dev {};
+	uint64_t messages = 0, seeds = 0, distinct = 0, deviceBytes = 0;
+	double inflateMs = 0, frameMs = 0, uploadMs = 0, decodeMs = 0, sortMs = 0;
+	std::vector<void*> allocations;
+	~gc_seed_store() { for (void* p : allocations) (void)hipFree(p); }
 };
 
 // the MUM / MEM index of a graph's forward segments (gc_mxm_index_create): suffix array, packed text, segment table and prefix table in HBM; read-only, shared by streams

@@ -65,9 +65,14 @@ struct Switches {
 	size_t testPoolShrinkFloor = 64u << 20;        // GC_TEST_POOL_SHRINK_FLOOR: pools below this many spare bytes do not shrink
 	bool testResultCachePoison = false;            // GC_TEST_RESULT_CACHE_POISON: result arrays are filled with 0xA5 when handed out
 	size_t testUploadSlice = (size_t)64 << 20;     // GC_TEST_UPLOAD_SLICE: backward links per slice of the graph upload
+	size_t testSeedfilePiece = (size_t)32 << 20;   // GC_TEST_SEEDFILE_PIECE: bytes of messages per piece a seed store uploads (a longer message makes the piece grow)
+	uint32_t testSeedfileHashBits = 64;            // GC_TEST_SEEDFILE_HASH_BITS: only that many bits of a seed store's name hash are kept (1..64), to force collisions
 
 	bool shareLongScratch() const { return longToken >= 1; }   // the pass works in the device's shared scratch (whoever holds the token owns it)
 	bool onePassAtATime() const { return longToken != 0; }     // the pass takes the device's token
+
+	// the two hooks of the seed store (gc_seed_store_open); tests/test_seedfile_switches_host.py holds their cases
+	static const char* seedfileSwitch(const char* name) { return getenv(name); }
 
 	static Switches fromEnvironment()
 	{
@@ -120,6 +125,8 @@ struct Switches {
 		if (const char* e = getenv("GC_TEST_POOL_SHRINK_FLOOR")) s.testPoolShrinkFloor = (size_t)std::max(0ll, atoll(e));
 		s.testResultCachePoison = getenv("GC_TEST_RESULT_CACHE_POISON") != nullptr;
 		if (const char* e = getenv("GC_TEST_UPLOAD_SLICE")) s.testUploadSlice = (size_t)std::max(1, atoi(e));
+		if (const char* e = seedfileSwitch("GC_TEST_SEEDFILE_PIECE")) s.testSeedfilePiece = (size_t)std::max(1ll, atoll(e));
+		if (const char* e = seedfileSwitch("GC_TEST_SEEDFILE_HASH_BITS")) s.testSeedfileHashBits = (uint32_t)std::max(1, std::min(64, atoi(e)));
 		return s;
 	}
 };

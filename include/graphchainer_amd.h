@@ -323,6 +323,40 @@ int gc_mxm_cache_check(const char* cache_prefix, uint64_t* info /* [5] or NULL *
  * min_len < 2, max_count == 0, an index built from another graph; from the device: 2^31 matches or more in the batch before the cut (split the batch). */
 int gc_seeds_mxm(const gc_graph* g, const gc_mxm_index* x, const gc_reads* reads, int32_t mode, uint64_t max_count, uint32_t min_len, gc_seeds** out);
 
+/* ---- seeds from GAM files (replaces -s / --seeds-file: the loop at src/Aligner.cpp:1169-1190, its reader stream::for_each, src/stream.hpp:81-123, and the lookup by read name
+ * of Seeder::Mode::File, src/Aligner.cpp:91-94) ---------- */
+/* A seed store: every seed of the files, decoded on the device and kept in HBM under a hash of its read's name. A file is a gzip (or zlib) stream, concatenated members read
+ * through, of groups `varint64 count`, count x (`varint32 size`, vg::Alignment of size bytes). A first count of 0 ends the file, a later one is an empty group, a size of 0
+ * gives no seed, an empty stream has none. The host inflates and finds the message boundaries, piece by piece; neither side ever holds a whole inflated file. One message is
+ * one gc_seed_hit, as the reference's lambda builds it (src/Aligner.cpp:1178): node_id = (int32) path.mapping(0).position.node_id, node_offset = ...position.offset, seq_pos =
+ * query_position, match_len = raw_goodness = path.mapping(0).edit(0).from_length as uint32, reverse = ...position.is_reverse, stored under `name`, with protobuf's rules for
+ * unknown, repeated and merged fields. A node_offset or seq_pos outside 0 .. 2^32 - 2 is stored as 2^32 - 1; nothing is clamped into range (see the join below).
+ * In HBM: 48 bytes per seed and its name's bytes.
+ * GC_ERR_INVALID, with the file's index and the message's index or byte offset in gc_last_error: a stream that is neither gzip nor zlib or ends inside a member, a count or
+ * size that runs past the end of the stream, a message that does not parse (a truncated field, a varint of more than 10 bytes, a group wire type, a length that runs past the
+ * message), a message without a mapping, a mapping without an edit, 2^31 - 1 messages or more (hipCUB counts in int). A file that cannot be opened is GC_ERR_GRAPH.
+ * Read-only once made; may be shared by streams. */
+typedef struct gc_seed_store gc_seed_store;
+int gc_seed_store_open(const char* const* paths, uint32_t n_paths, gc_seed_store** out);                                     /* src/Aligner.cpp:1171-1183 */
+/* The same from streams that are inflated already (hosts with their own reader, tests). */
+int gc_seed_store_from_memory(const void* const* streams, const uint64_t* lens, uint32_t n, gc_seed_store** out);         /* src/stream.hpp:93-116 */
+typedef struct gc_seed_store_stats {
+	uint64_t messages;          /* size-prefixed messages, the empty ones among them */
+	uint64_t seeds;             /* ... that gave a seed */
+	uint64_t distinct_hashes;   /* distinct name hashes: the read names of the files, unless two collide */
+	uint64_t hbm_bytes;
+	double host_ms;             /* inflate_ms + frame_ms */
+	double device_ms;           /* decode_ms + sort_ms */
+	double inflate_ms, frame_ms, upload_ms, decode_ms, sort_ms;   /* upload: host to device copies and their waits; decode: decode, name scan and name copy kernels */
+} gc_seed_store_stats;
+int gc_seed_store_info(const gc_seed_store* s, gc_seed_store_stats* out);                                                    /* the reference prints "<n> seeds", :1182 */
+void gc_seed_store_destroy(gc_seed_store* s);
+/* The seeds of a read batch (src/Aligner.cpp:91-94): read i gets every seed stored under its name - names[name_off[i] .. name_off[i+1] - 1), each name followed by one
+ * terminator byte: gc_fastx_table's layout, so the loader's table goes in unchanged - in file order, files in the order they were given; a read without an entry gets none.
+ * The names' bytes are compared, not only their hashes. Joined and resolved on the device; the result is an ordinary gc_seeds for gc_align_batch_seeded / gc_align_batch_ext,
+ * gc_seeds_hits reads it back and gc_seeds_kernel_ms is the join's device time. GC_ERR_INVALID as gc_seeds_upload documents, naming read and hit. */
+int gc_seeds_from_store(const gc_graph* g, const gc_seed_store* store, const gc_reads* reads, const char* names, const uint64_t* name_off /* [n_reads+1] */, uint64_t n_reads, gc_seeds** out);
+
 /* ---- the hot path ---------------------------------------------------------------------------------- */
 
 /* Flat (CSR) result of one batch. All arrays are host memory owned by the result; free with
