@@ -540,34 +540,48 @@ def _file_chunks(path, gz, size):
                 yield piece
 
 
-def read_files(paths, batch_bytes=100 << 20):
-    """Generator of (batch, ids) over read files, the reference's way (src/Aligner.cpp:167-187): the format by the file name (fastx_file_format; a file of another name
-    gives nothing), .gz inflated on the host with zlib, about batch_bytes of file text per batch. A record cut by the end of a chunk is carried over to the next one, a
-    record longer than the chunk makes the chunk grow; files are never joined - the end of each file is parsed as the end of a file."""
+def file_pieces(paths, batch_bytes=100 << 20):
+    """The reader's half of read_files, free of the library (a host thread of its own may run it: read() and zlib release the GIL): generator of (fmt, piece, last) over
+    the read files in order - about batch_bytes of file text, inflated, and whether the file ends with it. A file whose name gives no format gives nothing; an empty
+    file gives one empty last piece."""
     batch_bytes = max(int(batch_bytes), 1)
     for path in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths):
         fmt, gz = fastx_file_format(path)
         if fmt is None:
             continue
-        held = b""
         pieces = _file_chunks(path, gz, batch_bytes)
-        nxt = next(pieces, None)
-        while nxt is not None:
-            held += nxt
+        piece = next(pieces, b"")
+        while True:
             nxt = next(pieces, None)
+            yield fmt, piece, nxt is None
             if nxt is None:
-                break                      # `held` runs to the end of the file
-            batch, ids, consumed = ReadBatch.from_text(held, fmt, final=False)
-            held = held[consumed:]
-            if ids:
-                yield batch, ids
-            else:
-                batch.close()              # no complete record yet: the chunk grows
-        batch, ids, _ = ReadBatch.from_text(held, fmt, final=True)
+                break
+            piece = nxt
+
+
+def parse_pieces(pieces, before_parse=None):
+    """The parser's half of read_files: generator of (batch, ids) over what file_pieces gives. A record cut by the end of a piece is carried over to the next one, a
+    record longer than the piece makes the chunk grow, and the chunk that ends a file is parsed as the end of a file. Sequential by its nature: the next chunk begins
+    where gc_reads_parse says the previous one was consumed. before_parse() is called ahead of every gc_reads_parse (the command line selects the device there)."""
+    held = b""
+    for fmt, piece, last in pieces:
+        held += piece
+        if before_parse is not None:
+            before_parse()
+        batch, ids, consumed = ReadBatch.from_text(held, fmt, final=last)
+        held = b"" if last else held[consumed:]
         if ids:
             yield batch, ids
         else:
-            batch.close()
+            batch.close()                  # no complete record yet: the chunk grows
+
+
+def read_files(paths, batch_bytes=100 << 20):
+    """Generator of (batch, ids) over read files, the reference's way (src/Aligner.cpp:167-187): the format by the file name (fastx_file_format; a file of another name
+    gives nothing), .gz inflated on the host with zlib, about batch_bytes of file text per batch. A record cut by the end of a chunk is carried over to the next one, a
+    record longer than the chunk makes the chunk grow; files are never joined - the end of each file is parsed as the end of a file. (file_pieces and parse_pieces are
+    its two halves.)"""
+    return parse_pieces(file_pieces(paths, batch_bytes))
 
 
 # gc_seed_hit (include/graphchainer_amd.h): SeedHit as a seeder hands it over, src/GraphAlignerWrapper.h:14

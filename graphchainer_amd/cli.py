@@ -1,9 +1,9 @@
 """The command line: `python -m graphchainer_amd -g graph.gfa -f reads.fq.gz -a out.gaf`, the reference's GraphChainer binary over this library.
 
 resolve(argv) -> Config turns a command line into what a run needs - the reference's option names, short forms, defaults, checks and messages
-(src/AlignerMain.cpp:35-112,138-464) - and touches neither the library nor a device. main(argv) runs it: one stream, one batch of file text at a time
-(api.read_files: the reads are parsed on the device; the alignments are encoded on the device for the writers chosen), records written in input order, every output
-file through a temporary name and a rename.
+(src/AlignerMain.cpp:35-112,138-464) - and touches neither the library nor a device. main(argv) runs it (run, over pipeline.py): a reader thread, a parse thread (the reads are parsed on the device, about
+--batch-bytes of file text per batch), up to --inflight workers per device of --devices, each with an Aligner of its own (the alignments are encoded on the device for the
+writers chosen), and a writer thread: records written in input order, every output file through a temporary name and a rename.
 
 Accepted and without effect: -t / --threads (checked >= 1), --high-memory, --verbose, --short-verbose (the progress text and the closing statistics are not
 reproduced), and --greedy-E / --greedy-score, which the reference declares and never reads. --try-all-seeds (and --all-alignments, which sets it) does what it does
@@ -38,7 +38,10 @@ OPTIONS = {
     "greedy-length": (None, None, False), "greedy-E": (None, None, False), "greedy-score": (None, None, False), "no-colinear-chaining": (None, None, False),
     # this build's own
     "batch-bytes": (None, "size", False), "device": (None, "size", False), "index-cache": (None, "string", False),
+    "inflight": (None, "size", False), "devices": (None, "string", False),
 }
+MAX_INFLIGHT = 5                   # the most the benchmark keeps in flight on a device (bench.py: BATCH_MS_BY_INFLIGHT ends there)
+MAX_DEVICES = 16                   # the library's per-device slots
 REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "generate-path", "generate-path-seed", "graph-statistics")
 SELECT = {"greedy-length": 0, "schedule-inverse-E-sum": 3, "schedule-inverse-E-product": 4, "schedule-score": 5, "schedule-length": 6, "all-alignments": 7}   # GC_SELECT_*
 
@@ -90,6 +93,10 @@ Extension parameters:
 This build's own:
   --batch-bytes arg                     bytes of read file text per batch [100 MB]
   --device arg                          GPU to run on [0]
+  --devices arg                         GPUs to run on, comma-separated (0,1,2,3; at most 16): one copy of graph and index on each, the batches go to
+                                        the one with the fewest outstanding. --device N means --devices N. (A device named twice gets two copies:
+                                        that is for testing several copies on a one-GPU box.)
+  --inflight arg                        batches in flight per GPU, >= 1 [chosen: at most 5, cut by the usable host CPUs and the device's free memory]
   --index-cache arg                     load the graph and minimizer index from this file if it exists, else build them and save them there.
                                         An existing file wins: it is checked for the minimizer length and window only, not against -g or
                                         --seeds-minimizer-ignore-frequent
@@ -119,7 +126,9 @@ class Config:
     cigar_match_mismatch: bool = False
     threads: int = 1
     batch_bytes: int = 100 << 20
-    device: int = 0
+    device: int = 0                                      # the first (or only) device
+    devices: list = field(default_factory=lambda: [0])   # one replica of graph and index per entry
+    inflight: int = 0                                    # batches in flight per replica; 0: chosen (choose_inflight)
     index_cache: str = ""
     warnings: list = field(default_factory=list)         # what the reference prints and goes on
 
@@ -294,6 +303,19 @@ def resolve(argv):
             error(f"unknown output alignment format ({path}), must be either .gaf, .gam or .json")
     if cfg.threads < 1:
         error("number of threads must be >= 1")
+    if "inflight" in vm and vm["inflight"][-1] < 1:
+        error("batches in flight (--inflight) must be >= 1")
+    devices = None
+    if "devices" in vm:
+        text = vm["devices"][-1]
+        if "device" in vm:
+            error("--device and --devices are both set: give one of them")
+        if not re.fullmatch(r"[0-9]+(,[0-9]+)*", text):
+            error(f"--devices ({text}) must be a comma-separated list of device indices, as in 0,1,2,3")
+        else:
+            devices = [int(d) for d in text.split(",")]
+            if len(devices) > MAX_DEVICES:
+                error(f"--devices names {len(devices)} devices, this build runs on at most {MAX_DEVICES}")
     if bandwidth < 1:
         error("default bandwidth must be >= 1")
     if ramp != 0 and ramp <= bandwidth:
@@ -324,7 +346,7 @@ def resolve(argv):
     # what the library's fields can hold (the reference's are size_t and long long)
     for name, value, limit in (("bandwidth", bandwidth, 1 << 31), ("ramp-bandwidth", ramp, 1 << 31), ("colinear-split-len", split_len, 1 << 31), ("colinear-split-gap", split_gap, 1 << 31),
                                ("seeds-clustersize", cfg.min_cluster_size, 1 << 31), ("seeds-mxm-length", mxm_length, 1 << 32), ("seeds-minimizer-windowsize", minimizer_window, 1 << 31),
-                               ("device", last("device", 0), 1 << 31), ("tangle-effort", 0 if max_cells == UNLIMITED else max_cells, 1 << 63)):
+                               ("device", last("device", 0), 1 << 31), ("devices", max(devices or [0]), 1 << 31), ("inflight", last("inflight", 1), 1 << 31), ("tangle-effort", 0 if max_cells == UNLIMITED else max_cells, 1 << 63)):
         if not -limit <= value < limit:
             error(f"--{name} {value} is beyond what this build can hold")
     if errors:
@@ -344,7 +366,9 @@ def resolve(argv):
         colinear_chaining=chaining, selection_method=selection, fast_mode="fast-mode" in vm,
         precise_clipping=float(cutoff) if precise else 0.0, x_drop=x_drop)
     cfg.batch_bytes = max(1, last("batch-bytes", 100 << 20))
-    cfg.device = last("device", 0)
+    cfg.devices = devices if devices is not None else [last("device", 0)]
+    cfg.device = cfg.devices[0]
+    cfg.inflight = last("inflight", 0)
     cfg.index_cache = last("index-cache", "")
     return cfg
 
@@ -377,65 +401,180 @@ class _Outputs:
         return False
 
 
+# Device memory a batch in flight is counted with ("Sizing"): the largest of its figures per read base - 190 bytes for 10 kb reads on graphs up to a
+# few hundred Mbp, 280 for 50 kb reads, 420 at 960 Mbp - and the larger of its two whole-read scratch sizes per device (21 - 27 GB). Both err towards fewer batches
+# in flight; what they still miss, the pipeline's out-of-memory retirement catches.
+BATCH_BYTES_PER_READ_BASE = 420
+LONG_SCRATCH_BYTES = 27 * 10 ** 9
+FILE_BYTES_PER_READ_BASE = {"fasta": 1, "fastq": 2}     # at least: a FASTQ record holds a quality letter per base, so a batch of B bytes of text holds at most B / 2 bases
+
+
+def usable_cpus():
+    """CPUs this process can really use: the affinity mask, cut to the cgroup's CPU bandwidth quota when there is one (as bench.py reads it)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(float(quota) / float(period) + 0.5)))
+    except (OSError, ValueError):
+        try:
+            quota = int(open("/sys/fs/cgroup/cpu/cpu.cfs_quota_us").read())
+            period = int(open("/sys/fs/cgroup/cpu/cpu.cfs_period_us").read())
+            if quota > 0 and period > 0:
+                n = min(n, max(1, int(quota / period + 0.5)))
+        except (OSError, ValueError):
+            pass
+    return max(1, n)
+
+
+def choose_inflight(cpus, free_bytes, batch_bytes, fmt, replicas=1):
+    """Batches in flight per replica when --inflight is not given; a pure function. At most MAX_INFLIGHT; one worker thread per usable CPU after one CPU for the reader
+    and one for the writer are set aside, shared among the replicas; and as many batches as fit free_bytes - the device's free memory after set-up (a replica's share of
+    it where several are on one device) - beside the whole-read scratch, a batch counted as batch_bytes of `fmt` text at BATCH_BYTES_PER_READ_BASE per base. Never below 1."""
+    by_cpu = (int(cpus) - 2) // max(1, int(replicas))
+    bases = max(1, int(batch_bytes) // FILE_BYTES_PER_READ_BASE[fmt])
+    by_memory = (int(free_bytes) - LONG_SCRATCH_BYTES) // (bases * BATCH_BYTES_PER_READ_BASE)
+    return max(1, min(MAX_INFLIGHT, by_cpu, by_memory))
+
+
+class _Replica:
+    """One device's copy of what the workers read: graph, and minimizer index, MUM/MEM index or seed store."""
+
+    def __init__(self, device):
+        self.device, self.graph, self.seeder, self.index, self.store, self.setup_seconds = device, None, None, None, None, 0.0
+
+    def close(self):
+        for thing in (self.store, self.index, self.seeder, self.graph):
+            if thing is not None:
+                thing.close()
+        self.store = self.index = self.seeder = self.graph = None
+
+
+def _setup_replicas(cfg, api, replicas):
+    """Graph and index of every replica, one after the other, as the single device has been set up. With several replicas and no --index-cache (no
+    --seeds-mxm-cache-prefix) the first one's build is saved to a temporary file the others load, so the host build runs once."""
+    import shutil
+    import tempfile
+    kind = cfg.seeder["kind"]
+    minimizer = kind == "minimizer"
+    tmp = tempfile.mkdtemp(prefix="graphchainer_amd.") if len(replicas) > 1 and (not cfg.index_cache or (kind == "mxm" and not cfg.seeder["cache_prefix"])) else None
+    try:
+        index_cache = cfg.index_cache or (os.path.join(tmp, "index.gcidx") if tmp else "")
+        mxm_prefix = (cfg.seeder["cache_prefix"] or (os.path.join(tmp, "mxm") if tmp else None)) if kind == "mxm" else None
+        for rep in replicas:
+            started = time.time()
+            api.set_device(rep.device)
+            if index_cache and os.path.exists(index_cache):
+                info = api.check_index_cache(index_cache)
+                if minimizer and (not info["has_seeder"] or (info["k"], info["w"]) != (cfg.seeder["length"], cfg.seeder["window"])):
+                    raise RuntimeError(f"{index_cache} holds no minimizer index of length {cfg.seeder['length']} and window {cfg.seeder['window']}")
+                rep.graph, cached = api.load_index_cache(index_cache)
+                if minimizer:
+                    rep.seeder = cached
+                elif cached is not None:
+                    cached.close()
+            else:
+                rep.graph = api.AlignmentGraph(cfg.graph)
+                if minimizer:
+                    rep.seeder = api.MinimizerSeeder(rep.graph, cfg.seeder["length"], cfg.seeder["window"], cfg.seeder["keep_fraction"])
+                if index_cache:
+                    api.save_index_cache(rep.graph, rep.seeder, index_cache)
+            if kind == "file":
+                rep.store = api.SeedStore(cfg.seeder["paths"])             # every file, in command-line order, before any read is aligned (src/Aligner.cpp:1169-1190)
+            elif not minimizer:
+                rep.index = api.MxmIndex(rep.graph, cache_prefix=mxm_prefix)
+            rep.setup_seconds = time.time() - started
+    finally:
+        if tmp:
+            shutil.rmtree(tmp, ignore_errors=True)
+
+
 def run(cfg, stderr=sys.stderr):
-    """Aligns cfg.reads to cfg.graph and writes cfg.outputs. Returns the counts it reports."""
+    """Aligns cfg.reads to cfg.graph and writes cfg.outputs. Returns the counts it reports. Threads (pipeline.py): one reads the files and inflates a .gz, one cuts and
+    parses (and chooses the replica of each batch before it parses it, so that the reads live on the device that aligns them), up to `inflight` workers per replica seed
+    and align with an Aligner each, one writes the batches' bytes in input order."""
     import numpy as np
 
-    from . import api
+    from . import api, pipeline
     from_file = cfg.seeder["kind"] == "file"
     if from_file and not all(os.path.exists(p) for p in cfg.seeder["paths"]):
         raise CliExit(0, "No seeds file exists\n")            # src/Aligner.cpp:1185-1186: said, and the run ends with status 0 and no output
-    api.set_device(cfg.device)
-    seeder = index = store = None
-    minimizer = cfg.seeder["kind"] == "minimizer"
-    if cfg.index_cache and os.path.exists(cfg.index_cache):
-        info = api.check_index_cache(cfg.index_cache)
-        if minimizer and (not info["has_seeder"] or (info["k"], info["w"]) != (cfg.seeder["length"], cfg.seeder["window"])):
-            raise RuntimeError(f"{cfg.index_cache} holds no minimizer index of length {cfg.seeder['length']} and window {cfg.seeder['window']}")
-        graph, cached = api.load_index_cache(cfg.index_cache)
-        seeder = cached if minimizer else None
-    else:
-        graph = api.AlignmentGraph(cfg.graph)
-        if minimizer:
-            seeder = api.MinimizerSeeder(graph, cfg.seeder["length"], cfg.seeder["window"], cfg.seeder["keep_fraction"])
-        if cfg.index_cache:
-            api.save_index_cache(graph, seeder, cfg.index_cache)
-    if from_file:
-        store = api.SeedStore(cfg.seeder["paths"])             # every file, in command-line order, before any read is aligned (src/Aligner.cpp:1169-1190)
-    elif not minimizer:
-        index = api.MxmIndex(graph, cache_prefix=cfg.seeder["cache_prefix"] or None)
+    devices = list(cfg.devices) if cfg.devices else [cfg.device]
+    replicas = [_Replica(d) for d in devices]
     # what the chosen writers need: the whole-read pass and the two edit distances that pick the winner, and the final alignments encoded on the device, where their traces
     # are - the GAF pieces (= / X items, or M items with --cigar-match-mismatch) for a .gaf, the vg::Path bytes for a .json or .gam; no trace comes down (keep_traces=0)
     formats = tuple(f for f in ("gaf", "json", "gam") if f in cfg.outputs)
     device_output = ((2 if cfg.cigar_match_mismatch else 1) if "gaf" in formats else 0) | (4 if "json" in formats or "gam" in formats else 0)
-    aligner = api.Aligner(graph, seeder, long_pass=True, edit_distances=True, keep_traces=0, device_output=device_output, **cfg.aligner)
-    aligner.params.min_cluster_size = cfg.min_cluster_size
     counts = {"reads": 0, "flagged": 0, "failed_assertion": 0, "capacity_exceeded": 0, "batches": 0, "seconds": 0.0}   # seconds: reading, aligning and writing, setup left out
-    started = time.time()
-    with _Outputs(cfg.outputs) as outputs:
-        for batch, ids in api.read_files(cfg.reads, cfg.batch_bytes):
-            try:
-                if store is not None:
-                    seeds = store.seeds(graph, batch, ids)
-                else:
-                    seeds = index.seeds(batch, cfg.seeder["mode"], count=cfg.seeder["count"], min_len=cfg.seeder["min_len"]) if index is not None else None
+
+    def make_aligner(r):
+        rep = replicas[r]
+        api.set_device(rep.device)         # the current device belongs to the thread: every call of this worker runs under it
+        aligner = api.Aligner(rep.graph, rep.seeder, long_pass=True, edit_distances=True, keep_traces=0, device_output=device_output, **cfg.aligner)
+        aligner.params.min_cluster_size = cfg.min_cluster_size
+        return aligner
+
+    def align(aligner, r, item):
+        rep, (batch, ids) = replicas[r], item
+        if rep.store is not None:
+            seeds = rep.store.seeds(rep.graph, batch, ids)
+        else:
+            seeds = rep.index.seeds(batch, cfg.seeder["mode"], count=cfg.seeder["count"], min_len=cfg.seeder["min_len"]) if rep.index is not None else None
+        try:
+            out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
+        finally:
+            if seeds is not None:
+                seeds.close()
+        failed, capacity = np.asarray(out["failed_assertion"]) != 0, np.asarray(out["capacity_exceeded"]) != 0
+        return {f: out[f] for f in formats}, len(ids), int(failed.sum()), int(capacity.sum()), int((failed | capacity).sum())
+
+    try:
+        _setup_replicas(cfg, api, replicas)
+        inflight = cfg.inflight
+        if not inflight:
+            kinds = {api.fastx_file_format(p)[0] for p in cfg.reads}
+            chosen = []
+            for rep in replicas:           # the same count for every replica: the smallest any of them can hold
+                api.set_device(rep.device)
+                free, _ = api.device_memory()
+                chosen.append(choose_inflight(usable_cpus(), free // devices.count(rep.device), cfg.batch_bytes, "fasta" if "fasta" in kinds else "fastq", len(replicas)))
+            inflight = min(chosen)
+        reader_seconds = {}
+
+        def source(choose):
+            def place():
+                api.set_device(replicas[choose()].device)
+            with pipeline.Prefetch(api.file_pieces(cfg.reads, cfg.batch_bytes), name="pipeline-reader") as pieces:
                 try:
-                    out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
+                    yield from api.parse_pieces(pieces, before_parse=place)
                 finally:
-                    if seeds is not None:
-                        seeds.close()
+                    reader_seconds.update(busy=pieces.busy, waiting_in=0.0, waiting_out=pieces.waiting_out, parse_waiting_in=pieces.consumer_waiting)
+
+        started = time.time()
+        with _Outputs(cfg.outputs) as outputs:
+            def write(result):
+                texts, reads, failed, capacity, flagged = result
                 for f in formats:
-                    outputs.write(f, out[f])
-                failed, capacity = np.asarray(out["failed_assertion"]) != 0, np.asarray(out["capacity_exceeded"]) != 0
-                counts["reads"] += len(ids)
+                    outputs.write(f, texts[f])
+                counts["reads"] += reads
                 counts["batches"] += 1
-                counts["failed_assertion"] += int(failed.sum())
-                counts["capacity_exceeded"] += int(capacity.sum())
-                counts["flagged"] += int((failed | capacity).sum())
-                del out
-            finally:
-                batch.close()
-    counts["seconds"] = time.time() - started
+                counts["failed_assertion"] += failed
+                counts["capacity_exceeded"] += capacity
+                counts["flagged"] += flagged
+
+            report = pipeline.run(source, make_aligner, align, write, replicas=len(replicas), inflight=inflight, release=lambda item: item[0].close())
+        counts["seconds"] = time.time() - started
+    finally:
+        for rep in replicas:
+            rep.close()
+    stages = report["stage_seconds"]
+    waited = reader_seconds.pop("parse_waiting_in", 0.0)
+    parse = stages["source"]
+    counts.update(inflight=inflight, devices=devices, batches_per_replica=report["items_per_replica"], retired_workers=report["retired_workers"],
+                  setup_seconds=[round(rep.setup_seconds, 3) for rep in replicas],
+                  stage_seconds={"read": {k: round(v, 6) for k, v in reader_seconds.items()},
+                                 "parse": {"busy": round(max(0.0, parse["busy"] - waited), 6), "waiting_in": round(waited, 6), "waiting_out": parse["waiting_out"]},
+                                 "align": stages["work"], "write": stages["sink"]})
     if counts["flagged"]:
         print(f"{counts['flagged']} of {counts['reads']} reads were flagged and have no alignment written: {counts['failed_assertion']} failed an assertion "
               f"(a letter outside the nucleotide alphabet among them), {counts['capacity_exceeded']} exceeded a capacity", file=stderr)
@@ -451,6 +590,7 @@ def main(argv=None):
         return e.status
     for line in cfg.warnings:
         print(line, file=sys.stderr)
+    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # before the library is loaded: a batch in flight uses a dozen streams, and several share a device
     import zlib
     try:
         run(cfg)

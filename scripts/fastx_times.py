@@ -6,10 +6,10 @@ and gated by nothing. Two JSON lines:
    Python list comprehension the tests use and handed to ReadBatch(list) (cut_ms + upload_ms); for the .gz the host's zlib inflate on its own. Three rounds after one
    warm-up round, the two ways interleaved inside a round, medians.
 2. with --command: the command line's end-to-end reads/s (reading, parsing, aligning, writing a GAF; graph and index setup left out) on bench.py's default graph and read
-   set as a FASTQ file, and bench.py --full's e2e.gaf reads/s of the same build on the same box when --bench is given too (that leg keeps batches in flight and encodes on the
-   device; the command encodes on the device too but runs one batch at a time on one stream).
+   set as a FASTQ file and as a one-member .fq.gz, for every value of --inflight (0: not given, the command chooses) with the stage times of the last round, and
+   bench.py --full's e2e.gaf reads/s of the same build on the same box when --bench is given too (that leg keeps five batches in flight and encodes on the device).
 
-    python3 scripts/fastx_times.py [--reads N] [--read-len L] [--rounds K] [--command [--backbone BP] [--bench]]"""
+    python3 scripts/fastx_times.py [--reads N] [--read-len L] [--rounds K] [--command [--inflight K ...] [--batch-bytes B] [--backbone BP] [--bench]]"""
 import argparse
 import gzip
 import json
@@ -83,14 +83,33 @@ def command_times(gca, args, tmp):
         for i, r in enumerate(reads):
             r = r if isinstance(r, bytes) else r.encode()
             f.write(b"@read%d\n" % i + r + b"\n+\n" + b"I" * len(r) + b"\n")
-    rates = []
-    for i in range(args.rounds + 1):
-        cfg = cli.resolve(["-g", gfa, "-f", fq, "-a", os.path.join(tmp, "out.gaf"), "--index-cache", cache])
-        counts = cli.run(cfg)
-        if i:
-            rates.append(counts["reads"] / counts["seconds"])
-    out = {"command_reads_per_s": round(sorted(rates)[len(rates) // 2], 1), "reads": len(reads), "read_len": args.read_len, "graph_bp": args.backbone, "rounds": args.rounds,
-           "what": "python -m graphchainer_amd -g graph.gfa -f reads.fq -a out.gaf: reading, parsing on the device, aligning, formatting and writing; one stream, one batch at a time"}
+    with open(fq, "rb") as f, gzip.open(fq + ".gz", "wb", 1) as g:       # one member, as a compressor writes it
+        while True:
+            piece = f.read(1 << 24)
+            if not piece:
+                break
+            g.write(piece)
+    legs = {"fastq": fq, "fastq_gz": fq + ".gz"}
+    rates = {leg: {k: [] for k in args.inflight} for leg in legs}
+    last = {leg: {} for leg in legs}
+    for i in range(args.rounds + 1):            # a warm-up round, then the runs alternating inside every round
+        for leg, path in legs.items():
+            for k in args.inflight:
+                argv = ["-g", gfa, "-f", path, "-a", os.path.join(tmp, "out.gaf"), "--index-cache", cache] + (["--inflight", str(k)] if k else [])
+                if args.batch_bytes:
+                    argv += ["--batch-bytes", str(args.batch_bytes)]
+                counts = cli.run(cli.resolve(argv))
+                if i:
+                    rates[leg][k].append(counts["reads"] / counts["seconds"])
+                    last[leg][k] = counts
+    name = lambda k: str(k) if k else "chosen"   # noqa: E731
+    out = {"reads": len(reads), "read_len": args.read_len, "graph_bp": args.backbone, "rounds": args.rounds, "batch_bytes": args.batch_bytes or "default",
+           "what": "python -m graphchainer_amd -g graph.gfa -f reads.fq[.gz] -a out.gaf [--inflight K]: reading, parsing on the device, aligning, formatting and writing; reads/s, "
+                   "median and every round, per batches in flight (chosen: --inflight not given)"}
+    for leg in legs:
+        out[leg] = {name(k): {"reads_per_s": round(sorted(v)[len(v) // 2], 1), "rounds": [round(x, 1) for x in v], "inflight": last[leg][k]["inflight"], "batches": last[leg][k]["batches"],
+                              "retired_workers": last[leg][k]["retired_workers"], "stage_seconds": last[leg][k]["stage_seconds"]} for k, v in rates[leg].items()}
+    out["command_reads_per_s"] = out["fastq"][name(args.inflight[-1])]["reads_per_s"]
     if args.bench:
         bench = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--no-cpu-baseline", "--setup-dir", tmp], capture_output=True, text=True,
                                timeout=args.bench_timeout)
@@ -108,6 +127,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--command", action="store_true")
     ap.add_argument("--backbone", type=int, default=50_800_000)
+    ap.add_argument("--inflight", type=int, nargs="+", default=[0], help="with --command: the --inflight values to run, each in every round (0: not given, the command chooses)")
+    ap.add_argument("--batch-bytes", type=int, default=0, help="with --command: the command's --batch-bytes (default: its own, 100 MB)")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-timeout", type=int, default=900, help="seconds the bench.py child may take")
     args = ap.parse_args()
