@@ -11,6 +11,7 @@ There is no CPU fallback: if the HIP library is missing or no GPU is visible the
 """
 import ctypes as C
 import os
+import zlib
 
 import numpy as np
 
@@ -24,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "gc_seeds_upload", "gc_seeds_destroy", "gc_seeds_hits", "gc_seeds_kernel_ms", "gc_mxm_index_create", "gc_mxm_options_default", "gc_mxm_index_open", "gc_mxm_cache_check", "gc_mxm_index_destroy", "gc_mxm_index_array", "gc_seeds_mxm", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
-    "gc_reads_parse", "gc_fastx_table_free",
+    "gc_reads_parse", "gc_fastx_table_free", "gc_bgzf_inflate", "gc_reads_parse_bgzf",
     "gc_seed_store_open", "gc_seed_store_from_memory", "gc_seed_store_info", "gc_seed_store_destroy", "gc_seeds_from_store",
 ]
 
@@ -250,6 +251,36 @@ def gzip_streams(streams, lz=False):
     return [data[int(out_off[i]):int(out_off[i + 1])] for i in range(n)]
 
 
+BGZF_REFUSED = "could not be inflated"   # GC_BGZF_REFUSED (include/graphchainer_amd.h; tests/test_inflate_host.py holds the two together)
+
+
+class BgzfError(zlib.error):
+    """A BGZF block that the device inflater refuses: what zlib.error is for a gzip member that the host's zlib refuses."""
+
+
+def _check_bgzf(rc):
+    if rc != 0:
+        text = load_library().gc_last_error().decode()
+        if rc == -1 and BGZF_REFUSED in text:                  # GC_ERR_INVALID naming the block
+            raise BgzfError(f"graphchainer_amd error {rc}: {text}")
+        raise RuntimeError(f"graphchainer_amd error {rc}: {text}")
+
+
+def bgzf_inflate(data):
+    """The whole BGZF blocks at the front of data, inflated on the device (gc_bgzf_inflate): -> (text, consumed). consumed counts compressed bytes: a trailing partial
+    block is left, a member that is not BGZF stops the walk, and 0 says that data does not start with a whole BGZF block. BgzfError names a block that does not inflate."""
+    lib = load_library()
+    data = bytes(data) if not isinstance(data, bytes) else data
+    lib.gc_bgzf_inflate.restype = C.c_int
+    lib.gc_bgzf_inflate.argtypes = [C.c_char_p, C.c_uint64, _P(C.c_void_p), _P(C.c_uint64), _P(C.c_uint64)]
+    ptr, n, consumed = C.c_void_p(), C.c_uint64(), C.c_uint64()
+    _check_bgzf(lib.gc_bgzf_inflate(data, len(data), C.byref(ptr), C.byref(n), C.byref(consumed)))
+    try:
+        return C.string_at(ptr.value, n.value), int(consumed.value)
+    finally:
+        lib.gc_free(ptr)
+
+
 def evalue(min_identity, database_size, query_size, alignment_length, num_edits):
     """{alignment score, E-value} of the --E-cutoff model (host only)."""
     lib = load_library()
@@ -460,6 +491,10 @@ class ReadBatch:
         lib.gc_fastx_table_free.restype = None
         handle, table = C.c_void_p(), _P(GcFastxTable)()
         _check(lib.gc_reads_parse(data, len(data), code, FASTX_FINAL if final else 0, C.byref(handle), C.byref(table)))
+        return cls._from_table(lib, handle, table)
+
+    @classmethod
+    def _from_table(cls, lib, handle, table):
         try:
             t = table.contents
             n = int(t.n_reads)
@@ -475,6 +510,33 @@ class ReadBatch:
             return self, ids, int(t.consumed)
         finally:
             lib.gc_fastx_table_free(table)
+
+    @classmethod
+    def from_bgzf(cls, head, data, fmt, final=True):
+        """from_text on `head` followed by the inflated whole BGZF blocks at the front of `data` (gc_reads_parse_bgzf): -> (batch, ids, tail, consumed). The blocks are
+        inflated on the device and their text is parsed where it lies; `tail` is the text behind the last complete record - the next call's head - and the only text that
+        comes down, `consumed` counts compressed bytes as bgzf_inflate's does. batch.bgzf holds the blocks, their text, and the scan, upload and kernel milliseconds."""
+        lib = load_library()
+        code = FASTX_FORMATS.get(fmt, fmt)
+        if not isinstance(code, int):
+            raise ValueError("fmt is 'fasta' or 'fastq'")
+        head = bytes(head) if not isinstance(head, bytes) else head
+        data = bytes(data) if not isinstance(data, bytes) else data
+        lib.gc_reads_parse_bgzf.restype = C.c_int
+        lib.gc_reads_parse_bgzf.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int32, C.c_uint32, _P(C.c_void_p), _P(_P(GcFastxTable)), _P(C.c_void_p), _P(C.c_uint64),
+                                            _P(C.c_uint64), _P(GcBgzfStats)]
+        lib.gc_fastx_table_free.argtypes = [_P(GcFastxTable)]
+        lib.gc_fastx_table_free.restype = None
+        handle, table, tail, tail_len, consumed, stats = C.c_void_p(), _P(GcFastxTable)(), C.c_void_p(), C.c_uint64(), C.c_uint64(), GcBgzfStats()
+        _check_bgzf(lib.gc_reads_parse_bgzf(head, len(head), data, len(data), code, FASTX_FINAL if final else 0, C.byref(handle), C.byref(table), C.byref(tail), C.byref(tail_len),
+                                            C.byref(consumed), C.byref(stats)))
+        try:
+            text = C.string_at(tail.value, tail_len.value)
+        finally:
+            lib.gc_free(tail)
+        self, ids, _ = cls._from_table(lib, handle, table)
+        self.bgzf = {"blocks": int(stats.blocks), "inflated_bytes": int(stats.inflated_bytes), "scan_ms": float(stats.scan_ms), "upload_ms": float(stats.upload_ms), "kernel_ms": float(stats.kernel_ms)}
+        return self, ids, text, int(consumed.value)
 
     def close(self):
         if self.handle:
@@ -498,6 +560,11 @@ class GcFastxTable(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class GcBgzfStats(C.Structure):
+    """gc_bgzf_stats (include/graphchainer_amd.h)."""
+    _fields_ = [("blocks", C.c_uint64), ("inflated_bytes", C.c_uint64), ("scan_ms", C.c_double), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 def fastx_file_format(path):
     """FastQ::streamFastqFromFile's choice by file name (src/fastqloader.h:98-139): ("fasta" | "fastq" | None, gzipped). None: the reference reads nothing from such a
     file and reports nothing."""
@@ -510,8 +577,69 @@ def fastx_file_format(path):
     return ("fasta" if fasta else "fastq" if fastq else None), gz
 
 
-def _file_chunks(path, gz, size):
-    """The file's bytes in pieces of about `size`; a .gz is inflated piece by piece, concatenated members included (as zstr does)."""
+class BgzfPiece(bytes):
+    """A piece of file_pieces(bgzf="device"): whole BGZF blocks, still compressed; .text_bytes is what they inflate to."""
+    text_bytes = 0
+
+
+def bgzf_member(buf, at=0):
+    """The gzip member at buf[at:] as include/graphchainer_amd.h defines a BGZF block (1f 8b 08, FLG exactly 4, a BC subfield with SLEN 2, ISIZE at most 64 KiB): (block size, ISIZE) of a
+    whole block, 0 where it may be a block that the end of buf cuts, None where it is something else."""
+    avail = len(buf) - at
+    if buf[at:at + 4] != b"\x1f\x8b\x08\x04"[:max(0, min(4, avail))]:
+        return None
+    if avail < 12:
+        return 0
+    xlen = buf[at + 10] | buf[at + 11] << 8
+    if avail < 12 + xlen:
+        return 0
+    sub, size = 0, None
+    while sub + 4 <= xlen:
+        f = at + 12 + sub
+        slen = buf[f + 2] | buf[f + 3] << 8
+        if sub + 4 + slen > xlen:
+            return None
+        if size is None and buf[f:f + 2] == b"BC" and slen == 2:
+            size = (buf[f + 4] | buf[f + 5] << 8) + 1
+        sub += 4 + slen
+    if size is None or sub != xlen or size < 12 + xlen + 8:
+        return None
+    if avail < size:
+        return 0
+    isize = int.from_bytes(buf[at + size - 4:at + size], "little")
+    return (size, isize) if isize <= 65536 else None               # more text than a BGZF block holds: an ordinary member, zlib's
+
+
+def _bgzf_chunks(f, size):
+    """The whole BGZF blocks at the front of the open file, compressed, in pieces of about `size` bytes of text (the ISIZE sum); returns the file's bytes already read
+    behind them: empty at a clean end, else a member that is not a whole BGZF block, which is the host's from there on."""
+    raw, start, at, text = b"", 0, 0, 0
+    while True:
+        got = bgzf_member(raw, at)
+        if got == 0:
+            more = f.read(max(size // 4, 1 << 16))
+            if not more:
+                break
+            raw, at, start = raw[start:] + more, at - start, 0
+            continue
+        if got is None:
+            break
+        at += got[0]
+        text += got[1]
+        if text >= size:
+            piece = BgzfPiece(raw[start:at])
+            piece.text_bytes, start, text = text, at, 0
+            yield piece
+    if at > start:
+        piece = BgzfPiece(raw[start:at])
+        piece.text_bytes = text
+        yield piece
+    return raw[at:]
+
+
+def _file_chunks(path, gz, size, bgzf="host"):
+    """The file's bytes in pieces of about `size`; a .gz is inflated piece by piece, concatenated members included (as zstr does). bgzf="device": the BGZF blocks at the
+    front of a .gz are given as they are (BgzfPiece), and zlib takes over at the first member that is not one."""
     with open(path, "rb") as f:
         if not gz:
             while True:
@@ -519,9 +647,11 @@ def _file_chunks(path, gz, size):
                 if not piece:
                     return
                 yield piece
-        import zlib
+        raw = b""
+        if bgzf == "device":
+            raw = yield from _bgzf_chunks(f, size)
         inflate = zlib.decompressobj(47)   # gzip or zlib header, by itself
-        raw, started = b"", False   # started: inside a member
+        started = False   # started: inside a member
         while True:
             if not raw:
                 raw = f.read(max(size // 4, 1 << 16))
@@ -540,16 +670,20 @@ def _file_chunks(path, gz, size):
                 yield piece
 
 
-def file_pieces(paths, batch_bytes=100 << 20):
+def file_pieces(paths, batch_bytes=100 << 20, bgzf="host"):
     """The reader's half of read_files, free of the library (a host thread of its own may run it: read() and zlib release the GIL): generator of (fmt, piece, last) over
     the read files in order - about batch_bytes of file text, inflated, and whether the file ends with it. A file whose name gives no format gives nothing; an empty
-    file gives one empty last piece."""
+    file gives one empty last piece. bgzf="device": a .gz whose first member is a BGZF block gives its whole blocks still compressed, as BgzfPiece, cut where their
+    ISIZE sum reaches about batch_bytes - parse_pieces inflates them on the device; from a member that is not BGZF on (an ordinary gzip member appended to a BGZF file)
+    the rest of the file is inflated here as under "host", the default, under which every .gz is."""
+    if bgzf not in ("host", "device"):
+        raise ValueError("bgzf is 'host' or 'device'")
     batch_bytes = max(int(batch_bytes), 1)
     for path in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths):
         fmt, gz = fastx_file_format(path)
         if fmt is None:
             continue
-        pieces = _file_chunks(path, gz, batch_bytes)
+        pieces = _file_chunks(path, gz, batch_bytes, bgzf)
         piece = next(pieces, b"")
         while True:
             nxt = next(pieces, None)
@@ -559,29 +693,38 @@ def file_pieces(paths, batch_bytes=100 << 20):
             piece = nxt
 
 
-def parse_pieces(pieces, before_parse=None):
+def parse_pieces(pieces, before_parse=None, counts=None):
     """The parser's half of read_files: generator of (batch, ids) over what file_pieces gives. A record cut by the end of a piece is carried over to the next one, a
     record longer than the piece makes the chunk grow, and the chunk that ends a file is parsed as the end of a file. Sequential by its nature: the next chunk begins
-    where gc_reads_parse says the previous one was consumed. before_parse() is called ahead of every gc_reads_parse (the command line selects the device there)."""
+    where gc_reads_parse says the previous one was consumed. before_parse() is called ahead of every gc_reads_parse (the command line selects the device there). A
+    BgzfPiece goes through gc_reads_parse_bgzf with the carried text as its head; counts, a dict, gains the blocks inflated there under "bgzf_blocks"."""
     held = b""
     for fmt, piece, last in pieces:
-        held += piece
         if before_parse is not None:
             before_parse()
-        batch, ids, consumed = ReadBatch.from_text(held, fmt, final=last)
-        held = b"" if last else held[consumed:]
+        if isinstance(piece, BgzfPiece):
+            batch, ids, tail, consumed = ReadBatch.from_bgzf(held, piece, fmt, final=last)
+            if consumed != len(piece):
+                raise RuntimeError("parse_pieces: a piece of whole BGZF blocks was not consumed whole")
+            if counts is not None:
+                counts["bgzf_blocks"] = counts.get("bgzf_blocks", 0) + batch.bgzf["blocks"]
+            held = b"" if last else tail
+        else:
+            held += piece
+            batch, ids, consumed = ReadBatch.from_text(held, fmt, final=last)
+            held = b"" if last else held[consumed:]
         if ids:
             yield batch, ids
         else:
             batch.close()                  # no complete record yet: the chunk grows
 
 
-def read_files(paths, batch_bytes=100 << 20):
+def read_files(paths, batch_bytes=100 << 20, bgzf="host"):
     """Generator of (batch, ids) over read files, the reference's way (src/Aligner.cpp:167-187): the format by the file name (fastx_file_format; a file of another name
     gives nothing), .gz inflated on the host with zlib, about batch_bytes of file text per batch. A record cut by the end of a chunk is carried over to the next one, a
     record longer than the chunk makes the chunk grow; files are never joined - the end of each file is parsed as the end of a file. (file_pieces and parse_pieces are
     its two halves.)"""
-    return parse_pieces(file_pieces(paths, batch_bytes))
+    return parse_pieces(file_pieces(paths, batch_bytes, bgzf))
 
 
 # gc_seed_hit (include/graphchainer_amd.h): SeedHit as a seeder hands it over, src/GraphAlignerWrapper.h:14

@@ -505,7 +505,7 @@ def run(cfg, stderr=sys.stderr):
     # are - the GAF pieces (= / X items, or M items with --cigar-match-mismatch) for a .gaf, the vg::Path bytes for a .json or .gam; no trace comes down (keep_traces=0)
     formats = tuple(f for f in ("gaf", "json", "gam") if f in cfg.outputs)
     device_output = ((2 if cfg.cigar_match_mismatch else 1) if "gaf" in formats else 0) | (4 if "json" in formats or "gam" in formats else 0)
-    counts = {"reads": 0, "flagged": 0, "failed_assertion": 0, "capacity_exceeded": 0, "batches": 0, "seconds": 0.0}   # seconds: reading, aligning and writing, setup left out
+    counts = {"reads": 0, "flagged": 0, "failed_assertion": 0, "capacity_exceeded": 0, "batches": 0, "seconds": 0.0, "bgzf_blocks": 0}   # seconds: reading, aligning and writing, setup left out
 
     def make_aligner(r):
         rep = replicas[r]
@@ -544,9 +544,9 @@ def run(cfg, stderr=sys.stderr):
         def source(choose):
             def place():
                 api.set_device(replicas[choose()].device)
-            with pipeline.Prefetch(api.file_pieces(cfg.reads, cfg.batch_bytes), name="pipeline-reader") as pieces:
+            with pipeline.Prefetch(api.file_pieces(cfg.reads, cfg.batch_bytes, bgzf="device"), name="pipeline-reader") as pieces:
                 try:
-                    yield from api.parse_pieces(pieces, before_parse=place)
+                    yield from api.parse_pieces(pieces, before_parse=place, counts=counts)
                 finally:
                     reader_seconds.update(busy=pieces.busy, waiting_in=0.0, waiting_out=pieces.waiting_out, parse_waiting_in=pieces.consumer_waiting)
 

@@ -3,6 +3,7 @@
 #include "host/gc_stageclock.hpp"
 #include "hip/gc_seedhits_core.hpp"
 #include "hip/gc_fastx_core.hpp"
+#include "hip/gc_inflate_core.hpp"
 #include "host/gc_seedfile_frame.hpp"
 #include <malloc.h>
 #include <zlib.h>
@@ -980,21 +981,23 @@ int gc_reads_upload(const char* bases, const uint64_t* offsets, uint64_t n, gc_r
 }
 void gc_reads_destroy(gc_reads* r) { delete r; }
 
-// FASTA / FASTQ text -> the read batch gc_reads_upload builds from the same reads, and the host's table of them. The text goes up once; lines, roles, records, the
-// compacted bases and the ids are made on the device (hip/gc_fastx.hip); the per-read layout needs the lengths on the host, so the offsets come down before the gather.
-int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flags, gc_reads** reads, gc_fastx_table** table)
+// Where the text of a parse comes from. place() puts the len bytes at devText with work on q (pinnedText [len] is the call's staging block, free until the tables are built)
+// and returns the text's last byte (any value for an empty text); done(), if set, runs once the tables are built, while the text still lies on the device.
+struct FxSource {
+	uint32_t len = 0;
+	std::function<char(char* devText, char* pinnedText, hipStream_t q, int device)> place;
+	std::function<void(const char* devText, uint32_t consumed, hipStream_t q)> done;
+};
+struct InvalidInput : std::runtime_error { using std::runtime_error::runtime_error; };   // GC_ERR_INVALID from inside a guarded call
+
+// gc_reads_parse and gc_reads_parse_bgzf from the point where the text lies on the device
+static int readsParseFrom(const FxSource& src, int32_t format, uint32_t flags, gc_reads** reads, gc_fastx_table** table)
 {
-	// host checks first: a malformed call is GC_ERR_INVALID whether or not a device is present
-	if (!reads || !table || (!text && len)) return fail(GC_ERR_INVALID, "null argument");
-	*reads = nullptr; *table = nullptr;
-	if (format != GC_FASTX_FASTA && format != GC_FASTX_FASTQ) return fail(GC_ERR_INVALID, "gc_reads_parse: format is GC_FASTX_FASTA or GC_FASTX_FASTQ");
-	if (flags & ~(uint32_t)GC_FASTX_FINAL) return fail(GC_ERR_INVALID, "gc_reads_parse: unknown flag bits");
-	if (len >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_reads_parse: the loader uses 32-bit positions: split the text into chunks below 2^32 - 16 bytes");
-	static_assert(GC_FASTX_FASTA == gcdev::FX_FASTA && GC_FASTX_FASTQ == gcdev::FX_FASTQ && GC_FASTX_FINAL == gcdev::FX_FINAL, "the header's constants are the kernels'");
+	const uint64_t len = src.len;
 	gc_reads* R = new gc_reads();
 	gc_fastx_table* T = nullptr;
 	hipStream_t uploadStream = nullptr;
-	int rc = guarded([&]() {
+	auto body = [&]() {
 		requireDevice();
 		using namespace gcdev;
 		HIP_CHECK(hipGetDevice(&R->device));
@@ -1023,7 +1026,7 @@ int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flag
 		textBlock.p = g_readDeviceBlocks.get(pinnedBytes, device, textBlock.bytes);
 		char* devText = (char*)textBlock.p;
 		uint32_t* devMeta = (uint32_t*)(devText + hMeta);
-		if (L) { memcpy(H, text, L); HIP_CHECK(hipMemcpyAsync(devText, H, L, hipMemcpyHostToDevice, q)); }
+		const char lastByte = src.place(devText, H, q, device);
 		HIP_CHECK(hipEventRecord(ev.a, q));
 		HIP_CHECK(fxCountNewlines(q, devText, L, devMeta));
 		HIP_CHECK(hipEventRecord(ev.b, q));
@@ -1035,7 +1038,7 @@ int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flag
 		v.text = devText; v.len = L; v.format = format; v.final = final ? 1u : 0u;
 		v.nNewlines = hostMeta[FX_META_NEWLINES];
 		if (v.nNewlines > L) throw std::runtime_error("gc_reads_parse: more newlines than bytes");
-		v.nLines = v.nNewlines + (final && L && text[L - 1] != '\n' ? 1u : 0u);
+		v.nLines = v.nNewlines + (final && L && lastByte != '\n' ? 1u : 0u);
 
 		// ---- 2: line table, roles, destinations; the counts come down ----
 		// device: per line, then per record (at most one per line), then the ids (every id with its NUL is as long as its header line: at most L bytes in all), then the scans' scratch
@@ -1138,6 +1141,7 @@ int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flag
 		HIP_CHECK(hipStreamSynchronize(q));
 		addSegment();
 		if (n) memcpy(R->invalid.data(), S + sInvalid, n);
+		if (src.done) src.done(devText, consumed, q);
 
 		// ---- the host's table: one allocation, the struct | offsets | name_off | bases | names ----
 		const size_t tHead = (sizeof(gc_fastx_table) + 15) & ~(size_t)15, tArr = (n + 1) * sizeof(uint64_t);
@@ -1153,7 +1157,8 @@ int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flag
 		if (namesBytes) memcpy(T->names, H + total, namesBytes);
 		T->names[namesBytes] = 0;
 		return (int)GC_OK;
-	});
+	};
+	int rc = guarded([&]() { try { return body(); } catch (const InvalidInput& e) { return fail(GC_ERR_INVALID, e.what()); } });
 	if (rc != GC_OK) {
 		if (uploadStream) (void)hipStreamSynchronize(uploadStream);
 		delete R;
@@ -1164,7 +1169,174 @@ int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flag
 	*table = T;
 	return GC_OK;
 }
+
+// FASTA / FASTQ text -> the read batch gc_reads_upload builds from the same reads, and the host's table of them. The text goes up once; lines, roles, records, the
+// compacted bases and the ids are made on the device (hip/gc_fastx.hip); the per-read layout needs the lengths on the host, so the offsets come down before the gather.
+int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flags, gc_reads** reads, gc_fastx_table** table)
+{
+	// host checks first: a malformed call is GC_ERR_INVALID whether or not a device is present
+	if (!reads || !table || (!text && len)) return fail(GC_ERR_INVALID, "null argument");
+	*reads = nullptr; *table = nullptr;
+	if (format != GC_FASTX_FASTA && format != GC_FASTX_FASTQ) return fail(GC_ERR_INVALID, "gc_reads_parse: format is GC_FASTX_FASTA or GC_FASTX_FASTQ");
+	if (flags & ~(uint32_t)GC_FASTX_FINAL) return fail(GC_ERR_INVALID, "gc_reads_parse: unknown flag bits");
+	if (len >= 0xfffffff0ull) return fail(GC_ERR_INVALID, "gc_reads_parse: the loader uses 32-bit positions: split the text into chunks below 2^32 - 16 bytes");
+	static_assert(GC_FASTX_FASTA == gcdev::FX_FASTA && GC_FASTX_FASTQ == gcdev::FX_FASTQ && GC_FASTX_FINAL == gcdev::FX_FINAL, "the header's constants are the kernels'");
+	FxSource src;
+	src.len = (uint32_t)len;
+	src.place = [&](char* devText, char* pinnedText, hipStream_t q, int) {
+		if (!len) return '\n';
+		memcpy(pinnedText, text, len);
+		HIP_CHECK(hipMemcpyAsync(devText, pinnedText, len, hipMemcpyHostToDevice, q));
+		return text[len - 1];
+	};
+	return readsParseFrom(src, format, flags, reads, table);
+}
 void gc_fastx_table_free(gc_fastx_table* t) { free(t); }
+
+// ---- BGZF: the whole blocks at the front of a compressed piece, inflated on the device (hip/gc_inflate.hip) --------------
+namespace {
+
+struct BgzfScan {
+	std::vector<gcdev::InfBlock> blocks;   // inOff from the piece's start, outOff from the text's start (behind the head)
+	std::vector<uint64_t> starts;          // of every block in the piece
+	uint64_t consumed = 0, textBytes = 0;
+};
+
+// walks the BSIZE chain up to the first member that is not a whole BGZF block
+static void bgzfScan(const uint8_t* data, uint64_t len, uint64_t headLen, BgzfScan& s)
+{
+	using namespace gcdev;
+	while (s.consumed < len) {
+		InfBlock b;
+		uint32_t size = 0;
+		if (infHeader(data + s.consumed, len - s.consumed, b, size) != INF_FRAME_BLOCK) break;
+		b.inOff += s.consumed;
+		b.outOff = headLen + s.textBytes;
+		s.blocks.push_back(b);
+		s.starts.push_back(s.consumed);
+		s.textBytes += b.isize;
+		s.consumed += size;
+	}
+}
+
+struct BgzfHeld { BlockCache* cache; void* p = nullptr; size_t bytes = 0; int device = 0; hipStream_t q = nullptr;
+	~BgzfHeld() { if (p) { (void)hipStreamSynchronize(q); cache->put(p, bytes, device); } } };   // (waits: a copy or kernel of a failed call may still use the block)
+
+// The blocks of the scan from data into devText (outOff counts from there), with work on q; waits for it. Throws InvalidInput naming the first bad block. lastByte, if
+// asked for, is the byte at devText[lastAt]. Times: the copy to the staging block and up (uploadMs), the kernel (kernelMs).
+static void bgzfInflateTo(hipStream_t q, int device, const uint8_t* data, const BgzfScan& s, uint8_t* devText, uint64_t lastAt, char* lastByte, double& uploadMs, double& kernelMs)
+{
+	using namespace gcdev;
+	const size_t nBlocks = s.blocks.size();
+	auto round = [](size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; };
+	const size_t oTable = round(s.consumed), oStatus = oTable + round(nBlocks * sizeof(InfBlock)), total = oStatus + round(nBlocks * sizeof(uint32_t) + 16);
+	BgzfHeld dev { &g_readDeviceBlocks, nullptr, 0, device, q }, pin { &g_readPinnedBlocks, nullptr, 0, device, q };
+	struct Events { hipEvent_t a = nullptr, b = nullptr, c = nullptr; ~Events() { for (hipEvent_t e : { a, b, c }) if (e) (void)hipEventDestroy(e); } } ev;
+	HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); HIP_CHECK(hipEventCreate(&ev.c));
+	pin.p = g_readPinnedBlocks.get(total, device, pin.bytes);
+	dev.p = g_readDeviceBlocks.get(total, device, dev.bytes);
+	uint8_t* H = (uint8_t*)pin.p;
+	uint8_t* D = (uint8_t*)dev.p;
+	const auto t0 = std::chrono::steady_clock::now();
+	memcpy(H, data, s.consumed);
+	if (nBlocks) memcpy(H + oTable, s.blocks.data(), nBlocks * sizeof(InfBlock));
+	const double stageMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	uint32_t* hostStatus = (uint32_t*)(H + oStatus);
+	HIP_CHECK(hipEventRecord(ev.a, q));
+	HIP_CHECK(hipMemcpyAsync(D, H, oStatus, hipMemcpyHostToDevice, q));
+	HIP_CHECK(hipMemsetAsync(D + oStatus, 0xff, nBlocks * sizeof(uint32_t) + 16, q));
+	HIP_CHECK(hipEventRecord(ev.b, q));
+	HIP_CHECK(infLaunch(q, D, (const InfBlock*)(D + oTable), (uint32_t)nBlocks, devText, (uint32_t*)(D + oStatus)));
+	HIP_CHECK(hipEventRecord(ev.c, q));
+	HIP_CHECK(hipMemcpyAsync(hostStatus, D + oStatus, nBlocks * sizeof(uint32_t) + 16, hipMemcpyDeviceToHost, q));
+	char* hostLast = (char*)(H + oStatus + nBlocks * sizeof(uint32_t));   // (the 16 spare bytes behind the status words)
+	if (lastByte) HIP_CHECK(hipMemcpyAsync(hostLast, devText + lastAt, 1, hipMemcpyDeviceToHost, q));
+	HIP_CHECK(hipStreamSynchronize(q));
+	float ms = 0;
+	HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b)); uploadMs = stageMs + ms;
+	HIP_CHECK(hipEventElapsedTime(&ms, ev.b, ev.c)); kernelMs = ms;
+	for (size_t i = 0; i < nBlocks; i++) if (hostStatus[i] != INF_OK)
+		throw InvalidInput("BGZF block " + std::to_string(i) + " at byte " + std::to_string(s.starts[i]) + " " GC_BGZF_REFUSED ": " + infStatusName(hostStatus[i]));
+	if (lastByte) *lastByte = *hostLast;
+}
+
+} // namespace
+
+int gc_bgzf_inflate(const void* data, uint64_t len, void** out, uint64_t* out_len, uint64_t* consumed)
+{
+	if (!out || !out_len || !consumed || (!data && len)) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr; *out_len = 0; *consumed = 0;
+	char* text = nullptr;
+	int rc = guarded([&]() {
+		try {
+			BgzfScan s;
+			bgzfScan((const uint8_t*)data, len, 0, s);
+			text = (char*)malloc(s.textBytes + 1);
+			if (!text) throw std::runtime_error("gc_bgzf_inflate: out of host memory");
+			text[s.textBytes] = 0;
+			if (s.blocks.empty()) { *consumed = 0; return (int)GC_OK; }
+			requireDevice();
+			int device = 0;
+			HIP_CHECK(hipGetDevice(&device));
+			hipStream_t q = threadStream(device);
+			BgzfHeld devText { &g_readDeviceBlocks, nullptr, 0, device, q };
+			devText.p = g_readDeviceBlocks.get(s.textBytes + 256, device, devText.bytes);
+			double uploadMs = 0, kernelMs = 0;
+			bgzfInflateTo(q, device, (const uint8_t*)data, s, (uint8_t*)devText.p, 0, nullptr, uploadMs, kernelMs);
+			if (s.textBytes) HIP_CHECK(hipMemcpyAsync(text, devText.p, s.textBytes, hipMemcpyDeviceToHost, q));
+			HIP_CHECK(hipStreamSynchronize(q));
+			*out_len = s.textBytes; *consumed = s.consumed;
+			return (int)GC_OK;
+		} catch (const InvalidInput& e) { return fail(GC_ERR_INVALID, std::string("gc_bgzf_inflate: ") + e.what()); }
+	});
+	if (rc != GC_OK) { free(text); *out_len = 0; *consumed = 0; return rc; }
+	*out = text;
+	return GC_OK;
+}
+
+int gc_reads_parse_bgzf(const char* head, uint64_t head_len, const void* data, uint64_t len, int32_t format, uint32_t flags,
+	gc_reads** reads, gc_fastx_table** table, char** tail, uint64_t* tail_len, uint64_t* consumed, gc_bgzf_stats* stats)
+{
+	if (!reads || !table || !tail || !tail_len || !consumed || (!head && head_len) || (!data && len)) return fail(GC_ERR_INVALID, "null argument");
+	*reads = nullptr; *table = nullptr; *tail = nullptr; *tail_len = 0; *consumed = 0;
+	if (stats) *stats = gc_bgzf_stats {};
+	if (format != GC_FASTX_FASTA && format != GC_FASTX_FASTQ) return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: format is GC_FASTX_FASTA or GC_FASTX_FASTQ");
+	if (flags & ~(uint32_t)GC_FASTX_FINAL) return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: unknown flag bits");
+	BgzfScan s;
+	const auto t0 = std::chrono::steady_clock::now();
+	try { bgzfScan((const uint8_t*)data, len, head_len, s); }
+	catch (const InvalidInput& e) { return fail(GC_ERR_INVALID, std::string("gc_reads_parse_bgzf: ") + e.what()); }
+	catch (const std::exception& e) { return fail(GC_ERR_INTERNAL, e.what()); }
+	const double scanMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	if (head_len >= 0xfffffff0ull || head_len + s.textBytes >= 0xfffffff0ull)
+		return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: the loader uses 32-bit positions: head and inflated text must stay below 2^32 - 16 bytes");
+	double uploadMs = 0, kernelMs = 0;
+	char* tailMem = nullptr;
+	uint64_t tailBytes = 0;
+	FxSource src;
+	src.len = (uint32_t)(head_len + s.textBytes);
+	src.place = [&](char* devText, char* pinnedText, hipStream_t q, int device) {
+		if (head_len) { memcpy(pinnedText, head, head_len); HIP_CHECK(hipMemcpyAsync(devText, pinnedText, head_len, hipMemcpyHostToDevice, q)); }
+		char last = head_len ? head[head_len - 1] : '\n';
+		if (!s.blocks.empty()) {
+			try { bgzfInflateTo(q, device, (const uint8_t*)data, s, (uint8_t*)devText, src.len ? src.len - 1 : 0, s.textBytes ? &last : nullptr, uploadMs, kernelMs); }
+			catch (const InvalidInput& e) { throw InvalidInput(std::string("gc_reads_parse_bgzf: ") + e.what()); }
+		}
+		return last;
+	};
+	src.done = [&](const char* devText, uint32_t textConsumed, hipStream_t q) {
+		tailBytes = src.len - textConsumed;
+		tailMem = (char*)malloc(tailBytes + 1);
+		if (!tailMem) throw std::runtime_error("gc_reads_parse_bgzf: out of host memory");
+		if (tailBytes) { HIP_CHECK(hipMemcpyAsync(tailMem, devText + textConsumed, tailBytes, hipMemcpyDeviceToHost, q)); HIP_CHECK(hipStreamSynchronize(q)); }
+		tailMem[tailBytes] = 0;
+	};
+	const int rc = readsParseFrom(src, format, flags, reads, table);
+	if (rc != GC_OK) { free(tailMem); return rc; }
+	*tail = tailMem; *tail_len = tailBytes; *consumed = s.consumed;
+	if (stats) { stats->blocks = s.blocks.size(); stats->inflated_bytes = s.textBytes; stats->scan_ms = scanMs; stats->upload_ms = uploadMs; stats->kernel_ms = kernelMs; }
+	return GC_OK;
+}
 
 // ---- seed hits from the host's own seeder -------------------------------------------------------------------
 int gc_seeds_upload(const gc_graph* G, const gc_reads* R, const gc_seed_hit* hits, const uint64_t* read_hit_off, uint64_t n_reads, gc_seeds** out)

@@ -236,6 +236,35 @@ typedef struct gc_fastx_table {
 int gc_reads_parse(const char* text, uint64_t len, int32_t format, uint32_t flags, gc_reads** reads, gc_fastx_table** table);
 void gc_fastx_table_free(gc_fastx_table* t);
 
+/* BGZF - the blocked gzip that bgzip, htslib and `samtools fastq` write: a chain of gzip members of at most 64 KiB of text each, every member independent of the others and
+ * with its compressed size in its header. A BGZF member here is 1f 8b 08, FLG exactly 4, a BC subfield with SLEN 2 and an ISIZE of at most 64 KiB. The blocks are inflated on the device, one
+ * wavefront per block (hip/gc_inflate.hip), under zlib's acceptance rules and with the CRC-32 and ISIZE of every block checked there; any other gzip is the caller's.
+ *
+ * gc_bgzf_inflate: inflates the whole blocks at the front of data[0 .. len) and hands their text back in *out (malloc'd, *out_len bytes and a NUL; free with gc_free).
+ * *consumed is the compressed size of those blocks: a trailing partial block is left for the next call, and a member that is not BGZF stops the walk there, so
+ * *consumed == 0 (with *out_len 0, and no device needed) says that the data does not start with a whole BGZF block.
+ *
+ * gc_reads_parse_bgzf: gc_reads_parse on the text `head` followed by the inflated whole blocks at the front of data. head is plain text carried over from the call
+ * before (the *tail it returned); the text is put together in HBM and parsed there by gc_reads_parse's kernels under the same chunk protocol and flags, and never comes
+ * down: only *tail does, the text behind the table's consumed (the record cut by the end; malloc'd, NUL behind *tail_len bytes, gc_free), which is the next call's head.
+ * table->consumed counts bytes of head + inflated text, *consumed counts compressed bytes as in gc_bgzf_inflate. head_len plus the inflated text must stay below
+ * 2^32 - 16. stats, if not NULL: the blocks, their text, and where the time went.
+ *
+ * Both: GC_ERR_INVALID for a block that does not inflate (a bad deflate stream, a length or CRC that differs); gc_last_error names the first such block's index and its
+ * byte offset in data and holds the words of GC_BGZF_REFUSED, by which a caller tells this refusal from GC_ERR_INVALID's other causes. Nothing is returned then, and
+ * the device stays usable. */
+#define GC_BGZF_REFUSED "could not be inflated"
+typedef struct gc_bgzf_stats {
+	uint64_t blocks;          /* whole blocks inflated */
+	uint64_t inflated_bytes;  /* their text */
+	double scan_ms;           /* host: the walk over the block headers */
+	double upload_ms;         /* the compressed bytes to the staging block and up */
+	double kernel_ms;         /* the inflate kernel (the loader's kernels are in table->kernel_ms) */
+} gc_bgzf_stats;
+int gc_bgzf_inflate(const void* data, uint64_t len, void** out, uint64_t* out_len, uint64_t* consumed);
+int gc_reads_parse_bgzf(const char* head, uint64_t head_len, const void* data, uint64_t len, int32_t format, uint32_t flags,
+                        gc_reads** reads, gc_fastx_table** table, char** tail, uint64_t* tail_len, uint64_t* consumed, gc_bgzf_stats* stats /* may be NULL */);
+
 /* ---- seed hits from the host's own seeder ----------------------------------------------------------- */
 /* SeedHit as a seeder hands it over (src/GraphAlignerWrapper.h:14): what Seeder::getSeeds returns whether the hits come from minimizers, MUM / MEM matches or a
  * seeds file (src/Aligner.cpp:87-108), before OrderSeeds. */

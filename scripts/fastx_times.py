@@ -2,11 +2,13 @@
 """Times of the device FASTA / FASTQ loader (ReadBatch.from_text, gc_reads_parse) on about 100 MB of 10 kb reads, beside the host's way to the same batch. Not bench.py
 and gated by nothing. Two JSON lines:
 
-1. per input (FASTA of width 60, FASTQ, FASTQ.gz): the text's bytes; from_text's wall milliseconds and the loader's kernel_ms; the same reads cut from the text by the
+1. per input (FASTA of width 60, FASTQ, FASTQ.gz, and the FASTQ as BGZF - see below): the text's bytes; from_text's wall milliseconds and the loader's kernel_ms; the same reads cut from the text by the
    Python list comprehension the tests use and handed to ReadBatch(list) (cut_ms + upload_ms); for the .gz the host's zlib inflate on its own. Three rounds after one
-   warm-up round, the two ways interleaved inside a round, medians.
+   warm-up round, the two ways interleaved inside a round, medians. The BGZF file (blocks of 65 280 bytes of text at zlib level 1, as the .gz) has a row of its own,
+   "fastq_bgzf": ReadBatch.from_bgzf's wall milliseconds with the inflater's scan, upload and kernel milliseconds and the loader's kernel_ms, beside the host's zlib over
+   the same file followed by from_text.
 2. with --command: the command line's end-to-end reads/s (reading, parsing, aligning, writing a GAF; graph and index setup left out) on bench.py's default graph and read
-   set as a FASTQ file and as a one-member .fq.gz, for every value of --inflight (0: not given, the command chooses) with the stage times of the last round, and
+   set as a FASTQ file, as a one-member .fq.gz and as a BGZF .fq.gz, for every value of --inflight (0: not given, the command chooses) with the stage times of the last round, and
    bench.py --full's e2e.gaf reads/s of the same build on the same box when --bench is given too (that leg keeps five batches in flight and encodes on the device).
 
     python3 scripts/fastx_times.py [--reads N] [--read-len L] [--rounds K] [--command [--inflight K ...] [--batch-bytes B] [--backbone BP] [--bench]]"""
@@ -14,6 +16,7 @@ import argparse
 import gzip
 import json
 import os
+import struct
 import subprocess
 import sys
 import tempfile
@@ -22,6 +25,55 @@ import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def bgzf_compress(data, level=1, block=65280):
+    """data as bgzip frames it: gzip members of `block` bytes of text with their size in a BC subfield, and the empty block at the end."""
+    out = []
+    for k in list(range(0, len(data), block)) + [None]:
+        piece = data[k:k + block] if k is not None else b""
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        cdata = c.compress(piece) + c.flush()
+        out.append(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(cdata) + 25) + cdata + struct.pack("<II", zlib.crc32(piece), len(piece)))
+    return b"".join(out)
+
+
+def inflate_members(data):
+    """The host's zlib over a BGZF file, member by member, each cut out by its BSIZE (no copy of the rest of the file per member)."""
+    out, view, at = [], memoryview(data), 0
+    while at < len(data):
+        size = struct.unpack_from("<H", data, at + 16)[0] + 1
+        out.append(zlib.decompressobj(47).decompress(view[at:at + size]))
+        at += size
+    return b"".join(out)
+
+
+def bgzf_times(gca, np, fastq, n_reads, rounds):
+    data = bgzf_compress(fastq)
+    rows = {k: [] for k in ("device_wall_ms", "scan_ms", "upload_ms", "inflate_kernel_ms", "parse_kernel_ms", "host_inflate_ms", "host_from_text_ms")}
+    for i in range(rounds + 1):
+        t0 = time.time()
+        batch, ids, tail, consumed = gca.ReadBatch.from_bgzf(b"", data, "fastq")
+        t1 = time.time()
+        stats, kernel_ms, blob = batch.bgzf, batch.kernel_ms, batch.blob
+        batch.close()
+        assert len(ids) == n_reads and consumed == len(data) and tail == b""
+        t2 = time.time()
+        text = inflate_members(data)
+        t3 = time.time()
+        host, host_ids, _ = gca.ReadBatch.from_text(text, "fastq")
+        t4 = time.time()
+        assert host_ids == ids and host.blob == blob
+        host.close()
+        if i:
+            for k, v in (("device_wall_ms", (t1 - t0) * 1e3), ("scan_ms", stats["scan_ms"]), ("upload_ms", stats["upload_ms"]), ("inflate_kernel_ms", stats["kernel_ms"]),
+                         ("parse_kernel_ms", kernel_ms), ("host_inflate_ms", (t3 - t2) * 1e3), ("host_from_text_ms", (t4 - t3) * 1e3)):
+                rows[k].append(v)
+    med = {k: round(float(np.median(v)), 2) for k, v in rows.items()}
+    return {"file_bytes": len(data), "text_bytes": len(fastq), "blocks": stats["blocks"], "from_bgzf_wall_ms": med["device_wall_ms"], "scan_ms": med["scan_ms"], "upload_ms": med["upload_ms"],
+            "inflate_kernel_ms": med["inflate_kernel_ms"], "inflate_kernel_GBps": round(len(fastq) / max(med["inflate_kernel_ms"], 1e-3) / 1e6, 2), "parse_kernel_ms": med["parse_kernel_ms"],
+            "host_inflate_ms": med["host_inflate_ms"], "host_from_text_ms": med["host_from_text_ms"], "host_inflate_and_from_text_ms": round(med["host_inflate_ms"] + med["host_from_text_ms"], 2),
+            "rounds": {k: [round(x, 2) for x in v] for k, v in rows.items()}}
 
 
 def loader_times(gca, np, reads, rounds):
@@ -69,6 +121,7 @@ def loader_times(gca, np, reads, rounds):
                      "host_cut_ms": med["cut_ms"], "host_upload_ms": med["upload_ms"], "host_cut_and_upload_ms": round(med["cut_ms"] + med["upload_ms"], 2)}
         if inflate:
             out[name]["host_inflate_ms"] = med["inflate_ms"]
+    out["fastq_bgzf"] = bgzf_times(gca, np, fastq, len(reads), rounds)
     return out
 
 
@@ -89,7 +142,9 @@ def command_times(gca, args, tmp):
             if not piece:
                 break
             g.write(piece)
-    legs = {"fastq": fq, "fastq_gz": fq + ".gz"}
+    with open(fq, "rb") as f, open(os.path.join(tmp, "reads.bgzf.fq.gz"), "wb") as g:
+        g.write(bgzf_compress(f.read()))
+    legs = {"fastq": fq, "fastq_gz": fq + ".gz", "fastq_bgzf": os.path.join(tmp, "reads.bgzf.fq.gz")}
     rates = {leg: {k: [] for k in args.inflight} for leg in legs}
     last = {leg: {} for leg in legs}
     for i in range(args.rounds + 1):            # a warm-up round, then the runs alternating inside every round
@@ -108,7 +163,7 @@ def command_times(gca, args, tmp):
                    "median and every round, per batches in flight (chosen: --inflight not given)"}
     for leg in legs:
         out[leg] = {name(k): {"reads_per_s": round(sorted(v)[len(v) // 2], 1), "rounds": [round(x, 1) for x in v], "inflight": last[leg][k]["inflight"], "batches": last[leg][k]["batches"],
-                              "retired_workers": last[leg][k]["retired_workers"], "stage_seconds": last[leg][k]["stage_seconds"]} for k, v in rates[leg].items()}
+                              "retired_workers": last[leg][k]["retired_workers"], "bgzf_blocks": last[leg][k]["bgzf_blocks"], "stage_seconds": last[leg][k]["stage_seconds"]} for k, v in rates[leg].items()}
     out["command_reads_per_s"] = out["fastq"][name(args.inflight[-1])]["reads_per_s"]
     if args.bench:
         bench = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--no-cpu-baseline", "--setup-dir", tmp], capture_output=True, text=True,
