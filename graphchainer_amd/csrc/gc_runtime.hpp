@@ -1,5 +1,5 @@
-// Shared by the two translation units of the library's host side (r4: gc_capi.hip - the C entry points - and gc_batch.hip - gc_align_batch and the batch pipeline;
-// one 3 500-line file until then): error reporting, device / pinned buffers, the whole-read tokens and the device's shared scratch, the worker pool, the block caches, the
+// Shared by the translation units of the library's host side (capi/gc_capi_*.hip - the C entry points, one file per subject - and gc_batch.hip - gc_align_batch and the batch
+// pipeline; one 3 500-line file until r4): error reporting, device / pinned buffers, the whole-read tokens and the device's shared scratch, the worker pool, the block caches, the
 // opaque handle types of the C ABI, graph upload, the edit-distance launcher. Everything here has ONE definition in the library (inline functions and variables).
 #pragma once
 // C ABI of the MI355X GraphChainer hot path (include/graphchainer_amd.h) and the batched host pipeline that
@@ -17,6 +17,7 @@
 #include "host/gc_switches.hpp"
 #include "host/gc_mxm_build.hpp"
 #include "host/gc_mxm_cache.hpp"
+#include "host/gc_layout.hpp"
 #include "hip/gc_mxm_core.hpp"
 #include "hip/gc_seedfile_core.hpp"
 #include <hip/hip_runtime.h>
@@ -513,6 +514,31 @@ inline hipStream_t threadStream(int device)
 	return ts.q;
 }
 
+// A cache's block for the length of a call. It goes back to its cache only after the stream has drained: after an exception between a launch and the call's own wait the
+// block would otherwise be handed to the next caller while this call's copies and kernels still use it. release() hands the block on to an owner that outlives
+// the call (a read batch that was built without a failure).
+struct HeldBlock {
+	BlockCache& cache; int device; hipStream_t q;
+	void* p = nullptr; size_t bytes = 0;
+	HeldBlock(BlockCache& cache, int device, hipStream_t q) : cache(cache), device(device), q(q) {}
+	HeldBlock(const HeldBlock&) = delete;
+	void* acquire(size_t want) { p = cache.get(want, device, bytes); return p; }
+	void* release() { void* mine = p; p = nullptr; return mine; }
+	~HeldBlock() { if (p) { (void)hipStreamSynchronize(q); cache.put(p, bytes, device); } }
+};
+
+// N timing events for the length of a call
+template <int N> struct EventSet {
+	hipEvent_t e[N] {};
+	EventSet() { for (auto& x : e) { const hipError_t err = hipEventCreate(&x); if (err != hipSuccess) { destroy(); HIP_CHECK(err); } } }
+	EventSet(const EventSet&) = delete;
+	~EventSet() { destroy(); }
+	hipEvent_t operator[](int i) const { return e[i]; }
+	float elapsedMs(int i, int j) const { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[j])); return ms; }   // (after a synchronize behind both)
+private:
+	void destroy() { for (auto& x : e) if (x) { (void)hipEventDestroy(x); x = nullptr; } }
+};
+
 struct gc_reads {
 	void* deviceBlock = nullptr; size_t deviceBlockBytes = 0; int device = 0;   // every device array below is carved from this one block
 	std::vector<uint64_t> offsets;   // host copy [n+1]
@@ -525,6 +551,7 @@ struct gc_reads {
 	std::vector<uint64_t> maskOff;   // [n] word offset of read r's masks
 	std::vector<uint32_t> maskWords; // [n] words per bit vector
 	const uint64_t* devMaskOff = nullptr; const uint32_t* devMaskWords = nullptr;   // the two on the device (the fragment extension kernel reads its rows' masks through them)
+	const uint64_t* devEqOff = nullptr;   // [n] word offset of read r's exact-match masks (the pack kernel's)
 	// exact-match bit vectors of the forward strand [A,C,G,T][words] and the per-read records of the NW kernel (rows = read bases)
 	uint64_t* devEqMasks = nullptr;
 	EdRead* devEdReads = nullptr;
@@ -534,6 +561,31 @@ struct gc_reads {
 	uint8_t* devReadInvalid = nullptr;  // [n] the device's copy of `invalid`
 	~gc_reads() { g_readDeviceBlocks.put(deviceBlock, deviceBlockBytes, device); }
 };
+static_assert(sizeof(gc::EdReadRecord) == sizeof(EdRead) && offsetof(gc::EdReadRecord, eqOff) == offsetof(EdRead, eqOff) && offsetof(gc::EdReadRecord, len) == offsetof(EdRead, len) &&
+	offsetof(gc::EdReadRecord, words) == offsetof(EdRead, words), "the layout's record is the kernels' EdRead");
+
+// The one layout of a read batch (host/gc_layout.hpp) on a block of L.blockBytes: gc_reads_upload and the parsers build their batches through these two.
+// The block stays its HeldBlock's until the call has succeeded; R.deviceBlock is set then.
+inline void bindReads(gc_reads& R, const gc::ReadBatchLayout& L, void* block)
+{
+	char* D = (char*)block;
+	R.maskOff = L.maskOff; R.maskWords = L.maskWords;
+	R.devBases = D + L.oBases; R.devOffsets = (uint64_t*)(D + L.oOffsets); R.devMasks = (uint64_t*)(D + L.oMasks); R.devEqMasks = (uint64_t*)(D + L.oEqMasks); R.devEdReads = (EdRead*)(D + L.oEdReads);
+	R.devPacked = (uint64_t*)(D + L.oPacked); R.devInvalid = (uint64_t*)(D + L.oInvalid); R.devChunkRead = (uint32_t*)(D + L.oChunkRead); R.devReadInvalid = (uint8_t*)(D + L.oReadInvalid);
+	R.devMaskOff = (uint64_t*)(D + L.oMaskOff); R.devMaskWords = (uint32_t*)(D + L.oMaskWords); R.devEqOff = (uint64_t*)(D + L.oEqOff);
+}
+// the four per-read arrays through the caller's pinned staging (n elements each) to the device, behind the offsets' copy
+inline void stageReadLayout(const gc_reads& R, const gc::ReadBatchLayout& L, uint64_t* hMaskOff, uint32_t* hMaskWords, uint64_t* hEqOff, EdRead* hEdReads, hipStream_t q)
+{
+	const size_t n = L.maskOff.size();
+	if (!n) return;
+	memcpy(hMaskOff, L.maskOff.data(), n * sizeof(uint64_t)); memcpy(hMaskWords, L.maskWords.data(), n * sizeof(uint32_t));
+	memcpy(hEqOff, L.eqOff.data(), n * sizeof(uint64_t)); memcpy(hEdReads, L.edReads.data(), n * sizeof(EdRead));
+	HIP_CHECK(hipMemcpyAsync((void*)R.devMaskOff, hMaskOff, n * sizeof(uint64_t), hipMemcpyHostToDevice, q));
+	HIP_CHECK(hipMemcpyAsync((void*)R.devMaskWords, hMaskWords, n * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+	HIP_CHECK(hipMemcpyAsync((void*)R.devEqOff, hEqOff, n * sizeof(uint64_t), hipMemcpyHostToDevice, q));
+	HIP_CHECK(hipMemcpyAsync(R.devEdReads, hEdReads, n * sizeof(EdRead), hipMemcpyHostToDevice, q));
+}
 
 // a read batch's seed hits from the host's own seeder (gc_seeds_upload), resolved by k_seed_resolve: read-only afterwards, shared by streams
 struct gc_seeds {
@@ -547,6 +599,19 @@ struct gc_seeds {
 	double kernelMs = 0;                   // gc_seeds_mxm: device time from the first kernel to the last
 	~gc_seeds() { if (block) (void)hipFree(block); }
 };
+// The one layout of a seed batch (host/gc_layout.hpp): allocates H.block for H.nHits hits of nReads reads and points H's arrays into it. Returns the three words for the
+// kernels' first refused hit (resolve, match_len, raw_goodness), not yet set.
+inline unsigned long long* allocateSeedBlock(gc_seeds& H, uint64_t nReads)
+{
+	const gc::SeedBatchLayout L(nReads, H.nHits);
+	HIP_CHECK(hipMalloc(&H.block, L.blockBytes));
+	char* D = (char*)H.block;
+	H.devReadHitOff = (uint32_t*)(D + L.oOff);
+	uint32_t* arrays = (uint32_t*)(D + L.oArrays);
+	H.dev = SeedHitArrays { arrays, arrays + H.nHits, arrays + 2 * H.nHits, arrays + 3 * H.nHits, arrays + 4 * H.nHits };
+	H.devHits = (SeedHit*)(D + L.oHits);
+	return (unsigned long long*)(D + L.oBad);
+}
 
 // the seeds of the -s files (gc_seed_store_open), decoded and sorted by name hash in HBM: read-only, shared by streams
 struct gc_seed_store {

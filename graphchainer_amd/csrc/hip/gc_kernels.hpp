@@ -25,6 +25,9 @@
 
 namespace gcdev {
 
+// waits for the stream when it goes out of scope: declared AFTER the owners of the memory a call's kernels and copies use, so that it goes first and nothing is freed under them
+struct StreamDrain { hipStream_t q; ~StreamDrain() { (void)hipStreamSynchronize(q); } };
+
 struct SeedIndex {   // minimizer index in HBM (reference: MinimizerSeeder buckets, src/MinimizerSeeder.h:16-30)
 	const uint64_t* table;      // open addressing: (low 32 bits of the k-mer << 32) | keyIndex, empty = all ones
 	const uint64_t* wideKmers;  // k > 15 (the reference takes minimizer lengths up to 31, src/MinimizerSeeder.cpp:63): the k-mer of every key, checked when a slot's

@@ -9,6 +9,7 @@
 //                        `count` longest per read, and the final records in the block layout gc_seeds_upload builds.
 #include "gc_kernels.hpp"
 #include "gc_mxm_core.hpp"
+#include "../host/gc_layout.hpp"
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -151,9 +152,9 @@ hipError_t MxmSeedRun::candidates(hipStream_t q, const MxmIndexView& ix, const c
 	if (nCandidates == 0 || nCandidates > 0x7fffffffull) return hipSuccess;   // (the caller refuses the batch: hipCUB counts in int)
 	// pass 2: the records and their two sort keys
 	const uint64_t n = nCandidates;
-	auto part = [&](size_t bytes) { const size_t here = workBytes; workBytes += (bytes + 255) & ~(size_t)255; return here; };
-	workBytes = 0;
-	const size_t oHits = part(n * sizeof(SeedHit)), oInner = part(n * 8), oOuter = part(n * 8), oKeysA = part(n * 8), oKeysB = part(n * 8), oIdxA = part(n * 4), oIdxB = part(n * 4);
+	gc::Arena a;   // (n >= 1 here: no part is empty)
+	const size_t oHits = a.part(n * sizeof(SeedHit)), oInner = a.part(n * 8), oOuter = a.part(n * 8), oKeysA = a.part(n * 8), oKeysB = a.part(n * 8), oIdxA = a.part(n * 4), oIdxB = a.part(n * 4);
+	workBytes = a.bytes();
 	MXM_TRY(hipMalloc(&work, workBytes));
 	char* W = (char*)work;
 	cand = (SeedHit*)(W + oHits);

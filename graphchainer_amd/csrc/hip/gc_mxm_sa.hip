@@ -93,7 +93,7 @@ hipError_t launchMxmSuffixArray(hipStream_t q, const uint8_t* hostCodes, uint32_
 	if (!n) return hipSuccess;
 	if (n >= 0x7fffffffu) return hipErrorInvalidValue;   // (MXM_DEVICE_BUILD_MAX: the caller refuses such a text by name before it comes here: hipCUB counts in int)
 	Scratch scratch;
-	struct Drain { hipStream_t q; ~Drain() { (void)hipStreamSynchronize(q); } } drain { q };   // (declared after `scratch`: nothing is freed while a kernel of this build may still run)
+	StreamDrain drain { q };   // (declared after `scratch`: nothing is freed while a kernel of this build may still run)
 	uint8_t* codes = nullptr;
 	uint64_t *keyA = nullptr, *keyB = nullptr;
 	uint32_t *posA = nullptr, *posB = nullptr, *rank = nullptr, *count = nullptr;

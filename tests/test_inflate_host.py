@@ -204,4 +204,4 @@ def test_big_isize_goes_to_zlib_and_the_refusal_words_are_the_headers(tmp_path):
     assert b"".join(pieces[1:]) == text[900:]
     header = open(os.path.join(ROOT, "include", "graphchainer_amd.h")).read()
     assert f'#define GC_BGZF_REFUSED "{api.BGZF_REFUSED}"' in header
-    assert "GC_BGZF_REFUSED" in open(os.path.join(ROOT, "graphchainer_amd", "csrc", "gc_capi.hip")).read()
+    assert "GC_BGZF_REFUSED" in open(os.path.join(ROOT, "graphchainer_amd", "csrc", "capi", "gc_capi_reads.hip")).read()
