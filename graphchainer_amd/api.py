@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "gc_stream_create", "gc_stream_destroy", "gc_reads_upload", "gc_reads_destroy", "gc_align_batch",
     "gc_seeds_upload", "gc_seeds_destroy", "gc_seeds_hits", "gc_seeds_kernel_ms", "gc_mxm_index_create", "gc_mxm_options_default", "gc_mxm_index_open", "gc_mxm_cache_check", "gc_mxm_index_destroy", "gc_mxm_index_array", "gc_seeds_mxm", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
+    "gc_format_corrected", "gc_format_corrected_trace", "gc_corrected_pieces",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
     "gc_reads_parse", "gc_fastx_table_free", "gc_bgzf_inflate", "gc_reads_parse_bgzf",
     "gc_seed_store_open", "gc_seed_store_from_memory", "gc_seed_store_info", "gc_seed_store_destroy", "gc_seeds_from_store",
@@ -81,6 +82,7 @@ class GcResult(C.Structure):
         ("out_path_off", _P(C.c_uint64)), ("out_path_text", _P(C.c_char)), ("out_cigar_off", _P(C.c_uint64)), ("out_cigar_text", _P(C.c_char)),
         ("out_vg_off", _P(C.c_uint64)), ("out_vg_path", _P(C.c_uint8)),
         ("flatten_ties", _P(C.c_uint32)), ("flatten_ties_long", _P(C.c_uint32)), ("device_output", C.c_int32),
+        ("out_corrected_off", _P(C.c_uint64)), ("out_corrected_text", _P(C.c_char)),
     ]
 
 
@@ -321,6 +323,44 @@ def graph_letters(graph, node, offset):
     lib.gc_graph_letters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p]
     _check(lib.gc_graph_letters(graph.handle, node.ctypes.data, offset.ctypes.data, len(node), out))
     return out.raw[:len(node)]
+
+
+def format_corrected_trace(graph, node, offset, switch):
+    """The corrected piece (bytes) of one alignment given as a trace in output coordinates (gc_format_corrected_trace: GraphAligner's AddCorrected; host only)."""
+    lib = load_library()
+    node = np.ascontiguousarray(node, dtype=np.int32)
+    offset = np.ascontiguousarray(offset, dtype=np.uint32)
+    switch = np.ascontiguousarray(switch, dtype=np.uint8)
+    assert len(node) == len(offset) == len(switch)
+    text, length = C.c_void_p(), C.c_uint64()
+    lib.gc_format_corrected_trace.restype = C.c_int
+    lib.gc_format_corrected_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_void_p), _P(C.c_uint64)]
+    _check(lib.gc_format_corrected_trace(graph.handle, node.ctypes.data, offset.ctypes.data, switch.ctypes.data, len(node), C.byref(text), C.byref(length)))
+    piece = C.string_at(text.value, int(length.value))
+    lib.gc_free(text)
+    return piece
+
+
+def corrected_pieces(graph, traces):
+    """The corrected pieces of a list of traces, each (node, offset, switch), spelled by the device kernels (gc_corrected_pieces): a list of bytes, one per trace."""
+    lib = load_library()
+    n = len(traces)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(t[0]) for t in traces], dtype=np.uint64) if n else []
+    cat = lambda k, dtype: np.ascontiguousarray(np.concatenate([np.asarray(t[k], dtype=dtype) for t in traces]) if n else np.zeros(0, dtype=dtype), dtype=dtype)   # noqa: E731
+    node, offset, switch = cat(0, np.int32), cat(1, np.uint32), cat(2, np.uint8)
+    assert len(node) == len(offset) == len(switch) == int(off[n])
+    text, out_off = C.c_void_p(), C.c_void_p()
+    lib.gc_corrected_pieces.restype = C.c_int
+    lib.gc_corrected_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_void_p), _P(C.c_void_p)]
+    _check(lib.gc_corrected_pieces(graph.handle, node.ctypes.data, offset.ctypes.data, switch.ctypes.data, off.ctypes.data, n, C.byref(text), C.byref(out_off)))
+    try:
+        at = np.ctypeslib.as_array(C.cast(out_off, _P(C.c_uint64)), shape=(n + 1,)).copy()
+        data = C.string_at(text.value, int(at[n]))
+    finally:
+        lib.gc_free(text)
+        lib.gc_free(out_off)
+    return [data[int(at[i]):int(at[i + 1])] for i in range(n)]
 
 
 def _fetch_array(fn, handle, name):
@@ -958,7 +998,8 @@ class Aligner:
         """capacities: {field of gc_capacities: value} for the device-side tables (default: all automatic).
         seeder: the MinimizerSeeder, or None for a caller that brings its own seeds to every batch (align_batch(batch, seeds=SeedBatch(...))).
         device_output: gc_params::device_output - 1 / 2: the final alignments' GAF path and CIGAR text (= / X or M items), + 4: their vg::Path bytes, written
-        by the device from the traces it holds; align_batch(gaf_names=...) then needs no keep_traces.
+        by the device from the traces it holds; align_batch(gaf_names=...) then needs no keep_traces. + 8 (also alone): the corrected reads' pieces (GraphAligner's
+        --corrected-out / --corrected-clipped-out) for formats "corrected" / "corrected_clipped".
         ramp_bandwidth / max_cells_per_slice: the reference's -B / -C (gc_params; 0 and -1: off).
         force_global: the reference's --global-alignment (gc_params::force_global): every extension of both passes keeps all its slices, so an alignment
         reaches the read's end however poor its score. An int other than 0 / 1 is passed on as it is (and refused by the library).
@@ -1014,7 +1055,9 @@ class Aligner:
     def align_batch(self, batch, seeds=None, gaf_names=None, cigar_match_mismatch_merge=False, other_formats=False, formats=None, gam_level=None):
         """Runs the hot path for a ReadBatch; returns a dict of arrays. seeds: a SeedBatch made for this batch - its hits replace the seeder's. With gaf_names (one id per read; needs long_pass and
         keep_traces or device_output) the dict also holds "gaf" (bytes: the reference's GAF lines) and "gaf_chained_skipped"; with other_formats also "json" (JSON
-        lines) and "gam" (gzip members of framed vg::Alignment messages; gam_level: their zlib level, or GAM_DEVICE_HUFFMAN for the device's deflate)."""
+        lines) and "gam" (gzip members of framed vg::Alignment messages; gam_level: their zlib level, or GAM_DEVICE_HUFFMAN for the device's deflate). formats may also name
+        "corrected" / "corrected_clipped" (gc_format_corrected: FASTA records of the corrected reads / of every alignment's piece; device_output & 8 or keep_traces):
+        the dict then holds their bytes and, under "corrected_rec_off" / "corrected_clipped_rec_off", the records' byte offsets (one more entry than records)."""
         res = _P(GcResult)()
         ext_on = self.params_ext.precise_clipping != 0 or self.params_ext.x_drop != 0   # (with both off: the calls that take no block)
         if ext_on and (seeds is not None or self.seeder is not None):
@@ -1094,6 +1137,8 @@ class Aligner:
                 out["out_numbers"] = arr(r.out_numbers, 12 * n_out)
                 for name in ("out_path_off", "out_cigar_off", "out_vg_off"):
                     out[name] = arr(getattr(r, name), n_out + 1)
+                if self.params.device_output & 8:
+                    out["out_corrected_off"] = arr(r.out_corrected_off, n_out + 1)
             out["counters"] = np.array(list(r.counters), dtype=np.uint64)
             out["counters_long"] = np.array(list(r.counters_long), dtype=np.uint64)
             out["kernel_us"] = np.array(list(r.kernel_us))
@@ -1116,9 +1161,25 @@ class Aligner:
             self.lib.gc_free(text)
             return data, int(skipped.value)
 
+        def corrected(clipped):
+            text, length, rec_off, n_rec, skipped = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+            fn = self.lib.gc_format_corrected
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            _check(fn(self.graph.handle, res, names, batch.blob, batch.offsets.ctypes.data, int(clipped), C.byref(text), C.byref(length), C.byref(rec_off), C.byref(n_rec), C.byref(skipped)))
+            try:
+                data = C.string_at(text.value, length.value)
+                offsets = np.ctypeslib.as_array(C.cast(rec_off, _P(C.c_uint64)), shape=(int(n_rec.value) + 1,)).copy()
+            finally:
+                self.lib.gc_free(text)
+                self.lib.gc_free(rec_off)
+            return data, offsets, int(skipped.value)
+
         texts, skipped = {}, 0
         for fmt in formats:
-            if fmt == "gaf":
+            if fmt in ("corrected", "corrected_clipped"):
+                texts[fmt], texts[fmt + "_rec_off"], skipped = corrected(fmt == "corrected_clipped")
+            elif fmt == "gaf":
                 texts[fmt], skipped = encode(self.lib.gc_format_gaf, int(cigar_match_mismatch_merge))
             elif fmt == "gam" and gam_level is not None:
                 texts[fmt], skipped = encode(self.lib.gc_format_gam_level, int(gam_level))

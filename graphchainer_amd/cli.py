@@ -4,6 +4,8 @@ resolve(argv) -> Config turns a command line into what a run needs - the referen
 (src/AlignerMain.cpp:35-112,138-464) - and touches neither the library nor a device. main(argv) runs it (run, over pipeline.py): a reader thread, a parse thread (the reads are parsed on the device, about
 --batch-bytes of file text per batch), up to --inflight workers per device of --devices, each with an Aligner of its own (the alignments are encoded on the device for the
 writers chosen), and a writer thread: records written in input order, every output file through a temporary name and a rename.
+--corrected-out / --corrected-clipped-out are GraphAligner's (the reference keeps their mechanism, src/Aligner.cpp:313-374, and dropped the two option lines): the
+corrected reads, their pieces spelled on the device, beside -a or without it.
 
 Accepted and without effect: -t / --threads (checked >= 1), --high-memory, --verbose, --short-verbose (the progress text and the closing statistics are not
 reproduced), and --greedy-E / --greedy-score, which the reference declares and never reads. --try-all-seeds (and --all-alignments, which sets it) does what it does
@@ -39,9 +41,11 @@ OPTIONS = {
     # this build's own
     "batch-bytes": (None, "size", False), "device": (None, "size", False), "index-cache": (None, "string", False),
     "inflight": (None, "size", False), "devices": (None, "string", False),
+    "corrected-out": (None, "string", False), "corrected-clipped-out": (None, "string", False),   # GraphAligner's: the reference keeps their mechanism and dropped the two option lines
 }
 MAX_INFLIGHT = 5                   # the most the benchmark keeps in flight on a device (bench.py: BATCH_MS_BY_INFLIGHT ends there)
 MAX_DEVICES = 16                   # the library's per-device slots
+CORRECTED_SUFFIXES = (".fa", ".fasta", ".fa.gz", ".fasta.gz")   # src/AlignerMain.cpp:360,365 (a name shorter than a suffix does not end in it; the reference's substr would throw)
 REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "generate-path", "generate-path-seed", "graph-statistics")
 SELECT = {"greedy-length": 0, "schedule-inverse-E-sum": 3, "schedule-inverse-E-product": 4, "schedule-score": 5, "schedule-length": 6, "all-alignments": 7}   # GC_SELECT_*
 
@@ -100,6 +104,9 @@ This build's own:
   --index-cache arg                     load the graph and minimizer index from this file if it exists, else build them and save them there.
                                         An existing file wins: it is checked for the minimizer length and window only, not against -g or
                                         --seeds-minimizer-ignore-frequent
+  --corrected-out arg                   GraphAligner's: output corrected reads file (.fa/.fa.gz), every read with its aligned stretches
+                                        replaced by the graph's letters along the alignment (upper case; the rest lower case)
+  --corrected-clipped-out arg           GraphAligner's: output corrected clipped reads file (.fa/.fa.gz), one record per alignment
 
 Accepted and without effect: -t [ --threads ] arg (must be >= 1), --high-memory, --verbose, --short-verbose, --greedy-E, --greedy-score.
 Not supported by this build: --optimal-alignment, --seedless-DP, --DP-restart-stride, --generate-path, --generate-path-seed,
@@ -120,6 +127,7 @@ class Config:
     graph: str = ""
     reads: list = field(default_factory=list)
     outputs: dict = field(default_factory=dict)          # "gaf" / "json" / "gam" -> path (the last one given of each kind, as the reference keeps it)
+    corrected: dict = field(default_factory=dict)        # "corrected" / "corrected_clipped" -> path (--corrected-out / --corrected-clipped-out; a .gz name is compressed)
     aligner: dict = field(default_factory=dict)          # keyword arguments of api.Aligner
     min_cluster_size: int = 1                            # gc_params::min_cluster_size
     seeder: dict = field(default_factory=dict)           # {"kind": "minimizer", "length", "window", "keep_fraction"}, {"kind": "mxm", "mode", "count", "min_len", "cache_prefix"} or {"kind": "file", "paths"}
@@ -290,7 +298,8 @@ def resolve(argv):
         error("graph file must be given")
     if not cfg.reads:
         error("read file must be given")
-    if not outputs:
+    corrected_out, clipped_out = last("corrected-out", ""), last("corrected-clipped-out", "")
+    if not outputs and corrected_out == "" and clipped_out == "":      # src/AlignerMain.cpp:335
         error("alignments-out must be given")
     for path in outputs:
         if len(path) >= 4 and path.endswith(".gam"):
@@ -301,6 +310,11 @@ def resolve(argv):
             cfg.outputs["gaf"] = path
         else:
             error(f"unknown output alignment format ({path}), must be either .gaf, .gam or .json")
+    for fmt, path in (("corrected", corrected_out), ("corrected_clipped", clipped_out)):          # src/AlignerMain.cpp:360-369
+        if path != "":
+            if not path.endswith(CORRECTED_SUFFIXES):
+                error("unknown output corrected read format, must be .fa or .fa.gz")
+            cfg.corrected[fmt] = path
     if cfg.threads < 1:
         error("number of threads must be >= 1")
     if "inflight" in vm and vm["inflight"][-1] < 1:
@@ -489,6 +503,17 @@ def _setup_replicas(cfg, api, replicas):
             shutil.rmtree(tmp, ignore_errors=True)
 
 
+def device_output_for(cfg):
+    """gc_params::device_output for the files cfg names: 1 / 2 the GAF pieces, 4 the vg::Path bytes, 8 the corrected reads' pieces."""
+    gaf = (2 if cfg.cigar_match_mismatch else 1) if "gaf" in cfg.outputs else 0
+    return gaf | (4 if "json" in cfg.outputs or "gam" in cfg.outputs else 0) | (8 if cfg.corrected else 0)
+
+
+def gzip_records(api, text, rec_off):
+    """The records text[rec_off[k]:rec_off[k + 1]] as one gzip member each, deflated on the device (gc_gzip_streams_lz)."""
+    return b"".join(api.gzip_streams([text[int(rec_off[k]):int(rec_off[k + 1])] for k in range(len(rec_off) - 1)], lz=True))
+
+
 def run(cfg, stderr=sys.stderr):
     """Aligns cfg.reads to cfg.graph and writes cfg.outputs. Returns the counts it reports. Threads (pipeline.py): one reads the files and inflates a .gz, one cuts and
     parses (and chooses the replica of each batch before it parses it, so that the reads live on the device that aligns them), up to `inflight` workers per replica seed
@@ -504,7 +529,8 @@ def run(cfg, stderr=sys.stderr):
     # what the chosen writers need: the whole-read pass and the two edit distances that pick the winner, and the final alignments encoded on the device, where their traces
     # are - the GAF pieces (= / X items, or M items with --cigar-match-mismatch) for a .gaf, the vg::Path bytes for a .json or .gam; no trace comes down (keep_traces=0)
     formats = tuple(f for f in ("gaf", "json", "gam") if f in cfg.outputs)
-    device_output = ((2 if cfg.cigar_match_mismatch else 1) if "gaf" in formats else 0) | (4 if "json" in formats or "gam" in formats else 0)
+    corrected = tuple(f for f in ("corrected", "corrected_clipped") if f in cfg.corrected)       # the corrected reads' pieces are spelled on the device too (bit 8), also with no -a at all
+    device_output = device_output_for(cfg)
     counts = {"reads": 0, "flagged": 0, "failed_assertion": 0, "capacity_exceeded": 0, "batches": 0, "seconds": 0.0, "bgzf_blocks": 0}   # seconds: reading, aligning and writing, setup left out
 
     def make_aligner(r):
@@ -521,12 +547,15 @@ def run(cfg, stderr=sys.stderr):
         else:
             seeds = rep.index.seeds(batch, cfg.seeder["mode"], count=cfg.seeder["count"], min_len=cfg.seeder["min_len"]) if rep.index is not None else None
         try:
-            out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
+            out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats + corrected, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
         finally:
             if seeds is not None:
                 seeds.close()
         failed, capacity = np.asarray(out["failed_assertion"]) != 0, np.asarray(out["capacity_exceeded"]) != 0
-        return {f: out[f] for f in formats}, len(ids), int(failed.sum()), int(capacity.sum()), int((failed | capacity).sum())
+        texts = {f: out[f] for f in formats}
+        for f in corrected:                # a .gz name: one gzip member per record, as zstr::ostream per call gives (src/Aligner.cpp:316-336), deflated on the device
+            texts[f] = gzip_records(api, out[f], out[f + "_rec_off"]) if cfg.corrected[f].endswith(".gz") else out[f]
+        return texts, len(ids), int(failed.sum()), int(capacity.sum()), int((failed | capacity).sum())
 
     try:
         _setup_replicas(cfg, api, replicas)
@@ -551,10 +580,10 @@ def run(cfg, stderr=sys.stderr):
                     reader_seconds.update(busy=pieces.busy, waiting_in=0.0, waiting_out=pieces.waiting_out, parse_waiting_in=pieces.consumer_waiting)
 
         started = time.time()
-        with _Outputs(cfg.outputs) as outputs:
+        with _Outputs({**cfg.outputs, **cfg.corrected}) as outputs:
             def write(result):
                 texts, reads, failed, capacity, flagged = result
-                for f in formats:
+                for f in formats + corrected:
                     outputs.write(f, texts[f])
                 counts["reads"] += reads
                 counts["batches"] += 1

@@ -159,6 +159,7 @@
 	std::vector<uint64_t> readOutOff;
 	const OutRec* hOutRecs = nullptr; const uint64_t* hOutOffsets = nullptr;
 	const char* hOutPath = nullptr; const char* hOutCigar = nullptr; const uint8_t* hOutVg = nullptr;
+	const uint64_t* hCorrOffsets = nullptr; const char* hCorrText = nullptr;   // (device_output & 8) the corrected pieces of the jobs: [nOutJobs + 1], letters
 	uint64_t nOutJobs = 0;
 	std::vector<uint64_t> outJobOfEntry;
 	// Started by the whole-read pass's own thread as soon as the selection is known (the end of afterLongPass): the main thread is still in the fragment pipeline, the stitching and the
@@ -205,14 +206,33 @@
 		uint32_t* dMapSizes = (P->device_output & 4) ? st->outMapSizes.reserve<uint32_t>(std::max<uint64_t>(1, hLongSmall[0]))   /* one word per cell of the pool in use */ : nullptr;
 		unsigned long long* hTotals = st->hOutTotals.reserve<unsigned long long>(4);
 		HIP_CHECK(hipMemcpyAsync(dJobsOut, hJobsOut, nOutJobs * sizeof(OutJob), hipMemcpyHostToDevice, q));
+		hipEvent_t timed[6] = {};   // GC_DEBUG_TIMES: device time of the encoder's and the corrected reads' kernels, each pass between events of its own
+		if (sw.debugTimes) for (auto& e : timed) HIP_CHECK(hipEventCreate(&e));
+		auto mark = [&](int k) { if (timed[k]) HIP_CHECK(hipEventRecord(timed[k], q)); };
+		mark(0);
 		launchOutCount(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, dLongCells, R->devBases, dRecs, dOffsets, dMapSizes, dTotals);
+		mark(1);
 		HIP_CHECK(hipMemcpyAsync(hTotals, dTotals, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
+		// corrected reads (device_output & 8; gc_corrected.hip): their own kernels behind the encoder's on the same stream, their count and text beside the encoder's
+		const bool corrected = (P->device_output & 8) != 0;
+		uint32_t* dCorrLens = nullptr; uint64_t* dCorrOffsets = nullptr; unsigned long long* hCorrTotal = nullptr;
+		if (corrected) {
+			dCorrLens = st->corrLens.reserve<uint32_t>(nOutJobs);
+			dCorrOffsets = st->corrOffsets.reserve<uint64_t>(nOutJobs + 1);
+			unsigned long long* dCorrTotal = st->corrTotal.reserve<unsigned long long>(1);
+			hCorrTotal = st->hCorrTotal.reserve<unsigned long long>(1);
+			launchCorrectedCount(q, G->dev, dJobsOut, (uint32_t)nOutJobs, dLongCells, dCorrLens, dCorrOffsets, dCorrTotal);
+			HIP_CHECK(hipMemcpyAsync(hCorrTotal, dCorrTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
+		}
+		mark(2);
 		syncStream(q);
 		const uint64_t pathBytes = hTotals[0], cigarBytes = hTotals[1], vgBytes = hTotals[2];
 		char* dPath = st->outPathText.reserve<char>(pathBytes + 1);
 		char* dCigar = st->outCigarText.reserve<char>(cigarBytes + 1);
 		uint8_t* dVg = st->outVgBytes.reserve<uint8_t>(vgBytes + 1);
+		mark(3);
 		launchOutWrite(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, dLongCells, R->devBases, dRecs, dOffsets, dMapSizes, dPath, dCigar, dVg);
+		mark(4);
 		OutRec* recs = st->hOutRecs.reserve<OutRec>(nOutJobs);
 		uint64_t* offs = st->hOutOffsets.reserve<uint64_t>(3 * (nOutJobs + 1));
 		char* pathText = st->hOutPathText.reserve<char>(pathBytes + 1);
@@ -223,11 +243,34 @@
 		if (pathBytes) HIP_CHECK(hipMemcpyAsync(pathText, dPath, pathBytes, hipMemcpyDeviceToHost, q));
 		if (cigarBytes) HIP_CHECK(hipMemcpyAsync(cigarText, dCigar, cigarBytes, hipMemcpyDeviceToHost, q));
 		if (vgBytes) HIP_CHECK(hipMemcpyAsync(vg, dVg, vgBytes, hipMemcpyDeviceToHost, q));
+		uint64_t corrBytes = 0;
+		uint32_t* corrLens = nullptr;
+		if (corrected) {
+			corrBytes = *hCorrTotal;
+			char* dCorrText = st->corrText.reserve<char>(corrBytes + 1);
+			launchCorrectedWrite(q, G->dev, dJobsOut, (uint32_t)nOutJobs, dLongCells, dCorrLens, dCorrOffsets, dCorrText);
+			mark(5);
+			corrLens = st->hCorrLens.reserve<uint32_t>(nOutJobs);
+			uint64_t* corrOffs = st->hCorrOffsets.reserve<uint64_t>(nOutJobs + 1);
+			char* corrText = st->hCorrText.reserve<char>(corrBytes + 1);
+			HIP_CHECK(hipMemcpyAsync(corrLens, dCorrLens, nOutJobs * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+			HIP_CHECK(hipMemcpyAsync(corrOffs, dCorrOffsets, (nOutJobs + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, q));
+			if (corrBytes) HIP_CHECK(hipMemcpyAsync(corrText, dCorrText, corrBytes, hipMemcpyDeviceToHost, q));
+			hCorrOffsets = corrOffs; hCorrText = corrText;
+		}
 		syncStream(q);
+		if (corrected) for (uint64_t k = 0; k < nOutJobs; k++) if (corrLens[k] == 0xffffffffu) throw std::runtime_error("internal: the corrected-read kernel's two passes disagree on an alignment's size");
 		for (uint64_t k = 0; k < nOutJobs; k++) if (recs[k].steps == 0xffffffffu) throw std::runtime_error("internal: the output encoder's two passes disagree on an alignment's size");
 		hOutRecs = recs; hOutOffsets = offs; hOutPath = pathText; hOutCigar = cigarText; hOutVg = vg;
 		if (sw.debugTimes) fprintf(stderr, "[gc times] output encoding on the device: %llu alignments, %.1f MB of path text, %.1f MB of CIGAR, %.1f MB of vg::Path bytes, %.1f ms (on the whole-read pass's thread, beside the fragment pipeline)\n",
 			(unsigned long long)nOutJobs, pathBytes / 1e6, cigarBytes / 1e6, vgBytes / 1e6, (nowUs() - t0) / 1e3);
+		if (timed[0]) {
+			auto between = [&](int a, int b) { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, timed[a], timed[b])); return (double)ms; };
+			const double encodeMs = between(0, 1) + between(3, 4), correctedMs = corrected ? between(1, 2) + between(4, 5) : 0.0;
+			for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
+			fprintf(stderr, "[gc times] output kernels on the device: k_out_encode (both passes, k_out_place) %.3f ms; corrected reads (k_corr_walk both passes, k_corr_place) %.3f ms, %.1f MB of letters down\n",
+				encodeMs, correctedMs, corrBytes / 1e6);
+		}
 	}
 
 	// After the decision: which of the encoded alignments are the batch's output, in the reference's order
@@ -287,6 +330,26 @@
 			memcpy(res->out_vg_path + res->out_vg_off[e], hOutVg + hOutOffsets[2 * stride + k], hOutOffsets[2 * stride + k + 1] - hOutOffsets[2 * stride + k]);
 		});
 		res->out_path_text[pathBytes] = 0; res->out_cigar_text[cigarBytes] = 0;
+		if (P->device_output & 8) {   // the corrected pieces, compacted like the other three (entries of chained winners stay empty: the host spells them from chain_trace_*)
+			res->out_corrected_off = resultArray<uint64_t>(nOut + 1);
+			uint64_t corrBytes = 0;
+			for (uint64_t e = 0; e < nOut; e++) {
+				res->out_corrected_off[e] = corrBytes;
+				const uint64_t k = outJobOfEntry[e];
+				if (k != ~0ull) corrBytes += hCorrOffsets[k + 1] - hCorrOffsets[k];
+			}
+			res->out_corrected_off[nOut] = corrBytes;
+			res->out_corrected_text = resultArray<char>(corrBytes + 1);
+			if (allKept) pool.run(parts, [&](size_t part, size_t) {
+				const uint64_t b = corrBytes * part / parts, e = corrBytes * (part + 1) / parts;
+				if (e > b) memcpy(res->out_corrected_text + b, hCorrText + b, e - b);
+			});
+			else pool.run(nOut, [&](size_t e, size_t) {
+				const uint64_t k = outJobOfEntry[e];
+				if (k != ~0ull) memcpy(res->out_corrected_text + res->out_corrected_off[e], hCorrText + hCorrOffsets[k], hCorrOffsets[k + 1] - hCorrOffsets[k]);
+			});
+			res->out_corrected_text[corrBytes] = 0;
+		}
 		for (uint64_t e = 0; e < nOut; e++) {
 			const OutEntry& en = outEntries[e];
 			res->out_source[e] = en.source;

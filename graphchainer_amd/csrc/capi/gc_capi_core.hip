@@ -188,7 +188,8 @@ void gc_result_free(gc_result* r)
 		r->failed_assertion, r->seeds_extended, r->seeds_extended_long, r->read_path_off, r->path_node, r->path_first_offset, r->path_last_offset, r->path_cells,
 		r->read_long_off, r->long_index, r->long_edit_distance, r->chain_edit_distance, r->chained_better,
 		r->capacity_exceeded, r->read_chain_trace_off, r->chain_trace_node, r->chain_trace_offset, r->chain_trace_seqpos, r->chain_trace_switch, r->chain_aln_start, r->chain_aln_end,
-		r->read_out_off, r->out_source, r->out_numbers, r->out_path_off, r->out_path_text, r->out_cigar_off, r->out_cigar_text, r->out_vg_off, r->out_vg_path, r->flatten_ties, r->flatten_ties_long };
+		r->read_out_off, r->out_source, r->out_numbers, r->out_path_off, r->out_path_text, r->out_cigar_off, r->out_cigar_text, r->out_vg_off, r->out_vg_path, r->flatten_ties, r->flatten_ties_long,
+		r->out_corrected_off, r->out_corrected_text };
 	for (void* p : ptrs) g_resultBlocks.put(p);
 	free(r);
 }

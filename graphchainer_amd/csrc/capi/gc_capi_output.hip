@@ -1,6 +1,7 @@
 // C entry points, a batch's alignments in the reference's formats: gc_format_gaf / _json / _gam / _gam_level, gc_format_gaf_trace, gc_format_vg_trace / _digraph,
-// gc_graph_letters, gc_gzip_streams / _lz, and gzipGroupsOnDevice, the GAM groups' deflate staging.
+// gc_graph_letters, gc_gzip_streams / _lz, and gzipGroupsOnDevice, the GAM groups' deflate staging; gc_format_corrected / _trace and gc_corrected_pieces, the corrected reads.
 #include "../gc_runtime.hpp"
+#include "../hip/gc_corrected_core.hpp"
 
 extern "C" {
 
@@ -66,6 +67,8 @@ static int formatBatch(const gc_graph* G, const gc_result* r, const char* const*
 		if (kind == OUT_GAF && r->out_cigar_off[r->read_out_off[r->n_reads]] == 0 && r->out_vg_off[r->read_out_off[r->n_reads]] != 0) return fail(GC_ERR_INVALID, "the result was produced without the GAF pieces (gc_params::device_output & 3)");
 		if (kind != OUT_GAF && r->out_vg_off[r->read_out_off[r->n_reads]] == 0 && r->out_cigar_off[r->read_out_off[r->n_reads]] != 0) return fail(GC_ERR_INVALID, "the result was produced without the vg::Path bytes (gc_params::device_output & 4)");
 	}
+	if (pieces && (r->device_output & 8) && kind == OUT_GAF && !(r->device_output & 3)) return fail(GC_ERR_INVALID, "the result was produced without the GAF pieces (gc_params::device_output & 3)");
+	if (pieces && (r->device_output & 8) && kind != OUT_GAF && !(r->device_output & 4)) return fail(GC_ERR_INVALID, "the result was produced without the vg::Path bytes (gc_params::device_output & 4)");
 	if (!pieces && (!r->long_trace_off || !r->read_long_off || !r->long_index)) return fail(GC_ERR_INVALID, "the output encoders need a result with long_pass, keep_traces and edit_distances");
 	return guarded([&]() {
 		const uint64_t n = r->n_reads;
@@ -258,6 +261,162 @@ static int gzipStreams(const uint8_t* bytes, const uint64_t* offsets, uint64_t n
 		if (!buf) throw std::runtime_error("out of memory");
 		for (uint64_t i = 0; i < n; i++) memcpy(buf + out_offsets[i], groups[i].data(), groups[i].size());
 		*out_bytes = buf;
+		return (int)GC_OK;
+	});
+}
+
+// ---- corrected reads (GraphAligner's --corrected-out / --corrected-clipped-out)
+
+// AddCorrected (src/GraphAligner.h:220-231) on the host: the plain loop over one trace
+static std::string correctedPieceOnHost(const gc::AlignmentGraph& graph, const int32_t* node, const uint32_t* offset, const uint8_t* nodeSwitch, uint64_t n)
+{
+	std::string piece;
+	gc::GraphLetters letters(graph);
+	for (uint64_t i = 0; i < n; i++)
+		if (gcdev::corrKeeps(i == 0, i ? node[i - 1] : 0, i ? offset[i - 1] : 0, i ? nodeSwitch[i - 1] : 0, node[i], offset[i])) piece += letters.at(node[i], offset[i]);
+	return piece;
+}
+static char* mallocCopy(const std::string& s)
+{
+	char* buf = (char*)malloc(s.size() + 1);
+	if (!buf) throw std::runtime_error("out of memory");
+	memcpy(buf, s.data(), s.size());
+	buf[s.size()] = 0;
+	return buf;
+}
+
+int gc_format_corrected(const gc_graph* G, const gc_result* r, const char* const* read_names, const char* bases, const uint64_t* offsets, int clipped,
+	char** out_text, uint64_t* out_len, uint64_t** rec_off, uint64_t* n_rec, uint64_t* n_chained_skipped)
+{
+	if (!G || !r || !read_names || !bases || !offsets || !out_text || !out_len) return fail(GC_ERR_INVALID, "null argument");
+	const bool pieces = r->out_corrected_off != nullptr;   // the device spelled the pieces (gc_params::device_output & 8)
+	if (!pieces && (!r->long_trace_off || !r->read_long_off || !r->long_index || !r->read_longall_off || (r->read_longall_off[r->n_reads] > 0 && r->long_trace_off[r->read_longall_off[r->n_reads]] == 0))) return fail(GC_ERR_INVALID, "gc_format_corrected needs a result with device_output & 8, or with long_pass, keep_traces and edit_distances");
+	return guarded([&]() {
+		const uint64_t n = r->n_reads;
+		const size_t maxOverlap = 0;   // getDBGoverlap of the graphs this library loads (0M overlaps): getLongestOverlap is 0, nothing is trimmed
+		std::vector<std::string> perRead(n);
+		std::vector<std::vector<uint64_t>> recEnds(n);   // ends of the read's records inside perRead[i]
+		std::atomic<uint64_t> skipped { 0 };
+		WorkerPool::instance().run(n, [&](size_t i, size_t) {
+			if (r->failed_assertion[i] || r->capacity_exceeded[i]) return;   // the reference `continue`s: no record
+			std::string& text = perRead[i];
+			const std::string id = read_names[i] ? read_names[i] : "";
+			const char* raw = bases + offsets[i];
+			const uint64_t rawLen = offsets[i + 1] - offsets[i];
+			std::vector<std::string> spelled;            // pieces made here, on the host
+			std::vector<gcdev::CorrPiece> list;
+			if (r->chained_better[i]) {
+				// the chained alignment replaces the whole-read ones (src/Aligner.cpp:901-920): a single item
+				const uint64_t t0 = r->read_chain_trace_off ? r->read_chain_trace_off[i] : 0, t1 = r->read_chain_trace_off ? r->read_chain_trace_off[i + 1] : 0;
+				if (t1 == t0) { skipped++; return; }   // result produced without chain_traces
+				spelled.push_back(correctedPieceOnHost(G->host, r->chain_trace_node + t0, r->chain_trace_offset + t0, r->chain_trace_switch + t0, t1 - t0));
+				list.push_back(gcdev::CorrPiece { r->chain_aln_start[i], r->chain_aln_end[i], nullptr, 0 });
+			} else if (pieces) {
+				for (uint64_t e = r->read_out_off[i]; e < r->read_out_off[i + 1]; e++)
+					list.push_back(gcdev::CorrPiece { r->out_numbers[12 * e + 8], r->out_numbers[12 * e + 9], r->out_corrected_text + r->out_corrected_off[e], r->out_corrected_off[e + 1] - r->out_corrected_off[e] });
+			} else {
+				struct Item { uint32_t start; uint64_t aln; };
+				std::vector<Item> items;
+				for (uint64_t k = r->read_long_off[i]; k < r->read_long_off[i + 1]; k++) { const uint64_t a = r->read_longall_off[i] + r->long_index[k]; items.push_back(Item { r->longall_start[a], a }); }
+				auto byStart = [](const Item& l, const Item& rr) { return l.start < rr.start; };
+				std::sort(items.begin(), items.end(), byStart);   // src/Aligner.cpp:1003
+				std::sort(items.begin(), items.end(), byStart);   // :1023
+				for (const Item& it : items) {
+					const uint64_t t0 = r->long_trace_off[it.aln], t1 = r->long_trace_off[it.aln + 1];
+					spelled.push_back(correctedPieceOnHost(G->host, r->long_trace_node + t0, r->long_trace_offset + t0, r->long_trace_switch + t0, t1 - t0));
+					list.push_back(gcdev::CorrPiece { r->longall_start[it.aln], r->longall_end[it.aln], nullptr, 0 });
+				}
+			}
+			for (size_t k = 0, s = 0; k < list.size(); k++) if (!list[k].text) { list[k].text = spelled[s].data(); list[k].len = spelled[s].size(); s++; }
+			if (!clipped) { gcdev::corrRecord(text, id, raw, rawLen, list, maxOverlap); recEnds[i].push_back(text.size()); }
+			else for (size_t k = 0; k < list.size(); k++) { gcdev::corrClippedRecord(text, id, k, list[k]); recEnds[i].push_back(text.size()); }
+		});
+		uint64_t total = 0, records = 0;
+		for (uint64_t i = 0; i < n; i++) { total += perRead[i].size(); records += recEnds[i].size(); }
+		char* buf = (char*)malloc(total + 1);
+		uint64_t* off = rec_off ? (uint64_t*)malloc((records + 1) * sizeof(uint64_t)) : nullptr;
+		if (!buf || (rec_off && !off)) { free(buf); free(off); throw std::runtime_error("out of memory"); }
+		uint64_t at = 0, k = 0;
+		for (uint64_t i = 0; i < n; i++) {
+			memcpy(buf + at, perRead[i].data(), perRead[i].size());
+			if (off) for (uint64_t end : recEnds[i]) off[++k] = at + end;
+			at += perRead[i].size();
+		}
+		if (off) off[0] = 0;
+		buf[total] = 0;
+		*out_text = buf; *out_len = total;
+		if (rec_off) *rec_off = off;
+		if (n_rec) *n_rec = records;
+		if (n_chained_skipped) *n_chained_skipped = skipped.load();
+		return (int)GC_OK;
+	});
+}
+
+int gc_format_corrected_trace(const gc_graph* G, const int32_t* node, const uint32_t* offset, const uint8_t* node_switch, uint64_t n, char** out_text, uint64_t* out_len)
+{
+	if (!G || !out_text || !out_len || (n && (!node || !offset || !node_switch))) return fail(GC_ERR_INVALID, "null argument");
+	return guarded([&]() {
+		for (uint64_t i = 0; i < n; i++) {
+			const size_t* size = G->host.originalNodeSize.find(node[i]);
+			if (!size || offset[i] >= *size) throw std::runtime_error("gc_format_corrected_trace: no such node / offset");
+		}
+		const std::string piece = correctedPieceOnHost(G->host, node, offset, node_switch, n);
+		*out_text = mallocCopy(piece); *out_len = piece.size();
+		return (int)GC_OK;
+	});
+}
+
+int gc_corrected_pieces(const gc_graph* G, const int32_t* node, const uint32_t* offset, const uint8_t* node_switch, const uint64_t* trace_off, uint64_t n_aln, char** out_text, uint64_t** out_off)
+{
+	if (!G || !trace_off || !out_text || !out_off) return fail(GC_ERR_INVALID, "null argument");
+	const uint64_t cellsTotal = trace_off[n_aln];
+	if (cellsTotal && (!node || !offset || !node_switch)) return fail(GC_ERR_INVALID, "null argument");
+	if (n_aln >= 0xffffffffull) return fail(GC_ERR_INVALID, "gc_corrected_pieces: too many alignments");
+	if (trace_off[0] != 0) return fail(GC_ERR_INVALID, "gc_corrected_pieces: trace_off must start at 0");
+	for (uint64_t a = 0; a < n_aln; a++) if (trace_off[a + 1] < trace_off[a] || trace_off[a + 1] - trace_off[a] >= (1ull << 32)) return fail(GC_ERR_INVALID, "gc_corrected_pieces: trace_off must ascend, traces below 2^32 cells");
+	// the kernels index the graph's tables with what the cells say: every cell is checked here first
+	for (uint64_t i = 0; i < cellsTotal; i++) {
+		const size_t* size = G->host.originalNodeSize.find(node[i]);
+		if (!size || offset[i] >= *size) return fail(GC_ERR_INVALID, "gc_corrected_pieces: no such node / offset");
+	}
+	return guarded([&]() {
+		uint64_t* off = (uint64_t*)calloc(n_aln + 1, sizeof(uint64_t));
+		if (!off) throw std::runtime_error("out of memory");
+		if (n_aln == 0) { *out_text = mallocCopy(std::string()); *out_off = off; return (int)GC_OK; }
+		struct Free { void* p; ~Free() { free(p); } } offGuard { off };
+		requireDevice();
+		int device = 0;
+		HIP_CHECK(hipGetDevice(&device));
+		hipStream_t q = threadStream(device);
+		std::vector<LongCell> cells(std::max<uint64_t>(1, cellsTotal));
+		for (uint64_t i = 0; i < cellsTotal; i++) cells[i] = LongCell { node[i], offset[i], 0u, (uint32_t)(node_switch[i] != 0) };
+		std::vector<OutJob> jobs(n_aln);
+		for (uint64_t a = 0; a < n_aln; a++) jobs[a] = OutJob { trace_off[a], 0, (uint32_t)(trace_off[a + 1] - trace_off[a]), 0, 0, 0 };
+		DeviceBuffer dCells, dJobs, dLens, dOffsets, dTotal, dText;
+		LongCell* pCells = dCells.reserve<LongCell>(cells.size());
+		OutJob* pJobs = dJobs.reserve<OutJob>(n_aln);
+		uint32_t* pLens = dLens.reserve<uint32_t>(n_aln);
+		uint64_t* pOffsets = dOffsets.reserve<uint64_t>(n_aln + 1);
+		unsigned long long* pTotal = dTotal.reserve<unsigned long long>(1);
+		HIP_CHECK(hipMemcpyAsync(pCells, cells.data(), cells.size() * sizeof(LongCell), hipMemcpyHostToDevice, q));
+		HIP_CHECK(hipMemcpyAsync(pJobs, jobs.data(), n_aln * sizeof(OutJob), hipMemcpyHostToDevice, q));
+		launchCorrectedCount(q, G->dev, pJobs, (uint32_t)n_aln, pCells, pLens, pOffsets, pTotal);
+		unsigned long long total = 0;
+		HIP_CHECK(hipMemcpyAsync(&total, pTotal, sizeof total, hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		if (total > cellsTotal) throw std::runtime_error("internal: the corrected-read kernel counted more letters than cells");
+		char* pText = dText.reserve<char>(total + 1);
+		launchCorrectedWrite(q, G->dev, pJobs, (uint32_t)n_aln, pCells, pLens, pOffsets, pText);
+		std::vector<uint32_t> lens(n_aln);
+		std::string text(total, '\0');
+		HIP_CHECK(hipMemcpyAsync(lens.data(), pLens, n_aln * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipMemcpyAsync(off, pOffsets, (n_aln + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, q));
+		if (total) HIP_CHECK(hipMemcpyAsync(&text[0], pText, total, hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		for (uint32_t l : lens) if (l == 0xffffffffu) throw std::runtime_error("internal: the corrected-read kernel's two passes disagree on an alignment's size");
+		*out_text = mallocCopy(text);
+		offGuard.p = nullptr;
+		*out_off = off;
 		return (int)GC_OK;
 	});
 }

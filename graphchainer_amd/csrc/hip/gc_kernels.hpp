@@ -332,6 +332,11 @@ void launchOutCount(hipStream_t stream, const DGraph& g, const OutNames& names, 
 	OutRec* recs, uint64_t* offsets, uint32_t* mapSizeAtCell, unsigned long long* totals);
 void launchOutWrite(hipStream_t stream, const DGraph& g, const OutNames& names, const uint8_t* iupac, const OutJob* jobs, uint32_t nJobs, const LongCell* cellPool, const char* bases,
 	OutRec* recs, const uint64_t* offsets, uint32_t* mapSizeAtCell, char* pathText, char* cigarText, uint8_t* vgBytes);
+// ---- corrected reads (gc_corrected.hip; gc_params::device_output & 8): the graph's letters along every job's trace with the insertions left out (AddCorrected,
+// src/GraphAligner.h:220-231). Of an OutJob only cellOff / cellLen are read. Counting pass + placement: lens[nJobs], offsets[nJobs + 1] (the last entry and *total = the sum);
+// the writing pass fills text and sets lens[j] = ~0u where it did not land on the counted size
+void launchCorrectedCount(hipStream_t stream, const DGraph& g, const OutJob* jobs, uint32_t nJobs, const LongCell* cellPool, uint32_t* lens, uint64_t* offsets, unsigned long long* total);
+void launchCorrectedWrite(hipStream_t stream, const DGraph& g, const OutJob* jobs, uint32_t nJobs, const LongCell* cellPool, uint32_t* lens, const uint64_t* offsets, char* text);
 // ---- DEFLATE of independent byte streams (gc_deflate.hip): one dynamic-Huffman block of literals per stream (stored blocks where that is smaller or the code
 // would be deeper than 15 bits). plan[s] = { deflate bytes, mode }, lens[260 * s + symbol]; the caller places stream s at a 4-byte aligned outOff[s] with room for plan[s].x rounded up to 4
 void launchDeflatePlan(hipStream_t stream, const uint8_t* raw, const uint64_t* rawOff, uint32_t nStreams, uint8_t* lens, uint2* plan);

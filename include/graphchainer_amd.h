@@ -81,7 +81,9 @@ typedef struct gc_params {
 	                             *    only anchors and chains are wanted. */
 	int32_t device_output;      /* r4: encode the final alignments on the device, where their traces already are, instead of bringing the traces down (keep_traces)
 	                             *    for gc_format_*: bit 0 (1) the GAF path and cg:Z: CIGAR text with = / X items, bit 1 (2) the same with M items
-	                             *    (--cigar-match-mismatch merge; give one of the two), bit 2 (4) the vg::Path wire bytes that gc_format_gam / _json wrap.
+	                             *    (--cigar-match-mismatch merge; give one of the two), bit 2 (4) the vg::Path wire bytes that gc_format_gam / _json wrap,
+	                             *    bit 3 (8) the corrected reads' pieces (GraphAligner's --corrected-out / --corrected-clipped-out: AddCorrected, src/GraphAligner.h:220-231)
+	                             *    that gc_format_corrected puts into records; bit 3 also works alone, without GAF or vg pieces.
 	                             *    Fills gc_result::read_out_off / out_*; needs long_pass and edit_distances. (Sits in what used to be padding: the layout of the
 	                             *    other fields is unchanged.) */
 	double  e_cutoff;           /* --E-cutoff (src/AlignerMain.cpp:159,271-274; SelectECutoff src/AlignmentSelection.cpp:57-61,91-99):
@@ -480,6 +482,11 @@ typedef struct gc_result {
 	uint32_t* flatten_ties;       /* [n_reads] */
 	uint32_t* flatten_ties_long;  /* [n_reads] */
 	int32_t device_output;        /* the gc_params::device_output the batch ran with: gc_format_gaf refuses a cigar_match_mismatch_merge that differs from the pieces' style */
+	/* Appended (the layout above is unchanged; NULL unless device_output & 8): the corrected piece of every entry - the graph's letters along its trace, insertions left
+	 * out (AddCorrected, src/GraphAligner.h:220-231), as the device spelled them (hip/gc_corrected.hip). Entries with out_source 1 are empty: gc_format_corrected spells
+	 * those on the host from chain_trace_*. */
+	uint64_t* out_corrected_off;  /* [n_out+1] */
+	char*     out_corrected_text;
 } gc_result;
 
 /* Runs seeding, fragment seed-extension, anchor construction and co-linear chaining (and, with
@@ -591,6 +598,28 @@ int gc_format_vg_trace(const gc_graph* g, const char* read_name, const char* seq
 int gc_format_vg_trace_digraph(const gc_graph* g, const char* read_name, const char* sequence, uint64_t sequence_len, const int32_t* node, const uint32_t* offset, const uint32_t* seqpos,
                                const uint8_t* node_switch, uint64_t n, int32_t score, uint64_t alignment_start, uint64_t alignment_end, char** out_bytes, uint64_t* out_len);
 int gc_graph_letters(const gc_graph* g, const int32_t* node, const uint32_t* offset, uint64_t n, char* out);
+
+/* Corrected reads: GraphAligner's --corrected-out and --corrected-clipped-out (the mechanism the reference still carries: AddCorrected src/GraphAligner.h:220-231,
+ * getCorrected src/ReadCorrection.cpp:38-64, writeCorrectedToQueue / writeCorrectedClippedToQueue src/Aligner.cpp:313-374,984,1037,1050-1051).
+ * An alignment's piece is the graph letter (TraceItem::graphCharacter, what gc_graph_letters returns: IUPAC codes and the N of an all-zero column included) of its first
+ * trace cell, then of every cell that is not an insertion: cell i adds nothing when cell i-1 is not flagged nodeSwitch and cell i stands on its node and offset.
+ * clipped == 0: one record per read, ">" id "\n" body "\n", the id being the whole read_names[i]; the body takes the read's alignments in the result's output order
+ * (read_out_off) with currentEnd = 0: tolower(raw[currentEnd:start]) when start > currentEnd, then toupper(piece), currentEnd = end (even when that moves it backwards),
+ * and tolower(raw[currentEnd:]) after the last. maxOverlap is getDBGoverlap, 0 for the graphs this library loads: nothing is trimmed where start < currentEnd. A read
+ * without alignments gives its lower-cased self; a flagged read (failed_assertion, capacity_exceeded) gives no record. raw = bases[offsets[i] .. offsets[i+1]).
+ * clipped != 0: one record per alignment, ">" id "_" i "_" start "_" end "\n" piece "\n", i counting within the read's output list.
+ * Works from the device's pieces (device_output & 8) for out_source 0 and spells chained winners on the host from chain_trace_*; without the bit it works from a
+ * keep_traces result (long_pass, edit_distances, chain_traces >= 1), everything spelled on the host. rec_off (may be NULL): malloc'd [*n_rec + 1] byte offsets of the
+ * records in *out_text, for a host that compresses them one by one. n_chained_skipped counts winners the result holds no trace for. Free both with gc_free. */
+int gc_format_corrected(const gc_graph* g, const gc_result* result, const char* const* read_names, const char* bases, const uint64_t* offsets, int clipped,
+                        char** out_text, uint64_t* out_len, uint64_t** rec_off, uint64_t* n_rec, uint64_t* n_chained_skipped);
+/* One alignment's piece from its trace on the host (beside gc_format_gaf_trace; no device work): *out_text malloc'd, NUL-terminated, *out_len letters. */
+int gc_format_corrected_trace(const gc_graph* g, const int32_t* node, const uint32_t* offset, const uint8_t* node_switch, uint64_t n, char** out_text, uint64_t* out_len);
+/* The device kernels over a caller's own traces (a host that keeps its traces; the tests, which need exact shapes): alignment a is cells trace_off[a] .. trace_off[a+1]
+ * of node / offset / node_switch; *out_text holds the pieces back to back, piece a at (*out_off)[a] .. (*out_off)[a+1] (n_aln + 1 entries). Every (node, offset) is
+ * checked against the graph first (GC_ERR_INVALID). Free both with gc_free. */
+int gc_corrected_pieces(const gc_graph* g, const int32_t* node, const uint32_t* offset, const uint8_t* node_switch, const uint64_t* trace_off, uint64_t n_aln,
+                        char** out_text, uint64_t** out_off);
 
 /* gc_format_gam with the zlib level of the gzip members chosen by the caller (-1 = Z_DEFAULT_COMPRESSION, what the reference's GzipOutputStream uses and gc_format_gam
  * gives; 0..9). The inflated stream is the same at every level; deflate at the default level costs ~1 ms of CPU per 10 kb read - more than the whole alignment costs the
