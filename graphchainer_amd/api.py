@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = [
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_format_corrected", "gc_format_corrected_trace", "gc_corrected_pieces",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
-    "gc_reads_parse", "gc_fastx_table_free", "gc_bgzf_inflate", "gc_reads_parse_bgzf",
+    "gc_reads_parse", "gc_fastx_table_free", "gc_bgzf_inflate", "gc_reads_parse_bgzf", "gc_reads_parse_bam", "gc_reads_parse_bam_bgzf",
     "gc_seed_store_open", "gc_seed_store_from_memory", "gc_seed_store_info", "gc_seed_store_destroy", "gc_seeds_from_store",
 ]
 
@@ -578,6 +578,47 @@ class ReadBatch:
         self.bgzf = {"blocks": int(stats.blocks), "inflated_bytes": int(stats.inflated_bytes), "scan_ms": float(stats.scan_ms), "upload_ms": float(stats.upload_ms), "kernel_ms": float(stats.kernel_ms)}
         return self, ids, text, int(consumed.value)
 
+    @classmethod
+    def from_bam(cls, data, header, final=True):
+        """Inflated unaligned BAM bytes decoded on the device (gc_reads_parse_bam): -> (batch, ids, consumed), as from_text gives them. header: data starts with the
+        file's header (else at a record boundary). Records with flag 0x100 or 0x800 are left out; batch.bam holds the records seen, those skipped and the kernels'
+        milliseconds. final=True refuses a header or record that the end of data cuts."""
+        lib = load_library()
+        data = bytes(data) if not isinstance(data, bytes) else data
+        lib.gc_reads_parse_bam.restype = C.c_int
+        lib.gc_reads_parse_bam.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, _P(C.c_void_p), _P(_P(GcFastxTable)), _P(GcBamStats)]
+        lib.gc_fastx_table_free.argtypes = [_P(GcFastxTable)]
+        lib.gc_fastx_table_free.restype = None
+        handle, table, stats = C.c_void_p(), _P(GcFastxTable)(), GcBamStats()
+        _check(lib.gc_reads_parse_bam(data, len(data), (FASTX_FINAL if final else 0) | (BAM_HEADER if header else 0), C.byref(handle), C.byref(table), C.byref(stats)))
+        self, ids, consumed = cls._from_table(lib, handle, table)
+        self.bam = stats.as_dict()
+        return self, ids, consumed
+
+    @classmethod
+    def from_bam_bgzf(cls, head, data, header, final=True):
+        """from_bam on `head` followed by the inflated whole BGZF blocks at the front of `data` (gc_reads_parse_bam_bgzf): -> (batch, ids, tail, consumed), as from_bgzf
+        gives them: `tail` is the bytes behind the last whole record, the next call's head; `consumed` counts compressed bytes. batch.bgzf and batch.bam hold the counts."""
+        lib = load_library()
+        head = bytes(head) if not isinstance(head, bytes) else head
+        data = bytes(data) if not isinstance(data, bytes) else data
+        lib.gc_reads_parse_bam_bgzf.restype = C.c_int
+        lib.gc_reads_parse_bam_bgzf.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint32, _P(C.c_void_p), _P(_P(GcFastxTable)), _P(C.c_void_p), _P(C.c_uint64),
+                                                _P(C.c_uint64), _P(GcBgzfStats), _P(GcBamStats)]
+        lib.gc_fastx_table_free.argtypes = [_P(GcFastxTable)]
+        lib.gc_fastx_table_free.restype = None
+        handle, table, tail, tail_len, consumed, stats, bam = C.c_void_p(), _P(GcFastxTable)(), C.c_void_p(), C.c_uint64(), C.c_uint64(), GcBgzfStats(), GcBamStats()
+        _check_bgzf(lib.gc_reads_parse_bam_bgzf(head, len(head), data, len(data), (FASTX_FINAL if final else 0) | (BAM_HEADER if header else 0), C.byref(handle), C.byref(table),
+                                                C.byref(tail), C.byref(tail_len), C.byref(consumed), C.byref(stats), C.byref(bam)))
+        try:
+            rest = C.string_at(tail.value, tail_len.value)
+        finally:
+            lib.gc_free(tail)
+        self, ids, _ = cls._from_table(lib, handle, table)
+        self.bgzf = {"blocks": int(stats.blocks), "inflated_bytes": int(stats.inflated_bytes), "scan_ms": float(stats.scan_ms), "upload_ms": float(stats.upload_ms), "kernel_ms": float(stats.kernel_ms)}
+        self.bam = bam.as_dict()
+        return self, ids, rest, int(consumed.value)
+
     def close(self):
         if self.handle:
             self.lib.gc_reads_destroy(self.handle)
@@ -591,6 +632,7 @@ class ReadBatch:
 
 
 FASTX_FASTA, FASTX_FASTQ, FASTX_FINAL = 1, 2, 1   # GC_FASTX_FASTA / GC_FASTX_FASTQ / GC_FASTX_FINAL
+BAM_HEADER = 2                                    # GC_BAM_HEADER
 FASTX_FORMATS = {"fasta": FASTX_FASTA, "fastq": FASTX_FASTQ}
 
 
@@ -605,10 +647,21 @@ class GcBgzfStats(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("inflated_bytes", C.c_uint64), ("scan_ms", C.c_double), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class GcBamStats(C.Structure):
+    """gc_bam_stats (include/graphchainer_amd.h)."""
+    _fields_ = [("records", C.c_uint64), ("skipped", C.c_uint64), ("walk_ms", C.c_double), ("fields_ms", C.c_double), ("names_ms", C.c_double), ("unpack_ms", C.c_double)]
+
+    def as_dict(self):
+        return {"records": int(self.records), "skipped": int(self.skipped), "walk_ms": float(self.walk_ms), "fields_ms": float(self.fields_ms), "names_ms": float(self.names_ms),
+                "unpack_ms": float(self.unpack_ms)}
+
+
 def fastx_file_format(path):
     """FastQ::streamFastqFromFile's choice by file name (src/fastqloader.h:98-139): ("fasta" | "fastq" | None, gzipped). None: the reference reads nothing from such a
-    file and reports nothing."""
+    file and reports nothing. This build's own: a name that ends in .bam is ("bam", True) - unaligned BAM, which is BGZF throughout (a .bam.gz is not)."""
     name = os.fsdecode(path)
+    if len(name) > 4 and name.endswith(".bam"):
+        return "bam", True
     gz = len(name) > 3 and name.endswith(".gz")
     if gz:
         name = name[:-3]
@@ -715,7 +768,8 @@ def file_pieces(paths, batch_bytes=100 << 20, bgzf="host"):
     the read files in order - about batch_bytes of file text, inflated, and whether the file ends with it. A file whose name gives no format gives nothing; an empty
     file gives one empty last piece. bgzf="device": a .gz whose first member is a BGZF block gives its whole blocks still compressed, as BgzfPiece, cut where their
     ISIZE sum reaches about batch_bytes - parse_pieces inflates them on the device; from a member that is not BGZF on (an ordinary gzip member appended to a BGZF file)
-    the rest of the file is inflated here as under "host", the default, under which every .gz is."""
+    the rest of the file is inflated here as under "host", the default, under which every .gz is. A .bam file ("bam") goes the .gz way under both settings: it is BGZF
+    throughout, and its end-of-file block travels with the last piece."""
     if bgzf not in ("host", "device"):
         raise ValueError("bgzf is 'host' or 'device'")
     batch_bytes = max(int(batch_bytes), 1)
@@ -737,12 +791,32 @@ def parse_pieces(pieces, before_parse=None, counts=None):
     """The parser's half of read_files: generator of (batch, ids) over what file_pieces gives. A record cut by the end of a piece is carried over to the next one, a
     record longer than the piece makes the chunk grow, and the chunk that ends a file is parsed as the end of a file. Sequential by its nature: the next chunk begins
     where gc_reads_parse says the previous one was consumed. before_parse() is called ahead of every gc_reads_parse (the command line selects the device there). A
-    BgzfPiece goes through gc_reads_parse_bgzf with the carried text as its head; counts, a dict, gains the blocks inflated there under "bgzf_blocks"."""
-    held = b""
+    BgzfPiece goes through gc_reads_parse_bgzf with the carried text as its head; counts, a dict, gains the blocks inflated there under "bgzf_blocks". A "bam" piece goes
+    through from_bam / from_bam_bgzf the same way; the file's header is expected at the start of a file - the first piece, or the one after a `last` - until a call has
+    consumed it, and counts gains the records left out under "bam_skipped"."""
+    held, at_start = b"", True
     for fmt, piece, last in pieces:
         if before_parse is not None:
             before_parse()
-        if isinstance(piece, BgzfPiece):
+        if fmt == "bam":
+            if isinstance(piece, BgzfPiece):
+                batch, ids, tail, consumed = ReadBatch.from_bam_bgzf(held, piece, header=at_start, final=last)
+                if consumed != len(piece):
+                    raise RuntimeError("parse_pieces: a piece of whole BGZF blocks was not consumed whole")
+                if counts is not None:
+                    counts["bgzf_blocks"] = counts.get("bgzf_blocks", 0) + batch.bgzf["blocks"]
+                moved = len(held) + batch.bgzf["inflated_bytes"] - len(tail)
+                held = tail
+            else:
+                held += piece
+                batch, ids, moved = ReadBatch.from_bam(held, header=at_start, final=last)
+                held = held[moved:]
+            if counts is not None:
+                counts["bam_skipped"] = counts.get("bam_skipped", 0) + batch.bam["skipped"]
+            at_start = last or (at_start and not moved)
+            if last:
+                held = b""
+        elif isinstance(piece, BgzfPiece):
             batch, ids, tail, consumed = ReadBatch.from_bgzf(held, piece, fmt, final=last)
             if consumed != len(piece):
                 raise RuntimeError("parse_pieces: a piece of whole BGZF blocks was not consumed whole")

@@ -1,4 +1,5 @@
-"""The command line: `python -m graphchainer_amd -g graph.gfa -f reads.fq.gz -a out.gaf`, the reference's GraphChainer binary over this library.
+"""The command line: `python -m graphchainer_amd -g graph.gfa -f reads.fq.gz -a out.gaf`, the reference's GraphChainer binary over this library. -f also takes unaligned
+BAM (reads.bam), which the reference does not: its records are decoded on the device.
 
 resolve(argv) -> Config turns a command line into what a run needs - the reference's option names, short forms, defaults, checks and messages
 (src/AlignerMain.cpp:35-112,138-464) - and touches neither the library nor a device. main(argv) runs it (run, over pipeline.py): a reader thread, a parse thread (the reads are parsed on the device, about
@@ -51,7 +52,7 @@ SELECT = {"greedy-length": 0, "schedule-inverse-E-sum": 3, "schedule-inverse-E-p
 
 HELP = """Mandatory parameters:
   -g [ --graph ] arg                    input graph (.gfa)
-  -f [ --reads ] arg                    input reads (fasta or fastq, uncompressed or gzipped)
+  -f [ --reads ] arg                    input reads (fasta, fastq or unaligned bam; fasta and fastq uncompressed or gzipped)
   -a [ --alignments-out ] arg           output alignment file (.gaf/.gam/.json), may be given several times
 
 Colinear chaining parameters:
@@ -420,7 +421,9 @@ class _Outputs:
 # in flight; what they still miss, the pipeline's out-of-memory retirement catches.
 BATCH_BYTES_PER_READ_BASE = 420
 LONG_SCRATCH_BYTES = 27 * 10 ** 9
-FILE_BYTES_PER_READ_BASE = {"fasta": 1, "fastq": 2}     # at least: a FASTQ record holds a quality letter per base, so a batch of B bytes of text holds at most B / 2 bases
+# at least: a FASTQ record holds a quality letter per base, so a batch of B bytes of text holds at most B / 2 bases; a BAM record holds half a byte and a quality byte
+# per base, so B inflated bytes hold at most B * 2 / 3
+FILE_BYTES_PER_READ_BASE = {"fasta": 1, "fastq": 2, "bam": 1.5}
 
 
 def usable_cpus():
@@ -446,7 +449,7 @@ def choose_inflight(cpus, free_bytes, batch_bytes, fmt, replicas=1):
     and one for the writer are set aside, shared among the replicas; and as many batches as fit free_bytes - the device's free memory after set-up (a replica's share of
     it where several are on one device) - beside the whole-read scratch, a batch counted as batch_bytes of `fmt` text at BATCH_BYTES_PER_READ_BASE per base. Never below 1."""
     by_cpu = (int(cpus) - 2) // max(1, int(replicas))
-    bases = max(1, int(batch_bytes) // FILE_BYTES_PER_READ_BASE[fmt])
+    bases = max(1, int(batch_bytes) * 2 // 3 if fmt == "bam" else int(batch_bytes) // FILE_BYTES_PER_READ_BASE[fmt])
     by_memory = (int(free_bytes) - LONG_SCRATCH_BYTES) // (bases * BATCH_BYTES_PER_READ_BASE)
     return max(1, min(MAX_INFLIGHT, by_cpu, by_memory))
 
@@ -531,7 +534,7 @@ def run(cfg, stderr=sys.stderr):
     formats = tuple(f for f in ("gaf", "json", "gam") if f in cfg.outputs)
     corrected = tuple(f for f in ("corrected", "corrected_clipped") if f in cfg.corrected)       # the corrected reads' pieces are spelled on the device too (bit 8), also with no -a at all
     device_output = device_output_for(cfg)
-    counts = {"reads": 0, "flagged": 0, "failed_assertion": 0, "capacity_exceeded": 0, "batches": 0, "seconds": 0.0, "bgzf_blocks": 0}   # seconds: reading, aligning and writing, setup left out
+    counts = {"reads": 0, "flagged": 0, "failed_assertion": 0, "capacity_exceeded": 0, "batches": 0, "seconds": 0.0, "bgzf_blocks": 0, "bam_skipped": 0}   # seconds: reading, aligning and writing, setup left out
 
     def make_aligner(r):
         rep = replicas[r]
@@ -561,12 +564,13 @@ def run(cfg, stderr=sys.stderr):
         _setup_replicas(cfg, api, replicas)
         inflight = cfg.inflight
         if not inflight:
-            kinds = {api.fastx_file_format(p)[0] for p in cfg.reads}
+            kinds = {api.fastx_file_format(p)[0] for p in cfg.reads} - {None}
+            densest = min(kinds, key=FILE_BYTES_PER_READ_BASE.get) if kinds else "fastq"          # the format with the fewest bytes per base: the most bases in a batch
             chosen = []
             for rep in replicas:           # the same count for every replica: the smallest any of them can hold
                 api.set_device(rep.device)
                 free, _ = api.device_memory()
-                chosen.append(choose_inflight(usable_cpus(), free // devices.count(rep.device), cfg.batch_bytes, "fasta" if "fasta" in kinds else "fastq", len(replicas)))
+                chosen.append(choose_inflight(usable_cpus(), free // devices.count(rep.device), cfg.batch_bytes, densest, len(replicas)))
             inflight = min(chosen)
         reader_seconds = {}
 
@@ -604,6 +608,8 @@ def run(cfg, stderr=sys.stderr):
                   stage_seconds={"read": {k: round(v, 6) for k, v in reader_seconds.items()},
                                  "parse": {"busy": round(max(0.0, parse["busy"] - waited), 6), "waiting_in": round(waited, 6), "waiting_out": parse["waiting_out"]},
                                  "align": stages["work"], "write": stages["sink"]})
+    if counts["bam_skipped"]:
+        print(f"{counts['bam_skipped']} BAM records were left out (secondary or supplementary: flag 0x100 or 0x800)", file=stderr)
     if counts["flagged"]:
         print(f"{counts['flagged']} of {counts['reads']} reads were flagged and have no alignment written: {counts['failed_assertion']} failed an assertion "
               f"(a letter outside the nucleotide alphabet among them), {counts['capacity_exceeded']} exceeded a capacity", file=stderr)

@@ -1,6 +1,6 @@
 // C entry points, read batches: gc_reads_upload, gc_reads_destroy, gc_reads_parse, gc_reads_parse_bgzf, gc_bgzf_inflate, gc_fastx_table_free. Every batch is laid out by
 // host/gc_layout.hpp's ReadBatchLayout and bound by bindReads (gc_runtime.hpp).
-#include "../gc_runtime.hpp"
+#include "gc_capi_reads.hpp"
 #include "../hip/gc_fastx_core.hpp"
 #include "../hip/gc_inflate_core.hpp"
 
@@ -49,14 +49,55 @@ int gc_reads_upload(const char* bases, const uint64_t* offsets, uint64_t n, gc_r
 }
 void gc_reads_destroy(gc_reads* r) { delete r; }
 
-// Where the text of a parse comes from. place() puts the len bytes at devText with work on q (pinnedText [len] is the call's staging block, free until the tables are built)
-// and returns the text's last byte (any value for an empty text); done(), if set, runs once the tables are built, while the text still lies on the device.
-struct FxSource {
-	uint32_t len = 0;
-	std::function<char(char* devText, char* pinnedText, hipStream_t q, int device)> place;
-	std::function<void(const char* devText, uint32_t consumed, hipStream_t q)> done;
-};
-struct InvalidInput : std::runtime_error { using std::runtime_error::runtime_error; };   // GC_ERR_INVALID from inside a guarded call
+} // extern "C"
+
+void finishParsedBatch(const char* what, gc_reads* R, gc_fastx_table** T, hipStream_t q, EventSet<2>& ev, double& kernelMs, uint64_t n, uint32_t total, uint32_t limit, uint32_t consumed,
+	char* S, const BatchStaging& st, char* H, const char* devNames, HeldBlock& batchBlock, const std::function<hipError_t(char* devBases)>& gather, const std::function<void()>& done)
+{
+	const std::string name(what);
+	const uint64_t* hostOff = (const uint64_t*)(S + st.off);
+	const uint32_t* hostNameOff = (const uint32_t*)(S + st.nameOff);
+	const uint64_t namesBytes = hostNameOff[n];
+	if (hostOff[n] != total || namesBytes + total > limit) throw std::runtime_error(name + ": the read offsets disagree with the base count");
+	for (uint64_t r = 0; r < n; r++) if (hostOff[r + 1] < hostOff[r] || hostNameOff[r + 1] <= hostNameOff[r]) throw std::runtime_error(name + ": offsets decrease");
+
+	R->offsets.assign(hostOff, hostOff + n + 1);
+	R->totalBases = total;
+	const gc::ReadBatchLayout lay(hostOff, n);
+	bindReads(*R, lay, batchBlock.acquire(lay.blockBytes));
+	HIP_CHECK(hipMemcpyAsync(R->devOffsets, hostOff, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, q));
+	stageReadLayout(*R, lay, (uint64_t*)(S + st.maskOff), (uint32_t*)(S + st.maskWords), (uint64_t*)(S + st.eqOff), (EdRead*)(S + st.edReads), q);
+	HIP_CHECK(hipEventRecord(ev[0], q));
+	HIP_CHECK(gather(R->devBases));
+	launchPackReads(q, R->devOffsets, (uint32_t)n, total, R->devBases, R->devMaskOff, R->devMaskWords, R->devMasks, R->devEqOff, R->devEqMasks, R->devReadInvalid, R->devPacked, R->devInvalid, R->devChunkRead);
+	HIP_CHECK(hipEventRecord(ev[1], q));
+	R->invalid.assign(n, 0);
+	if (n) HIP_CHECK(hipMemcpyAsync(S + st.invalid, R->devReadInvalid, n, hipMemcpyDeviceToHost, q));
+	if (total) HIP_CHECK(hipMemcpyAsync(H, R->devBases, total, hipMemcpyDeviceToHost, q));
+	if (namesBytes) HIP_CHECK(hipMemcpyAsync(H + total, devNames, namesBytes, hipMemcpyDeviceToHost, q));
+	HIP_CHECK(hipStreamSynchronize(q));
+	kernelMs += ev.elapsedMs(0, 1);
+	if (n) memcpy(R->invalid.data(), S + st.invalid, n);
+	if (done) done();
+
+	// the host's table: one allocation, the struct | offsets | name_off | bases | names
+	const size_t tHead = (sizeof(gc_fastx_table) + 15) & ~(size_t)15, tArr = (n + 1) * sizeof(uint64_t);
+	char* mem = (char*)malloc(tHead + 2 * tArr + total + namesBytes + 2);
+	if (!mem) throw std::runtime_error(name + ": out of host memory");
+	gc_fastx_table* t = (gc_fastx_table*)mem;
+	*T = t;
+	t->n_reads = n; t->consumed = consumed; t->kernel_ms = kernelMs;
+	t->offsets = (uint64_t*)(mem + tHead); t->name_off = (uint64_t*)(mem + tHead + tArr); t->bases = mem + tHead + 2 * tArr; t->names = t->bases + total + 1;
+	memcpy(t->offsets, hostOff, tArr);
+	for (uint64_t r = 0; r <= n; r++) t->name_off[r] = hostNameOff[r];
+	if (total) memcpy(t->bases, H, total);
+	t->bases[total] = 0;
+	if (namesBytes) memcpy(t->names, H + total, namesBytes);
+	t->names[namesBytes] = 0;
+	R->deviceBlockBytes = batchBlock.bytes; R->deviceBlock = batchBlock.release();
+}
+
+extern "C" {
 
 // gc_reads_parse and gc_reads_parse_bgzf from the point where the text lies on the device
 static int readsParseFrom(const FxSource& src, int32_t format, uint32_t flags, gc_reads** reads, gc_fastx_table** table)
@@ -132,12 +173,10 @@ static int readsParseFrom(const FxSource& src, int32_t format, uint32_t flags, g
 		const uint64_t n = nRecords;
 
 		// ---- 3: read offsets and id offsets, down to the host for the per-read layout ----
-		// a second, small pinned block: offsets | id offsets | invalid flags | the four layout arrays that go up
-		gc::Arena s;
-		const size_t sOff = s.part((n + 1) * 8), sNameOff = s.part((n + 1) * 4), sInvalid = s.part(n), sMaskOff = s.part(n * 8), sMaskWords = s.part(n * 4), sEqOff = s.part(n * 8), sEdReads = s.part(n * sizeof(EdRead));
-		char* S = (char*)small.acquire(s.bytes());
-		uint64_t* hostOff = (uint64_t*)(S + sOff);
-		uint32_t* hostNameOff = (uint32_t*)(S + sNameOff);
+		const BatchStaging st(n);
+		char* S = (char*)small.acquire(st.bytes);
+		uint64_t* hostOff = (uint64_t*)(S + st.off);
+		uint32_t* hostNameOff = (uint32_t*)(S + st.nameOff);
 		hostOff[0] = 0; hostNameOff[0] = 0;
 		if (v.nLines) {
 			HIP_CHECK(hipEventRecord(ev[0], q));
@@ -149,44 +188,10 @@ static int readsParseFrom(const FxSource& src, int32_t format, uint32_t flags, g
 			HIP_CHECK(hipStreamSynchronize(q));
 			addSegment();
 		}
-		const uint64_t namesBytes = hostNameOff[n];
-		if (hostOff[n] != total || namesBytes + total > L) throw std::runtime_error("gc_reads_parse: the read offsets disagree with the base count");
-		for (uint64_t r = 0; r < n; r++) if (hostOff[r + 1] < hostOff[r] || hostNameOff[r + 1] <= hostNameOff[r]) throw std::runtime_error("gc_reads_parse: offsets decrease");
 
-		// ---- 4: the read batch, in the one layout gc_reads_upload builds its batch in; the gather writes the bases where the upload's copy would have put them ----
-		R->offsets.assign(hostOff, hostOff + n + 1);
-		R->totalBases = total;
-		const gc::ReadBatchLayout lay(hostOff, n);
-		bindReads(*R, lay, batchBlock.acquire(lay.blockBytes));
-		HIP_CHECK(hipMemcpyAsync(R->devOffsets, hostOff, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, q));
-		stageReadLayout(*R, lay, (uint64_t*)(S + sMaskOff), (uint32_t*)(S + sMaskWords), (uint64_t*)(S + sEqOff), (EdRead*)(S + sEdReads), q);
-		HIP_CHECK(hipEventRecord(ev[0], q));
-		if (v.nLines) HIP_CHECK(fxGatherBases(q, v, t, total, R->devBases));
-		launchPackReads(q, R->devOffsets, (uint32_t)n, total, R->devBases, R->devMaskOff, R->devMaskWords, R->devMasks, R->devEqOff, R->devEqMasks, R->devReadInvalid, R->devPacked, R->devInvalid, R->devChunkRead);
-		HIP_CHECK(hipEventRecord(ev[1], q));
-		R->invalid.assign(n, 0);
-		if (n) HIP_CHECK(hipMemcpyAsync(S + sInvalid, R->devReadInvalid, n, hipMemcpyDeviceToHost, q));
-		if (total) HIP_CHECK(hipMemcpyAsync(H, R->devBases, total, hipMemcpyDeviceToHost, q));
-		if (namesBytes) HIP_CHECK(hipMemcpyAsync(H + total, D + oNames, namesBytes, hipMemcpyDeviceToHost, q));
-		HIP_CHECK(hipStreamSynchronize(q));
-		addSegment();
-		if (n) memcpy(R->invalid.data(), S + sInvalid, n);
-		if (src.done) src.done(devText, consumed, q);
-
-		// ---- the host's table: one allocation, the struct | offsets | name_off | bases | names ----
-		const size_t tHead = (sizeof(gc_fastx_table) + 15) & ~(size_t)15, tArr = (n + 1) * sizeof(uint64_t);
-		char* mem = (char*)malloc(tHead + 2 * tArr + total + namesBytes + 2);
-		if (!mem) throw std::runtime_error("gc_reads_parse: out of host memory");
-		T = (gc_fastx_table*)mem;
-		T->n_reads = n; T->consumed = consumed; T->kernel_ms = kernelMs;
-		T->offsets = (uint64_t*)(mem + tHead); T->name_off = (uint64_t*)(mem + tHead + tArr); T->bases = mem + tHead + 2 * tArr; T->names = T->bases + total + 1;
-		memcpy(T->offsets, hostOff, tArr);
-		for (uint64_t r = 0; r <= n; r++) T->name_off[r] = hostNameOff[r];
-		if (total) memcpy(T->bases, H, total);
-		T->bases[total] = 0;
-		if (namesBytes) memcpy(T->names, H + total, namesBytes);
-		T->names[namesBytes] = 0;
-		R->deviceBlockBytes = batchBlock.bytes; R->deviceBlock = batchBlock.release();
+		// ---- 4: the read batch and the host's table ----
+		finishParsedBatch("gc_reads_parse", R, &T, q, ev, kernelMs, n, total, L, consumed, S, st, H, D + oNames, batchBlock,
+			[&](char* devBases) { return v.nLines ? fxGatherBases(q, v, t, total, devBases) : hipSuccess; }, [&]() { if (src.done) src.done(devText, consumed, q); });
 		return (int)GC_OK;
 	};
 	int rc = guarded([&]() { try { return body(); } catch (const InvalidInput& e) { return fail(GC_ERR_INVALID, e.what()); } });
@@ -318,22 +323,20 @@ int gc_bgzf_inflate(const void* data, uint64_t len, void** out, uint64_t* out_le
 	return GC_OK;
 }
 
-int gc_reads_parse_bgzf(const char* head, uint64_t head_len, const void* data, uint64_t len, int32_t format, uint32_t flags,
-	gc_reads** reads, gc_fastx_table** table, char** tail, uint64_t* tail_len, uint64_t* consumed, gc_bgzf_stats* stats)
+} // extern "C"
+
+int parseOverBgzf(const char* what, const char* head, uint64_t head_len, const void* data, uint64_t len, const std::function<int(const FxSource&)>& parse,
+	char** tail, uint64_t* tail_len, uint64_t* consumed, gc_bgzf_stats* stats)
 {
-	if (!reads || !table || !tail || !tail_len || !consumed || (!head && head_len) || (!data && len)) return fail(GC_ERR_INVALID, "null argument");
-	*reads = nullptr; *table = nullptr; *tail = nullptr; *tail_len = 0; *consumed = 0;
-	if (stats) *stats = gc_bgzf_stats {};
-	if (format != GC_FASTX_FASTA && format != GC_FASTX_FASTQ) return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: format is GC_FASTX_FASTA or GC_FASTX_FASTQ");
-	if (flags & ~(uint32_t)GC_FASTX_FINAL) return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: unknown flag bits");
+	const std::string name = std::string(what) + ": ";
 	BgzfScan s;
 	const auto t0 = std::chrono::steady_clock::now();
 	try { bgzfScan((const uint8_t*)data, len, head_len, s); }
-	catch (const InvalidInput& e) { return fail(GC_ERR_INVALID, std::string("gc_reads_parse_bgzf: ") + e.what()); }
+	catch (const InvalidInput& e) { return fail(GC_ERR_INVALID, name + e.what()); }
 	catch (const std::exception& e) { return fail(GC_ERR_INTERNAL, e.what()); }
 	const double scanMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	if (head_len >= 0xfffffff0ull || head_len + s.textBytes >= 0xfffffff0ull)
-		return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: the loader uses 32-bit positions: head and inflated text must stay below 2^32 - 16 bytes");
+		return fail(GC_ERR_INVALID, name + "the loader uses 32-bit positions: head and inflated text must stay below 2^32 - 16 bytes");
 	double uploadMs = 0, kernelMs = 0;
 	char* tailMem = nullptr;
 	uint64_t tailBytes = 0;
@@ -344,22 +347,35 @@ int gc_reads_parse_bgzf(const char* head, uint64_t head_len, const void* data, u
 		char last = head_len ? head[head_len - 1] : '\n';
 		if (!s.blocks.empty()) {
 			try { bgzfInflateTo(q, device, (const uint8_t*)data, s, (uint8_t*)devText, src.len ? src.len - 1 : 0, s.textBytes ? &last : nullptr, uploadMs, kernelMs); }
-			catch (const InvalidInput& e) { throw InvalidInput(std::string("gc_reads_parse_bgzf: ") + e.what()); }
+			catch (const InvalidInput& e) { throw InvalidInput(name + e.what()); }
 		}
 		return last;
 	};
 	src.done = [&](const char* devText, uint32_t textConsumed, hipStream_t q) {
 		tailBytes = src.len - textConsumed;
 		tailMem = (char*)malloc(tailBytes + 1);
-		if (!tailMem) throw std::runtime_error("gc_reads_parse_bgzf: out of host memory");
+		if (!tailMem) throw std::runtime_error(name + "out of host memory");
 		if (tailBytes) { HIP_CHECK(hipMemcpyAsync(tailMem, devText + textConsumed, tailBytes, hipMemcpyDeviceToHost, q)); HIP_CHECK(hipStreamSynchronize(q)); }
 		tailMem[tailBytes] = 0;
 	};
-	const int rc = readsParseFrom(src, format, flags, reads, table);
+	const int rc = parse(src);
 	if (rc != GC_OK) { free(tailMem); return rc; }
 	*tail = tailMem; *tail_len = tailBytes; *consumed = s.consumed;
 	if (stats) { stats->blocks = s.blocks.size(); stats->inflated_bytes = s.textBytes; stats->scan_ms = scanMs; stats->upload_ms = uploadMs; stats->kernel_ms = kernelMs; }
 	return GC_OK;
+}
+
+extern "C" {
+
+int gc_reads_parse_bgzf(const char* head, uint64_t head_len, const void* data, uint64_t len, int32_t format, uint32_t flags,
+	gc_reads** reads, gc_fastx_table** table, char** tail, uint64_t* tail_len, uint64_t* consumed, gc_bgzf_stats* stats)
+{
+	if (!reads || !table || !tail || !tail_len || !consumed || (!head && head_len) || (!data && len)) return fail(GC_ERR_INVALID, "null argument");
+	*reads = nullptr; *table = nullptr; *tail = nullptr; *tail_len = 0; *consumed = 0;
+	if (stats) *stats = gc_bgzf_stats {};
+	if (format != GC_FASTX_FASTA && format != GC_FASTX_FASTQ) return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: format is GC_FASTX_FASTA or GC_FASTX_FASTQ");
+	if (flags & ~(uint32_t)GC_FASTX_FINAL) return fail(GC_ERR_INVALID, "gc_reads_parse_bgzf: unknown flag bits");
+	return parseOverBgzf("gc_reads_parse_bgzf", head, head_len, data, len, [&](const FxSource& src) { return readsParseFrom(src, format, flags, reads, table); }, tail, tail_len, consumed, stats);
 }
 
 } // extern "C"

@@ -267,6 +267,36 @@ int gc_bgzf_inflate(const void* data, uint64_t len, void** out, uint64_t* out_le
 int gc_reads_parse_bgzf(const char* head, uint64_t head_len, const void* data, uint64_t len, int32_t format, uint32_t flags,
                         gc_reads** reads, gc_fastx_table** table, char** tail, uint64_t* tail_len, uint64_t* consumed, gc_bgzf_stats* stats /* may be NULL */);
 
+/* Unaligned BAM (uBAM, what ONT basecallers and PacBio instruments deliver) to a read batch, decoded on the device (hip/gc_bam.hip). A .bam file is a chain of BGZF blocks;
+ * the bytes here are the inflated ones. The format as this build defines it (SAMv1 section 4.2; little-endian throughout):
+ *   file header, only at the start of a file: "BAM\1", l_text u32, text[l_text], n_ref u32, n_ref x (l_name u32, name[l_name], l_ref u32). Stepped over whole, nothing of it used.
+ *   record: block_size u32 (the bytes that follow it), refID i32, pos i32, l_read_name u8, mapq u8, bin u16, n_cigar_op u16, flag u16, l_seq u32, next_refID i32,
+ *           next_pos i32, tlen i32, read_name[l_read_name] (NUL-terminated, the NUL counted), cigar u32 x n_cigar_op, seq[(l_seq + 1) / 2], qual[l_seq], tags to the end
+ *           of the block. Base i is the high nibble of seq[i / 2] for even i, the low one for odd i, spelled by "=ACMGRSVTWYHKDBN".
+ * A record becomes a read: its id is read_name without the NUL, its letters are the l_seq bases, reverse-complemented when flag 0x10 is set (in nibble space the complement
+ * is the 4-bit reversal; '=' and N stay). Records with flag 0x100 or 0x800 are left out, as `samtools fastq` leaves them out by default, and counted. Qualities, CIGAR and
+ * tags are stepped over. l_seq 0 gives a read of length 0, as an empty FASTQ sequence line does. '=' is outside IUPAC: gc_reads_upload's rule flags that read in the result.
+ * flags: GC_BAM_HEADER - the bytes start with the file's header; GC_FASTX_FINAL - they run to the end of the file. The chunk protocol is gc_reads_parse's: data begins at the
+ * header or at a record boundary, only whole records are returned, table->consumed is the byte where the next chunk must begin (0 with n_reads 0 when not even the header
+ * is whole), and under GC_FASTX_FINAL consumed == len or the call is refused: a truncated file is an error here, unlike FASTQ's lenient end.
+ * GC_ERR_INVALID, nothing returned, the device still usable, gc_last_error naming the record's index among the chunk's records (kept or not) and its byte offset in the
+ * bytes: a wrong magic where a header is expected; block_size < 32; l_read_name 0 or a name whose last byte is not NUL;
+ * 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq > block_size; l_seq >= 2^31; under GC_FASTX_FINAL a header or record that the end of the bytes cuts.
+ * GC_ERR_INVALID, checked before a device is needed: a null pointer, unknown flag bits, len (head_len + inflated bytes) of 2^32 - 16 or more.
+ * gc_reads_parse_bam_bgzf is to gc_reads_parse_bam what gc_reads_parse_bgzf is to gc_reads_parse: head, the bytes behind the previous call's consumed, then the inflated
+ * whole BGZF blocks at the front of data (the end-of-file block of ISIZE 0 among them), put together and decoded in HBM; only *tail comes down.
+ * The gc_reads is the object gc_reads_upload builds from the same strings; the table is gc_reads_parse's. stats, if not NULL: the records seen, those left out, and the
+ * milliseconds of the walk, of fields and scans, of the ids and of the unpacking (all within table->kernel_ms, which holds the packing kernels too). */
+#define GC_BAM_HEADER 2u
+typedef struct gc_bam_stats {
+	uint64_t records;         /* whole records in the bytes */
+	uint64_t skipped;         /* of them, left out for flag 0x100 or 0x800 */
+	double walk_ms, fields_ms, names_ms, unpack_ms;
+} gc_bam_stats;
+int gc_reads_parse_bam(const void* data, uint64_t len, uint32_t flags, gc_reads** reads, gc_fastx_table** table, gc_bam_stats* stats /* may be NULL */);
+int gc_reads_parse_bam_bgzf(const void* head, uint64_t head_len, const void* data, uint64_t len, uint32_t flags, gc_reads** reads, gc_fastx_table** table,
+                            void** tail, uint64_t* tail_len, uint64_t* consumed, gc_bgzf_stats* stats /* may be NULL */, gc_bam_stats* bam_stats /* may be NULL */);
+
 /* ---- seed hits from the host's own seeder ----------------------------------------------------------- */
 /* SeedHit as a seeder hands it over (src/GraphAlignerWrapper.h:14): what Seeder::getSeeds returns whether the hits come from minimizers, MUM / MEM matches or a
  * seeds file (src/Aligner.cpp:87-108), before OrderSeeds. */
