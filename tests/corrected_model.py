@@ -68,9 +68,23 @@ def clipped_records(name, corrections):
 
 # ---- over a batch result of graphchainer_amd (keep_traces=True, chain_traces >= 1): what the two files hold for it
 
-def result_corrections(out, r, letter):
+def output_order(starts, std_sort=None, sorts=2):
+    """The order in which the reference writes alignments whose starts, in the order the selection left them, are `starts`: std::sort by alignmentStart at
+    src/Aligner.cpp:1003 and once more at :1023. `std_sort` is libstdc++'s std::sort as a permutation function (tests/stdsort/std_sort_perm.cpp): an insertion sort up to
+    16 elements and unstable beyond, so the order of tied starts is defined only by replaying it - and the second sort of an already sorted list may move ties again.
+    Without `std_sort` the order is the stable one (what a read with at most 16 alignments gets in any case). Returns indices into `starts`."""
+    starts = [int(s) for s in starts]
+    if std_sort is None:
+        return sorted(range(len(starts)), key=lambda i: starts[i])
+    order = list(range(len(starts)))
+    for _ in range(sorts):
+        order = [order[i] for i in std_sort([starts[i] for i in order])]
+    return order
+
+
+def result_corrections(out, r, letter, std_sort=None):
     """(start, end, piece) of read r's final alignments in output order, from the kept traces: the chained alignment when it won, else the selected whole-read
-    alignments sorted by start (src/Aligner.cpp:901-920,1003,1023). None for a flagged read."""
+    alignments sorted by start (src/Aligner.cpp:901-920,1003,1023; output_order). None for a flagged read."""
     if out["failed_assertion"][r] or out["capacity_exceeded"][r]:
         return None
     if out["chained_better"][r]:
@@ -78,7 +92,8 @@ def result_corrections(out, r, letter):
         trace = list(zip(out["chain_trace_node"][t0:t1].tolist(), out["chain_trace_offset"][t0:t1].tolist(), out["chain_trace_switch"][t0:t1].tolist()))
         return [(int(out["chain_aln_start"][r]), int(out["chain_aln_end"][r]), add_corrected(trace, letter))]
     base = int(out["read_longall_off"][r])
-    alns = sorted((base + int(k) for k in out["long_index"][int(out["read_long_off"][r]):int(out["read_long_off"][r + 1])]), key=lambda a: int(out["longall_start"][a]))
+    alns = [base + int(k) for k in out["long_index"][int(out["read_long_off"][r]):int(out["read_long_off"][r + 1])]]
+    alns = [alns[i] for i in output_order([out["longall_start"][a] for a in alns], std_sort)]
     got = []
     for a in alns:
         t0, t1 = int(out["long_trace_off"][a]), int(out["long_trace_off"][a + 1])
@@ -87,11 +102,11 @@ def result_corrections(out, r, letter):
     return got
 
 
-def batch_records(out, names, reads, letter):
+def batch_records(out, names, reads, letter, std_sort=None):
     """(records of --corrected-out, records of --corrected-clipped-out) of a batch, in input order."""
     bodies, clipped = [], []
     for r, (name, raw) in enumerate(zip(names, reads)):
-        corrections = result_corrections(out, r, letter)
+        corrections = result_corrections(out, r, letter, std_sort)
         if corrections is None:
             continue
         bodies.append(corrected_record(name, raw, corrections))

@@ -1,12 +1,16 @@
 """tests/corrected_model.py on hand cases: each expected string is worked out by hand from the reference's three functions (src/GraphAligner.h:220-231,
-src/ReadCorrection.cpp:22-64, src/Aligner.cpp:313-374)."""
+src/ReadCorrection.cpp:22-64, src/Aligner.cpp:313-374). The order of a read's alignments (output_order: std::sort by start, twice) is worked out from the permutation
+function of tests/stdsort, on a hand case and on the tandem-array reads that tests/test_corrected_modes_gpu.py runs on the device."""
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import corrected_model as cm   # noqa: E402
+import numpy as np                          # noqa: E402
+
+import corrected_model as cm                # noqa: E402
+from test_seeding_model import std_sort     # noqa: E402,F401  (the fixture: libstdc++'s std::sort as a permutation function)
 
 # two nodes: 0 = "ACGTRN" (an IUPAC code and an N in the graph), 2 = "TTGCA"
 NODES = {0: b"ACGTRN", 2: b"TTGCA"}
@@ -101,3 +105,79 @@ def test_record_formats():
     assert cm.corrected_record(b"r1 desc", RAW, corrections) == b">r1 desc\nacGGTTryacgtacTNacgt\n"
     assert cm.clipped_records(b"r1 desc", corrections) == [b">r1 desc_0_2_6\nggtt\n", b">r1 desc_1_14_16\nTN\n"]
     assert cm.clipped_records(b"r1", []) == []
+
+
+# ---- the order of a read's alignments: src/Aligner.cpp:1003 and :1023 sort by alignmentStart with libstdc++'s std::sort, twice
+
+
+def _stable(keys):
+    return sorted(range(len(keys)), key=lambda i: keys[i])
+
+
+def tied_keys(std_sort, n=24, distinct=5):   # noqa: F811
+    """`n` > 16 keys over `distinct` values on which two std::sorts, one std::sort and a stable sort give three different orders: the first such list of a
+    fixed-seed search, found with the permutation function itself."""
+    import random
+    rng = random.Random(5)
+    for _ in range(2000):
+        keys = [rng.randrange(distinct) for _ in range(n)]
+        once, twice, stable = cm.output_order(keys, std_sort, sorts=1), cm.output_order(keys, std_sort), _stable(keys)
+        if len({tuple(once), tuple(twice), tuple(stable)}) == 3:
+            return keys, once, twice, stable
+    raise AssertionError("no list of tied keys tells the three orders apart")
+
+
+def test_the_output_order_is_the_sort_replayed_twice(std_sort):   # noqa: F811
+    keys, once, twice, stable = tied_keys(std_sort)
+    print("keys", keys, "once", once, "twice", twice, "stable", stable)
+    assert len(keys) >= 17 and len(set(keys)) < len(keys)
+    for order in (once, twice, stable):                                        # three orders of the same keys, each sorted, no two alike
+        assert sorted(order) == list(range(len(keys))) and [keys[i] for i in order] == sorted(keys)
+    assert once != twice and twice != stable and once != stable
+    assert twice == [once[i] for i in std_sort([keys[i] for i in once])]       # the second sort works on what the first one left
+    assert cm.output_order(keys) == stable                                     # without the function: the stable order, as before
+    # up to 16 elements std::sort is an insertion sort: stable, once or twice
+    assert all(cm.output_order(keys[:n], std_sort) == cm.output_order(keys[:n], std_sort, sorts=1) == _stable(keys[:n]) for n in range(17))
+    # through result_corrections: one read, every alignment one cell long, its letter naming the alignment
+    n = len(keys)
+    out = {"failed_assertion": [0], "capacity_exceeded": [0], "chained_better": [0], "read_longall_off": [0, n], "read_long_off": [0, n], "long_index": list(range(n)),
+           "longall_start": keys, "longall_end": [k + 1 for k in keys], "long_trace_off": list(range(n + 1)),
+           "long_trace_node": np.arange(n), "long_trace_offset": np.zeros(n, dtype=np.int64), "long_trace_switch": np.zeros(n, dtype=np.int64)}
+    name = lambda node, offset: b"%c" % (65 + node)                            # noqa: E731
+    assert [c[2] for c in cm.result_corrections(out, 0, name, std_sort)] == [b"%c" % (65 + i) for i in twice]
+    assert [c[2] for c in cm.result_corrections(out, 0, name)] == [b"%c" % (65 + i) for i in stable]
+    out["long_index"] = list(range(n))[::-1]                                   # the sort starts from the selection's order, not from the list's
+    reverse = [n - 1 - i for i in cm.output_order(keys[::-1], std_sort)]
+    assert [c[2] for c in cm.result_corrections(out, 0, name, std_sort)] == [b"%c" % (65 + i) for i in reverse]
+    bodies, clipped = cm.batch_records(out, [b"r"], [b"a" * 8], name, std_sort)
+    assert len(bodies) == 1 and [c.split(b"\n")[1] for c in clipped] == [b"%c" % (65 + i) for i in reverse]
+
+
+def tie_shape(starts, ends, std_sort):   # noqa: F811
+    """Of one read's alignments in the selection's order: (alignments, those whose start an earlier one has, twice != stable, once != stable, once != twice,
+    times an end moves currentEnd backwards in the twice-sorted order)."""
+    starts, ends = [int(s) for s in starts], [int(e) for e in ends]
+    once, twice, stable = cm.output_order(starts, std_sort, sorts=1), cm.output_order(starts, std_sort), _stable(starts)
+    tied = len(starts) - len(set(starts))
+    backwards = sum(ends[b] < ends[a] for a, b in zip(twice, twice[1:]))
+    return len(starts), tied, twice != stable, once != stable, once != twice, backwards
+
+
+def test_tier_c_has_the_ties_the_device_tests_rest_on(tmp_path, std_sort):   # noqa: F811
+    """The oracle's whole-read alignments of tests/lowcomplexity.py's tier c, reads 1 to 5: more than 16 per read with tied starts, and the order after two
+    std::sorts, after one and after a stable sort differ as tests/test_corrected_modes_gpu.py needs them to. A generator that drifts is noticed here."""
+    import lowcomplexity as lc
+    from oracle import Oracle
+    g, reads, _ = lc.tier("c")
+    gfa = str(tmp_path / "c.gfa")
+    g.write_gfa(gfa)
+    want = Oracle(gfa, long_pass=True).align(reads[:6])
+    shapes = {}
+    for r in range(1, 6):
+        a0, a1 = int(want["read_longall_off"][r]), int(want["read_longall_off"][r + 1])
+        shapes[r] = tie_shape(want["longall_start"][a0:a1], want["longall_end"][a0:a1], std_sort)
+    print("read: (alignments, tied starts, twice != stable, once != stable, once != twice, ends moving backwards)", shapes)
+    assert {r: s[:2] for r, s in shapes.items()} == {1: (50, 6), 2: (25, 2), 3: (23, 2), 4: (35, 20), 5: (27, 20)}
+    assert {r: s[2] for r, s in shapes.items()} == {1: False, 2: False, 3: True, 4: True, 5: True}      # twice != stable
+    assert {r: s[3] for r, s in shapes.items()} == {1: True, 2: True, 3: True, 4: True, 5: True}        # once != stable
+    assert sum(s[4] for s in shapes.values()) >= 2 and all(s[5] >= 1 for s in shapes.values())
