@@ -4,80 +4,17 @@
 	void fragmentPipeline()
 	{
 		double tLongStarted = nowUs();
-		double tWindows = tLongStarted, tReserved = tLongStarted;
-		if (!deviceGlue && !poolsSized) {   // (this stage may run twice - fragmentPoolsOverflowed - and the block below builds sums and arrays that the second run finds as they are: ADVICE r5)
-		pool.run(n, [&](size_t r, size_t) {
-			ReadGlue& gl = glue[r];
-			if (gl.seeds.empty()) return;
-			gc::fragmentWindows(gl.seeds, R->offsets[r + 1] - R->offsets[r], (size_t)P->split_len, (size_t)P->split_gap, gl.windows);
-		});
-		tWindows = nowUs();
-		for (uint64_t r = 0; r < n; r++) {
-			glue[r].slotBegin = nSlots;
-			glue[r].fragBegin = nFrags;
-			glue[r].seedBegin = nSeedsTotal;
-			glue[r].nSeedsR = (uint32_t)glue[r].seeds.size();
-			glue[r].nWindows = (uint32_t)glue[r].windows.size();
-			for (const auto& w : glue[r].windows) nSlots += w.sr - w.sl;
-			nFrags += glue[r].windows.size();
-			nSeedsTotal += glue[r].seeds.size();
-		}
-		// The per-slot records (seed in fragment order + its two extensions) are expanded on the device (k_build_fragment_work) from what the
-		// host decides: the read's seeds in the reference's order after its sort by position, and the windows.
-		frags = st->hFrags.reserve<Fragment>(nFrags);
-		fragFirstSeed = st->hFragFirstSeed.reserve<uint32_t>(nFrags);
-		readSeeds = st->hReadSeeds.reserve<FragSeed>(nSeedsTotal);
-		jobs = st->hJobs.reserve<ReadChainJob>(n);
-		std::vector<uint64_t> traceBudgets(pool.size(), 0);
-		std::vector<uint32_t> windowSeeds(pool.size(), 0);   // per worker: the most seeds a window holds
-		tReserved = nowUs();
-		pool.run(n, [&](size_t r, size_t worker) {
-			const ReadGlue& gl = glue[r];
-			size_t len = R->offsets[r + 1] - R->offsets[r];
-			for (size_t k = 0; k < gl.seeds.size(); k++) readSeeds[gl.seedBegin + k] = FragSeed { gl.seeds[k].node, gl.seeds[k].offset, gl.seeds[k].seqPos, gl.seeds[k].goodness };
-			uint64_t slot = gl.slotBegin;
-			uint64_t budget = 0;
-			for (size_t f = 0; f < gl.windows.size(); f++) {
-				const gc::FragmentWindow& w = gl.windows[f];
-				Fragment& fr = frags[gl.fragBegin + f];
-				fr.read = (uint32_t)r;
-				fr.l = w.l;
-				fr.seedBegin = (uint32_t)slot;
-				fragFirstSeed[gl.fragBegin + f] = (uint32_t)(gl.seedBegin + w.sl);
-				for (uint32_t k = w.sl; k < w.sr; k++, slot++) {
-					// trace cells the two extensions of this seed may need: backward p rows, forward split_len - 1 - p (src/GraphAligner.h:499-511)
-					const uint32_t p = gl.seeds[k].seqPos - w.l, q = (uint32_t)P->split_len - 1 - p;
-					// (rows + 1 + score cells: the HMM keeps a one-slice extension only below a score of 24; under force_global the score reaches the rows)
-					budget += P->force_global || clip.on() ? (p ? 2 * p + 1 : 0) + (q ? 2 * q + 1 : 0) : (p ? p + 24 : 0) + (q ? q + 24 : 0);
-				}
-				fr.seedEnd = (uint32_t)slot;
-				windowSeeds[worker] = std::max(windowSeeds[worker], w.sr - w.sl);
-			}
-			traceBudgets[worker] += budget;
-			ReadChainJob& job = jobs[r];
-			job.slotBegin = (uint32_t)gl.slotBegin;
-			job.nSlots = (uint32_t)(slot - gl.slotBegin);
-			job.chainBegin = (uint32_t)gl.slotBegin;
-			job.nKeys = len >= (size_t)P->split_len ? (uint32_t)((len - P->split_len) / P->split_gap + 1) : 1;
-			job.fragBegin = (uint32_t)gl.fragBegin;
-			job.nFrags = (uint32_t)gl.windows.size();
-		});
-		for (uint64_t b : traceBudgets) traceBudget += b;
-		for (uint32_t m : windowSeeds) maxWindowSeeds = std::max(maxWindowSeeds, m);
-		for (uint64_t r = 0; r < n; r++) maxSlotsPerRead = std::max(maxSlotsPerRead, jobs[r].nSlots);
-		}
 		if (2 * nSlots >= 0xffffffffull) throw std::runtime_error("batch too large: more than 2^31 fragment seeds; split the batch");
 		if (!poolsSized) {
 			traceWorst = traceBudget + traceBudget / 4 + (1u << 20);   // every slot's two extensions at full length + room for the extensions that only fit the retry launch's larger trace buffers
 			pathWorst = nSlots * 24 + 4096;
-			// by use (device glue; GC_POOLS_WORST_CASE=1 and the host glue path keep the worst case): what the stream's earlier batches needed per slot, with 15 % of slack; a
+			// by use: what the stream's earlier batches needed per slot, with 15 % of slack; a
 			// stream's first batch starts from a low guess (60 trace cells - 8 bytes each since r6, and reserved by rows + 1 + score per extension - and 4 path words per slot of the 103 and 24 the worst case reserves) and
 			// runs its fragment pipeline again with what it asked for when that was short - in the warm-up batch, once per stream - so that the pools are never larger than a batch needs
-			const bool byUse = deviceGlue && !sw.poolsWorstCase;
 			double traceGuess = 60.0, pathGuess = 4.0, slackCells = (double)(1u << 20), slackWords = 4096.0;
 			if (sw.testPoolFirstGuess) { traceGuess = *sw.testPoolFirstGuess; pathGuess = traceGuess / 8; slackCells = slackWords = 64; }   // test hook: a stream's first batch outgrows its pools
-			traceBudget = byUse ? std::min<uint64_t>(traceWorst, (uint64_t)((double)nSlots * (st->traceCellsPerSlot > 0 ? st->traceCellsPerSlot * 1.15 : traceGuess) + slackCells)) : traceWorst;
-			pathCapacity = byUse ? std::min<uint64_t>(pathWorst, (uint64_t)((double)nSlots * (st->pathWordsPerSlot > 0 ? st->pathWordsPerSlot * 1.15 : pathGuess) + slackWords)) : pathWorst;
+			traceBudget = std::min<uint64_t>(traceWorst, (uint64_t)((double)nSlots * (st->traceCellsPerSlot > 0 ? st->traceCellsPerSlot * 1.15 : traceGuess) + slackCells));
+			pathCapacity = std::min<uint64_t>(pathWorst, (uint64_t)((double)nSlots * (st->pathWordsPerSlot > 0 ? st->pathWordsPerSlot * 1.15 : pathGuess) + slackWords));
 			poolsSized = true;
 		}
 		ChainCaps caps { 1, 1, 1, 1 };
@@ -86,9 +23,8 @@
 		caps.capTable = std::max(1u, G->maxMpcWidth);
 		caps.capBack = (uint32_t)std::min<uint64_t>(0x7fffffffull, (uint64_t)caps.capAnchors * ((uint64_t)G->maxBackPerNode + G->maxPathsPerNode));   // threshold lists: backward links + paths of the start node
 		res->host_us[0] = nowUs() - tGlue;
-		if (sw.debugTimes) fprintf(stderr, "[gc cpu] %.0f ms of process CPU up to the end of the host glue\n", processCpuMs() - cpuCall);
-		if (sw.debugTimes) fprintf(stderr, "[gc times] seed expand+order %.1f ms, whole-read setup %.1f ms, fragment windows+arrays %.1f ms (windows %.1f, sizes+buffers %.1f, arrays %.1f)\n", (tOrdered - tGlue) / 1e3, (tLongStarted - tOrdered) / 1e3, (nowUs() - tLongStarted) / 1e3,
-			(tWindows - tLongStarted) / 1e3, (tReserved - tWindows) / 1e3, (nowUs() - tReserved) / 1e3);
+		if (sw.debugTimes) fprintf(stderr, "[gc cpu] %.0f ms of process CPU up to the end of the seed glue and the pools' sizing\n", processCpuMs() - cpuCall);
+		if (sw.debugTimes) fprintf(stderr, "[gc times] seed expand+order %.1f ms, whole-read setup %.1f ms, fragment windows+arrays %.1f ms\n", (tOrdered - tGlue) / 1e3, (tLongStarted - tOrdered) / 1e3, (nowUs() - tLongStarted) / 1e3);
 
 		// ---------------- K3 / K3b / K4
 		tDev = nowUs();
@@ -133,7 +69,6 @@
 			st->poolsRerun = false;
 		}
 		dTrace = st->tracePool.reserve<PoolCell>(traceBudget, true);
-		if (!deviceGlue) dFrags = st->frags.reserve<Fragment>(nFrags);
 		FragSeed* dFragSeeds = st->fragSeeds.reserve<FragSeed>(nSlots);
 		dAnchors = st->anchors.reserve<AnchorRec>(nSlots);
 		dFragStatus = st->fragStatus.reserve<uint32_t>(nFrags);
@@ -141,7 +76,6 @@
 		dReadTies = st->readTies.reserve<uint32_t>(n);
 		if (n) HIP_CHECK(hipMemsetAsync(dReadTies, 0, n * sizeof(uint32_t), stream));
 		dPathPool = st->pathPool.reserve<uint32_t>(pathCapacity, true);
-		if (!deviceGlue) dJobs = st->jobs.reserve<ReadChainJob>(n);
 		dChainOut = st->chainOut.reserve<uint32_t>(nSlots);
 		dChainLen = st->chainLen.reserve<uint32_t>(n);
 		dChainScore = st->chainScore.reserve<unsigned long long>(n);
@@ -153,13 +87,6 @@
 		// both launches index the scratch by block (the LDS launch keeps its threshold lists there); a batch of long reads has no LDS launch
 		uint32_t chainBlocks = chainLdsLaunch(fewestSlots, forceChainScratch) ? std::max(chainGridBlocks((uint32_t)n), chainScratchBlocks((uint32_t)n)) : chainScratchBlocks((uint32_t)n);
 		uint8_t* dChainScratch = st->chainScratch.reserve<uint8_t>((uint64_t)std::max(1u, chainBlocks) * chainScratchBytes(caps));
-		if (!deviceGlue) {
-			dReadSeeds = st->readSeeds.reserve<FragSeed>(nSeedsTotal);
-			dFragFirstSeed = st->fragFirstSeed.reserve<uint32_t>(nFrags);
-			if (nFrags) HIP_CHECK(hipMemcpyAsync(dFrags, frags, nFrags * sizeof(Fragment), hipMemcpyHostToDevice, stream));
-			if (nFrags) HIP_CHECK(hipMemcpyAsync(dFragFirstSeed, fragFirstSeed, nFrags * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-			if (nSeedsTotal) HIP_CHECK(hipMemcpyAsync(dReadSeeds, readSeeds, nSeedsTotal * sizeof(FragSeed), hipMemcpyHostToDevice, stream));
-		}
 		// Lazy extension (default): a seed is extended only when the reference would extend it - when it does not lie on an earlier alignment of its
 		// fragment (src/GraphAligner.h:163-173). Round 0 extends every fragment's first seed; k_build_anchors parks the fragments that reach another
 		// seed they must extend and queues that seed for the next round (the launches size themselves from counts on the device, no host round
@@ -167,7 +94,6 @@
 		// seeds the windows hold. GC_EXT_LAZY=0: every seed is extended up front.
 		const bool lazyExtend = sw.extLazy && nFrags > 0;
 		launchBuildFragmentWork(stream, G->dev, dFrags, dFragFirstSeed, (uint32_t)nFrags, dReadSeeds, R->devOffsets, R->totalBases, (uint32_t)P->split_len, dFragSeeds, dWork, lazyExtend ? dResults : nullptr);
-		if (n && !deviceGlue) HIP_CHECK(hipMemcpyAsync(dJobs, jobs, n * sizeof(ReadChainJob), hipMemcpyHostToDevice, stream));
 		mark();   // 2
 		// extensions that outgrew their slab (a dense variant cluster: more tiles, queue entries or trace cells than the common case is sized
 		// for) run again in a small grid with 16x the room; lanes whose items are fine only read the status array. What overflows even

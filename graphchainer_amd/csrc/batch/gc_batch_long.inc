@@ -19,10 +19,8 @@
 		// reads that are already finished when the rounds turn latency-bound, so these kernels run beside the last rounds - the
 		// rounds slow down by more than the 11 ms the tail saves: 304-319 -> 318-337 ms per batch. So: all reads, after the rounds.)
 		if (P->long_pass) {
-			if (deviceGlue) nLongSeeds = nSeedsTotal;   // (the device's seed lists sit at the reads' capacity offsets)
-			else for (uint64_t r = 0; r < n; r++) { glue[r].longSeedBegin = nLongSeeds; nLongSeeds += glue[r].longSeeds.size(); }
+			nLongSeeds = nSeedsTotal;   // (the glue's seed lists sit at the reads' capacity offsets)
 			if (nLongSeeds >= 0xffffffffull) throw std::runtime_error("batch too large for the whole-read pass");
-			LongSeed* hSeeds = st->hLongSeeds.reserve<LongSeed>(deviceGlue ? 0 : nLongSeeds);
 			hJobs = st->hLongJobs.reserve<LongJob>(n);
 			// merged-trace cells per read base: 8 hold the few partial alignments a 10 kb ONT read collects before its end-to-end one (cfg2 uses ~1.1);
 			// noisy 50 kb CLR reads on a genome with repeats collect 8-9 alignments each and overflowed it (a quarter of the reads flagged, which reads
@@ -33,11 +31,6 @@
 			cellBudget = cellBudgetFor(cellsPerBase);
 			pool.run(n, [&](size_t r, size_t) {
 				const ReadGlue& gl = glue[r];
-				uint64_t at = gl.longSeedBegin;
-				if (deviceGlue) at += gl.nSeedsR;
-				else for (const gc::SeedRec& s : gl.longSeeds) {
-					hSeeds[at++] = LongSeed { s.node, s.seqPos, s.goodness, s.clusterSize, s.offset, 0 };
-				}
 				LongJob& j = hJobs[r];
 				j.maskOff = R->maskOff[r];
 				j.maskWords = R->maskWords[r];
@@ -45,7 +38,7 @@
 				j.readOff = R->offsets[r];
 				j.readLen = (uint32_t)(R->offsets[r + 1] - R->offsets[r]);
 				j.seedBegin = (uint32_t)gl.longSeedBegin;
-				j.seedEnd = (uint32_t)at;
+				j.seedEnd = (uint32_t)(gl.longSeedBegin + gl.nSeedsR);
 				j.alnBegin = (uint32_t)(r * firstAlnCap);
 				// size_t extendSeeds = seedExtendDensity * sequence.size() + 1, in double and then truncated; -1: the read's seed count (src/GraphAligner.h:121-122)
 				j.extendSeeds = j.seedEnd - j.seedBegin;
@@ -70,7 +63,6 @@
 			lcfg.maxItems = (uint32_t)std::max<int64_t>(64, capacityOr(sw.testLongMaxItems, P->capacity.long_max_items, lcfg.maxItems));
 			if (sw.testLongRegCap) lcfg.regCap = *sw.testLongRegCap;   // test hook: force the LDS-table retry
 			waveWords = longWaveWordsPerLane(lcfg);
-			if (!deviceGlue) dLongSeeds = st->longSeeds.reserve<LongSeed>(nLongSeeds);
 			dLongJobs = st->longJobs.reserve<LongJob>(n);
 			dLongAlns = st->longAlns.reserve<LongAln>(alnSlots);
 			LongReadResult* dLongResults = st->longResults.reserve<LongReadResult>(n);
@@ -85,7 +77,6 @@
 			hLongSmall = st->hLongSmall.reserve<unsigned long long>(cursorWords);
 			ls = st->longStream;
 			HIP_CHECK(hipMemsetAsync(dLongCursor, 0, cursorWords * sizeof(unsigned long long), ls));
-			if (nLongSeeds && !deviceGlue) HIP_CHECK(hipMemcpyAsync(dLongSeeds, hSeeds, nLongSeeds * sizeof(LongSeed), hipMemcpyHostToDevice, ls));
 			if (n) HIP_CHECK(hipMemcpyAsync(dLongJobs, hJobs, n * sizeof(LongJob), hipMemcpyHostToDevice, ls));
 			syncStream(ls);   // the round stream starts from uploaded inputs
 			// rounds: select -> extend -> merge until no read has a seed left to extend (see gc_kernels.hip, "K3-long in rounds")

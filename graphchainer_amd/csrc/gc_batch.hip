@@ -27,15 +27,14 @@ struct BatchRun {
 	double tTotal = 0;
 	// ---- what the stages hand on (set by the stage named in the comment of each group)
 	// seeds()
-	bool deviceGlue = true;
 	double tGlue = 0;
 	uint64_t nSlots = 0, nFrags = 0, nSeedsTotal = 0, traceBudget = 0;
 	uint32_t maxSlotsPerRead = 1, maxWindowSeeds = 0;
-	Fragment* frags = nullptr; ReadChainJob* jobs = nullptr;                 // host copies
-	FragSeed* readSeeds = nullptr; uint32_t* fragFirstSeed = nullptr;        // host copies (device glue: only with keep_seeds / keep_traces)
-	Fragment* dFrags = nullptr; uint32_t* dFragFirstSeed = nullptr; FragSeed* dReadSeeds = nullptr; ReadChainJob* dJobs = nullptr;
-	LongSeed* dLongSeeds = nullptr;
-	hipEvent_t glueCopied = nullptr;   // device glue: the host copies of frags / seeds have arrived (waited for before the result assembly)
+	Fragment* dFrags = nullptr; uint32_t* dFragFirstSeed = nullptr; FragSeed* dReadSeeds = nullptr; ReadChainJob* dJobs = nullptr;   // written by the glue kernels
+	LongSeed* dLongSeeds = nullptr;                                          // the same seeds in the whole-read pass's order (long_pass)
+	Fragment* frags = nullptr; ReadChainJob* jobs = nullptr;                 // host copies of dFrags / dJobs
+	FragSeed* readSeeds = nullptr; uint32_t* fragFirstSeed = nullptr;        // host copies of dReadSeeds / dFragFirstSeed, only with keep_seeds / keep_traces
+	hipEvent_t glueCopied = nullptr;   // the host copies of frags / seeds have arrived (waited for before the result assembly)
 	double tOrdered = 0;
 	unsigned long long* hSmall = nullptr;
 	unsigned long long* dCursors = nullptr;
@@ -280,7 +279,6 @@ int gc_align_batch_ext(const gc_graph* G, const gc_seeder* S, gc_stream* st, con
 	if (H) {
 		if (H->readOffsets != R->offsets) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds were uploaded for another read batch");
 		if (H->device != st->device) return fail(GC_ERR_INVALID, "gc_align_batch_seeded: the seeds live on another device than the stream");
-		if (!sw.deviceGlue) return fail(GC_ERR_INVALID, "gc_align_batch_seeded needs the device seed glue (GC_DEVICE_GLUE=0 keeps the host glue, which only expands minimizer matches)");
 	}
 	return alignBatch(sw, G, S, H, st, R, P, clip, out);
 }

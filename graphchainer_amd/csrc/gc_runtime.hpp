@@ -9,7 +9,7 @@
 #include "hip/gc_kernels.hpp"
 #include "host/gc_graph.hpp"
 #include "host/gc_hashorder.hpp"
-#include "host/gc_glue.hpp"
+#include "host/gc_evalue.hpp"
 #include "host/gc_output.hpp"
 #include "host/gc_index_cache.hpp"
 #include "host/gc_correctness.hpp"
@@ -102,7 +102,7 @@ struct DeviceBuffer {   // growable device allocation owned by a stream object
 
 // One whole-read pass at a time per device: its rounds saturate the scalar issue ports of the whole chip, so two passes side by side
 // (two batches in flight on two gc_streams) only take turns at a finer grain and both finish late. With the token the second batch's
-// seeding, host glue and fragment pipeline overlap the first batch's whole-read pass, and its own pass starts the moment the first
+// seeding, seed glue and fragment pipeline overlap the first batch's whole-read pass, and its own pass starts the moment the first
 // one ends - a software pipeline over batches (GC_LONG_TOKEN=0 turns it off).
 // r4 / r5: two tokens per device, each with a scratch of its own, for passes that cannot fill the chip (longTokenCount below)
 using gc::LONG_TOKENS_MAX;
@@ -245,7 +245,7 @@ inline void syncEvent(hipEvent_t ev)
 	}
 }
 
-// Persistent worker pool for the per-read host glue (threads are created once per process).
+// Persistent worker pool for the per-read host work between the kernels: bookkeeping, selection, host stitching, result assembly (threads are created once per process).
 class WorkerPool {
 public:
 	static WorkerPool& instance() { static WorkerPool p(0); return p; }
@@ -644,9 +644,6 @@ struct gc_mxm_index {
 struct StitchedPath { std::vector<uint32_t> nodes; uint32_t firstOffset = 0, lastOffset = 0; uint64_t cells = 0; };
 
 struct ReadGlue {
-	std::vector<gc::SeedRec> seeds;       // fragment-pass order (by seqPos)
-	std::vector<gc::SeedRec> longSeeds;   // whole-read pass order (by goodness), only with long_pass
-	std::vector<gc::FragmentWindow> windows;
 	std::vector<LongAln> longAlns;        // final order (the reference's repeated sort by alignmentStart)
 	uint64_t longBegin = 0, longTraceBegin = 0, longSeedBegin = 0;
 	bool failed = false;
@@ -671,7 +668,7 @@ struct ReadGlue {
 	// every batch (allocating and destroying 10 k x 6 vectors per batch cost ~10 ms of teardown plus the allocations)
 	void reset()
 	{
-		seeds.clear(); longSeeds.clear(); windows.clear(); longAlns.clear(); longSelected.clear();
+		longAlns.clear(); longSelected.clear();
 		stitched.nodes.clear(); stitched.firstOffset = stitched.lastOffset = 0; stitched.cells = 0;
 		longBegin = longTraceBegin = longSeedBegin = 0;
 		failed = longFailed = capacityExceeded = capacityExceededLong = false;
@@ -704,7 +701,7 @@ struct gc_stream {
 	hipEvent_t ev[12] {};
 	hipEvent_t fragEv[16] {};   // r5: a (begin, end) pair around each of the lazy rounds' k_extend launches [0..7] and k_build_anchors launches [8..15]: kernel_us[1] / [2] are sums of exactly those
 	DeviceBuffer tmp, matches, readMatchOff, readMatchCount, cursors, readSeeds, fragFirstSeed, longRetryList, extLists, fragItems, fragRetryList, fragClaims, pendingFrags, fragNext, roundCounts, work, results, scratch, scratchRetry, tracePool, frags, fragSeeds, anchors, fragStatus, fragExtended, readTies, pathPool, jobs, chainOut, chainLen, chainScore, chainStatus, chainScratch, counters;
-	PinnedBuffer hFragDeclined, hMatches, hReadSeeds, hFragFirstSeed, hFrags, hJobs, hAnchors, hFragStatus, hFragExtended, hReadTies, hChainOut, hChainLen, hChainScore, hChainStatus, hPathPool, hSmall;
+	PinnedBuffer hFragDeclined, hReadSeeds, hFragFirstSeed, hFrags, hJobs, hAnchors, hFragStatus, hFragExtended, hReadTies, hChainOut, hChainLen, hChainScore, hChainStatus, hPathPool, hSmall;
 	// whole-read pass: runs on its own stream, concurrently with the fragment kernels
 	hipStream_t longStream = nullptr;
 	hipEvent_t longEv[2] {};
@@ -742,7 +739,7 @@ struct gc_stream {
 	DeviceBuffer gluePerRead, glueCursors, glueOut, glueSeedCap, glueSeedOff, glueWinCapOff, glueU32[8], glueSort, gluePos, glueWin;   // seed glue on the device (gc_seedglue.hip)
 	PinnedBuffer hGlueOut, hGlueWinCapOff, hGlueSmall;
 	DeviceBuffer longState, longWork, longWorkResults, longRoundTrace, longCandSeed, longWorkLen, longOrder;
-	PinnedBuffer hLongSeeds, hLongJobs, hLongAlns, hLongResults, hLongSmall, hLongCells;
+	PinnedBuffer hLongJobs, hLongAlns, hLongResults, hLongSmall, hLongCells;
 	// every device allocation of the stream with its size (GC_DEBUG_TIMES: "[gc mem]" lines; the whole-read decision's and the edit-distance runs' own buffers are listed by their owners)
 	template <typename F> void forEachDeviceBuffer(F f) const
 	{

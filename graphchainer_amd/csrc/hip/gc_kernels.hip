@@ -1520,8 +1520,8 @@ void launchLongExtend(hipStream_t stream, const DGraph& g, const CorrectnessTabl
 #undef GC_LAUNCH_TEAM
 #undef GC_LAUNCH_ONE
 }
-// Work items of the fragment pass, built where they are used (src/GraphAligner.h:499-511 per seed of a fragment window): the host sorts each
-// read's seeds and cuts the windows (order-critical, host/gc_glue.cpp) and hands over 16 B per fragment and per seed; one thread per fragment
+// Work items of the fragment pass, built where they are used (src/GraphAligner.h:499-511 per seed of a fragment window): the seed glue sorts each
+// read's seeds and cuts the windows (order-critical, gc_seedglue.hip) and leaves 16 B per fragment and per seed; one thread per fragment
 // expands its seed window into the per-slot records - the seed in fragment order and the two extensions (backward: reverse complement of the
 // fragment's prefix from the seed's reverse-strand twin; forward: the suffix from the seed). On the host this was 70 ms per 10 k reads
 // (345 MB of records through pinned memory, a twin lookup per slot) on the fragment pipeline's critical path, plus the upload.

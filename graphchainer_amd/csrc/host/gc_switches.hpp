@@ -29,11 +29,9 @@ struct Switches {
 	bool debugTimes = false;                       // GC_DEBUG_TIMES: stage times, CPU, pool sizes to stderr
 	bool debugEd = false;                          // GC_DEBUG_ED: every chain edit-distance pair with its band to stderr
 	// ---- fall-back paths kept for A/B and tests, same results
-	bool deviceGlue = true;                        // GC_DEVICE_GLUE=0: the seed glue on the host
 	bool hostAnchors = false;                      // GC_HOST_ANCHORS=1: the result's anchor arrays from the host's walk over the slots
 	bool extLazy = true;                           // GC_EXT_LAZY=0: every seed extended up front
 	bool extendSlab = false;                       // GC_EXTEND_SLAB=1: fragment extensions by the plain-layout kernel on per-lane slabs
-	bool poolsWorstCase = false;                   // GC_POOLS_WORST_CASE=1: trace and path pools by every slot's worst case instead of by use
 	bool hostStitch = false;                       // GC_HOST_STITCH: chain stitching on the host workers
 	std::optional<int> stitchClass;                // GC_STITCH_CLASS: forces the stitching kernel's class, 3 or 0 (unset: by read length)
 	bool chainPlainScan = false;                   // GC_CHAIN_PLAIN_SCAN=1: the chaining scratch launch scans its threshold lists plainly
@@ -89,11 +87,9 @@ struct Switches {
 		s.debugTimes = getenv("GC_DEBUG_TIMES") != nullptr;
 		s.debugEd = getenv("GC_DEBUG_ED") != nullptr;
 
-		if (const char* e = getenv("GC_DEVICE_GLUE")) s.deviceGlue = !(atoi(e) == 0);
 		if (const char* e = getenv("GC_HOST_ANCHORS")) s.hostAnchors = atoi(e) == 1;
 		if (const char* e = getenv("GC_EXT_LAZY")) s.extLazy = !(atoi(e) == 0);
 		if (const char* e = getenv("GC_EXTEND_SLAB")) s.extendSlab = atoi(e) == 1;
-		if (const char* e = getenv("GC_POOLS_WORST_CASE")) s.poolsWorstCase = atoi(e) == 1;
 		if (const char* e = getenv("GC_HOST_STITCH")) s.hostStitch = atoi(e) != 0;
 		if (const char* e = getenv("GC_STITCH_CLASS")) s.stitchClass = atoi(e) == 3 ? 3 : 0;
 		if (const char* e = getenv("GC_CHAIN_PLAIN_SCAN")) s.chainPlainScan = atoi(e) == 1;

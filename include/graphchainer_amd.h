@@ -527,8 +527,7 @@ void gc_result_free(gc_result* r);
 /* The same from the host's own seed hits (gc_seeds_upload) in place of MinimizerSeeder::getSeeds: OrderSeeds, the fragment windows and everything after them run on those hits,
  * each with its own match_len. No gc_seeder is needed - a host with its own seeds never builds or uploads the minimizer index. params->seed_density is not used (it belongs to
  * MinimizerSeeder::getSeeds); min_cluster_size and everything else behave as in gc_align_batch. Where the reference leaves the order of equal keys inside a seed cluster to
- * std::sort (hits of one cluster at one read position with different match_len) the cluster's matching base pairs follow a stable sort. Needs the device seed glue
- * (GC_DEVICE_GLUE=0: GC_ERR_INVALID). */
+ * std::sort (hits of one cluster at one read position with different match_len) the cluster's matching base pairs follow a stable sort. */
 int gc_align_batch_seeded(const gc_graph* g, gc_stream* st, const gc_reads* reads, const gc_seeds* seeds, const gc_params* params, gc_result** out);
 
 /* Extension block of gc_params, whose layout is frozen: options added after it, starting with the reference's --precise-clipping and --X-drop.

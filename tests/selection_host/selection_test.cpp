@@ -2,7 +2,7 @@
 //   method graphSize readSize eCutoff n  start end score  (n triples)
 // and gives one output line: the indices of the alignments kept, in the order they are returned. tests/test_graphaligner_model.py compares them with the selection of
 // tests/graphaligner_model.py; built with -fsanitize=address,undefined the same run has to stay clean.
-#include "gc_glue.hpp"
+#include "gc_evalue.hpp"
 #include "gc_selection.hpp"
 #include <cstdio>
 #include <iostream>

@@ -34,7 +34,7 @@ int main()
 		out << "hostThreads=" << text(s.hostThreads) << " batchThreads=" << text(s.batchThreads) << " buildThreads=" << text(s.buildThreads) << " resultCacheMin=" << s.resultCacheMin
 			<< " spinSync=" << s.spinSync << " syncPollUs=" << s.syncPollUs << " longToken=" << s.longToken << " shareLongScratch=" << s.shareLongScratch() << " onePassAtATime=" << s.onePassAtATime()
 			<< " longTokens=" << text(s.longTokens) << " debugTimes=" << s.debugTimes << " debugEd=" << s.debugEd
-			<< " deviceGlue=" << s.deviceGlue << " hostAnchors=" << s.hostAnchors << " extLazy=" << s.extLazy << " extendSlab=" << s.extendSlab << " poolsWorstCase=" << s.poolsWorstCase
+			<< " hostAnchors=" << s.hostAnchors << " extLazy=" << s.extLazy << " extendSlab=" << s.extendSlab
 			<< " hostStitch=" << s.hostStitch << " stitchClass=" << text(s.stitchClass) << " chainPlainScan=" << s.chainPlainScan << " edFirstK=" << text(s.edFirstK)
 			<< " seederBuildOnHost=" << s.seederBuildOnHost << " buildReferenceContainers=" << s.buildReferenceContainers
 			<< " testExtMaxItems=" << text(s.testExtMaxItems) << " testExtMaxPending=" << text(s.testExtMaxPending) << " testExtMaxTrace=" << text(s.testExtMaxTrace)

@@ -238,7 +238,7 @@ def _build_selection_program(tmp_path, flags=()):
     host = os.path.join(ROOT, "graphchainer_amd", "csrc", "host")
     exe = str(tmp_path / "selection_test")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *flags, "-I" + host, os.path.join(ROOT, "tests", "selection_host", "selection_test.cpp"),
-                    os.path.join(host, "gc_glue.cpp"), os.path.join(host, "gc_graph.cpp"), "-o", exe, "-lpthread", "-lz"], check=True, timeout=900)
+                    os.path.join(host, "gc_evalue.cpp"), os.path.join(host, "gc_graph.cpp"), "-o", exe, "-lpthread", "-lz"], check=True, timeout=900)
     return exe
 
 

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULTS = {
     "hostThreads": "unset", "batchThreads": "unset", "buildThreads": "unset", "resultCacheMin": str(32 << 20),
     "spinSync": "2", "syncPollUs": "40", "longToken": "1", "shareLongScratch": "1", "onePassAtATime": "1", "longTokens": "unset", "debugTimes": "0", "debugEd": "0",
-    "deviceGlue": "1", "hostAnchors": "0", "extLazy": "1", "extendSlab": "0", "poolsWorstCase": "0", "hostStitch": "0", "stitchClass": "unset", "chainPlainScan": "0",
+    "hostAnchors": "0", "extLazy": "1", "extendSlab": "0", "hostStitch": "0", "stitchClass": "unset", "chainPlainScan": "0",
     "edFirstK": "unset", "seederBuildOnHost": "0", "buildReferenceContainers": "0",
     "testExtMaxItems": "unset", "testExtMaxPending": "unset", "testExtMaxTrace": "unset", "testExtRetryMaxItems": "unset", "testLongMaxItems": "unset",
     "testLongMaxCols": "unset", "testLongCellsPerBase": "unset", "testLongMaxAlignments": "unset", "testLongScratchGb": "unset", "testStitchSetMax": "unset",
@@ -44,9 +44,8 @@ def _cases():
     one("GC_DEBUG_TIMES", "debugTimes", [(1, 1), (0, 1), ("", 1)])                                              # set at all
     one("GC_DEBUG_ED", "debugEd", [(1, 1), (0, 1), ("", 1)])
     # ---- fall-back paths. "exactly 0 turns the default off" (the empty string is atoi's 0), "exactly 1", "any non-zero value"
-    for name, field in (("GC_DEVICE_GLUE", "deviceGlue"), ("GC_EXT_LAZY", "extLazy")):
-        one(name, field, [(0, 0), (1, 1), (2, 1), ("", 0)])
-    for name, field in (("GC_HOST_ANCHORS", "hostAnchors"), ("GC_EXTEND_SLAB", "extendSlab"), ("GC_POOLS_WORST_CASE", "poolsWorstCase"), ("GC_CHAIN_PLAIN_SCAN", "chainPlainScan"),
+    one("GC_EXT_LAZY", "extLazy", [(0, 0), (1, 1), (2, 1), ("", 0)])
+    for name, field in (("GC_HOST_ANCHORS", "hostAnchors"), ("GC_EXTEND_SLAB", "extendSlab"), ("GC_CHAIN_PLAIN_SCAN", "chainPlainScan"),
                         ("GC_BUILD_REFERENCE_CONTAINERS", "buildReferenceContainers")):
         one(name, field, [(0, 0), (1, 1), (2, 0), ("", 0)])
     one("GC_HOST_STITCH", "hostStitch", [(0, 0), (1, 1), (2, 1), ("", 0)])
@@ -94,7 +93,7 @@ def test_switches_are_parsed_as_their_sites_parsed_them(tmp_path, sanitize):
     exe = _build(tmp_path, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all") if sanitize else ())
     cases = _cases()
     env = {k: v for k, v in os.environ.items() if not k.startswith("GC_")}
-    env["GC_DEVICE_GLUE"] = "0"   # (what the program inherits must not leak into a case)
+    env["GC_EXT_LAZY"] = "0"   # (what the program inherits must not leak into a case)
     run = subprocess.run([exe], input="".join(c[0] + "\n" for c in cases), capture_output=True, text=True, timeout=300, env=env)
     assert run.returncode == 0, run.stderr[-2000:]
     got = run.stdout.split("\n")[:-1]
