@@ -25,6 +25,8 @@ EXPORTED_SYMBOLS = [
     "gc_seeds_upload", "gc_seeds_destroy", "gc_seeds_hits", "gc_seeds_kernel_ms", "gc_mxm_index_create", "gc_mxm_options_default", "gc_mxm_index_open", "gc_mxm_cache_check", "gc_mxm_index_destroy", "gc_mxm_index_array", "gc_seeds_mxm", "gc_align_batch_seeded", "gc_params_ext_default", "gc_align_batch_ext", "gc_test_max_x_score",
     "gc_result_free", "gc_last_error", "gc_free", "gc_device_count", "gc_set_device", "gc_device_memory", "gc_edit_distance", "gc_edit_path", "gc_evalue", "gc_format_gaf", "gc_format_json", "gc_format_gam", "gc_format_gam_level", "gc_gzip_streams", "gc_gzip_streams_lz", "gc_format_gaf_trace", "gc_format_vg_trace", "gc_format_vg_trace_digraph", "gc_graph_letters", "gc_std_sort_permutations",
     "gc_format_corrected", "gc_format_corrected_trace", "gc_corrected_pieces",
+    "gc_coverage_create", "gc_coverage_destroy", "gc_stream_set_coverage", "gc_coverage_add_traces", "gc_coverage_counts", "gc_coverage_merge",
+    "gc_coverage_format_segments", "gc_coverage_format_bases",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
     "gc_reads_parse", "gc_fastx_table_free", "gc_bgzf_inflate", "gc_reads_parse_bgzf", "gc_reads_parse_bam", "gc_reads_parse_bam_bgzf",
     "gc_seed_store_open", "gc_seed_store_from_memory", "gc_seed_store_info", "gc_seed_store_destroy", "gc_seeds_from_store",
@@ -361,6 +363,89 @@ def corrected_pieces(graph, traces):
         lib.gc_free(text)
         lib.gc_free(out_off)
     return [data[int(at[i]):int(at[i + 1])] for i in range(n)]
+
+
+class Coverage:
+    """How often every segment and every base of the graph lies under a final alignment (gc_coverage_*; include/graphchainer_amd.h has the meaning). The accumulators
+    live on the current device, across batches: Aligner.align_batch(..., coverage=cov) or Aligner.set_coverage(cov) counts a batch's output alignments before the call
+    returns, and several aligners may share one handle. per_base: also a 32-bit depth per forward base (4 bytes each on the device; RuntimeError when that does not fit).
+    Integers added with atomics: the same reads give the same counts however they were batched."""
+
+    def __init__(self, graph, per_base=False):
+        self.lib = load_library()
+        self.graph, self.per_base = graph, bool(per_base)          # (the graph must outlive the handle)
+        self.handle = C.c_void_p()
+        self.lib.gc_coverage_create.restype = C.c_int
+        self.lib.gc_coverage_create.argtypes = [C.c_void_p, C.c_int, _P(C.c_void_p)]
+        _check(self.lib.gc_coverage_create(graph.handle, int(self.per_base), C.byref(self.handle)))
+
+    def add_traces(self, traces):
+        """Counts a list of traces, each (node, offset) in output coordinates, with the kernel the batches use (gc_coverage_add_traces); every cell is checked against the graph first."""
+        n = len(traces)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(t[0]) for t in traces], dtype=np.uint64) if n else []
+        cat = lambda k, dtype: np.ascontiguousarray(np.concatenate([np.asarray(t[k], dtype=dtype) for t in traces]) if n else np.zeros(0, dtype=dtype), dtype=dtype)   # noqa: E731
+        node, offset = cat(0, np.int32), cat(1, np.uint32)
+        assert len(node) == len(offset) == int(off[n])
+        self.lib.gc_coverage_add_traces.restype = C.c_int
+        self.lib.gc_coverage_add_traces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        _check(self.lib.gc_coverage_add_traces(self.handle, node.ctypes.data, offset.ctypes.data, off.ctypes.data, n))
+
+    def counts(self):
+        """-> (bases [segments] uint64, depth [forward bases] uint32 or None without per_base): the accumulators as they stand."""
+        bases, depth, n_seg, n_bases = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        self.lib.gc_coverage_counts.restype = C.c_int
+        self.lib.gc_coverage_counts.argtypes = [C.c_void_p, _P(C.c_void_p), _P(C.c_uint64), _P(C.c_void_p), _P(C.c_uint64)]
+        _check(self.lib.gc_coverage_counts(self.handle, C.byref(bases), C.byref(n_seg), C.byref(depth), C.byref(n_bases)))
+        try:
+            b = np.ctypeslib.as_array(C.cast(bases, _P(C.c_uint64)), shape=(int(n_seg.value),)).copy() if n_seg.value else np.zeros(0, dtype=np.uint64)
+            d = None
+            if depth:
+                d = np.ctypeslib.as_array(C.cast(depth, _P(C.c_uint32)), shape=(int(n_bases.value),)).copy() if n_bases.value else np.zeros(0, dtype=np.uint32)
+        finally:
+            self.lib.gc_free(bases)
+            self.lib.gc_free(depth)
+        return b, d
+
+    def merge(self, other):
+        """self += other (gc_coverage_merge): handles of one device or of two, made for graphs of the same shape."""
+        self.lib.gc_coverage_merge.restype = C.c_int
+        self.lib.gc_coverage_merge.argtypes = [C.c_void_p, C.c_void_p]
+        _check(self.lib.gc_coverage_merge(self.handle, other.handle))
+
+    def _table(self, fn):
+        text, length, line_off, n_lines = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, _P(C.c_void_p), _P(C.c_uint64), _P(C.c_void_p), _P(C.c_uint64)]
+        _check(fn(self.handle, C.byref(text), C.byref(length), C.byref(line_off), C.byref(n_lines)))
+        try:
+            data = C.string_at(text.value, int(length.value))
+            offsets = np.ctypeslib.as_array(C.cast(line_off, _P(C.c_uint64)), shape=(int(n_lines.value) + 1,)).copy()
+        finally:
+            self.lib.gc_free(text)
+            self.lib.gc_free(line_off)
+        return data, offsets
+
+    def segment_table(self, line_offsets=False):
+        """The --coverage-out table (bytes), spelled on the device: "#segment\tlength\tbases", then a line per segment. line_offsets: -> (bytes, byte offsets of the lines)."""
+        data, offsets = self._table(self.lib.gc_coverage_format_segments)
+        return (data, offsets) if line_offsets else data
+
+    def base_table(self, line_offsets=False):
+        """The --base-coverage-out table (bytes; needs per_base): "segment\tstart\tend\tdepth" per maximal run of equal non-zero depth inside a segment."""
+        data, offsets = self._table(self.lib.gc_coverage_format_bases)
+        return (data, offsets) if line_offsets else data
+
+    def close(self):
+        if self.handle:
+            self.lib.gc_coverage_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _fetch_array(fn, handle, name):
@@ -1125,13 +1210,31 @@ class Aligner:
             setattr(self.params.capacity, name, int(value))
         self.stream = C.c_void_p()
         _check(self.lib.gc_stream_create(C.byref(self.stream)))
+        self.coverage = None
 
-    def align_batch(self, batch, seeds=None, gaf_names=None, cigar_match_mismatch_merge=False, other_formats=False, formats=None, gam_level=None):
+    def set_coverage(self, coverage):
+        """From now on every batch of this aligner (device_output != 0) is counted into `coverage` (a Coverage of this device; None: off) before align_batch returns."""
+        self.lib.gc_stream_set_coverage.restype = C.c_int
+        self.lib.gc_stream_set_coverage.argtypes = [C.c_void_p, C.c_void_p]
+        _check(self.lib.gc_stream_set_coverage(self.stream, coverage.handle if coverage is not None else None))
+        self.coverage = coverage
+
+    def align_batch(self, batch, seeds=None, gaf_names=None, cigar_match_mismatch_merge=False, other_formats=False, formats=None, gam_level=None, coverage=None):
         """Runs the hot path for a ReadBatch; returns a dict of arrays. seeds: a SeedBatch made for this batch - its hits replace the seeder's. With gaf_names (one id per read; needs long_pass and
         keep_traces or device_output) the dict also holds "gaf" (bytes: the reference's GAF lines) and "gaf_chained_skipped"; with other_formats also "json" (JSON
         lines) and "gam" (gzip members of framed vg::Alignment messages; gam_level: their zlib level, or GAM_DEVICE_HUFFMAN for the device's deflate). formats may also name
         "corrected" / "corrected_clipped" (gc_format_corrected: FASTA records of the corrected reads / of every alignment's piece; device_output & 8 or keep_traces):
-        the dict then holds their bytes and, under "corrected_rec_off" / "corrected_clipped_rec_off", the records' byte offsets (one more entry than records)."""
+        the dict then holds their bytes and, under "corrected_rec_off" / "corrected_clipped_rec_off", the records' byte offsets (one more entry than records).
+        coverage: a Coverage this one batch is counted into (needs device_output; set_coverage's handle, if any, is back in place afterwards)."""
+        if coverage is not None:
+            if not self.params.device_output:
+                raise ValueError("coverage counts the batch's output alignments: the Aligner needs device_output != 0")
+            standing = self.coverage
+            self.set_coverage(coverage)
+            try:
+                return self.align_batch(batch, seeds=seeds, gaf_names=gaf_names, cigar_match_mismatch_merge=cigar_match_mismatch_merge, other_formats=other_formats, formats=formats, gam_level=gam_level)
+            finally:
+                self.set_coverage(standing)
         res = _P(GcResult)()
         ext_on = self.params_ext.precise_clipping != 0 or self.params_ext.x_drop != 0   # (with both off: the calls that take no block)
         if ext_on and (seeds is not None or self.seeder is not None):

@@ -7,6 +7,8 @@ resolve(argv) -> Config turns a command line into what a run needs - the referen
 writers chosen), and a writer thread: records written in input order, every output file through a temporary name and a rename.
 --corrected-out / --corrected-clipped-out are GraphAligner's (the reference keeps their mechanism, src/Aligner.cpp:313-374, and dropped the two option lines): the
 corrected reads, their pieces spelled on the device, beside -a or without it.
+--coverage-out / --base-coverage-out are this build's own: how often every segment / every base of the graph lies under an alignment the run writes, counted on the
+device while the traces are there (api.Coverage), one handle per device, merged and spelled at the end; beside -a or without it.
 
 Accepted and without effect: -t / --threads (checked >= 1), --high-memory, --verbose, --short-verbose (the progress text and the closing statistics are not
 reproduced), and --greedy-E / --greedy-score, which the reference declares and never reads. --try-all-seeds (and --all-alignments, which sets it) does what it does
@@ -43,9 +45,11 @@ OPTIONS = {
     "batch-bytes": (None, "size", False), "device": (None, "size", False), "index-cache": (None, "string", False),
     "inflight": (None, "size", False), "devices": (None, "string", False),
     "corrected-out": (None, "string", False), "corrected-clipped-out": (None, "string", False),   # GraphAligner's: the reference keeps their mechanism and dropped the two option lines
+    "coverage-out": (None, "string", False), "base-coverage-out": (None, "string", False),
 }
 MAX_INFLIGHT = 5                   # the most the benchmark keeps in flight on a device (bench.py: BATCH_MS_BY_INFLIGHT ends there)
 MAX_DEVICES = 16                   # the library's per-device slots
+COVERAGE_GZ_PIECE = 1 << 20         # a .gz coverage table is written as gzip members of about this many bytes of whole lines
 CORRECTED_SUFFIXES = (".fa", ".fasta", ".fa.gz", ".fasta.gz")   # src/AlignerMain.cpp:360,365 (a name shorter than a suffix does not end in it; the reference's substr would throw)
 REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "generate-path", "generate-path-seed", "graph-statistics")
 SELECT = {"greedy-length": 0, "schedule-inverse-E-sum": 3, "schedule-inverse-E-product": 4, "schedule-score": 5, "schedule-length": 6, "all-alignments": 7}   # GC_SELECT_*
@@ -108,6 +112,10 @@ This build's own:
   --corrected-out arg                   GraphAligner's: output corrected reads file (.fa/.fa.gz), every read with its aligned stretches
                                         replaced by the graph's letters along the alignment (upper case; the rest lower case)
   --corrected-clipped-out arg           GraphAligner's: output corrected clipped reads file (.fa/.fa.gz), one record per alignment
+  --coverage-out arg                    table "#segment length bases" (tab-separated; gzipped for a .gz name): for every segment of the graph the
+                                        number of its bases under the alignments written, each counted as often as it is covered
+  --base-coverage-out arg               table "segment start end depth" (no header; 0-based, half-open, forward strand; gzipped for a .gz name): one
+                                        line per stretch of equal non-zero depth. Holds 4 bytes per base of the graph on every device
 
 Accepted and without effect: -t [ --threads ] arg (must be >= 1), --high-memory, --verbose, --short-verbose, --greedy-E, --greedy-score.
 Not supported by this build: --optimal-alignment, --seedless-DP, --DP-restart-stride, --generate-path, --generate-path-seed,
@@ -129,6 +137,7 @@ class Config:
     reads: list = field(default_factory=list)
     outputs: dict = field(default_factory=dict)          # "gaf" / "json" / "gam" -> path (the last one given of each kind, as the reference keeps it)
     corrected: dict = field(default_factory=dict)        # "corrected" / "corrected_clipped" -> path (--corrected-out / --corrected-clipped-out; a .gz name is compressed)
+    coverage: dict = field(default_factory=dict)         # "coverage" / "base_coverage" -> path (--coverage-out / --base-coverage-out; a .gz name is compressed)
     aligner: dict = field(default_factory=dict)          # keyword arguments of api.Aligner
     min_cluster_size: int = 1                            # gc_params::min_cluster_size
     seeder: dict = field(default_factory=dict)           # {"kind": "minimizer", "length", "window", "keep_fraction"}, {"kind": "mxm", "mode", "count", "min_len", "cache_prefix"} or {"kind": "file", "paths"}
@@ -300,7 +309,8 @@ def resolve(argv):
     if not cfg.reads:
         error("read file must be given")
     corrected_out, clipped_out = last("corrected-out", ""), last("corrected-clipped-out", "")
-    if not outputs and corrected_out == "" and clipped_out == "":      # src/AlignerMain.cpp:335
+    coverage_out, base_coverage_out = last("coverage-out", ""), last("base-coverage-out", "")
+    if not outputs and corrected_out == "" and clipped_out == "" and coverage_out == "" and base_coverage_out == "":      # src/AlignerMain.cpp:335 (this build's own outputs count as the corrected reads do)
         error("alignments-out must be given")
     for path in outputs:
         if len(path) >= 4 and path.endswith(".gam"):
@@ -316,6 +326,9 @@ def resolve(argv):
             if not path.endswith(CORRECTED_SUFFIXES):
                 error("unknown output corrected read format, must be .fa or .fa.gz")
             cfg.corrected[fmt] = path
+    for fmt, path in (("coverage", coverage_out), ("base_coverage", base_coverage_out)):
+        if path != "":
+            cfg.coverage[fmt] = path
     if cfg.threads < 1:
         error("number of threads must be >= 1")
     if "inflight" in vm and vm["inflight"][-1] < 1:
@@ -458,13 +471,13 @@ class _Replica:
     """One device's copy of what the workers read: graph, and minimizer index, MUM/MEM index or seed store."""
 
     def __init__(self, device):
-        self.device, self.graph, self.seeder, self.index, self.store, self.setup_seconds = device, None, None, None, None, 0.0
+        self.device, self.graph, self.seeder, self.index, self.store, self.coverage, self.setup_seconds = device, None, None, None, None, None, 0.0
 
     def close(self):
-        for thing in (self.store, self.index, self.seeder, self.graph):
+        for thing in (self.coverage, self.store, self.index, self.seeder, self.graph):
             if thing is not None:
                 thing.close()
-        self.store = self.index = self.seeder = self.graph = None
+        self.coverage = self.store = self.index = self.seeder = self.graph = None
 
 
 def _setup_replicas(cfg, api, replicas):
@@ -500,6 +513,8 @@ def _setup_replicas(cfg, api, replicas):
                 rep.store = api.SeedStore(cfg.seeder["paths"])             # every file, in command-line order, before any read is aligned (src/Aligner.cpp:1169-1190)
             elif not minimizer:
                 rep.index = api.MxmIndex(rep.graph, cache_prefix=mxm_prefix)
+            if cfg.coverage:               # the accumulators of this device, here so that choose_inflight measures the free memory with them in place
+                rep.coverage = api.Coverage(rep.graph, per_base="base_coverage" in cfg.coverage)
             rep.setup_seconds = time.time() - started
     finally:
         if tmp:
@@ -507,9 +522,22 @@ def _setup_replicas(cfg, api, replicas):
 
 
 def device_output_for(cfg):
-    """gc_params::device_output for the files cfg names: 1 / 2 the GAF pieces, 4 the vg::Path bytes, 8 the corrected reads' pieces."""
+    """gc_params::device_output for the files cfg names: 1 / 2 the GAF pieces, 4 the vg::Path bytes, 8 the corrected reads' pieces. Coverage alone asks for the GAF pieces
+    (the bit with the least to bring down) and leaves them unused: the output jobs the counting works from exist only with some bit set."""
     gaf = (2 if cfg.cigar_match_mismatch else 1) if "gaf" in cfg.outputs else 0
-    return gaf | (4 if "json" in cfg.outputs or "gam" in cfg.outputs else 0) | (8 if cfg.corrected else 0)
+    bits = gaf | (4 if "json" in cfg.outputs or "gam" in cfg.outputs else 0) | (8 if cfg.corrected else 0)
+    return bits or (1 if cfg.coverage else 0)
+
+
+def gzip_lines(api, text, line_off, piece=COVERAGE_GZ_PIECE):
+    """text as gzip members of whole lines, about `piece` bytes each, deflated on the device (gc_gzip_streams_lz); line_off: the byte offsets of the lines, the end included."""
+    cuts, total = [0], len(text)
+    for at in line_off[1:]:
+        if int(at) - cuts[-1] >= piece:
+            cuts.append(int(at))
+    if cuts[-1] != total:
+        cuts.append(total)
+    return b"".join(api.gzip_streams([text[cuts[k]:cuts[k + 1]] for k in range(len(cuts) - 1)], lz=True))
 
 
 def gzip_records(api, text, rec_off):
@@ -541,6 +569,8 @@ def run(cfg, stderr=sys.stderr):
         api.set_device(rep.device)         # the current device belongs to the thread: every call of this worker runs under it
         aligner = api.Aligner(rep.graph, rep.seeder, long_pass=True, edit_distances=True, keep_traces=0, device_output=device_output, **cfg.aligner)
         aligner.params.min_cluster_size = cfg.min_cluster_size
+        if rep.coverage is not None:       # every worker of the replica counts into the replica's handle: a batch is counted by the worker that finishes it
+            aligner.set_coverage(rep.coverage)
         return aligner
 
     def align(aligner, r, item):
@@ -550,7 +580,16 @@ def run(cfg, stderr=sys.stderr):
         else:
             seeds = rep.index.seeds(batch, cfg.seeder["mode"], count=cfg.seeder["count"], min_len=cfg.seeder["min_len"]) if rep.index is not None else None
         try:
-            out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats + corrected, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
+            if rep.coverage is None:
+                out = aligner.align_batch(batch, seeds=seeds, gaf_names=ids, formats=formats + corrected, cigar_match_mismatch_merge=cfg.cigar_match_mismatch)
+            else:
+                # the batch is counted when align_batch returns. What follows must not send it to another worker (pipeline.py retires a worker whose error says
+                # "out of memory" and hands its item on): it would be counted twice, so such an error ends the run instead
+                out = aligner.align_batch(batch, seeds=seeds)
+                try:
+                    out.update(aligner.format_batch(out, batch, ids, formats + corrected, cfg.cigar_match_mismatch)[0])
+                except RuntimeError as e:
+                    raise RuntimeError("formatting a batch that was already counted into the coverage failed: " + str(e).replace(pipeline.OUT_OF_MEMORY, "out of device memory")) from e
         finally:
             if seeds is not None:
                 seeds.close()
@@ -584,7 +623,7 @@ def run(cfg, stderr=sys.stderr):
                     reader_seconds.update(busy=pieces.busy, waiting_in=0.0, waiting_out=pieces.waiting_out, parse_waiting_in=pieces.consumer_waiting)
 
         started = time.time()
-        with _Outputs({**cfg.outputs, **cfg.corrected}) as outputs:
+        with _Outputs({**cfg.outputs, **cfg.corrected, **cfg.coverage}) as outputs:
             def write(result):
                 texts, reads, failed, capacity, flagged = result
                 for f in formats + corrected:
@@ -596,6 +635,15 @@ def run(cfg, stderr=sys.stderr):
                 counts["flagged"] += flagged
 
             report = pipeline.run(source, make_aligner, align, write, replicas=len(replicas), inflight=inflight, release=lambda item: item[0].close())
+            if cfg.coverage:               # every batch is in: the replicas' counts into the first one's, the tables spelled on its device
+                total = replicas[0].coverage
+                api.set_device(replicas[0].device)
+                for rep in replicas[1:]:
+                    total.merge(rep.coverage)
+                for fmt, table in (("coverage", total.segment_table), ("base_coverage", total.base_table)):
+                    if fmt in cfg.coverage:
+                        text, line_off = table(line_offsets=True)
+                        outputs.write(fmt, gzip_lines(api, text, line_off) if cfg.coverage[fmt].endswith(".gz") else text)
         counts["seconds"] = time.time() - started
     finally:
         for rep in replicas:

@@ -288,6 +288,62 @@
 			for (uint64_t k = readJobBegin[r]; k < readJobBegin[r + 1]; k++) { outEntries.push_back(OutEntry { (uint32_t)r, jobAln[k], 0 }); outJobOfEntry.push_back(k); }
 		}
 		readOutOff[n] = outEntries.size();
+		if (st->coverage) countCoverage();
+	}
+
+	// gc_stream_set_coverage: the batch's output entries - exactly the alignments the writers will print - are counted into the handle (gc_coverage.hip). Here and not beside the
+	// encoder: the encoder runs before the chained-versus-whole-read decision and drops the losers' pieces afterwards, and a count cannot be dropped. Entries of source 0 are
+	// read where they lie, in the cell pool (still resident: nothing reserves it again before the next batch), under a keep byte per encoder job; the chained winners' traces
+	// exist only on the host (chain_trace_*: edlib's path walked, or the fast mode's stitched cells) and go up for the same kernel. The stream is waited for: a finished batch
+	// is a counted batch.
+	void countCoverage()
+	{
+		gc_coverage* cov = st->coverage;
+		const double t0 = nowUs();
+		hipEvent_t timed[2] = {};
+		if (sw.debugTimes) for (auto& e : timed) HIP_CHECK(hipEventCreate(&e));
+		if (timed[0]) HIP_CHECK(hipEventRecord(timed[0], stream));
+		uint64_t nKept = 0, nWinners = 0, winnerCells = 0;
+		if (nOutJobs) {
+			uint8_t* hKeep = st->hCovKeep.reserve<uint8_t>(nOutJobs);
+			memset(hKeep, 0, nOutJobs);
+			for (uint64_t k : outJobOfEntry) if (k != ~0ull) { hKeep[k] = 1; nKept++; }
+			if (nKept) {
+				uint8_t* dKeep = st->covKeep.reserve<uint8_t>(nOutJobs);
+				HIP_CHECK(hipMemcpyAsync(dKeep, hKeep, nOutJobs, hipMemcpyHostToDevice, stream));
+				launchCoverageAdd(stream, cov->dev, (const OutJob*)st->outJobs.ptr, (uint32_t)nOutJobs, dKeep, dLongCells, cov->dBases, cov->dDepth, cov->dBad);
+			}
+		}
+		for (const OutEntry& en : outEntries) if (en.source == 1) { nWinners++; winnerCells += glue[en.read].chainTraceNode.size(); }
+		if (nWinners) {
+			if (nWinners >= 0xffffffffull) throw std::runtime_error("too many chained alignments in one batch for the coverage kernel");
+			LongCell* hCells = st->hCovCells.reserve<LongCell>(winnerCells);
+			OutJob* hJobsCov = st->hCovJobs.reserve<OutJob>(nWinners);
+			uint64_t at = 0, w = 0;
+			for (const OutEntry& en : outEntries) {
+				if (en.source != 1) continue;
+				const ReadGlue& gl = glue[en.read];
+				const size_t cells = gl.chainTraceNode.size();
+				if (cells == 0) throw std::runtime_error("coverage: a chained alignment won and the batch holds no trace for it (chain_traces == 0?)");
+				hJobsCov[w++] = OutJob { at, 0, (uint32_t)cells, 0, 0, 0 };
+				for (size_t i = 0; i < cells; i++) hCells[at++] = LongCell { gl.chainTraceNode[i], gl.chainTraceOffset[i], gl.chainTraceSeqPos[i], gl.chainTraceSwitch[i] };
+			}
+			LongCell* dCells = st->covCells.reserve<LongCell>(winnerCells);
+			OutJob* dJobsCov = st->covJobs.reserve<OutJob>(nWinners);
+			HIP_CHECK(hipMemcpyAsync(dCells, hCells, winnerCells * sizeof(LongCell), hipMemcpyHostToDevice, stream));
+			HIP_CHECK(hipMemcpyAsync(dJobsCov, hJobsCov, nWinners * sizeof(OutJob), hipMemcpyHostToDevice, stream));
+			launchCoverageAdd(stream, cov->dev, dJobsCov, (uint32_t)nWinners, nullptr, dCells, cov->dBases, cov->dDepth, cov->dBad);
+		}
+		if (timed[1]) HIP_CHECK(hipEventRecord(timed[1], stream));
+		HIP_CHECK(hipGetLastError());
+		syncStream(stream);
+		if (timed[0]) {
+			float ms = 0;
+			HIP_CHECK(hipEventElapsedTime(&ms, timed[0], timed[1]));
+			for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
+			fprintf(stderr, "[gc times] coverage: k_cov_add over %llu alignments in the cell pool and %llu chained winners (%llu cells up), %.3f ms on the device, %.1f ms in all; per-base depth %s\n",
+				(unsigned long long)nKept, (unsigned long long)nWinners, (unsigned long long)winnerCells, ms, (nowUs() - t0) / 1e3, cov->dDepth ? "on" : "off");
+		}
 	}
 
 	void assembleOutput()   // the pieces into the result (entries of chained winners stay empty: source 1)

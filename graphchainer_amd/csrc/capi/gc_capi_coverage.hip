@@ -1,0 +1,223 @@
+// C entry points of the coverage accumulators: gc_coverage_create / _destroy, gc_stream_set_coverage, gc_coverage_add_traces, gc_coverage_counts, gc_coverage_merge,
+// gc_coverage_format_segments / _bases. The kernels are in hip/gc_coverage.hip, the per-batch counting in batch/gc_batch_output.inc (countCoverage).
+#include "../gc_runtime.hpp"
+
+namespace {
+
+// the handle's device for the calling thread while a call works on it, the caller's afterwards
+struct OnDevice {
+	int before = 0;
+	explicit OnDevice(int device) { HIP_CHECK(hipGetDevice(&before)); if (before != device) HIP_CHECK(hipSetDevice(device)); }
+	~OnDevice() { int now = 0; if (hipGetDevice(&now) == hipSuccess && now != before) (void)hipSetDevice(before); }
+};
+
+void checkFlags(gc_coverage* cov, hipStream_t q)
+{
+	uint32_t flags = 0;
+	HIP_CHECK(hipMemcpyAsync(&flags, cov->dBad, sizeof flags, hipMemcpyDeviceToHost, q));
+	HIP_CHECK(hipStreamSynchronize(q));
+	if (flags & 1u) throw std::runtime_error("internal: the coverage kernel met a trace cell outside the graph (it was not counted)");
+}
+
+} // namespace
+
+extern "C" {
+
+int gc_coverage_create(const gc_graph* G, int per_base, gc_coverage** out)
+{
+	if (!G || !out) return fail(GC_ERR_INVALID, "null argument");
+	*out = nullptr;
+	gc_coverage* cov = new gc_coverage();
+	int rc = guarded([&]() {
+		requireDevice();
+		HIP_CHECK(hipGetDevice(&cov->device));
+		const size_t nIds = G->hOrigSize.size(), nSeg = (nIds + 1) / 2;
+		cov->graph = G; cov->nIds = (uint32_t)nIds; cov->names = G->devNames;
+		cov->segStart.assign(nSeg + 1, 0);
+		for (size_t s = 0; s < nSeg; s++) {
+			const uint32_t fw = G->hOrigSize[2 * s], bw = 2 * s + 1 < nIds ? G->hOrigSize[2 * s + 1] : 0;
+			if (fw && bw && fw != bw) throw std::runtime_error("gc_coverage_create: a segment's two strands differ in length");
+			cov->segStart[s + 1] = cov->segStart[s] + (fw ? fw : bw);
+		}
+		const uint64_t nBases = cov->segStart[nSeg];
+		HIP_CHECK(hipMalloc(&cov->dSegStart, (nSeg + 1) * sizeof(uint64_t)));
+		HIP_CHECK(hipMemcpy(cov->dSegStart, cov->segStart.data(), (nSeg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+		HIP_CHECK(hipMalloc((void**)&cov->dBases, std::max<size_t>(1, nSeg) * sizeof(unsigned long long)));
+		HIP_CHECK(hipMemset(cov->dBases, 0, std::max<size_t>(1, nSeg) * sizeof(unsigned long long)));
+		HIP_CHECK(hipMalloc((void**)&cov->dBad, sizeof(uint32_t)));
+		HIP_CHECK(hipMemset(cov->dBad, 0, sizeof(uint32_t)));
+		if (per_base) {
+			const size_t bytes = std::max<uint64_t>(1, nBases) * sizeof(uint32_t);
+			if (hipMalloc((void**)&cov->dDepth, bytes) != hipSuccess) {
+				(void)hipGetLastError();
+				cov->dDepth = nullptr;
+				throw DeviceError("gc_coverage_create: the per-base depth needs " + std::to_string(bytes) + " bytes of device memory (4 per forward base of the graph) and they could not be allocated");
+			}
+			HIP_CHECK(hipMemset(cov->dDepth, 0, bytes));
+		}
+		HIP_CHECK(hipDeviceSynchronize());
+		cov->dev = CovGraph { (const uint64_t*)cov->dSegStart, (uint64_t)nSeg, nBases, (uint32_t)nIds };
+		return (int)GC_OK;
+	});
+	if (rc != GC_OK) {
+		int current = 0;
+		if (hipGetDevice(&current) == hipSuccess && current != cov->device) { (void)hipSetDevice(cov->device); delete cov; (void)hipSetDevice(current); } else delete cov;
+		return rc;
+	}
+	*out = cov;
+	return GC_OK;
+}
+
+void gc_coverage_destroy(gc_coverage* cov)
+{
+	if (!cov) return;
+	int current = 0;
+	const int device = cov->device;
+	const bool known = hipGetDevice(&current) == hipSuccess;
+	if (known && current != device) (void)hipSetDevice(device);
+	delete cov;
+	if (known && current != device) (void)hipSetDevice(current);
+}
+
+int gc_stream_set_coverage(gc_stream* st, gc_coverage* cov)
+{
+	if (!st) return fail(GC_ERR_INVALID, "null argument");
+	if (cov && cov->device != st->device) return fail(GC_ERR_INVALID, "gc_stream_set_coverage: the handle lives on another device than the stream");
+	st->coverage = cov;
+	return GC_OK;
+}
+
+int gc_coverage_add_traces(gc_coverage* cov, const int32_t* node, const uint32_t* offset, const uint64_t* trace_off, uint64_t n_aln)
+{
+	if (!cov || !trace_off) return fail(GC_ERR_INVALID, "null argument");
+	const uint64_t cellsTotal = trace_off[n_aln];
+	if (cellsTotal && (!node || !offset)) return fail(GC_ERR_INVALID, "null argument");
+	if (n_aln >= 0xffffffffull) return fail(GC_ERR_INVALID, "gc_coverage_add_traces: too many alignments");
+	if (trace_off[0] != 0) return fail(GC_ERR_INVALID, "gc_coverage_add_traces: trace_off must start at 0");
+	for (uint64_t a = 0; a < n_aln; a++) if (trace_off[a + 1] < trace_off[a] || trace_off[a + 1] - trace_off[a] >= (1ull << 32)) return fail(GC_ERR_INVALID, "gc_coverage_add_traces: trace_off must ascend, traces below 2^32 cells");
+	// every cell against the graph before the kernel indexes anything with it
+	const std::vector<uint32_t>& size = cov->graph->hOrigSize;
+	for (uint64_t i = 0; i < cellsTotal; i++)
+		if (node[i] < 0 || (uint64_t)node[i] >= size.size() || offset[i] >= size[node[i]]) return fail(GC_ERR_INVALID, "gc_coverage_add_traces: no such node / offset");
+	if (n_aln == 0 || cellsTotal == 0) return GC_OK;
+	return guarded([&]() {
+		requireDevice();
+		OnDevice here(cov->device);
+		hipStream_t q = threadStream(cov->device);
+		std::vector<LongCell> cells(cellsTotal);
+		for (uint64_t i = 0; i < cellsTotal; i++) cells[i] = LongCell { node[i], offset[i], 0u, 0u };
+		std::vector<OutJob> jobs(n_aln);
+		for (uint64_t a = 0; a < n_aln; a++) jobs[a] = OutJob { trace_off[a], 0, (uint32_t)(trace_off[a + 1] - trace_off[a]), 0, 0, 0 };
+		DeviceBuffer dCells, dJobs;
+		LongCell* pCells = dCells.reserve<LongCell>(cells.size());
+		OutJob* pJobs = dJobs.reserve<OutJob>(n_aln);
+		HIP_CHECK(hipMemcpyAsync(pCells, cells.data(), cells.size() * sizeof(LongCell), hipMemcpyHostToDevice, q));
+		HIP_CHECK(hipMemcpyAsync(pJobs, jobs.data(), n_aln * sizeof(OutJob), hipMemcpyHostToDevice, q));
+		launchCoverageAdd(q, cov->dev, pJobs, (uint32_t)n_aln, nullptr, pCells, cov->dBases, cov->dDepth, cov->dBad);
+		HIP_CHECK(hipGetLastError());
+		HIP_CHECK(hipStreamSynchronize(q));   // (the buffers go when this returns)
+		return (int)GC_OK;
+	});
+}
+
+int gc_coverage_counts(gc_coverage* cov, uint64_t** bases, uint64_t* n_segments, uint32_t** depth, uint64_t* n_bases)
+{
+	if (!cov || !bases || !n_segments || !depth || !n_bases) return fail(GC_ERR_INVALID, "null argument");
+	*bases = nullptr; *depth = nullptr;
+	return guarded([&]() {
+		requireDevice();
+		OnDevice here(cov->device);
+		hipStream_t q = threadStream(cov->device);
+		checkFlags(cov, q);
+		const uint64_t nSeg = cov->dev.nSegments, nBases = cov->dev.nBases;
+		uint64_t* b = mallocArray<uint64_t>(nSeg);
+		uint32_t* d = cov->dDepth ? mallocArray<uint32_t>(nBases) : nullptr;
+		if (!b || (cov->dDepth && !d)) { free(b); free(d); throw std::runtime_error("out of memory"); }
+		struct Free { void* p; ~Free() { free(p); } } gb { b }, gd { d };
+		static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit counts");
+		if (nSeg) HIP_CHECK(hipMemcpyAsync(b, cov->dBases, nSeg * sizeof(uint64_t), hipMemcpyDeviceToHost, q));
+		if (d && nBases) HIP_CHECK(hipMemcpyAsync(d, cov->dDepth, nBases * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		gb.p = nullptr; gd.p = nullptr;
+		*bases = b; *n_segments = nSeg; *depth = d; *n_bases = nBases;
+		return (int)GC_OK;
+	});
+}
+
+int gc_coverage_merge(gc_coverage* dst, const gc_coverage* src)
+{
+	if (!dst || !src) return fail(GC_ERR_INVALID, "null argument");
+	if (dst == src) return fail(GC_ERR_INVALID, "gc_coverage_merge: a handle cannot be merged into itself");
+	if (dst->segStart != src->segStart || dst->nIds != src->nIds) return fail(GC_ERR_INVALID, "gc_coverage_merge: the handles were made for graphs of different shape");
+	if ((dst->dDepth != nullptr) != (src->dDepth != nullptr)) return fail(GC_ERR_INVALID, "gc_coverage_merge: one handle counts per base and the other does not");
+	return guarded([&]() {
+		requireDevice();
+		OnDevice here(dst->device);
+		hipStream_t q = threadStream(dst->device);
+		const uint64_t nSeg = dst->dev.nSegments, nDepth = dst->dDepth ? dst->dev.nBases : 0;
+		uint32_t srcFlags = 0;
+		if (src->device == dst->device) {
+			HIP_CHECK(hipMemcpyAsync(&srcFlags, src->dBad, sizeof srcFlags, hipMemcpyDeviceToHost, q));
+			launchCoverageMerge(q, dst->dBases, src->dBases, nSeg, dst->dDepth, src->dDepth, nDepth);
+			HIP_CHECK(hipGetLastError());
+			HIP_CHECK(hipStreamSynchronize(q));
+		} else {
+			// two devices: through the host, the depth in slices so that neither side holds a second copy of it
+			const uint64_t slice = 64ull << 20;   // words
+			std::vector<unsigned long long> hBases(std::max<uint64_t>(1, nSeg));
+			std::vector<uint32_t> hDepth(std::max<uint64_t>(1, std::min(slice, nDepth)));
+			DeviceBuffer dBases, dDepth;
+			unsigned long long* pBases = dBases.reserve<unsigned long long>(nSeg);
+			uint32_t* pDepth = dDepth.reserve<uint32_t>(hDepth.size());
+			{
+				OnDevice there(src->device);
+				HIP_CHECK(hipMemcpy(&srcFlags, src->dBad, sizeof srcFlags, hipMemcpyDeviceToHost));
+				if (nSeg) HIP_CHECK(hipMemcpy(hBases.data(), src->dBases, nSeg * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+			}
+			if (nSeg) HIP_CHECK(hipMemcpyAsync(pBases, hBases.data(), nSeg * sizeof(unsigned long long), hipMemcpyHostToDevice, q));
+			launchCoverageMerge(q, dst->dBases, pBases, nSeg, nullptr, nullptr, 0);
+			HIP_CHECK(hipStreamSynchronize(q));
+			for (uint64_t at = 0; at < nDepth; at += slice) {
+				const uint64_t m = std::min(slice, nDepth - at);
+				{
+					OnDevice there(src->device);
+					HIP_CHECK(hipMemcpy(hDepth.data(), src->dDepth + at, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+				}
+				HIP_CHECK(hipMemcpyAsync(pDepth, hDepth.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+				launchCoverageMerge(q, nullptr, nullptr, 0, dst->dDepth + at, pDepth, m);
+				HIP_CHECK(hipGetLastError());
+				HIP_CHECK(hipStreamSynchronize(q));
+			}
+		}
+		if (srcFlags & 1u) throw std::runtime_error("internal: the merged handle's kernel met a trace cell outside the graph (it was not counted)");
+		return (int)GC_OK;
+	});
+}
+
+static int formatTable(gc_coverage* cov, bool perBase, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines)
+{
+	if (!cov || !text || !len) return fail(GC_ERR_INVALID, "null argument");
+	if (perBase && !cov->dDepth) return fail(GC_ERR_INVALID, "gc_coverage_format_bases: the handle was created without per-base depth");
+	*text = nullptr;
+	if (line_off) *line_off = nullptr;
+	return guarded([&]() {
+		requireDevice();
+		OnDevice here(cov->device);
+		hipStream_t q = threadStream(cov->device);
+		checkFlags(cov, q);
+		char* t = nullptr; uint64_t l = 0, n = 0; uint64_t* off = nullptr;
+		const hipError_t e = perBase ? coverageFormatBases(q, cov->dev, cov->names, cov->dDepth, cov->dBad, &t, &l, &off, &n)
+		                             : coverageFormatSegments(q, cov->dev, cov->names, cov->dBases, &t, &l, &off, &n);
+		if (e == hipErrorInvalidValue) throw std::runtime_error("internal: the coverage tables' counting and placing passes disagree, or a table has 2^31 lines or more");
+		HIP_CHECK(e);
+		*text = t; *len = l;
+		if (line_off) *line_off = off; else free(off);
+		if (n_lines) *n_lines = n;
+		return (int)GC_OK;
+	});
+}
+
+int gc_coverage_format_segments(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines) { return formatTable(cov, false, text, len, line_off, n_lines); }
+int gc_coverage_format_bases(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines) { return formatTable(cov, true, text, len, line_off, n_lines); }
+
+} // extern "C"

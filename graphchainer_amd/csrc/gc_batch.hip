@@ -257,6 +257,10 @@ static int alignBatch(const gc::Switches& sw, const gc_graph* G, const gc_seeder
 		// (src/Aligner.cpp:904): with a cut-off set the traces are made whatever chain_traces says
 		gc_params effective = *P;
 		if (effective.chain_traces == 0 && effective.e_cutoff >= 0 && effective.stitch && effective.edit_distances) effective.chain_traces = 1;
+		// coverage (gc_stream_set_coverage) counts the chained winners from their traces: the winners' traces are made whatever chain_traces says
+		if (st->coverage && effective.device_output && effective.chain_traces == 0 && effective.stitch && effective.edit_distances) effective.chain_traces = 1;
+		if (st->coverage && effective.device_output && (st->coverage->device != st->device || st->coverage->nIds != G->hOrigSize.size()))
+			throw std::runtime_error("the stream's coverage handle was made on another device or for another graph");
 		BatchRun batch(sw, G, S, H, st, R, &effective, clip, res, tCall, cpuCall);
 		batch.run();
 		return (int)GC_OK;

@@ -694,8 +694,26 @@ struct EditDistanceRun {
 	~EditDistanceRun() { for (auto& q : streams) if (q) (void)hipStreamDestroy(q); if (ready) (void)hipEventDestroy(ready); }
 };
 
+// Coverage accumulators (gc_coverage_*; hip/gc_coverage.hip): they live across batches, across the streams set to the handle and, merged, across devices
+struct gc_coverage {
+	int device = 0;
+	uint32_t nIds = 0;                 // bigraph node ids of the graph it was made for
+	std::vector<uint64_t> segStart;    // [segments + 1] first forward base of every segment: the graph's shape as gc_coverage_merge compares it
+	CovGraph dev {};
+	OutNames names {};                 // the graph's (it must outlive the handle)
+	const gc_graph* graph = nullptr;
+	unsigned long long* dBases = nullptr;   // [segments]
+	uint32_t* dDepth = nullptr;             // [forward bases], only with per_base
+	uint32_t* dBad = nullptr;               // flag word: 1 a cell outside the graph was met (and not counted), 2 the finish step's runs did not pair up
+	void* dSegStart = nullptr;
+	~gc_coverage() { for (void* p : { (void*)dBases, (void*)dDepth, (void*)dBad, dSegStart }) if (p) (void)hipFree(p); }
+};
+
 struct gc_stream {
 	std::vector<ReadGlue> glue;   // per-read host records of the batch in flight (storage reused)
+	gc_coverage* coverage = nullptr;   // gc_stream_set_coverage: the batches of this stream with device_output != 0 are counted into it
+	DeviceBuffer covKeep, covCells, covJobs;   // a batch's keep bytes over its output jobs; the chained winners' cells and jobs
+	PinnedBuffer hCovKeep, hCovCells, hCovJobs;
 	int device = 0;             // the device the stream was created on; gc_align_batch selects it for the calling thread
 	hipStream_t stream = nullptr;
 	hipEvent_t ev[12] {};

@@ -1,0 +1,257 @@
+// Coverage of the graph by the final alignments (gc_coverage; --coverage-out / --base-coverage-out). This build's own: the reference stops at one record per alignment,
+// and the first thing done with those records is to count how often every segment and every base was aligned to. The counts need only what is already in HBM - the final
+// alignments' trace cells - so they are taken there, a fourth reading of the cells the GAF / vg encoder (gc_output.hip) and the corrected reads (gc_corrected.hip) walk.
+// Unlike those, the result outlives the batch: bases[segment] (64 bits) and depth[forward base] (32 bits, optional) belong to a gc_coverage handle that every batch of
+// every stream set to it adds into, with atomics. The sums are integers: the order of the atomics does not show in them.
+//
+// k_cov_add: one wave per alignment, 64 cells per step, the cell before the chunk carried in registers. covCovers (gc_coverage_core.hpp) from a lane's own cell and
+// its predecessor's; one ballot of the covering lanes, one of the lanes that open a run of the same segment; the opening lane adds the run's length to bases[segment];
+// with depth on every covering lane adds 1 to its word (neighbouring lanes, neighbouring words, except across a strand flip where they run the other way).
+// A cell outside the graph is not counted and raises *bad (the batch's own cells never are; a caller's traces are checked on the host before they get here).
+// Measured alternative for the depth (difference marks at run ends + a segmented scan in the finish step): see DESIGN.md §10.
+//
+// The finish step spells both tables on the device, as the GAF encoder spells its text: per segment / per run a line length, a scan, the lines. The runs of the base table
+// (maximal stretches of equal non-zero depth inside a segment) are found per tile of 2048 bases: starts and ends counted, scanned over the tiles, then placed.
+#include "gc_kernels.hpp"
+#include "gc_coverage_core.hpp"
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <cstdlib>
+#include <cstring>
+
+namespace gcdev {
+
+namespace {
+
+constexpr uint32_t COV_TILE_THREADS = 256, COV_TILE_ITEMS = 8, COV_TILE = COV_TILE_THREADS * COV_TILE_ITEMS;
+
+__global__ void __launch_bounds__(64) k_cov_add(CovGraph g, const OutJob* __restrict__ jobs, uint32_t nJobs, const uint8_t* __restrict__ keep, const LongCell* __restrict__ cellPool,
+	unsigned long long* __restrict__ bases, uint32_t* __restrict__ depth, uint32_t* __restrict__ bad)
+{
+	const uint32_t j = blockIdx.x, lane = threadIdx.x;
+	if (j >= nJobs || (keep && !keep[j])) return;
+	const uint32_t n = jobs[j].cellLen;
+	if (n == 0) return;
+	const LongCell* cells = cellPool + jobs[j].cellOff;
+	int32_t carryNode = 0; uint32_t carryOffset = 0;   // the cell before this chunk's first
+	for (uint32_t base = 0; base < n; base += 64) {
+		const uint32_t pos = base + lane;
+		const bool valid = pos < n;
+		const uint32_t nValid = n - base < 64 ? n - base : 64;
+		const LongCell c = cells[valid ? pos : n - 1];
+		int32_t pNode = __shfl_up(c.node, 1); uint32_t pOffset = __shfl_up(c.offset, 1);
+		if (lane == 0) { pNode = carryNode; pOffset = carryOffset; }
+		bool covers = valid && covCovers(pos == 0, pNode, pOffset, c.node, c.offset);
+		uint32_t seg = 0; uint64_t at = 0;
+		if (covers) {
+			// bounds before anything is indexed with what the cell says
+			bool ok = c.node >= 0 && (uint32_t)c.node < g.nIds;
+			if (ok) {
+				seg = covSegment(c.node);
+				const uint64_t s0 = g.segStart[seg], len = g.segStart[seg + 1] - s0;
+				ok = c.offset < len;
+				if (ok) at = s0 + covForward(c.node, c.offset, (uint32_t)len);
+			}
+			if (!ok) { covers = false; atomicOr(bad, 1u); }
+		}
+		const uint64_t coverMask = __ballot(covers);
+		const uint32_t prevSeg = __shfl(seg, (int)covPrevCovering(coverMask, lane));
+		const bool opens = covOpens(coverMask, lane, seg, prevSeg);
+		const uint64_t openMask = __ballot(opens);
+		if (opens) atomicAdd(bases + seg, (unsigned long long)covRunLength(coverMask, openMask, lane));
+		if (depth && covers && atomicAdd(depth + at, 1u) == 0xffffffffu) atomicExch(depth + at, 0xffffffffu);   // a full word stays full: whoever wraps it puts it back, and the last of any interleaving is such a store
+		carryNode = __shfl(c.node, (int)nValid - 1); carryOffset = __shfl(c.offset, (int)nValid - 1);
+	}
+}
+
+__global__ void __launch_bounds__(256) k_cov_merge(unsigned long long* __restrict__ dstBases, const unsigned long long* __restrict__ srcBases, uint64_t nSegments,
+	uint32_t* __restrict__ dstDepth, const uint32_t* __restrict__ srcDepth, uint64_t nDepth)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	for (uint64_t i = first; i < nSegments; i += stride) dstBases[i] += srcBases[i];
+	for (uint64_t i = first; i < nDepth; i += stride) dstDepth[i] = covSatAdd(dstDepth[i], srcDepth[i]);
+}
+
+// ---- the segment table
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_cov_segments(CovGraph g, OutNames names, const unsigned long long* __restrict__ bases, uint32_t* __restrict__ lens, const uint64_t* __restrict__ off, char* __restrict__ text)
+{
+	const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (s > g.nSegments) return;
+	if (s == g.nSegments) { if (!WRITE) lens[s] = 0; return; }   // (the scan's last entry is the total)
+	const uint32_t id = (uint32_t)(2 * s);
+	const uint32_t nameLen = names.nameOff[id + 1] - names.nameOff[id];
+	const uint64_t length = g.segStart[s + 1] - g.segStart[s];
+	if (!WRITE) lens[s] = covSegmentLineLen(nameLen, s, length, bases[s]);
+	else covSegmentLine(text + off[s], names.nameBytes + names.nameOff[id], nameLen, s, length, bases[s]);
+}
+
+// ---- the base table: runs per tile
+// One thread, COV_TILE_ITEMS consecutive bases: visit(i, starts, ends)
+template <typename F>
+__device__ __forceinline__ void covWalk(const CovGraph& g, const uint32_t* __restrict__ depth, uint64_t first, F&& visit)
+{
+	if (first >= g.nBases) return;
+	uint64_t s = covSegmentOfBase(g.segStart, g.nSegments, first);
+	uint64_t segBegin = g.segStart[s], segEnd = g.segStart[s + 1];
+	uint32_t left = first > 0 ? depth[first - 1] : 0, here = depth[first];
+	for (uint32_t k = 0; k < COV_TILE_ITEMS; k++) {
+		const uint64_t i = first + k;
+		if (i >= g.nBases) break;
+		while (i >= segEnd) { s++; segBegin = segEnd; segEnd = g.segStart[s + 1]; }   // (empty segments are stepped over)
+		const uint32_t right = i + 1 < g.nBases ? depth[i + 1] : 0;
+		visit(i, covRunStarts(i == segBegin, left, here), covRunEnds(i + 1 == segEnd, here, right));
+		left = here; here = right;
+	}
+}
+
+template <bool PLACE>
+__global__ void __launch_bounds__(COV_TILE_THREADS) k_cov_tiles(CovGraph g, const uint32_t* __restrict__ depth, uint64_t nTiles, uint32_t* __restrict__ tileStarts, uint32_t* __restrict__ tileEnds,
+	const uint64_t* __restrict__ tileStartOff, const uint64_t* __restrict__ tileEndOff, uint64_t* __restrict__ runStart, uint64_t* __restrict__ runEnd)
+{
+	using Scan = hipcub::BlockScan<uint32_t, COV_TILE_THREADS>;
+	__shared__ typename Scan::TempStorage tmpA, tmpB;
+	const uint64_t tile = blockIdx.x;
+	const uint64_t first = tile * COV_TILE + (uint64_t)threadIdx.x * COV_TILE_ITEMS;
+	uint32_t nStarts = 0, nEnds = 0;
+	covWalk(g, depth, first, [&](uint64_t, bool st, bool en) { nStarts += st; nEnds += en; });
+	uint32_t startsBefore = 0, endsBefore = 0, startsAll = 0, endsAll = 0;
+	Scan(tmpA).ExclusiveSum(nStarts, startsBefore, startsAll);
+	Scan(tmpB).ExclusiveSum(nEnds, endsBefore, endsAll);
+	if (!PLACE) {
+		if (threadIdx.x == 0) { tileStarts[tile] = startsAll; tileEnds[tile] = endsAll; if (tile == 0) { tileStarts[nTiles] = 0; tileEnds[nTiles] = 0; } }
+		return;
+	}
+	uint64_t sAt = tileStartOff[tile] + startsBefore, eAt = tileEndOff[tile] + endsBefore;
+	covWalk(g, depth, first, [&](uint64_t i, bool st, bool en) { if (st) runStart[sAt++] = i; if (en) runEnd[eAt++] = i + 1; });
+}
+
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_cov_runs(CovGraph g, OutNames names, const uint32_t* __restrict__ depth, const uint64_t* __restrict__ runStart, const uint64_t* __restrict__ runEnd, uint64_t nRuns,
+	uint32_t* __restrict__ lens, const uint64_t* __restrict__ off, char* __restrict__ text, uint32_t* __restrict__ bad)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r > nRuns) return;
+	if (r == nRuns) { if (!WRITE) lens[r] = 0; return; }
+	const uint64_t b = runStart[r], e = runEnd[r];
+	const uint64_t s = covSegmentOfBase(g.segStart, g.nSegments, b);
+	const uint64_t s0 = g.segStart[s];
+	const uint32_t id = (uint32_t)(2 * s);
+	const uint32_t nameLen = names.nameOff[id + 1] - names.nameOff[id];
+	if (!WRITE) {
+		if (e <= b || e > g.segStart[s + 1]) atomicOr(bad, 2u);   // the k-th start and the k-th end belong to one run inside one segment
+		lens[r] = covRunLineLen(nameLen, s, b - s0, e - s0, depth[b]);
+	} else covRunLine(text + off[r], names.nameBytes + names.nameOff[id], nameLen, s, b - s0, e - s0, depth[b]);
+}
+
+struct Scratch {   // device memory of one finish call
+	void* p = nullptr;
+	hipError_t get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+	~Scratch() { if (p) (void)hipFree(p); }
+};
+#define COV_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+
+// exclusive sums of n 32-bit counts as 64-bit offsets
+hipError_t scanCounts(hipStream_t q, const uint32_t* counts, uint64_t* off, uint64_t n)
+{
+	using Widen = hipcub::TransformInputIterator<uint64_t, hipcub::CastOp<uint64_t>, const uint32_t*>;
+	size_t bytes = 0;
+	COV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, Widen(counts, hipcub::CastOp<uint64_t>()), off, (int)n, q));
+	Scratch tmp;
+	COV_TRY(tmp.get(bytes));
+	COV_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, Widen(counts, hipcub::CastOp<uint64_t>()), off, (int)n, q));
+	return hipStreamSynchronize(q);   // (tmp goes when this returns)
+}
+
+// the text and the line offsets down: *text malloc'd (head + the device's bytes, NUL-terminated), *lineOff malloc'd [nLines + 1 (+ 1 with a head line)]
+hipError_t bringDown(hipStream_t q, const char* head, const char* dText, uint64_t total, const uint64_t* dOff, uint64_t nLines, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLinesOut)
+{
+	const uint64_t h = head ? strlen(head) : 0, extra = head ? 1 : 0;
+	char* t = (char*)malloc(h + total + 1);
+	uint64_t* o = (uint64_t*)malloc((nLines + 1 + extra) * sizeof(uint64_t));
+	if (!t || !o) { free(t); free(o); return hipErrorOutOfMemory; }
+	if (h) memcpy(t, head, h);
+	hipError_t e = total ? hipMemcpyAsync(t + h, dText, total, hipMemcpyDeviceToHost, q) : hipSuccess;
+	if (e == hipSuccess) e = hipMemcpyAsync(o + extra, dOff, (nLines + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, q);
+	if (e == hipSuccess) e = hipStreamSynchronize(q);
+	if (e != hipSuccess) { free(t); free(o); return e; }
+	if (extra) { o[0] = 0; for (uint64_t i = 1; i <= nLines + 1; i++) o[i] += h; }
+	t[h + total] = 0;
+	*text = t; *len = h + total; *lineOff = o; *nLinesOut = nLines + extra;
+	return hipSuccess;
+}
+
+} // namespace
+
+void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad)
+{
+	if (!nJobs) return;
+	hipLaunchKernelGGL(k_cov_add, dim3(nJobs), dim3(64), 0, stream, g, jobs, nJobs, keep, cellPool, bases, depth, bad);
+}
+
+void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth)
+{
+	const uint64_t most = nSegments > nDepth ? nSegments : nDepth;
+	if (!most) return;
+	const uint64_t blocks = (most + 255) / 256;
+	hipLaunchKernelGGL(k_cov_merge, dim3((uint32_t)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, dstBases, srcBases, nSegments, dstDepth, srcDepth, nDepth);
+}
+
+hipError_t coverageFormatSegments(hipStream_t q, const CovGraph& g, const OutNames& names, const unsigned long long* bases, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
+{
+	const uint64_t n = g.nSegments;
+	if (n + 1 >= 0x7fffffffull) return hipErrorInvalidValue;
+	Scratch lens, off, out;
+	COV_TRY(lens.get((n + 1) * sizeof(uint32_t)));
+	COV_TRY(off.get((n + 1) * sizeof(uint64_t)));
+	const dim3 grid((uint32_t)((n + 1 + 255) / 256));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_segments<false>), grid, dim3(256), 0, q, g, names, bases, (uint32_t*)lens.p, (const uint64_t*)nullptr, (char*)nullptr);
+	COV_TRY(scanCounts(q, (const uint32_t*)lens.p, (uint64_t*)off.p, n + 1));
+	uint64_t total = 0;
+	COV_TRY(hipMemcpyAsync(&total, (uint64_t*)off.p + n, sizeof total, hipMemcpyDeviceToHost, q));
+	COV_TRY(hipStreamSynchronize(q));
+	COV_TRY(out.get(total));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_segments<true>), grid, dim3(256), 0, q, g, names, bases, (uint32_t*)nullptr, (const uint64_t*)off.p, (char*)out.p);
+	COV_TRY(hipGetLastError());
+	return bringDown(q, "#segment\tlength\tbases\n", (const char*)out.p, total, (const uint64_t*)off.p, n, text, len, lineOff, nLines);
+}
+
+hipError_t coverageFormatBases(hipStream_t q, const CovGraph& g, const OutNames& names, const uint32_t* depth, uint32_t* bad, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
+{
+	const uint64_t nTiles = (g.nBases + COV_TILE - 1) / COV_TILE;
+	if (nTiles + 1 >= 0x7fffffffull) return hipErrorInvalidValue;
+	Scratch counts, offs, runs, lens, off, out;
+	COV_TRY(counts.get(2 * (nTiles + 1) * sizeof(uint32_t)));
+	COV_TRY(offs.get(2 * (nTiles + 1) * sizeof(uint64_t)));
+	uint32_t* tileStarts = (uint32_t*)counts.p; uint32_t* tileEnds = tileStarts + nTiles + 1;
+	uint64_t* tileStartOff = (uint64_t*)offs.p; uint64_t* tileEndOff = tileStartOff + nTiles + 1;
+	uint64_t nRuns = 0, nRunEnds = 0;
+	if (nTiles) {
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_tiles<false>), dim3((uint32_t)nTiles), dim3(COV_TILE_THREADS), 0, q, g, depth, nTiles, tileStarts, tileEnds, (const uint64_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
+		COV_TRY(scanCounts(q, tileStarts, tileStartOff, nTiles + 1));
+		COV_TRY(scanCounts(q, tileEnds, tileEndOff, nTiles + 1));
+		COV_TRY(hipMemcpyAsync(&nRuns, tileStartOff + nTiles, sizeof nRuns, hipMemcpyDeviceToHost, q));
+		COV_TRY(hipMemcpyAsync(&nRunEnds, tileEndOff + nTiles, sizeof nRunEnds, hipMemcpyDeviceToHost, q));
+		COV_TRY(hipStreamSynchronize(q));
+	}
+	if (nRuns != nRunEnds || nRuns + 1 >= 0x7fffffffull) return hipErrorInvalidValue;   // (as many ends as starts; hipCUB counts in int)
+	COV_TRY(runs.get(2 * nRuns * sizeof(uint64_t)));
+	uint64_t* runStart = (uint64_t*)runs.p; uint64_t* runEnd = runStart + nRuns;
+	if (nRuns) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_tiles<true>), dim3((uint32_t)nTiles), dim3(COV_TILE_THREADS), 0, q, g, depth, nTiles, (uint32_t*)nullptr, (uint32_t*)nullptr, (const uint64_t*)tileStartOff, (const uint64_t*)tileEndOff, runStart, runEnd);
+	COV_TRY(lens.get((nRuns + 1) * sizeof(uint32_t)));
+	COV_TRY(off.get((nRuns + 1) * sizeof(uint64_t)));
+	const dim3 grid((uint32_t)((nRuns + 1 + 255) / 256));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_runs<false>), grid, dim3(256), 0, q, g, names, depth, (const uint64_t*)runStart, (const uint64_t*)runEnd, nRuns, (uint32_t*)lens.p, (const uint64_t*)nullptr, (char*)nullptr, bad);
+	COV_TRY(scanCounts(q, (const uint32_t*)lens.p, (uint64_t*)off.p, nRuns + 1));
+	uint64_t total = 0; uint32_t flags = 0;
+	COV_TRY(hipMemcpyAsync(&total, (uint64_t*)off.p + nRuns, sizeof total, hipMemcpyDeviceToHost, q));
+	COV_TRY(hipMemcpyAsync(&flags, bad, sizeof flags, hipMemcpyDeviceToHost, q));
+	COV_TRY(hipStreamSynchronize(q));
+	if (flags & 2u) return hipErrorInvalidValue;   // starts and ends did not pair up: nothing is written from them
+	COV_TRY(out.get(total));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_runs<true>), grid, dim3(256), 0, q, g, names, depth, (const uint64_t*)runStart, (const uint64_t*)runEnd, nRuns, (uint32_t*)nullptr, (const uint64_t*)off.p, (char*)out.p, bad);
+	COV_TRY(hipGetLastError());
+	return bringDown(q, nullptr, (const char*)out.p, total, (const uint64_t*)off.p, nRuns, text, len, lineOff, nLines);
+}
+
+} // namespace gcdev

@@ -337,6 +337,17 @@ void launchOutWrite(hipStream_t stream, const DGraph& g, const OutNames& names, 
 // the writing pass fills text and sets lens[j] = ~0u where it did not land on the counted size
 void launchCorrectedCount(hipStream_t stream, const DGraph& g, const OutJob* jobs, uint32_t nJobs, const LongCell* cellPool, uint32_t* lens, uint64_t* offsets, unsigned long long* total);
 void launchCorrectedWrite(hipStream_t stream, const DGraph& g, const OutJob* jobs, uint32_t nJobs, const LongCell* cellPool, uint32_t* lens, const uint64_t* offsets, char* text);
+// ---- coverage (gc_coverage.hip; gc_coverage_*): how often every segment and every forward base is under a covering cell of a final alignment (gc_coverage_core.hpp has the rule)
+struct CovGraph { const uint64_t* segStart; uint64_t nSegments, nBases; uint32_t nIds; };   // segStart[nSegments + 1]: first forward base of segment id / 2 in `depth`; nIds: bigraph node ids
+// bases[nSegments] += covering cells per segment, depth[nBases] += 1 per covering cell (depth may be null); of an OutJob only cellOff / cellLen are read; keep (may be null): jobs with
+// keep[j] == 0 are skipped; *bad |= 1 where a cell lies outside the graph (it is not counted)
+void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad);
+// dst += src (depth saturating at 2^32 - 1); both on the stream's device, nothing else adding into them meanwhile
+void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth);
+// The two tables spelled on the device; they wait for the stream where a total comes back. *text: malloc'd, NUL-terminated, *len bytes; *lineOff: malloc'd [*nLines + 1] byte offsets
+// of the lines (the segment table's head line included). bad: the handle's flag word (bit 1: the run starts and ends did not pair up - nothing is written then)
+hipError_t coverageFormatSegments(hipStream_t stream, const CovGraph& g, const OutNames& names, const unsigned long long* bases, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
+hipError_t coverageFormatBases(hipStream_t stream, const CovGraph& g, const OutNames& names, const uint32_t* depth, uint32_t* bad, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
 // ---- DEFLATE of independent byte streams (gc_deflate.hip): one dynamic-Huffman block of literals per stream (stored blocks where that is smaller or the code
 // would be deeper than 15 bits). plan[s] = { deflate bytes, mode }, lens[260 * s + symbol]; the caller places stream s at a 4-byte aligned outOff[s] with room for plan[s].x rounded up to 4
 void launchDeflatePlan(hipStream_t stream, const uint8_t* raw, const uint64_t* rawOff, uint32_t nStreams, uint8_t* lens, uint2* plan);

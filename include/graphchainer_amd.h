@@ -650,6 +650,41 @@ int gc_format_corrected_trace(const gc_graph* g, const int32_t* node, const uint
 int gc_corrected_pieces(const gc_graph* g, const int32_t* node, const uint32_t* offset, const uint8_t* node_switch, const uint64_t* trace_off, uint64_t n_aln,
                         char** out_text, uint64_t** out_off);
 
+/* Coverage: how often every segment and every base of the graph lies under a final alignment (--coverage-out / --base-coverage-out). This library's own; the reference has
+ * no counterpart, so the meaning is defined here. The alignments counted are the entries of gc_result::out_* - the set and order of the GAF lines: the chained alignment where
+ * it won, otherwise the selected whole-read alignments; flagged reads count nothing. Each is a trace of cells (node, offset) in output coordinates. Cell i covers the graph
+ * base under it iff i == 0 or (node, offset) differs from cell i-1's: insertions cover nothing, matches, mismatches and deletions one base each. The base is reported on
+ * segment node / 2 (the internal segment number: the order in which the GFA first names them) in forward coordinates: offset for an even id, length - 1 - offset for an odd one.
+ * depth[segment][pos] = covering cells over all counted alignments, bases[segment] = the sum of its depth. This is what the vg JSON of the same run shows: every mapping
+ * covers [position.offset, position.offset + sum of from_length) of its node in its orientation.
+ * The accumulators live on the device the handle was created on (the current one) and across batches: bases is 8 bytes per segment; depth, only with per_base != 0, 4 bytes per
+ * forward base (gc_graph_size_bp / 2: 20 MB at 5 Mbp, 12.4 GB at 3.1 Gbp) - when that does not fit, GC_ERR_DEVICE and gc_last_error says how much was asked for. A host sizing
+ * its batches by gc_device_memory creates the handle first. All counts are integers added with atomics: they do not depend on the order of the batches or of anything inside one.
+ * Limit: a depth word holds 2^32 - 1 and stays there once it is reached, in a batch's additions and in gc_coverage_merge.
+ * The graph must outlive the handle. */
+typedef struct gc_coverage gc_coverage;
+int gc_coverage_create(const gc_graph* g, int per_base, gc_coverage** out);
+void gc_coverage_destroy(gc_coverage* cov);
+/* From now on every batch aligned on the stream with device_output != 0 (which needs long_pass and edit_distances) is counted into cov before its call returns: a finished batch is
+ * a counted batch. The winners' traces are made for it whatever chain_traces says. NULL turns it off. Several streams of one device may share a handle - that is the batches in
+ * flight; the handle must live on the stream's device (GC_ERR_INVALID) and outlive its use. */
+int gc_stream_set_coverage(gc_stream* stream, gc_coverage* cov);
+/* The same kernel over a caller's own traces (a host that keeps its traces; the tests, which need exact shapes): alignment a is cells trace_off[a] .. trace_off[a+1] of
+ * node / offset. Every (node, offset) is checked against the graph first (GC_ERR_INVALID, nothing counted). Returns when the counts are in. */
+int gc_coverage_add_traces(gc_coverage* cov, const int32_t* node, const uint32_t* offset, const uint64_t* trace_off, uint64_t n_aln);
+/* The counts as they stand: *bases malloc'd [*n_segments]; *depth malloc'd [*n_bases], segment after segment in forward coordinates, or NULL without per_base. Free with gc_free.
+ * This and the calls below read the accumulators: no batch may be in flight on a stream set to the handle. */
+int gc_coverage_counts(gc_coverage* cov, uint64_t** bases, uint64_t* n_segments, uint32_t** depth, uint64_t* n_bases);
+/* dst += src. One device or two (two go through the host, the depth in slices). Handles for graphs of different shape, or only one of them per_base: GC_ERR_INVALID. */
+int gc_coverage_merge(gc_coverage* dst, const gc_coverage* src);
+/* The two tables, spelled on the device; only text comes down. Segments: "#segment\tlength\tbases\n", then one line per segment, zero rows included, in ascending segment number;
+ * the name is the GFA's, or the number where that is empty, as the GAF path prints it. Bases (per_base handles): "segment\tstart\tend\tdepth\n" without a head line, 0-based
+ * half-open forward coordinates, one line per maximal run of equal non-zero depth inside one segment, segments ascending, runs ascending within a segment.
+ * *text malloc'd, NUL-terminated, *len bytes; *line_off (may be NULL) malloc'd [*n_lines + 1] byte offsets of the lines, the head line counted, for a host that compresses
+ * the text in pieces of whole lines. Free both with gc_free. */
+int gc_coverage_format_segments(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
+int gc_coverage_format_bases(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
+
 /* gc_format_gam with the zlib level of the gzip members chosen by the caller (-1 = Z_DEFAULT_COMPRESSION, what the reference's GzipOutputStream uses and gc_format_gam
  * gives; 0..9). The inflated stream is the same at every level; deflate at the default level costs ~1 ms of CPU per 10 kb read - more than the whole alignment costs the
  * GPU - so a host that writes GAM at the hot path's rate wants level 1 (or its own compressor on the bytes of level 0), or GC_GAM_DEVICE_HUFFMAN: the members are then
