@@ -79,7 +79,7 @@
 			HIP_CHECK(hipMemsetAsync(dLongCursor, 0, cursorWords * sizeof(unsigned long long), ls));
 			if (n) HIP_CHECK(hipMemcpyAsync(dLongJobs, hJobs, n * sizeof(LongJob), hipMemcpyHostToDevice, ls));
 			syncStream(ls);   // the round stream starts from uploaded inputs
-			// rounds: select -> extend -> merge until no read has a seed left to extend (see gc_kernels.hip, "K3-long in rounds")
+			// rounds: select -> extend -> merge until no read has a seed left to extend (see gc_long_rounds.hip, "K3-long in rounds")
 			dLongState = st->longState.reserve<LongState>(n);
 			workCapacity = 8 * n + 64;
 			dLongWork = st->longWork.reserve<LongWork>(workCapacity);
@@ -176,7 +176,7 @@
 		return true;
 	}
 
-	void runLongRounds()   // the round loop: select -> extend -> merge until no read has a seed left to extend (see gc_kernels.hip, "K3-long in rounds")
+	void runLongRounds()   // the round loop: select -> extend -> merge until no read has a seed left to extend (see gc_long_rounds.hip, "K3-long in rounds")
 	{
 		if (n == 0) return;
 		unsigned long long* dLongScratch = nullptr;   // (set when the token is taken - before the first extension launch)

@@ -187,7 +187,7 @@ static void uploadSeeder(gc_seeder* S, std::optional<uint32_t> filterBitsOverrid
 	}
 	uint64_t* dTable = uploadVector(table);
 	S->allocations.push_back(dTable);
-	// membership filter in front of the table (see filterBit in gc_kernels.hip): ~8 bits per key, at most 2^28 bits; on cfg2 (5 M keys)
+	// membership filter in front of the table (see filterBit in gc_seedlookup.hip): ~8 bits per key, at most 2^28 bits; on cfg2 (5 M keys)
 	// 2^25 bits = 4 MB, which stays in every XCD's L2 (a 32 MB filter missed to the fabric on every probe)
 	uint32_t filterBits = 20;
 	while (filterBits < 28 && (1ull << filterBits) < 8 * nKeys) filterBits++;

@@ -103,6 +103,14 @@ __device__ __forceinline__ EdgeRange recInRange(const DGraph& g, uint32_t node, 
 }
 __device__ __forceinline__ uint32_t gcOutAdj(const DGraph& g, uint32_t e) { return gcK(g.outAdj + e); }
 __device__ __forceinline__ uint32_t gcInAdj(const DGraph& g, uint32_t e) { return gcK(g.inAdj + e); }
+// reverse-strand twin of (split node, offset): GetReversePosition + GetUnitigNode (src/AlignmentGraph.cpp:832-868)
+__device__ __forceinline__ void twinOf(const DGraph& g, uint32_t node, uint32_t offset, uint32_t& twinNode, uint32_t& twinOffset)
+{
+	const int32_t id = g.nodeIDs[node];
+	const uint32_t rev = g.origSize[id] - 1 - (g.nodeOffset[node] + offset);
+	twinNode = g.lookup[g.lookupOff[id ^ 1] + rev / 64];
+	twinOffset = rev - g.nodeOffset[twinNode];
+}
 
 struct WS {   // one DP column over 64 read rows (reference: src/WordSlice.h:150-166)
 	uint64_t VP, VN;
@@ -297,6 +305,19 @@ struct LaneScratch {
 	TraceCell* trace;
 	uint32_t* itemNodes; // the items' node ids again, packed (r4): "is this node in that slice" scans 4 B per item instead of pulling a 64 B item record per probe
 };
+__device__ __forceinline__ LaneScratch laneScratch(uint8_t* slab, const ExtendConfig& cfg)
+{
+	LaneScratch sc;
+	uint8_t* p = slab;
+	sc.slices = (SliceInfo*)p;   p += sizeof(SliceInfo) * cfg.maxSlices;
+	sc.items = (NodeItem*)p;     p += sizeof(NodeItem) * cfg.maxItems;
+	sc.pending = (Pending*)p;    p += sizeof(Pending) * cfg.maxPending;
+	sc.columns = (WCol*)p;       p += sizeof(WCol) * 64;
+	sc.colMask = 63; sc.colStride = 1;
+	sc.trace = (TraceCell*)p;    p += sizeof(TraceCell) * cfg.maxTrace;
+	sc.itemNodes = (uint32_t*)p;
+	return sc;
+}
 
 struct ExtCounters {
 	// 32-bit: they are per lane (per wave in the whole-read kernel) and flushed with one 64-bit atomic each at the kernel's end; in the

@@ -1,7 +1,7 @@
 // K3 (r6) - fragment seed extension: one extension per lane, the lanes of a wave in lockstep phases (the core and the reasons: gc_frag_core.hpp).
 // reference: GraphAlignerBitvectorBanded::getReverseTraceFromSeed, src/GraphAlignerBitvectorBanded.h:46-71, called per seed and direction from
 // src/GraphAligner.h:499-511. What this kernel declines (EXT_OVERFLOW: more than 64 rows, an ambiguous graph node, more pending nodes / tiles than its tables hold)
-// is rerun by the plain-layout kernel k_extend_slab (gc_kernels.hip) right behind it.
+// is rerun by the plain-layout kernel k_extend_slab (gc_extend_slab.hip) right behind it.
 #include "gc_kernels.hpp"
 #include "gc_frag_core.hpp"
 

@@ -19,7 +19,7 @@
 // lane-interleaved region of HBM (coalesced 16 B per lane); trace cells are written straight into the shared trace pool (the room an extension needs is bounded
 // by rows + 1 + score before its walk starts). The graph is read through one 32-byte record per node (NodeRec).
 //
-// The file is plain C++ over a memory policy M: the kernel instantiates it with LDS / HBM accessors (gc_kernels.hip), tests/frag_host/frag_host_test.cpp with
+// The file is plain C++ over a memory policy M: the kernel instantiates it with LDS / HBM accessors (gc_extend_frag.hip), tests/frag_host/frag_host_test.cpp with
 // arrays and drives single lanes on the CPU against the oracle.
 #pragma once
 #include "gc_device.hpp"

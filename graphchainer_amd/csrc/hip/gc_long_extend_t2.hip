@@ -1,0 +1,3 @@
+// k_long_extend for teams of 2 lanes per wave: plain, band controls, band controls + clipping, each persistent or not
+#include "gc_long_extend.hpp"
+GC_LONG_EXTEND_TEAM(2)

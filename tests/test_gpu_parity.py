@@ -270,7 +270,8 @@ def test_whole_read_assertion_drops_the_read(gca, tmp_path, monkeypatch):
     assert got["chained_better"][3] == 0 and got["chain_edit_distance"][3] == -1 and got["long_edit_distance"][3] == -1
 
 
-@pytest.mark.parametrize("env", [{"GC_TEST_LONG_TEAM": "8"}, {"GC_TEST_LONG_TEAM": "64", "GC_TEST_LONG_ORDER": "0"}, {"GC_TEST_LONG_MAX_BLOCKS": "7"}, {"GC_TEST_LONG_MAX_BLOCKS": "3", "GC_TEST_LONG_TEAM": "4"}, {"GC_TEST_LONG_REG_CAP": "3"}, {"GC_TEST_LONG_REG_CAP": "6", "GC_TEST_LONG_MAX_BLOCKS": "5"}])
+@pytest.mark.parametrize("env", [{"GC_TEST_LONG_TEAM": "8"}, {"GC_TEST_LONG_TEAM": "64", "GC_TEST_LONG_ORDER": "0"}, {"GC_TEST_LONG_MAX_BLOCKS": "7"}, {"GC_TEST_LONG_MAX_BLOCKS": "3", "GC_TEST_LONG_TEAM": "4"}, {"GC_TEST_LONG_REG_CAP": "3"}, {"GC_TEST_LONG_REG_CAP": "6", "GC_TEST_LONG_MAX_BLOCKS": "5"},
+                                 {"GC_TEST_LONG_TEAM": "2"}, {"GC_TEST_LONG_TEAM": "16"}, {"GC_TEST_LONG_TEAM": "32"}])
 def test_whole_read_pass_launch_shapes(gca, tmp_path, monkeypatch, env):
     """Launch-shape knobs of the whole-read pass (concurrent read groups, lanes per wave, execution order, persistent waves, register-table cap -> LDS-table retry) never change results."""
     from graphchainer_amd.synth import SynthGraph

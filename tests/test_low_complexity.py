@@ -23,7 +23,7 @@ CSRC = os.path.join(ROOT, "graphchainer_amd", "csrc")
 
 def product_thresholds():
     """The capacities the tiers are placed against, read from the sources that define them (never by running the product)."""
-    kernels = open(os.path.join(CSRC, "hip", "gc_kernels.hip")).read()
+    kernels = open(os.path.join(CSRC, "hip", "gc_chain.hip")).read()
     long_pass = open(os.path.join(CSRC, "batch", "gc_batch_long.inc")).read()
     lds_anchors = int(re.search(r"#define CHAIN_LDS_ANCHORS (\d+)", kernels).group(1))
     assert "job.nSlots > 2 * LDS_ANCHORS" in kernels and "LDS == 2 ? CHAIN_LDS_ANCHORS / 2 : CHAIN_LDS_ANCHORS" in kernels
