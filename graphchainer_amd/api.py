@@ -27,10 +27,14 @@ EXPORTED_SYMBOLS = [
     "gc_format_corrected", "gc_format_corrected_trace", "gc_corrected_pieces",
     "gc_coverage_create", "gc_coverage_destroy", "gc_stream_set_coverage", "gc_coverage_add_traces", "gc_coverage_counts", "gc_coverage_merge",
     "gc_coverage_format_segments", "gc_coverage_format_bases",
+    "gc_coverage_link_counts", "gc_coverage_format_links", "gc_coverage_format_gfa_segments", "gc_coverage_format_gfa_links",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
     "gc_reads_parse", "gc_fastx_table_free", "gc_bgzf_inflate", "gc_reads_parse_bgzf", "gc_reads_parse_bam", "gc_reads_parse_bam_bgzf",
     "gc_seed_store_open", "gc_seed_store_from_memory", "gc_seed_store_info", "gc_seed_store_destroy", "gc_seeds_from_store",
 ]
+EXPORTED_SYMBOLS_NUMBERED = ["gc_coverage_create2"]   # declared in the header too; apart because tests/test_library_exports.py reads the header for names of letters and underscores only
+GC_COVERAGE_PER_BASE, GC_COVERAGE_LINKS = 1, 2
+GFA_PIECE_BYTES = 64 << 20           # Coverage.gfa_pieces / link_table: about this much text per call into the library
 
 
 class GcCapacities(C.Structure):
@@ -365,19 +369,31 @@ def corrected_pieces(graph, traces):
     return [data[int(at[i]):int(at[i + 1])] for i in range(n)]
 
 
+def _join_pieces(pieces, line_offsets):
+    """(bytes, line offsets) pieces as one text (and its line offsets)."""
+    texts, offsets, at = [], [np.zeros(1, dtype=np.uint64)], 0
+    for text, off in pieces:
+        texts.append(text)
+        offsets.append(off[1:] + np.uint64(at))
+        at += len(text)
+    data = b"".join(texts)
+    return (data, np.concatenate(offsets)) if line_offsets else data
+
+
 class Coverage:
     """How often every segment and every base of the graph lies under a final alignment (gc_coverage_*; include/graphchainer_amd.h has the meaning). The accumulators
     live on the current device, across batches: Aligner.align_batch(..., coverage=cov) or Aligner.set_coverage(cov) counts a batch's output alignments before the call
     returns, and several aligners may share one handle. per_base: also a 32-bit depth per forward base (4 bytes each on the device; RuntimeError when that does not fit).
+    links: also how often every link of the graph is walked (16 bytes per link on the device; the header has the meaning of a link and its canonical form).
     Integers added with atomics: the same reads give the same counts however they were batched."""
 
-    def __init__(self, graph, per_base=False):
+    def __init__(self, graph, per_base=False, links=False):
         self.lib = load_library()
-        self.graph, self.per_base = graph, bool(per_base)          # (the graph must outlive the handle)
+        self.graph, self.per_base, self.links = graph, bool(per_base), bool(links)          # (the graph must outlive the handle)
         self.handle = C.c_void_p()
-        self.lib.gc_coverage_create.restype = C.c_int
-        self.lib.gc_coverage_create.argtypes = [C.c_void_p, C.c_int, _P(C.c_void_p)]
-        _check(self.lib.gc_coverage_create(graph.handle, int(self.per_base), C.byref(self.handle)))
+        self.lib.gc_coverage_create2.restype = C.c_int
+        self.lib.gc_coverage_create2.argtypes = [C.c_void_p, C.c_uint, _P(C.c_void_p)]
+        _check(self.lib.gc_coverage_create2(graph.handle, (GC_COVERAGE_PER_BASE if self.per_base else 0) | (GC_COVERAGE_LINKS if self.links else 0), C.byref(self.handle)))
 
     def add_traces(self, traces):
         """Counts a list of traces, each (node, offset) in output coordinates, with the kernel the batches use (gc_coverage_add_traces); every cell is checked against the graph first."""
@@ -435,6 +451,76 @@ class Coverage:
         """The --base-coverage-out table (bytes; needs per_base): "segment\tstart\tend\tdepth" per maximal run of equal non-zero depth inside a segment."""
         data, offsets = self._table(self.lib.gc_coverage_format_bases)
         return (data, offsets) if line_offsets else data
+
+    def link_counts(self):
+        """-> (from, to [links] int32, traversals [links] uint64): the graph's links in link order, canonical bigraph ids (2 * segment + strand), and how often each was walked."""
+        src, dst, counts, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self.lib.gc_coverage_link_counts.restype = C.c_int
+        self.lib.gc_coverage_link_counts.argtypes = [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_uint64)]
+        _check(self.lib.gc_coverage_link_counts(self.handle, C.byref(src), C.byref(dst), C.byref(counts), C.byref(n)))
+        try:
+            take = lambda p, t, dtype: np.ctypeslib.as_array(C.cast(p, _P(t)), shape=(int(n.value),)).copy() if n.value else np.zeros(0, dtype=dtype)   # noqa: E731
+            return take(src, C.c_int32, np.int32), take(dst, C.c_int32, np.int32), take(counts, C.c_uint64, np.uint64)
+        finally:
+            for p in (src, dst, counts):
+                self.lib.gc_free(p)
+
+    def _rows(self, fn, first, count, *flags):
+        text, length, line_off, n_lines = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_int] * len(flags) + [_P(C.c_void_p), _P(C.c_uint64), _P(C.c_void_p), _P(C.c_uint64)]
+        _check(fn(self.handle, int(first), int(count), *[int(f) for f in flags], C.byref(text), C.byref(length), C.byref(line_off), C.byref(n_lines)))
+        try:
+            data = C.string_at(text.value, int(length.value))
+            offsets = np.ctypeslib.as_array(C.cast(line_off, _P(C.c_uint64)), shape=(int(n_lines.value) + 1,)).copy()
+        finally:
+            self.lib.gc_free(text)
+            self.lib.gc_free(line_off)
+        return data, offsets
+
+    def _n_links(self):
+        if getattr(self, "_link_total", None) is None:
+            self._link_total = len(self.link_counts()[0])
+        return self._link_total
+
+    def _segment_lengths(self):
+        """Forward length of every segment, from the graph's split nodes (what the S ranges of gfa_pieces are chosen by)."""
+        if getattr(self, "_lengths", None) is None:
+            ids, lengths = self.graph.array("nodeIDs"), self.graph.array("nodeLength")
+            per_id = np.bincount(ids, weights=lengths).astype(np.int64) if len(ids) else np.zeros(0, dtype=np.int64)
+            per_id = np.concatenate([per_id, np.zeros(len(per_id) & 1, dtype=np.int64)])
+            self._lengths = np.maximum(per_id[0::2], per_id[1::2])
+        return self._lengths
+
+    def link_pieces(self, piece_bytes=GFA_PIECE_BYTES):
+        """The --link-coverage-out table (needs links) as a generator of (bytes, byte offsets of the lines): "#from\tfrom_orient\tto\tto_orient\ttraversals", then a
+        line per link in link order, zero rows included; about piece_bytes of text per piece."""
+        n, step = self._n_links(), max(1, int(piece_bytes) // 48)
+        for first in range(0, max(n, 1), step):
+            yield self._rows(self.lib.gc_coverage_format_links, first, step)
+
+    def link_table(self, line_offsets=False, piece_bytes=GFA_PIECE_BYTES):
+        """The --link-coverage-out table (bytes; needs links), spelled on the device. line_offsets: -> (bytes, byte offsets of the lines)."""
+        return _join_pieces(self.link_pieces(piece_bytes), line_offsets)
+
+    def gfa_pieces(self, supported_only=False, piece_bytes=GFA_PIECE_BYTES):
+        """The graph as a GFA with coverage tags (--coverage-gfa-out; needs links), spelled on the device, as a generator of (bytes, byte offsets of the lines): the line
+        "H\tVN:Z:1.0", the segments "S\tname\tLETTERS\tLN:i:length\tRC:i:bases" (RC / LN = mean depth) in ranges chosen from the segment lengths so that a piece stays near
+        piece_bytes, then the links "L\tfrom\t+-\tto\t+-\t0M\tRC:i:traversals" in link order. supported_only (--supported-subgraph-out): only segments with
+        bases > 0 and links with traversals > 0."""
+        head = b"H\tVN:Z:1.0\n"
+        yield head, np.array([0, len(head)], dtype=np.uint64)
+        lengths = self._segment_lengths()
+        ends = np.cumsum(lengths + 48)                              # a line is its letters and about 48 bytes of name and tags
+        first = 0
+        while first < len(lengths):
+            before = int(ends[first - 1]) if first else 0
+            last = max(first + 1, int(np.searchsorted(ends, before + int(piece_bytes), side="right")))
+            yield self._rows(self.lib.gc_coverage_format_gfa_segments, first, last - first, supported_only)
+            first = last
+        n, step = self._n_links(), max(1, int(piece_bytes) // 48)
+        for first in range(0, n, step):
+            yield self._rows(self.lib.gc_coverage_format_gfa_links, first, step, supported_only)
 
     def close(self):
         if self.handle:

@@ -9,6 +9,8 @@ writers chosen), and a writer thread: records written in input order, every outp
 corrected reads, their pieces spelled on the device, beside -a or without it.
 --coverage-out / --base-coverage-out are this build's own: how often every segment / every base of the graph lies under an alignment the run writes, counted on the
 device while the traces are there (api.Coverage), one handle per device, merged and spelled at the end; beside -a or without it.
+--link-coverage-out / --coverage-gfa-out / --supported-subgraph-out, this build's own too, come from the same handles: how often every link of the graph is walked, as a
+table, as the graph itself with RC tags on segments and links, and as the part of the graph the alignments touch.
 
 Accepted and without effect: -t / --threads (checked >= 1), --high-memory, --verbose, --short-verbose (the progress text and the closing statistics are not
 reproduced), and --greedy-E / --greedy-score, which the reference declares and never reads. --try-all-seeds (and --all-alignments, which sets it) does what it does
@@ -46,10 +48,15 @@ OPTIONS = {
     "inflight": (None, "size", False), "devices": (None, "string", False),
     "corrected-out": (None, "string", False), "corrected-clipped-out": (None, "string", False),   # GraphAligner's: the reference keeps their mechanism and dropped the two option lines
     "coverage-out": (None, "string", False), "base-coverage-out": (None, "string", False),
+    "link-coverage-out": (None, "string", False), "coverage-gfa-out": (None, "string", False), "supported-subgraph-out": (None, "string", False),
 }
 MAX_INFLIGHT = 5                   # the most the benchmark keeps in flight on a device (bench.py: BATCH_MS_BY_INFLIGHT ends there)
 MAX_DEVICES = 16                   # the library's per-device slots
 COVERAGE_GZ_PIECE = 1 << 20         # a .gz coverage table is written as gzip members of about this many bytes of whole lines
+COVERAGE_OUTPUTS = (("coverage", "coverage-out"), ("base_coverage", "base-coverage-out"), ("link_coverage", "link-coverage-out"), ("coverage_gfa", "coverage-gfa-out"),
+                    ("supported_subgraph", "supported-subgraph-out"))          # Config.coverage key, option
+FULL_NAME_ONLY = ("coverage-gfa-out",)   # spelled out in full: the abbreviations of --coverage-out that scripts use (--cov, --coverage) were there first and keep their meaning
+LINK_OUTPUTS = ("link_coverage", "coverage_gfa", "supported_subgraph")     # these need the handles' link table
 CORRECTED_SUFFIXES = (".fa", ".fasta", ".fa.gz", ".fasta.gz")   # src/AlignerMain.cpp:360,365 (a name shorter than a suffix does not end in it; the reference's substr would throw)
 REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "generate-path", "generate-path-seed", "graph-statistics")
 SELECT = {"greedy-length": 0, "schedule-inverse-E-sum": 3, "schedule-inverse-E-product": 4, "schedule-score": 5, "schedule-length": 6, "all-alignments": 7}   # GC_SELECT_*
@@ -116,6 +123,12 @@ This build's own:
                                         number of its bases under the alignments written, each counted as often as it is covered
   --base-coverage-out arg               table "segment start end depth" (no header; 0-based, half-open, forward strand; gzipped for a .gz name): one
                                         line per stretch of equal non-zero depth. Holds 4 bytes per base of the graph on every device
+  --link-coverage-out arg               table "#from from_orient to to_orient traversals" (tab-separated; gzipped for a .gz name): for every link of the
+                                        graph how many of the alignments written walk it, on either strand. Holds 16 bytes per link on every device
+  --coverage-gfa-out arg                the graph as GFA (gzipped for a .gz name) with coverage tags: RC:i on a segment is its "bases" count of
+                                        --coverage-out (divide by LN:i for the mean depth), RC:i on a link its traversals. Letters in upper case.
+                                        The option's name is not abbreviated (--cov stays --coverage-out)
+  --supported-subgraph-out arg          the same GFA without the segments no alignment covers and the links no alignment walks
 
 Accepted and without effect: -t [ --threads ] arg (must be >= 1), --high-memory, --verbose, --short-verbose, --greedy-E, --greedy-score.
 Not supported by this build: --optimal-alignment, --seedless-DP, --DP-restart-stride, --generate-path, --generate-path-seed,
@@ -137,7 +150,7 @@ class Config:
     reads: list = field(default_factory=list)
     outputs: dict = field(default_factory=dict)          # "gaf" / "json" / "gam" -> path (the last one given of each kind, as the reference keeps it)
     corrected: dict = field(default_factory=dict)        # "corrected" / "corrected_clipped" -> path (--corrected-out / --corrected-clipped-out; a .gz name is compressed)
-    coverage: dict = field(default_factory=dict)         # "coverage" / "base_coverage" -> path (--coverage-out / --base-coverage-out; a .gz name is compressed)
+    coverage: dict = field(default_factory=dict)         # "coverage" / "base_coverage" / "link_coverage" / "coverage_gfa" / "supported_subgraph" -> path (COVERAGE_OUTPUTS; a .gz name is compressed)
     aligner: dict = field(default_factory=dict)          # keyword arguments of api.Aligner
     min_cluster_size: int = 1                            # gc_params::min_cluster_size
     seeder: dict = field(default_factory=dict)           # {"kind": "minimizer", "length", "window", "keep_fraction"}, {"kind": "mxm", "mode", "count", "min_len", "cache_prefix"} or {"kind": "file", "paths"}
@@ -188,7 +201,7 @@ def parse(argv):
         if token.startswith("--") and len(token) > 2:
             key, eq, value = token[2:].partition("=")
             if key not in OPTIONS:
-                guesses = [n for n in OPTIONS if n.startswith(key)]
+                guesses = [n for n in OPTIONS if n.startswith(key) and n not in FULL_NAME_ONLY]
                 if len(guesses) > 1:
                     fail(f"option '--{key}' is ambiguous and matches " + ", ".join(f"'--{g}'" for g in sorted(guesses)))
                 if not guesses:
@@ -309,8 +322,8 @@ def resolve(argv):
     if not cfg.reads:
         error("read file must be given")
     corrected_out, clipped_out = last("corrected-out", ""), last("corrected-clipped-out", "")
-    coverage_out, base_coverage_out = last("coverage-out", ""), last("base-coverage-out", "")
-    if not outputs and corrected_out == "" and clipped_out == "" and coverage_out == "" and base_coverage_out == "":      # src/AlignerMain.cpp:335 (this build's own outputs count as the corrected reads do)
+    coverage_outs = [(fmt, last(option, "")) for fmt, option in COVERAGE_OUTPUTS]
+    if not outputs and corrected_out == "" and clipped_out == "" and all(path == "" for _, path in coverage_outs):      # src/AlignerMain.cpp:335 (this build's own outputs count as the corrected reads do)
         error("alignments-out must be given")
     for path in outputs:
         if len(path) >= 4 and path.endswith(".gam"):
@@ -326,7 +339,7 @@ def resolve(argv):
             if not path.endswith(CORRECTED_SUFFIXES):
                 error("unknown output corrected read format, must be .fa or .fa.gz")
             cfg.corrected[fmt] = path
-    for fmt, path in (("coverage", coverage_out), ("base_coverage", base_coverage_out)):
+    for fmt, path in coverage_outs:
         if path != "":
             cfg.coverage[fmt] = path
     if cfg.threads < 1:
@@ -514,7 +527,7 @@ def _setup_replicas(cfg, api, replicas):
             elif not minimizer:
                 rep.index = api.MxmIndex(rep.graph, cache_prefix=mxm_prefix)
             if cfg.coverage:               # the accumulators of this device, here so that choose_inflight measures the free memory with them in place
-                rep.coverage = api.Coverage(rep.graph, per_base="base_coverage" in cfg.coverage)
+                rep.coverage = api.Coverage(rep.graph, per_base="base_coverage" in cfg.coverage, links=any(f in cfg.coverage for f in LINK_OUTPUTS))
             rep.setup_seconds = time.time() - started
     finally:
         if tmp:
@@ -644,6 +657,10 @@ def run(cfg, stderr=sys.stderr):
                     if fmt in cfg.coverage:
                         text, line_off = table(line_offsets=True)
                         outputs.write(fmt, gzip_lines(api, text, line_off) if cfg.coverage[fmt].endswith(".gz") else text)
+                for fmt, pieces in (("link_coverage", total.link_pieces), ("coverage_gfa", total.gfa_pieces), ("supported_subgraph", lambda: total.gfa_pieces(supported_only=True))):
+                    if fmt in cfg.coverage:    # piece by piece: the text of a large graph is never whole on either side
+                        for text, line_off in pieces():
+                            outputs.write(fmt, gzip_lines(api, text, line_off) if cfg.coverage[fmt].endswith(".gz") else text)
         counts["seconds"] = time.time() - started
     finally:
         for rep in replicas:

@@ -311,7 +311,7 @@
 			if (nKept) {
 				uint8_t* dKeep = st->covKeep.reserve<uint8_t>(nOutJobs);
 				HIP_CHECK(hipMemcpyAsync(dKeep, hKeep, nOutJobs, hipMemcpyHostToDevice, stream));
-				launchCoverageAdd(stream, cov->dev, (const OutJob*)st->outJobs.ptr, (uint32_t)nOutJobs, dKeep, dLongCells, cov->dBases, cov->dDepth, cov->dBad);
+				launchCoverageAdd(stream, cov->dev, cov->links, (const OutJob*)st->outJobs.ptr, (uint32_t)nOutJobs, dKeep, dLongCells, cov->dBases, cov->dDepth, cov->dBad);
 			}
 		}
 		for (const OutEntry& en : outEntries) if (en.source == 1) { nWinners++; winnerCells += glue[en.read].chainTraceNode.size(); }
@@ -332,7 +332,7 @@
 			OutJob* dJobsCov = st->covJobs.reserve<OutJob>(nWinners);
 			HIP_CHECK(hipMemcpyAsync(dCells, hCells, winnerCells * sizeof(LongCell), hipMemcpyHostToDevice, stream));
 			HIP_CHECK(hipMemcpyAsync(dJobsCov, hJobsCov, nWinners * sizeof(OutJob), hipMemcpyHostToDevice, stream));
-			launchCoverageAdd(stream, cov->dev, dJobsCov, (uint32_t)nWinners, nullptr, dCells, cov->dBases, cov->dDepth, cov->dBad);
+			launchCoverageAdd(stream, cov->dev, cov->links, dJobsCov, (uint32_t)nWinners, nullptr, dCells, cov->dBases, cov->dDepth, cov->dBad);
 		}
 		if (timed[1]) HIP_CHECK(hipEventRecord(timed[1], stream));
 		HIP_CHECK(hipGetLastError());
@@ -341,8 +341,8 @@
 			float ms = 0;
 			HIP_CHECK(hipEventElapsedTime(&ms, timed[0], timed[1]));
 			for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
-			fprintf(stderr, "[gc times] coverage: k_cov_add over %llu alignments in the cell pool and %llu chained winners (%llu cells up), %.3f ms on the device, %.1f ms in all; per-base depth %s\n",
-				(unsigned long long)nKept, (unsigned long long)nWinners, (unsigned long long)winnerCells, ms, (nowUs() - t0) / 1e3, cov->dDepth ? "on" : "off");
+			fprintf(stderr, "[gc times] coverage: k_cov_add over %llu alignments in the cell pool and %llu chained winners (%llu cells up), %.3f ms on the device, %.1f ms in all; per-base depth %s, links %s\n",
+				(unsigned long long)nKept, (unsigned long long)nWinners, (unsigned long long)winnerCells, ms, (nowUs() - t0) / 1e3, cov->dDepth ? "on" : "off", cov->hasLinks ? "on" : "off");
 		}
 	}
 

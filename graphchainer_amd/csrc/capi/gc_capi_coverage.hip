@@ -1,6 +1,7 @@
-// C entry points of the coverage accumulators: gc_coverage_create / _destroy, gc_stream_set_coverage, gc_coverage_add_traces, gc_coverage_counts, gc_coverage_merge,
-// gc_coverage_format_segments / _bases. The kernels are in hip/gc_coverage.hip, the per-batch counting in batch/gc_batch_output.inc (countCoverage).
+// C entry points of the coverage accumulators: gc_coverage_create / _create2 / _destroy, gc_stream_set_coverage, gc_coverage_add_traces, gc_coverage_counts, _link_counts,
+// gc_coverage_merge, gc_coverage_format_segments / _bases / _links / _gfa_segments / _gfa_links. The kernels are in hip/gc_coverage.hip, the per-batch counting in batch/gc_batch_output.inc (countCoverage).
 #include "../gc_runtime.hpp"
+#include "../hip/gc_coverage_links_core.hpp"
 
 namespace {
 
@@ -17,16 +18,34 @@ void checkFlags(gc_coverage* cov, hipStream_t q)
 	HIP_CHECK(hipMemcpyAsync(&flags, cov->dBad, sizeof flags, hipMemcpyDeviceToHost, q));
 	HIP_CHECK(hipStreamSynchronize(q));
 	if (flags & 1u) throw std::runtime_error("internal: the coverage kernel met a trace cell outside the graph (it was not counted)");
+	if (flags & 4u) throw std::runtime_error("internal: the coverage kernel met a node change that is no link of the graph (it was not counted)");
+}
+
+// The graph's links (include/graphchainer_amd.h): the distinct canonical forms of (nodeIDs[x], nodeIDs[y]) over the out-edges x -> y of the split nodes with different ids,
+// ascending. Read from nodeIDs and outNeighbors, which gc_graph_trim_host leaves in place.
+std::vector<uint64_t> linkKeysOf(const gc::AlignmentGraph& h)
+{
+	std::vector<uint64_t> keys;
+	for (size_t x = 0; x < h.outNeighbors.size(); x++)
+		for (size_t y : h.outNeighbors[x])
+			if (h.nodeIDs[x] != h.nodeIDs[y]) keys.push_back(gcdev::covLinkKey((uint32_t)h.nodeIDs[x], (uint32_t)h.nodeIDs[y]));
+	std::sort(keys.begin(), keys.end());
+	keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+	return keys;
 }
 
 } // namespace
 
 extern "C" {
 
-int gc_coverage_create(const gc_graph* G, int per_base, gc_coverage** out)
+int gc_coverage_create(const gc_graph* G, int per_base, gc_coverage** out) { return gc_coverage_create2(G, per_base ? GC_COVERAGE_PER_BASE : 0, out); }
+
+int gc_coverage_create2(const gc_graph* G, unsigned flags, gc_coverage** out)
 {
 	if (!G || !out) return fail(GC_ERR_INVALID, "null argument");
 	*out = nullptr;
+	if (flags & ~(unsigned)(GC_COVERAGE_PER_BASE | GC_COVERAGE_LINKS)) return fail(GC_ERR_INVALID, "gc_coverage_create2: unknown flag");
+	const bool per_base = (flags & GC_COVERAGE_PER_BASE) != 0;
 	gc_coverage* cov = new gc_coverage();
 	int rc = guarded([&]() {
 		requireDevice();
@@ -54,6 +73,18 @@ int gc_coverage_create(const gc_graph* G, int per_base, gc_coverage** out)
 				throw DeviceError("gc_coverage_create: the per-base depth needs " + std::to_string(bytes) + " bytes of device memory (4 per forward base of the graph) and they could not be allocated");
 			}
 			HIP_CHECK(hipMemset(cov->dDepth, 0, bytes));
+		}
+		if (flags & GC_COVERAGE_LINKS) {
+			cov->linkKeys = linkKeysOf(G->host);
+			const size_t n = cov->linkKeys.size(), room = std::max<size_t>(1, n);
+			if (hipMalloc((void**)&cov->dLinkKeys, room * sizeof(uint64_t)) != hipSuccess || hipMalloc((void**)&cov->dLinkCounts, room * sizeof(unsigned long long)) != hipSuccess) {
+				(void)hipGetLastError();
+				throw DeviceError("gc_coverage_create2: the link table needs " + std::to_string(16 * room) + " bytes of device memory (16 per link of the graph) and they could not be allocated");
+			}
+			if (n) HIP_CHECK(hipMemcpy(cov->dLinkKeys, cov->linkKeys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+			HIP_CHECK(hipMemset(cov->dLinkCounts, 0, room * sizeof(unsigned long long)));
+			cov->hasLinks = true;
+			cov->links = CovLinks { cov->dLinkKeys, cov->dLinkCounts, (uint64_t)n };
 		}
 		HIP_CHECK(hipDeviceSynchronize());
 		cov->dev = CovGraph { (const uint64_t*)cov->dSegStart, (uint64_t)nSeg, nBases, (uint32_t)nIds };
@@ -99,6 +130,15 @@ int gc_coverage_add_traces(gc_coverage* cov, const int32_t* node, const uint32_t
 	const std::vector<uint32_t>& size = cov->graph->hOrigSize;
 	for (uint64_t i = 0; i < cellsTotal; i++)
 		if (node[i] < 0 || (uint64_t)node[i] >= size.size() || offset[i] >= size[node[i]]) return fail(GC_ERR_INVALID, "gc_coverage_add_traces: no such node / offset");
+	// with links: every node change must leave its segment at the last base (in that orientation), enter the next at offset 0 and be a link of the graph
+	if (cov->hasLinks)
+		for (uint64_t a = 0; a < n_aln; a++)
+			for (uint64_t i = trace_off[a] + 1; i < trace_off[a + 1]; i++) {
+				if (node[i] == node[i - 1]) continue;
+				if (offset[i - 1] != size[node[i - 1]] - 1 || offset[i] != 0) return fail(GC_ERR_INVALID, "gc_coverage_add_traces: a trace changes its node elsewhere than from a segment's last base to the next one's first");
+				if (gcdev::covLinkFind(cov->linkKeys.data(), cov->linkKeys.size(), gcdev::covLinkKey((uint32_t)node[i - 1], (uint32_t)node[i])) == cov->linkKeys.size())
+					return fail(GC_ERR_INVALID, "gc_coverage_add_traces: a trace changes its node along no link of the graph");
+			}
 	if (n_aln == 0 || cellsTotal == 0) return GC_OK;
 	return guarded([&]() {
 		requireDevice();
@@ -113,7 +153,7 @@ int gc_coverage_add_traces(gc_coverage* cov, const int32_t* node, const uint32_t
 		OutJob* pJobs = dJobs.reserve<OutJob>(n_aln);
 		HIP_CHECK(hipMemcpyAsync(pCells, cells.data(), cells.size() * sizeof(LongCell), hipMemcpyHostToDevice, q));
 		HIP_CHECK(hipMemcpyAsync(pJobs, jobs.data(), n_aln * sizeof(OutJob), hipMemcpyHostToDevice, q));
-		launchCoverageAdd(q, cov->dev, pJobs, (uint32_t)n_aln, nullptr, pCells, cov->dBases, cov->dDepth, cov->dBad);
+		launchCoverageAdd(q, cov->dev, cov->links, pJobs, (uint32_t)n_aln, nullptr, pCells, cov->dBases, cov->dDepth, cov->dBad);
 		HIP_CHECK(hipGetLastError());
 		HIP_CHECK(hipStreamSynchronize(q));   // (the buffers go when this returns)
 		return (int)GC_OK;
@@ -144,38 +184,68 @@ int gc_coverage_counts(gc_coverage* cov, uint64_t** bases, uint64_t* n_segments,
 	});
 }
 
+int gc_coverage_link_counts(gc_coverage* cov, int32_t** from, int32_t** to, uint64_t** traversals, uint64_t* n_links)
+{
+	if (!cov || !from || !to || !traversals || !n_links) return fail(GC_ERR_INVALID, "null argument");
+	*from = nullptr; *to = nullptr; *traversals = nullptr;
+	if (!cov->hasLinks) return fail(GC_ERR_INVALID, "gc_coverage_link_counts: the handle was created without links");
+	return guarded([&]() {
+		requireDevice();
+		OnDevice here(cov->device);
+		hipStream_t q = threadStream(cov->device);
+		checkFlags(cov, q);
+		const uint64_t n = cov->linkKeys.size();
+		int32_t* f = mallocArray<int32_t>(n);
+		int32_t* t = mallocArray<int32_t>(n);
+		uint64_t* c = mallocArray<uint64_t>(n);
+		struct Free { void* p; ~Free() { free(p); } } gf { f }, gt { t }, gc { c };
+		if (!f || !t || !c) throw std::runtime_error("out of memory");
+		for (uint64_t i = 0; i < n; i++) { f[i] = (int32_t)gcdev::covLinkFrom(cov->linkKeys[i]); t[i] = (int32_t)gcdev::covLinkTo(cov->linkKeys[i]); }
+		if (n) HIP_CHECK(hipMemcpyAsync(c, cov->dLinkCounts, n * sizeof(uint64_t), hipMemcpyDeviceToHost, q));
+		HIP_CHECK(hipStreamSynchronize(q));
+		gf.p = nullptr; gt.p = nullptr; gc.p = nullptr;
+		*from = f; *to = t; *traversals = c; *n_links = n;
+		return (int)GC_OK;
+	});
+}
+
 int gc_coverage_merge(gc_coverage* dst, const gc_coverage* src)
 {
 	if (!dst || !src) return fail(GC_ERR_INVALID, "null argument");
 	if (dst == src) return fail(GC_ERR_INVALID, "gc_coverage_merge: a handle cannot be merged into itself");
 	if (dst->segStart != src->segStart || dst->nIds != src->nIds) return fail(GC_ERR_INVALID, "gc_coverage_merge: the handles were made for graphs of different shape");
 	if ((dst->dDepth != nullptr) != (src->dDepth != nullptr)) return fail(GC_ERR_INVALID, "gc_coverage_merge: one handle counts per base and the other does not");
+	if (dst->hasLinks != src->hasLinks) return fail(GC_ERR_INVALID, "gc_coverage_merge: one handle counts links and the other does not");
+	if (dst->linkKeys != src->linkKeys) return fail(GC_ERR_INVALID, "gc_coverage_merge: the handles were made for graphs of different shape");
 	return guarded([&]() {
 		requireDevice();
 		OnDevice here(dst->device);
 		hipStream_t q = threadStream(dst->device);
-		const uint64_t nSeg = dst->dev.nSegments, nDepth = dst->dDepth ? dst->dev.nBases : 0;
+		const uint64_t nSeg = dst->dev.nSegments, nDepth = dst->dDepth ? dst->dev.nBases : 0, nLinks = dst->linkKeys.size();
 		uint32_t srcFlags = 0;
 		if (src->device == dst->device) {
 			HIP_CHECK(hipMemcpyAsync(&srcFlags, src->dBad, sizeof srcFlags, hipMemcpyDeviceToHost, q));
-			launchCoverageMerge(q, dst->dBases, src->dBases, nSeg, dst->dDepth, src->dDepth, nDepth);
+			launchCoverageMerge(q, dst->dBases, src->dBases, nSeg, dst->dDepth, src->dDepth, nDepth, dst->dLinkCounts, src->dLinkCounts, nLinks);
 			HIP_CHECK(hipGetLastError());
 			HIP_CHECK(hipStreamSynchronize(q));
 		} else {
 			// two devices: through the host, the depth in slices so that neither side holds a second copy of it
 			const uint64_t slice = 64ull << 20;   // words
-			std::vector<unsigned long long> hBases(std::max<uint64_t>(1, nSeg));
+			std::vector<unsigned long long> hBases(std::max<uint64_t>(1, nSeg)), hLinks(std::max<uint64_t>(1, nLinks));
 			std::vector<uint32_t> hDepth(std::max<uint64_t>(1, std::min(slice, nDepth)));
-			DeviceBuffer dBases, dDepth;
+			DeviceBuffer dBases, dDepth, dLinks;
 			unsigned long long* pBases = dBases.reserve<unsigned long long>(nSeg);
+			unsigned long long* pLinks = dLinks.reserve<unsigned long long>(nLinks);
 			uint32_t* pDepth = dDepth.reserve<uint32_t>(hDepth.size());
 			{
 				OnDevice there(src->device);
 				HIP_CHECK(hipMemcpy(&srcFlags, src->dBad, sizeof srcFlags, hipMemcpyDeviceToHost));
 				if (nSeg) HIP_CHECK(hipMemcpy(hBases.data(), src->dBases, nSeg * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+				if (nLinks) HIP_CHECK(hipMemcpy(hLinks.data(), src->dLinkCounts, nLinks * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 			}
 			if (nSeg) HIP_CHECK(hipMemcpyAsync(pBases, hBases.data(), nSeg * sizeof(unsigned long long), hipMemcpyHostToDevice, q));
-			launchCoverageMerge(q, dst->dBases, pBases, nSeg, nullptr, nullptr, 0);
+			if (nLinks) HIP_CHECK(hipMemcpyAsync(pLinks, hLinks.data(), nLinks * sizeof(unsigned long long), hipMemcpyHostToDevice, q));
+			launchCoverageMerge(q, dst->dBases, pBases, nSeg, nullptr, nullptr, 0, dst->dLinkCounts, pLinks, nLinks);
 			HIP_CHECK(hipStreamSynchronize(q));
 			for (uint64_t at = 0; at < nDepth; at += slice) {
 				const uint64_t m = std::min(slice, nDepth - at);
@@ -190,6 +260,7 @@ int gc_coverage_merge(gc_coverage* dst, const gc_coverage* src)
 			}
 		}
 		if (srcFlags & 1u) throw std::runtime_error("internal: the merged handle's kernel met a trace cell outside the graph (it was not counted)");
+		if (srcFlags & 4u) throw std::runtime_error("internal: the merged handle's kernel met a node change that is no link of the graph (it was not counted)");
 		return (int)GC_OK;
 	});
 }
@@ -219,5 +290,38 @@ static int formatTable(gc_coverage* cov, bool perBase, char** text, uint64_t* le
 
 int gc_coverage_format_segments(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines) { return formatTable(cov, false, text, len, line_off, n_lines); }
 int gc_coverage_format_bases(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines) { return formatTable(cov, true, text, len, line_off, n_lines); }
+
+// kind 0: the link table, 1: the GFA's S lines, 2: its L lines
+static int formatRows(gc_coverage* cov, int kind, uint64_t first, uint64_t count, int supported_only, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines)
+{
+	if (!cov || !text || !len) return fail(GC_ERR_INVALID, "null argument");
+	*text = nullptr;
+	if (line_off) *line_off = nullptr;
+	if (kind != 1 && !cov->hasLinks) return fail(GC_ERR_INVALID, "the handle was created without links");
+	const uint64_t rows = kind == 1 ? cov->dev.nSegments : cov->linkKeys.size();
+	if (first > rows) return fail(GC_ERR_INVALID, "the first row lies behind the table's end");
+	count = std::min(count, rows - first);
+	if (count + 1 >= 0x7fffffffull) return fail(GC_ERR_INVALID, "2^31 rows or more in one call: ask for a smaller range");
+	return guarded([&]() {
+		requireDevice();
+		OnDevice here(cov->device);
+		hipStream_t q = threadStream(cov->device);
+		checkFlags(cov, q);
+		char* t = nullptr; uint64_t l = 0, n = 0; uint64_t* off = nullptr;
+		const hipError_t e = kind == 0 ? coverageFormatLinks(q, cov->names, cov->links, first, count, &t, &l, &off, &n)
+		                   : kind == 1 ? coverageFormatGfaSegments(q, cov->dev, cov->graph->dev, cov->names, cov->dBases, cov->dBad, first, count, supported_only != 0, &t, &l, &off, &n)
+		                               : coverageFormatGfaLinks(q, cov->names, cov->links, first, count, supported_only != 0, &t, &l, &off, &n);
+		if (e == hipErrorInvalidValue) throw std::runtime_error("internal: a range outside the table, or a segment's line of 2^32 bytes or more");
+		HIP_CHECK(e);
+		*text = t; *len = l;
+		if (line_off) *line_off = off; else free(off);
+		if (n_lines) *n_lines = n;
+		return (int)GC_OK;
+	});
+}
+
+int gc_coverage_format_links(gc_coverage* cov, uint64_t first, uint64_t count, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines) { return formatRows(cov, 0, first, count, 0, text, len, line_off, n_lines); }
+int gc_coverage_format_gfa_segments(gc_coverage* cov, uint64_t first, uint64_t count, int supported_only, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines) { return formatRows(cov, 1, first, count, supported_only, text, len, line_off, n_lines); }
+int gc_coverage_format_gfa_links(gc_coverage* cov, uint64_t first, uint64_t count, int supported_only, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines) { return formatRows(cov, 2, first, count, supported_only, text, len, line_off, n_lines); }
 
 } // extern "C"

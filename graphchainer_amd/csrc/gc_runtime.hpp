@@ -706,7 +706,12 @@ struct gc_coverage {
 	uint32_t* dDepth = nullptr;             // [forward bases], only with per_base
 	uint32_t* dBad = nullptr;               // flag word: 1 a cell outside the graph was met (and not counted), 2 the finish step's runs did not pair up
 	void* dSegStart = nullptr;
-	~gc_coverage() { for (void* p : { (void*)dBases, (void*)dDepth, (void*)dBad, dSegStart }) if (p) (void)hipFree(p); }
+	bool hasLinks = false;                  // GC_COVERAGE_LINKS: the graph's links, sorted canonical keys (gc_coverage_links_core.hpp), here and on the device with a 64-bit counter each
+	std::vector<uint64_t> linkKeys;
+	uint64_t* dLinkKeys = nullptr;
+	unsigned long long* dLinkCounts = nullptr;
+	CovLinks links {};                      // (counts == nullptr without links: launchCoverageAdd then takes the kernel without the traversal step)
+	~gc_coverage() { for (void* p : { (void*)dBases, (void*)dDepth, (void*)dBad, dSegStart, (void*)dLinkKeys, (void*)dLinkCounts }) if (p) (void)hipFree(p); }
 };
 
 struct gc_stream {

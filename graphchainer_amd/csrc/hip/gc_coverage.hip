@@ -8,14 +8,21 @@
 // its predecessor's; one ballot of the covering lanes, one of the lanes that open a run of the same segment; the opening lane adds the run's length to bases[segment];
 // with depth on every covering lane adds 1 to its word (neighbouring lanes, neighbouring words, except across a strand flip where they run the other way).
 // A cell outside the graph is not counted and raises *bad (the batch's own cells never are; a caller's traces are checked on the host before they get here).
+// k_cov_add<true> (a handle with links; gc_coverage_links_core.hpp): the traversal step. A lane whose node differs from its predecessor's - the lane below, the carry for
+// lane 0 - forms the canonical key of the pair, finds it among the graph's sorted link keys by binary search and adds 1 to the link's 64-bit counter. A pair that is no link
+// is not counted and raises *bad (4). k_cov_add<false> is the kernel of a handle without links: the step is compiled out, not branched over (DESIGN.md §3.14 has both
+// resource lines).
 // Measured alternative for the depth (difference marks at run ends + a segmented scan in the finish step): see DESIGN.md §10.
 //
 // The finish step spells both tables on the device, as the GAF encoder spells its text: per segment / per run a line length, a scan, the lines. The runs of the base table
 // (maximal stretches of equal non-zero depth inside a segment) are found per tile of 2048 bases: starts and ends counted, scanned over the tiles, then placed.
 #include "gc_kernels.hpp"
 #include "gc_coverage_core.hpp"
+#include "gc_coverage_links_core.hpp"
+#include "gc_corrected_core.hpp"
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -25,7 +32,8 @@ namespace {
 
 constexpr uint32_t COV_TILE_THREADS = 256, COV_TILE_ITEMS = 8, COV_TILE = COV_TILE_THREADS * COV_TILE_ITEMS;
 
-__global__ void __launch_bounds__(64) k_cov_add(CovGraph g, const OutJob* __restrict__ jobs, uint32_t nJobs, const uint8_t* __restrict__ keep, const LongCell* __restrict__ cellPool,
+template <bool LINKS>
+__global__ void __launch_bounds__(64) k_cov_add(CovGraph g, CovLinks links, const OutJob* __restrict__ jobs, uint32_t nJobs, const uint8_t* __restrict__ keep, const LongCell* __restrict__ cellPool,
 	unsigned long long* __restrict__ bases, uint32_t* __restrict__ depth, uint32_t* __restrict__ bad)
 {
 	const uint32_t j = blockIdx.x, lane = threadIdx.x;
@@ -60,15 +68,23 @@ __global__ void __launch_bounds__(64) k_cov_add(CovGraph g, const OutJob* __rest
 		const uint64_t openMask = __ballot(opens);
 		if (opens) atomicAdd(bases + seg, (unsigned long long)covRunLength(coverMask, openMask, lane));
 		if (depth && covers && atomicAdd(depth + at, 1u) == 0xffffffffu) atomicExch(depth + at, 0xffffffffu);   // a full word stays full: whoever wraps it puts it back, and the last of any interleaving is such a store
+		if (LINKS) {
+			// the traversal step: a lane whose node differs from its predecessor's walks a link. Only the sorted keys are indexed, whatever the cell says.
+			if (valid && covTraverses(pos == 0, pNode, c.node)) {
+				const uint64_t link = covLinkFind(links.keys, links.n, covLinkKey((uint32_t)pNode, (uint32_t)c.node));
+				if (link < links.n) atomicAdd(links.counts + link, 1ull); else atomicOr(bad, 4u);
+			}
+		}
 		carryNode = __shfl(c.node, (int)nValid - 1); carryOffset = __shfl(c.offset, (int)nValid - 1);
 	}
 }
 
 __global__ void __launch_bounds__(256) k_cov_merge(unsigned long long* __restrict__ dstBases, const unsigned long long* __restrict__ srcBases, uint64_t nSegments,
-	uint32_t* __restrict__ dstDepth, const uint32_t* __restrict__ srcDepth, uint64_t nDepth)
+	uint32_t* __restrict__ dstDepth, const uint32_t* __restrict__ srcDepth, uint64_t nDepth, unsigned long long* __restrict__ dstLinks, const unsigned long long* __restrict__ srcLinks, uint64_t nLinks)
 {
 	const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	for (uint64_t i = first; i < nSegments; i += stride) dstBases[i] += srcBases[i];
+	for (uint64_t i = first; i < nLinks; i += stride) dstLinks[i] += srcLinks[i];
 	for (uint64_t i = first; i < nDepth; i += stride) dstDepth[i] = covSatAdd(dstDepth[i], srcDepth[i]);
 }
 
@@ -84,6 +100,78 @@ __global__ void __launch_bounds__(256) k_cov_segments(CovGraph g, OutNames names
 	const uint64_t length = g.segStart[s + 1] - g.segStart[s];
 	if (!WRITE) lens[s] = covSegmentLineLen(nameLen, s, length, bases[s]);
 	else covSegmentLine(text + off[s], names.nameBytes + names.nameOff[id], nameLen, s, length, bases[s]);
+}
+
+// ---- the link table and the tagged GFA: rows [first, first + count) of the links / the segments, a thread per row; a row left out (supportedOnly, zero count) has length 0
+// KIND 0: the link table's line, 1: the GFA's L line
+template <bool WRITE, int KIND>
+__global__ void __launch_bounds__(256) k_cov_links(OutNames names, CovLinks links, uint64_t first, uint64_t count, bool supportedOnly, uint32_t* __restrict__ lens, const uint64_t* __restrict__ off, char* __restrict__ text)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r > count) return;
+	if (r == count) { if (!WRITE) lens[r] = 0; return; }   // (the scan's last entry is the total)
+	const uint64_t key = links.keys[first + r], traversals = links.counts[first + r];
+	const uint32_t from = covLinkFrom(key), to = covLinkTo(key);
+	if (supportedOnly && traversals == 0) { if (!WRITE) lens[r] = 0; return; }
+	// (a link's two names are looked up by the segment's forward id, as the segment table does: both strands carry the same name, and an odd id past an odd nIds has none)
+	const uint32_t fromId = from & ~1u, toId = to & ~1u;
+	const uint32_t fromLen = names.nameOff[fromId + 1] - names.nameOff[fromId], toLen = names.nameOff[toId + 1] - names.nameOff[toId];
+	const char* fromName = names.nameBytes + names.nameOff[fromId];
+	const char* toName = names.nameBytes + names.nameOff[toId];
+	if (!WRITE) lens[r] = KIND == 0 ? covLinkLineLen(fromLen, toLen, from, to, traversals) : covGfaLinkLineLen(fromLen, toLen, from, to, traversals);
+	else if (KIND == 0) covLinkLine(text + off[r], fromName, fromLen, toName, toLen, from, to, traversals);
+	else covGfaLinkLine(text + off[r], fromName, fromLen, toName, toLen, from, to, traversals);
+}
+
+// the S line without its letters (they are k_cov_gfa_letters'): a thread per segment
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_cov_gfa_segments(CovGraph g, OutNames names, const unsigned long long* __restrict__ bases, uint64_t first, uint64_t count, bool supportedOnly,
+	uint32_t* __restrict__ lens, const uint64_t* __restrict__ off, char* __restrict__ text, uint32_t* __restrict__ bad)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r > count) return;
+	if (r == count) { if (!WRITE) lens[r] = 0; return; }
+	const uint64_t s = first + r;
+	if (supportedOnly && bases[s] == 0) { if (!WRITE) lens[r] = 0; return; }
+	const uint32_t id = (uint32_t)(2 * s);
+	const uint32_t nameLen = names.nameOff[id + 1] - names.nameOff[id];
+	const uint64_t length = g.segStart[s + 1] - g.segStart[s];
+	if (!WRITE) {
+		const uint64_t bytes = covGfaSegmentLineLen(nameLen, s, length, bases[s]);
+		if (bytes > 0xffffffffull) atomicOr(bad, 8u);
+		lens[r] = (uint32_t)bytes;
+	} else covGfaSegmentLine(text + off[r], names.nameBytes + names.nameOff[id], nameLen, s, nullptr, length, bases[s]);
+}
+
+// the set of plain bases (A 1, C 2, G 4, T 8) of forward base `pos` of segment s, as gc_corrected.hip reads it; a segment the graph holds only the reverse strand of is read
+// there and complemented (the set's four bits reversed)
+__device__ __forceinline__ uint32_t covForwardSet(const DGraph& dg, uint32_t nIds, uint64_t s, uint32_t pos, uint32_t length)
+{
+	uint32_t id = (uint32_t)(2 * s), offset = pos;
+	const bool flip = dg.origSize[id] == 0 && id + 1 < nIds;
+	if (flip) { id++; offset = length - 1 - pos; }
+	const uint32_t split = dg.lookup[dg.lookupOff[id] + (offset >> 6)];
+	const uint32_t at = offset & 63u;
+	uint32_t set;
+	if (split < dg.firstAmbiguous) set = 1u << ((dg.nodeSeq[2 * (size_t)split + (at >> 5)] >> ((at & 31u) * 2)) & 3u);
+	else {
+		const uint64_t* p = dg.ambSeq + 4 * (size_t)(split - dg.firstAmbiguous);
+		set = (uint32_t)((p[0] >> at) & 1) | (uint32_t)(((p[1] >> at) & 1) << 1) | (uint32_t)(((p[2] >> at) & 1) << 2) | (uint32_t)(((p[3] >> at) & 1) << 3);
+	}
+	return flip ? ((set & 1u) << 3 | (set & 2u) << 1 | (set & 4u) >> 1 | (set & 8u) >> 3) : set;
+}
+
+// the letters of the S lines: a thread per forward base of segments [first, first + count), neighbouring threads neighbouring bytes
+__global__ void __launch_bounds__(256) k_cov_gfa_letters(CovGraph g, DGraph dg, OutNames names, uint64_t first, uint64_t count, const uint32_t* __restrict__ lens, const uint64_t* __restrict__ off, char* __restrict__ text)
+{
+	const uint64_t i = g.segStart[first] + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= g.segStart[first + count]) return;
+	const uint64_t s = covSegmentOfBase(g.segStart, g.nSegments, i);
+	if (s < first || s >= first + count || lens[s - first] == 0) return;   // (a segment left out has no line to write into)
+	const uint64_t s0 = g.segStart[s];
+	const uint32_t id = (uint32_t)(2 * s);
+	const uint32_t nameLen = names.nameOff[id + 1] - names.nameOff[id];
+	text[off[s - first] + covGfaSegmentLettersAt(nameLen, s) + (i - s0)] = corrLetter(covForwardSet(dg, g.nIds, s, (uint32_t)(i - s0), (uint32_t)(g.segStart[s + 1] - s0)));
 }
 
 // ---- the base table: runs per tile
@@ -183,18 +271,20 @@ hipError_t bringDown(hipStream_t q, const char* head, const char* dText, uint64_
 
 } // namespace
 
-void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad)
+void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const CovLinks& links, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad)
 {
 	if (!nJobs) return;
-	hipLaunchKernelGGL(k_cov_add, dim3(nJobs), dim3(64), 0, stream, g, jobs, nJobs, keep, cellPool, bases, depth, bad);
+	if (links.counts) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_add<true>), dim3(nJobs), dim3(64), 0, stream, g, links, jobs, nJobs, keep, cellPool, bases, depth, bad);
+	else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_add<false>), dim3(nJobs), dim3(64), 0, stream, g, links, jobs, nJobs, keep, cellPool, bases, depth, bad);
 }
 
-void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth)
+void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth,
+	unsigned long long* dstLinks, const unsigned long long* srcLinks, uint64_t nLinks)
 {
-	const uint64_t most = nSegments > nDepth ? nSegments : nDepth;
+	const uint64_t most = std::max(std::max(nSegments, nDepth), nLinks);
 	if (!most) return;
 	const uint64_t blocks = (most + 255) / 256;
-	hipLaunchKernelGGL(k_cov_merge, dim3((uint32_t)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, dstBases, srcBases, nSegments, dstDepth, srcDepth, nDepth);
+	hipLaunchKernelGGL(k_cov_merge, dim3((uint32_t)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, dstBases, srcBases, nSegments, dstDepth, srcDepth, nDepth, dstLinks, srcLinks, nLinks);
 }
 
 hipError_t coverageFormatSegments(hipStream_t q, const CovGraph& g, const OutNames& names, const unsigned long long* bases, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
@@ -252,6 +342,75 @@ hipError_t coverageFormatBases(hipStream_t q, const CovGraph& g, const OutNames&
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_runs<true>), grid, dim3(256), 0, q, g, names, depth, (const uint64_t*)runStart, (const uint64_t*)runEnd, nRuns, (uint32_t*)nullptr, (const uint64_t*)off.p, (char*)out.p, bad);
 	COV_TRY(hipGetLastError());
 	return bringDown(q, nullptr, (const char*)out.p, total, (const uint64_t*)off.p, nRuns, text, len, lineOff, nLines);
+}
+
+namespace {
+
+// rows left out have no line: their (equal) offsets go, *nLines counts what is left
+void dropEmptyLines(uint64_t* lineOff, uint64_t* nLines)
+{
+	*nLines = (uint64_t)(std::unique(lineOff, lineOff + *nLines + 1) - lineOff) - 1;
+}
+
+template <int KIND>
+hipError_t formatLinkRows(hipStream_t q, const OutNames& names, const CovLinks& links, uint64_t first, uint64_t count, bool supportedOnly, const char* head, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
+{
+	if (first > links.n || count > links.n - first || count + 1 >= 0x7fffffffull) return hipErrorInvalidValue;
+	Scratch lens, off, out;
+	COV_TRY(lens.get((count + 1) * sizeof(uint32_t)));
+	COV_TRY(off.get((count + 1) * sizeof(uint64_t)));
+	const dim3 grid((uint32_t)((count + 1 + 255) / 256));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_links<false, KIND>), grid, dim3(256), 0, q, names, links, first, count, supportedOnly, (uint32_t*)lens.p, (const uint64_t*)nullptr, (char*)nullptr);
+	COV_TRY(scanCounts(q, (const uint32_t*)lens.p, (uint64_t*)off.p, count + 1));
+	uint64_t total = 0;
+	COV_TRY(hipMemcpyAsync(&total, (uint64_t*)off.p + count, sizeof total, hipMemcpyDeviceToHost, q));
+	COV_TRY(hipStreamSynchronize(q));
+	COV_TRY(out.get(total));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_links<true, KIND>), grid, dim3(256), 0, q, names, links, first, count, supportedOnly, (uint32_t*)nullptr, (const uint64_t*)off.p, (char*)out.p);
+	COV_TRY(hipGetLastError());
+	COV_TRY(bringDown(q, head, (const char*)out.p, total, (const uint64_t*)off.p, count, text, len, lineOff, nLines));
+	if (supportedOnly) dropEmptyLines(*lineOff, nLines);
+	return hipSuccess;
+}
+
+} // namespace
+
+hipError_t coverageFormatLinks(hipStream_t q, const OutNames& names, const CovLinks& links, uint64_t first, uint64_t count, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
+{
+	return formatLinkRows<0>(q, names, links, first, count, false, first == 0 ? "#from\tfrom_orient\tto\tto_orient\ttraversals\n" : nullptr, text, len, lineOff, nLines);
+}
+
+hipError_t coverageFormatGfaLinks(hipStream_t q, const OutNames& names, const CovLinks& links, uint64_t first, uint64_t count, bool supportedOnly, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
+{
+	return formatLinkRows<1>(q, names, links, first, count, supportedOnly, nullptr, text, len, lineOff, nLines);
+}
+
+hipError_t coverageFormatGfaSegments(hipStream_t q, const CovGraph& g, const DGraph& dg, const OutNames& names, const unsigned long long* bases, uint32_t* bad, uint64_t first, uint64_t count, bool supportedOnly,
+	char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
+{
+	if (first > g.nSegments || count > g.nSegments - first || count + 1 >= 0x7fffffffull) return hipErrorInvalidValue;
+	Scratch lens, off, out;
+	COV_TRY(lens.get((count + 1) * sizeof(uint32_t)));
+	COV_TRY(off.get((count + 1) * sizeof(uint64_t)));
+	const dim3 grid((uint32_t)((count + 1 + 255) / 256));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_gfa_segments<false>), grid, dim3(256), 0, q, g, names, bases, first, count, supportedOnly, (uint32_t*)lens.p, (const uint64_t*)nullptr, (char*)nullptr, bad);
+	COV_TRY(scanCounts(q, (const uint32_t*)lens.p, (uint64_t*)off.p, count + 1));
+	uint64_t total = 0, range[2] = { 0, 0 }; uint32_t flags = 0;
+	COV_TRY(hipMemcpyAsync(&total, (uint64_t*)off.p + count, sizeof total, hipMemcpyDeviceToHost, q));
+	COV_TRY(hipMemcpyAsync(&flags, bad, sizeof flags, hipMemcpyDeviceToHost, q));
+	COV_TRY(hipMemcpyAsync(&range[0], g.segStart + first, sizeof(uint64_t), hipMemcpyDeviceToHost, q));
+	COV_TRY(hipMemcpyAsync(&range[1], g.segStart + first + count, sizeof(uint64_t), hipMemcpyDeviceToHost, q));
+	COV_TRY(hipStreamSynchronize(q));
+	if (flags & 8u) return hipErrorInvalidValue;   // a line of 2^32 bytes or more: nothing is written from the counts
+	COV_TRY(out.get(total));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_gfa_segments<true>), grid, dim3(256), 0, q, g, names, bases, first, count, supportedOnly, (uint32_t*)nullptr, (const uint64_t*)off.p, (char*)out.p, bad);
+	const uint64_t nLetters = range[1] - range[0], blocks = (nLetters + 255) / 256;
+	if (blocks >= 0x7fffffffull) return hipErrorInvalidValue;
+	if (blocks) hipLaunchKernelGGL(k_cov_gfa_letters, dim3((uint32_t)blocks), dim3(256), 0, q, g, dg, names, first, count, (const uint32_t*)lens.p, (const uint64_t*)off.p, (char*)out.p);
+	COV_TRY(hipGetLastError());
+	COV_TRY(bringDown(q, nullptr, (const char*)out.p, total, (const uint64_t*)off.p, count, text, len, lineOff, nLines));
+	if (supportedOnly) dropEmptyLines(*lineOff, nLines);
+	return hipSuccess;
 }
 
 } // namespace gcdev

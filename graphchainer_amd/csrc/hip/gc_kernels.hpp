@@ -341,13 +341,25 @@ void launchCorrectedWrite(hipStream_t stream, const DGraph& g, const OutJob* job
 struct CovGraph { const uint64_t* segStart; uint64_t nSegments, nBases; uint32_t nIds; };   // segStart[nSegments + 1]: first forward base of segment id / 2 in `depth`; nIds: bigraph node ids
 // bases[nSegments] += covering cells per segment, depth[nBases] += 1 per covering cell (depth may be null); of an OutJob only cellOff / cellLen are read; keep (may be null): jobs with
 // keep[j] == 0 are skipped; *bad |= 1 where a cell lies outside the graph (it is not counted)
-void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad);
+// links (gc_coverage_links_core.hpp): keys[n] the graph's sorted canonical link keys, counts[n] += 1 per traversal; counts == nullptr: a handle without links, and the kernel
+// without the traversal step (its own instantiation). *bad |= 4 where a node change is no link of the graph (it is not counted)
+struct CovLinks { const uint64_t* keys; unsigned long long* counts; uint64_t n; };
+void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const CovLinks& links, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad);
 // dst += src (depth saturating at 2^32 - 1); both on the stream's device, nothing else adding into them meanwhile
-void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth);
+void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth,
+	unsigned long long* dstLinks = nullptr, const unsigned long long* srcLinks = nullptr, uint64_t nLinks = 0);
 // The two tables spelled on the device; they wait for the stream where a total comes back. *text: malloc'd, NUL-terminated, *len bytes; *lineOff: malloc'd [*nLines + 1] byte offsets
 // of the lines (the segment table's head line included). bad: the handle's flag word (bit 1: the run starts and ends did not pair up - nothing is written then)
 hipError_t coverageFormatSegments(hipStream_t stream, const CovGraph& g, const OutNames& names, const unsigned long long* bases, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
 hipError_t coverageFormatBases(hipStream_t stream, const CovGraph& g, const OutNames& names, const uint32_t* depth, uint32_t* bad, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
+// The link table and the tagged GFA's two line kinds, rows [first, first + count) each (the caller bounds the text of one call by the range). Links: the head line
+// "#from\tfrom_orient\tto\tto_orient\ttraversals\n" with first == 0, then a line per link in link order. GFA segments: the letters are the forward strand read from the graph
+// (dg), upper case, IUPAC codes where a base is ambiguous. supportedOnly: rows with a zero count are left out (*nLines counts the lines written). bad: as above (bit 8: a line
+// of 2^32 bytes or more - nothing is written then)
+hipError_t coverageFormatLinks(hipStream_t stream, const OutNames& names, const CovLinks& links, uint64_t first, uint64_t count, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
+hipError_t coverageFormatGfaLinks(hipStream_t stream, const OutNames& names, const CovLinks& links, uint64_t first, uint64_t count, bool supportedOnly, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
+hipError_t coverageFormatGfaSegments(hipStream_t stream, const CovGraph& g, const DGraph& dg, const OutNames& names, const unsigned long long* bases, uint32_t* bad, uint64_t first, uint64_t count, bool supportedOnly,
+	char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
 // ---- DEFLATE of independent byte streams (gc_deflate.hip): one dynamic-Huffman block of literals per stream (stored blocks where that is smaller or the code
 // would be deeper than 15 bits). plan[s] = { deflate bytes, mode }, lens[260 * s + symbol]; the caller places stream s at a 4-byte aligned outOff[s] with room for plan[s].x rounded up to 4
 void launchDeflatePlan(hipStream_t stream, const uint8_t* raw, const uint64_t* rawOff, uint32_t nStreams, uint8_t* lens, uint2* plan);

@@ -685,6 +685,38 @@ int gc_coverage_merge(gc_coverage* dst, const gc_coverage* src);
 int gc_coverage_format_segments(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
 int gc_coverage_format_bases(gc_coverage* cov, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
 
+/* Link coverage: which links the counted alignments walk (--link-coverage-out / --coverage-gfa-out / --supported-subgraph-out). This library's own as well. The alignments
+ * counted are the same. Cell i > 0 of a trace is a traversal iff node[i] != node[i-1]; it walks the directed pair (u, v) = (node[i-1], node[i]) of bigraph ids
+ * (2 * segment + strand). An insertion cell repeats its predecessor's position and never traverses; the graph is a DAG, so an alignment walks a link at most once.
+ * The mate of (u, v) is (v ^ 1, u ^ 1), the same link read on the other strand; the canonical form of a pair is the lexicographically smaller of the pair and its mate
+ * (a hairpin (u, u ^ 1) is its own mate). The graph's links are the distinct canonical forms of all (nodeIDs[x], nodeIDs[y]) with y an out-neighbour of split node x and
+ * nodeIDs[x] != nodeIDs[y], numbered in ascending canonical (u, v); they are taken from the handle's host graph (after gc_graph_create, gc_graph_create_from_gfa or
+ * gc_index_load alike, and after gc_graph_trim_host). traversals[link] = the traversals over all counted alignments whose canonical form is that link.
+ * gc_coverage_create2 is gc_coverage_create with flags: GC_COVERAGE_LINKS builds the link table once and keeps it on the device, 16 bytes per link (the sorted keys
+ * u << 32 | v and a 64-bit counter each); GC_ERR_DEVICE when that does not fit. Without the flag nothing here costs anything: the batches' counting kernel is then the one
+ * without the traversal step. */
+#define GC_COVERAGE_PER_BASE 1u
+#define GC_COVERAGE_LINKS 2u
+int gc_coverage_create2(const gc_graph* g, unsigned flags, gc_coverage** out);
+/* On a handle with links gc_coverage_add_traces additionally checks every traversal before anything is counted: the predecessor's offset is its segment's last base in that
+ * orientation, the new offset is 0, and the pair is a link of the graph - otherwise GC_ERR_INVALID and nothing is counted, segments included.
+ * gc_coverage_merge adds the link counters too; handles of which only one has links: GC_ERR_INVALID.
+ * The links as they stand: *from / *to malloc'd [*n_links] canonical bigraph ids in link order, *traversals malloc'd [*n_links]. Free with gc_free. */
+int gc_coverage_link_counts(gc_coverage* cov, int32_t** from, int32_t** to, uint64_t** traversals, uint64_t* n_links);
+/* Three more texts spelled on the device, each over rows [first, first + count) (count is cut at the table's end; first behind it: GC_ERR_INVALID), so that the caller bounds
+ * the text one call makes; text, len, line_off and n_lines as above.
+ * Links: "from\tfrom_orient\tto\tto_orient\ttraversals\n" per link, zero rows included, in link order; the call with first == 0 puts the head line
+ * "#from\tfrom_orient\tto\tto_orient\ttraversals\n" in front (counted in n_lines). A canonical (u, v) is spelled name(u >> 1), + for even u and - for odd, name(v >> 1) and
+ * likewise for v; a segment without a name prints its number.
+ * GFA segments (any handle): "S\tname\tLETTERS\tLN:i:<length>\tRC:i:<bases>\n" per segment in ascending segment number; LETTERS is the forward strand read from the graph on
+ * the device, upper case, the IUPAC code where a base is ambiguous; RC is the segment's bases count (RC / LN = its mean depth).
+ * GFA links: "L\tfrom\t+-\tto\t+-\t0M\tRC:i:<traversals>\n" per link in link order.
+ * supported_only != 0 leaves out the segments with bases == 0 / the links with traversals == 0 (n_lines counts the lines written). A link that is kept has both its
+ * segments kept: a traversal covers a base on either side. */
+int gc_coverage_format_links(gc_coverage* cov, uint64_t first, uint64_t count, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
+int gc_coverage_format_gfa_segments(gc_coverage* cov, uint64_t first, uint64_t count, int supported_only, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
+int gc_coverage_format_gfa_links(gc_coverage* cov, uint64_t first, uint64_t count, int supported_only, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
+
 /* gc_format_gam with the zlib level of the gzip members chosen by the caller (-1 = Z_DEFAULT_COMPRESSION, what the reference's GzipOutputStream uses and gc_format_gam
  * gives; 0..9). The inflated stream is the same at every level; deflate at the default level costs ~1 ms of CPU per 10 kb read - more than the whole alignment costs the
  * GPU - so a host that writes GAM at the hot path's rate wants level 1 (or its own compressor on the bytes of level 0), or GC_GAM_DEVICE_HUFFMAN: the members are then

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Times of the coverage accumulators (gc_coverage_*; --coverage-out / --base-coverage-out) on bench.py's default graph and read set (config 2: SynthGraph(50.8 Mbp,
 seed=7), 10 000 reads of 10 kb, seed 11). Not bench.py and gated by nothing: one JSON line. Reported: the device time of k_cov_add per batch by HIP events (the library's
-GC_DEBUG_TIMES line; medians of --repeat batches after one warm-up) with and without the per-base depth, beside the whole call's wall time with and without a handle;
-the finish step's wall time for each table and the bytes that come down; and with --command the command's reads/s with -a x.gaf alone and with both tables beside it.
+GC_DEBUG_TIMES line; medians of --repeat batches after one warm-up) with and without the per-base depth and with the link table (--link-coverage-out /
+--coverage-gfa-out / --supported-subgraph-out), beside the whole call's wall time with and without a handle; the finish step's wall time for each table and for the two
+tagged graphs and the bytes that come down; and with --command the command's reads/s with -a x.gaf alone and with both tables beside it.
     python3 scripts/coverage_times.py [--backbone BP] [--reads N] [--read-len L] [--repeat K] [--command]"""
 import argparse
 import json
@@ -69,8 +70,8 @@ def main():
         aligner = gca.Aligner(graph, seeder, long_pass=True, device_output=1)
         line = re.compile(r"coverage: k_cov_add over ([0-9]+) alignments in the cell pool and ([0-9]+) chained winners \(([0-9]+) cells up\), ([0-9.]+) ms on the device, ([0-9.]+) ms in all")
         out["device_ms"], out["align_batch_wall_ms_with_debug_times"], out["finish"] = {}, {}, {}
-        for key, per_base in (("without_handle", None), ("bases_only", False), ("with_per_base_depth", True)):
-            cov = gca.Coverage(graph, per_base=per_base) if per_base is not None else None
+        for key, per_base, links in (("without_handle", None, False), ("bases_only", False, False), ("with_per_base_depth", True, False), ("bases_and_links", False, True), ("bases_only_again", False, False)):
+            cov = gca.Coverage(graph, per_base=per_base, links=links) if per_base is not None else None
             aligner.set_coverage(cov)
             kernel, in_all, walls = [], [], []
             for i in range(args.repeat + 1):
@@ -100,6 +101,14 @@ def main():
                     finish.update(base_table_ms=round((time.time() - t0) * 1e3, 3), base_table_bytes=len(runs), runs=runs.count(b"\n"),
                                   depth_bytes_on_the_device=4 * (int(graph.SizeInBP()) // 2))
                     del runs
+                if links:
+                    for name, spell in (("link_table", cov.link_table), ("coverage_gfa", lambda: b"".join(t for t, _ in cov.gfa_pieces())),
+                                        ("supported_subgraph", lambda: b"".join(t for t, _ in cov.gfa_pieces(supported_only=True)))):
+                        t0 = time.time()
+                        text = spell()
+                        finish.update({name + "_ms": round((time.time() - t0) * 1e3, 3), name + "_bytes": len(text), name + "_lines": text.count(b"\n")})
+                        del text
+                    finish["link_bytes_on_the_device"] = 16 * len(cov.link_counts()[0])
                 out["finish"][key] = finish
                 aligner.set_coverage(None)
                 cov.close()
