@@ -182,7 +182,7 @@
 			stitchInfo = st->hStitchInfo.reserve<StitchInfo>(n);
 			hStitchCursor = st->hStitchCursor.reserve<unsigned long long>(1);
 			HIP_CHECK(hipMemsetAsync(dCursor, 0, sizeof(unsigned long long), stream));
-			const int stitchClass = sw.stitchClass.value_or(maxReadLen > 16384 ? 3 : 0);
+			const int stitchClass = sw.stitchClass.value_or(pass.longestRead() > 16384 ? 3 : 0);
 			launchStitch(stream, G->dev, dJobs, (uint32_t)n, dAnchors, dFrags, dFragStatus, dChainOut, dChainLen, dChainStatus, dPathPool, pathCapacity, (long long)P->colinear_gap, dSlotOf,
 				dRegions, dStitchNodes, stitchDenseCap, dCursor, dStitchInfo,
 				(uint32_t)capacityOr(sw.testStitchSetMax, P->capacity.stitch_set_max, 0), (uint32_t)capacityOr(sw.testStitchBfsCap, P->capacity.stitch_bfs_cap, 0),

@@ -198,19 +198,19 @@
 				const LongAln& al = glue[r].longAlns[jobAln[k]];
 				hJobsOut[k] = OutJob { al.traceOff, R->offsets[r], al.traceLen, (uint32_t)(R->offsets[r + 1] - R->offsets[r]), flags, 0 };
 			}
-		hipStream_t q = st->longStream;   // (the pass and its decision are done with it)
+		hipStream_t q = st->longPass.longStream;   // (the pass and its decision are done with it)
 		OutJob* dJobsOut = st->outJobs.reserve<OutJob>(nOutJobs);
 		OutRec* dRecs = st->outRecs.reserve<OutRec>(nOutJobs);
 		uint64_t* dOffsets = st->outOffsets.reserve<uint64_t>(3 * (nOutJobs + 1));
 		unsigned long long* dTotals = st->outTotals.reserve<unsigned long long>(4);
-		uint32_t* dMapSizes = (P->device_output & 4) ? st->outMapSizes.reserve<uint32_t>(std::max<uint64_t>(1, hLongSmall[0]))   /* one word per cell of the pool in use */ : nullptr;
+		uint32_t* dMapSizes = (P->device_output & 4) ? st->outMapSizes.reserve<uint32_t>(std::max<uint64_t>(1, pass.cellsAsked()))   /* one word per cell of the pool in use */ : nullptr;
 		unsigned long long* hTotals = st->hOutTotals.reserve<unsigned long long>(4);
 		HIP_CHECK(hipMemcpyAsync(dJobsOut, hJobsOut, nOutJobs * sizeof(OutJob), hipMemcpyHostToDevice, q));
 		hipEvent_t timed[6] = {};   // GC_DEBUG_TIMES: device time of the encoder's and the corrected reads' kernels, each pass between events of its own
 		if (sw.debugTimes) for (auto& e : timed) HIP_CHECK(hipEventCreate(&e));
 		auto mark = [&](int k) { if (timed[k]) HIP_CHECK(hipEventRecord(timed[k], q)); };
 		mark(0);
-		launchOutCount(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, dLongCells, R->devBases, dRecs, dOffsets, dMapSizes, dTotals);
+		launchOutCount(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), R->devBases, dRecs, dOffsets, dMapSizes, dTotals);
 		mark(1);
 		HIP_CHECK(hipMemcpyAsync(hTotals, dTotals, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
 		// corrected reads (device_output & 8; gc_corrected.hip): their own kernels behind the encoder's on the same stream, their count and text beside the encoder's
@@ -221,7 +221,7 @@
 			dCorrOffsets = st->corrOffsets.reserve<uint64_t>(nOutJobs + 1);
 			unsigned long long* dCorrTotal = st->corrTotal.reserve<unsigned long long>(1);
 			hCorrTotal = st->hCorrTotal.reserve<unsigned long long>(1);
-			launchCorrectedCount(q, G->dev, dJobsOut, (uint32_t)nOutJobs, dLongCells, dCorrLens, dCorrOffsets, dCorrTotal);
+			launchCorrectedCount(q, G->dev, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), dCorrLens, dCorrOffsets, dCorrTotal);
 			HIP_CHECK(hipMemcpyAsync(hCorrTotal, dCorrTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
 		}
 		mark(2);
@@ -231,7 +231,7 @@
 		char* dCigar = st->outCigarText.reserve<char>(cigarBytes + 1);
 		uint8_t* dVg = st->outVgBytes.reserve<uint8_t>(vgBytes + 1);
 		mark(3);
-		launchOutWrite(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, dLongCells, R->devBases, dRecs, dOffsets, dMapSizes, dPath, dCigar, dVg);
+		launchOutWrite(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), R->devBases, dRecs, dOffsets, dMapSizes, dPath, dCigar, dVg);
 		mark(4);
 		OutRec* recs = st->hOutRecs.reserve<OutRec>(nOutJobs);
 		uint64_t* offs = st->hOutOffsets.reserve<uint64_t>(3 * (nOutJobs + 1));
@@ -248,7 +248,7 @@
 		if (corrected) {
 			corrBytes = *hCorrTotal;
 			char* dCorrText = st->corrText.reserve<char>(corrBytes + 1);
-			launchCorrectedWrite(q, G->dev, dJobsOut, (uint32_t)nOutJobs, dLongCells, dCorrLens, dCorrOffsets, dCorrText);
+			launchCorrectedWrite(q, G->dev, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), dCorrLens, dCorrOffsets, dCorrText);
 			mark(5);
 			corrLens = st->hCorrLens.reserve<uint32_t>(nOutJobs);
 			uint64_t* corrOffs = st->hCorrOffsets.reserve<uint64_t>(nOutJobs + 1);
@@ -311,7 +311,7 @@
 			if (nKept) {
 				uint8_t* dKeep = st->covKeep.reserve<uint8_t>(nOutJobs);
 				HIP_CHECK(hipMemcpyAsync(dKeep, hKeep, nOutJobs, hipMemcpyHostToDevice, stream));
-				launchCoverageAdd(stream, cov->dev, cov->links, (const OutJob*)st->outJobs.ptr, (uint32_t)nOutJobs, dKeep, dLongCells, cov->dBases, cov->dDepth, cov->dBad);
+				launchCoverageAdd(stream, cov->dev, cov->links, (const OutJob*)st->outJobs.ptr, (uint32_t)nOutJobs, dKeep, pass.deviceCells(), cov->dBases, cov->dDepth, cov->dBad);
 			}
 		}
 		for (const OutEntry& en : outEntries) if (en.source == 1) { nWinners++; winnerCells += glue[en.read].chainTraceNode.size(); }
@@ -452,7 +452,7 @@
 				chainLen[r] = 0; chainScore[r] = 0; chainStatus[r] = 0;
 				gl.stitched = StitchedPath();
 				gl.chainEditDistance = -1;
-				if (P->long_pass) seedsExtendedLong[r] = hLongResults[r].seedsExtended;
+				if (P->long_pass) seedsExtendedLong[r] = pass.results()[r].seedsExtended;
 				return;
 			}
 			if (chainStatus[r] != 0) { gl.capacityExceeded = true; chainLen[r] = 0; chainScore[r] = 0; }
@@ -470,8 +470,8 @@
 				seedsExtended[r] += fragExtended[F];
 			}
 			if (P->long_pass) {
-				seedsExtendedLong[r] = hLongResults[r].seedsExtended;
-				if (hLongResults[r].status == 1) failedAssertion[r] = 1;
+				seedsExtendedLong[r] = pass.results()[r].seedsExtended;
+				if (pass.results()[r].status == 1) failedAssertion[r] = 1;
 			}
 			if (!deviceAnchors) forEachAnchor(r, [&](uint64_t slot, uint64_t F) {
 				gl.nAnchors++;
@@ -562,7 +562,7 @@
 			res->seeds_extended[r] = seedsExtended[r];
 			res->seeds_extended_long[r] = seedsExtendedLong[r];
 			res->flatten_ties[r] = readTies[r];                                        // (counted for every extension the reference would have run, whatever became of the read)
-			res->flatten_ties_long[r] = P->long_pass ? hLongResults[r].pad : 0;
+			res->flatten_ties_long[r] = P->long_pass ? pass.results()[r].pad : 0;
 			res->read_longall_off[r] = gl.longBegin;
 			res->read_path_off[r] = gl.stitchedBegin;
 			res->read_long_off[r] = gl.longSelectedBegin;
@@ -587,7 +587,7 @@
 					res->longall_start[la] = al.start; res->longall_end[la] = al.end; res->longall_score[la] = al.score;
 					res->long_trace_off[la] = P->keep_traces ? lt : 0;
 					if (P->keep_traces) for (uint32_t i = 0; i < al.traceLen; i++, lt++) {
-						const LongCell& c = longCells[al.traceOff + i];
+						const LongCell& c = pass.stagedCells()[al.traceOff + i];
 						res->long_trace_node[lt] = c.node; res->long_trace_offset[lt] = c.offset; res->long_trace_seqpos[lt] = c.seqPos; res->long_trace_switch[lt] = (uint8_t)c.nodeSwitch;
 					}
 					la++;
@@ -661,8 +661,8 @@
 			fprintf(stderr, "[gc mem] stream %p holds %.2f GB on the device:%s\n", (void*)st, total / 1073741824.0, line.c_str());
 			fprintf(stderr, "[gc mem] %llu reads, %llu seed occurrences, %llu fragments, %llu anchor slots (%llu extensions run); trace pool %.2f of %.2f G cells, anchor path pool %.2f of %.2f G words, whole-read cells %.2f of %.2f G\n",
 				(unsigned long long)n, (unsigned long long)nSeedsTotal, (unsigned long long)nFrags, (unsigned long long)nSlots, (unsigned long long)res->counters[4], hSmall[1] / 1e9, traceBudget / 1e9, hSmall[2] / 1e9, pathCapacity / 1e9,
-				P->long_pass ? hLongSmall[0] / 1e9 : 0.0, cellBudget / 1e9);
+				P->long_pass ? pass.cellsAsked() / 1e9 : 0.0, pass.cellCapacity() / 1e9);
 		}
 		if (sw.debugTimes) fprintf(stderr, "[gc cpu] %.0f ms up to the end of the batch (the join came at %.0f)\n", processCpuMs() - cpuCall, cpuJoined - cpuCall);
-		if (sw.debugTimes) fprintf(stderr, "[gc times] batch timeline (ms from the call): whole-read pass started %.1f, joined %.1f, assembly began %.1f, done %.1f\n", (tLongWall0 - tTotal) / 1e3, (tJoined - tTotal) / 1e3, (tAsm - tTotal) / 1e3, (nowUs() - tTotal) / 1e3);
+		if (sw.debugTimes) fprintf(stderr, "[gc times] batch timeline (ms from the call): whole-read pass started %.1f, joined %.1f, assembly began %.1f, done %.1f\n", (pass.startedUs() - tTotal) / 1e3, (tJoined - tTotal) / 1e3, (tAsm - tTotal) / 1e3, (nowUs() - tTotal) / 1e3);
 	}

@@ -310,32 +310,4 @@
 		chainScore = zeroLongs.data();
 	}
 
-	// ---------------- the pass thread ends (its after-pass stage included)
-	void joinWholeReadPass()
-	{
-		// ---------------- whole-read pass results
-		tJoined = nowUs();
-		if (P->long_pass) {
-			double tJoin0 = nowUs();
-			longThread.join();
-			tJoined = nowUs();
-			cpuJoined = processCpuMs();
-			if (sw.debugTimes) fprintf(stderr, "[gc times] main thread waited %.1f ms for the whole-read pass\n", (tJoined - tJoin0) / 1e3);
-			if (longError) std::rethrow_exception(longError);
-			res->kernel_us[4] = longExtendUs;
-			res->counters_long[6] = longRounds;
-			res->kernel_us[5] = longWallEndUs - (longWallBeginUs > 0.0 ? longWallBeginUs : tLongWall0);   // whole-read pass, wall clock from the token to its release
-			for (uint64_t r = 0; r < n; r++) if (glue[r].capacityExceededLong) glue[r].capacityExceeded = true;
-			if (P->keep_traces) {
-				const uint64_t cellsUsed = std::min<uint64_t>(hLongSmall[0], cellBudget);   // (the cursor counts refused requests too: a full pool leaves it beyond the pool's end)
-				LongCell* staged = st->hLongCells.reserve<LongCell>(cellsUsed);
-				if (cellsUsed) HIP_CHECK(hipMemcpyAsync(staged, dLongCells, cellsUsed * sizeof(LongCell), hipMemcpyDeviceToHost, st->longStream));
-				syncStream(st->longStream);
-				longCells = staged;
-			}
-		}
-
-		if (sw.debugTimes) fprintf(stderr, "[gc times] after the whole-read pass: selection + its edit distances %.1f ms\n", (nowUs() - tJoined) / 1e3);
-
-	}
 

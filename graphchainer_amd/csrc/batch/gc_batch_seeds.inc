@@ -55,7 +55,7 @@
 		stg.sortBuf = (GlueElem*)st->glueSort.reserve<uint8_t>(seedCap * glueElemBytes());
 		stg.sortScratch = st->gluePos.reserve<uint32_t>(3 * seedCap + 64 * n + 64);
 		stg.winBuf = st->glueWin.reserve<uint32_t>(4 * winCap);
-		dLongSeeds = st->longSeeds.reserve<LongSeed>(P->long_pass ? seedCap : 0);
+		dPassSeeds = st->longSeeds.reserve<LongSeed>(P->long_pass ? seedCap : 0);
 		dReadSeeds = st->readSeeds.reserve<FragSeed>(seedCap);
 		dFrags = st->frags.reserve<Fragment>(winCap);
 		dFragFirstSeed = st->fragFirstSeed.reserve<uint32_t>(winCap);
@@ -64,9 +64,9 @@
 		GlueRead* hGlueOut = st->hGlueOut.reserve<GlueRead>(n);
 		jobs = st->hJobs.reserve<ReadChainJob>(n);
 		if (H) launchSeedGlueHits(stream, G->dev, R->devOffsets, (uint32_t)n, R->devReadInvalid, H->dev, dSeedOff, dWinCapOff, (uint32_t)P->split_len, (uint32_t)P->split_gap, P->long_pass != 0, stg,
-			st->gluePerRead.reserve<uint32_t>(6 * (n + 1)), dLongSeeds, dReadSeeds, dFrags, dFragFirstSeed, dJobs, dGlueOut, dGlueCursors, P->force_global != 0 || clip.on());
+			st->gluePerRead.reserve<uint32_t>(6 * (n + 1)), dPassSeeds, dReadSeeds, dFrags, dFragFirstSeed, dJobs, dGlueOut, dGlueCursors, P->force_global != 0 || clip.on());
 		else launchSeedGlue(stream, S->dev, G->dev, R->devOffsets, (uint32_t)n, R->devReadInvalid, dMatches, dReadMatchOff, dReadMatchCount, dSeedOff, dWinCapOff, P->seed_density,
-			(uint32_t)P->split_len, (uint32_t)P->split_gap, P->long_pass != 0, stg, st->gluePerRead.reserve<uint32_t>(6 * (n + 1)), dLongSeeds, dReadSeeds, dFrags, dFragFirstSeed, dJobs, dGlueOut, dGlueCursors, P->force_global != 0 || clip.on());
+			(uint32_t)P->split_len, (uint32_t)P->split_gap, P->long_pass != 0, stg, st->gluePerRead.reserve<uint32_t>(6 * (n + 1)), dPassSeeds, dReadSeeds, dFrags, dFragFirstSeed, dJobs, dGlueOut, dGlueCursors, P->force_global != 0 || clip.on());
 		if (n) HIP_CHECK(hipMemcpyAsync(hGlueOut, dGlueOut, n * sizeof(GlueRead), hipMemcpyDeviceToHost, stream));
 		if (n) HIP_CHECK(hipMemcpyAsync(jobs, dJobs, n * sizeof(ReadChainJob), hipMemcpyDeviceToHost, stream));
 		HIP_CHECK(hipMemcpyAsync(hGlueSmall, dGlueCursors, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));

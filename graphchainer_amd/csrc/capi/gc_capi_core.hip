@@ -151,10 +151,9 @@ int gc_stream_create(gc_stream** out)
 		HIP_CHECK(hipGetDevice(&st->device));
 		if (st->device < 0 || st->device >= 16) throw std::runtime_error("gc_stream_create: device index beyond the 16 per-device slots of the whole-read token and scratch");
 		createStream(&st->stream);       // non-blocking: uploads of another batch on the null stream do not serialise with this one
-		createStream(&st->longStream);
+		createStream(&st->longPass.longStream);
 		for (auto& e : st->ev) HIP_CHECK(hipEventCreate(&e));
 		for (auto& e : st->fragEv) HIP_CHECK(hipEventCreate(&e));
-		for (auto& e : st->longEv) HIP_CHECK(hipEventCreate(&e));
 		return (int)GC_OK;
 	});
 	if (rc != GC_OK) { delete st; return rc; }

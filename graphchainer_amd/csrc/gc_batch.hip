@@ -1,16 +1,9 @@
-// gc_align_batch: the batch pipeline (BatchRun) - seeding, the whole-read pass on its own thread, the fragment pipeline, chaining, stitching, edit distances, the decision, output encoding, result assembly.
+// gc_align_batch: the batch pipeline (BatchRun) - seeding, the whole-read pass on its own thread (WholeReadPass, batch/gc_long_pass.hpp), the fragment pipeline, chaining, stitching,
+// edit distances, the decision, output encoding, result assembly.
 #include "gc_runtime.hpp"
+#include "batch/gc_long_pass.hpp"
 
 extern "C" {
-
-// gc_params_ext as the batch runs with it: the cut-off the reference would run with (0.66 for an X-drop without one, src/AlignerMain.cpp:443-448) and its error cost in double
-struct ClipOptions {
-	double cutoff = 0;     // preciseClippingIdentityCutoff; 0: clipping off
-	double errorCost = 0;  // XscoreErrorCost = c / (1 - c) + 1 (src/GraphAlignerCommon.h:108)
-	int32_t xDrop = 0;     // Xdropcutoff
-	bool on() const { return cutoff != 0; }
-	void apply(ExtendConfig& cfg) const { if (on()) { cfg.setClipErrorCost(errorCost); cfg.xDrop = xDrop; } }
-};
 
 struct BatchRun {
 	// ---- the call
@@ -22,7 +15,7 @@ struct BatchRun {
 	const gc::AlignmentGraph& hg;
 	WorkerPool& pool;
 	std::vector<ReadGlue>& glue;             // per-read host records, storage reused across batches
-	const hipStream_t stream;                // the fragment pipeline's stream (the whole-read pass has st->longStream / st->roundStream)
+	const hipStream_t stream;                // the fragment pipeline's stream (the whole-read pass has its own: st->longPass)
 	int evIdx = 0;
 	double tTotal = 0;
 	// ---- what the stages hand on (set by the stage named in the comment of each group)
@@ -31,7 +24,7 @@ struct BatchRun {
 	uint64_t nSlots = 0, nFrags = 0, nSeedsTotal = 0, traceBudget = 0;
 	uint32_t maxSlotsPerRead = 1, maxWindowSeeds = 0;
 	Fragment* dFrags = nullptr; uint32_t* dFragFirstSeed = nullptr; FragSeed* dReadSeeds = nullptr; ReadChainJob* dJobs = nullptr;   // written by the glue kernels
-	LongSeed* dLongSeeds = nullptr;                                          // the same seeds in the whole-read pass's order (long_pass)
+	LongSeed* dPassSeeds = nullptr;                                          // the same seeds in the whole-read pass's order (long_pass)
 	Fragment* frags = nullptr; ReadChainJob* jobs = nullptr;                 // host copies of dFrags / dJobs
 	FragSeed* readSeeds = nullptr; uint32_t* fragFirstSeed = nullptr;        // host copies of dReadSeeds / dFragFirstSeed, only with keep_seeds / keep_traces
 	hipEvent_t glueCopied = nullptr;   // the host copies of frags / seeds have arrived (waited for before the result assembly)
@@ -39,55 +32,9 @@ struct BatchRun {
 	unsigned long long* hSmall = nullptr;
 	unsigned long long* dCursors = nullptr;
 	unsigned long long* dCounters = nullptr;
-	// prepareWholeReadPass()
-	uint32_t firstAlnCap = 0;                     // alignment slots every read starts with
-	uint64_t alnSlots = 0;                        // slots of the batch: n * firstAlnCap, plus the new slots of reads that outgrew theirs (growAlnSlots)
-	LongAln* hLongAlns = nullptr;
-	unsigned long long* hLongSmall = nullptr;
-	LongReadResult* hLongResults = nullptr;
-	LongCell* dLongCells = nullptr;
-	uint64_t cellBudget = 0;                      // capacity of the merged-trace cell pool (grown and the pass rerun when a batch overflows it)
-	unsigned long long* longScratchOfToken = nullptr;   // the device's shared extension scratch, set by the pass once it holds the token
-	// r4: the token is taken when the pass's FIRST extension kernel is about to be queued and given back when the last round's count (zero) has come down: a pass's first
-	// init / select / order / publish and the host's wait for the work count (each a launch that queues among the other batches' kernels), and its k_long_finish at the
-	// end, no longer sit between two passes' extension kernels
-	std::function<void()> longTokenTake, longTokenDrop;   // (set by the pass thread for its round loop)
-	RoundStream* passRounds = nullptr;   // between take and drop: the round loop's stream and events - the token slot's, or the gc_stream's own without a token (GC_LONG_TOKEN=0)
-	uint64_t longScratchWords = 0;
-	bool shareLongScratch = false;
-	double longExtendUs = 0; uint32_t longRounds = 0;   // the rounds' extension kernels (event pairs) and how many rounds had work, reruns of the pass included
 	const gc::EValueModel evalueModel { clip.on() ? clip.cutoff : 0.7 };   // src/Aligner.cpp:474-482: the clipping cut-off is the model's identity
-	struct DecisionPointers { EdPair* hPairs = nullptr; int64_t* hOut = nullptr; EdPair* dPairs = nullptr; int64_t* dOut = nullptr; char* dLetters = nullptr; uint32_t* dLettersLen = nullptr; } decisionPtr[2];
-	// ... the whole-read pass's own buffers and sizes (prepareWholeReadPass sets them; runLongRounds / growLongCells / longFallback / afterLongPass run on the pass thread)
-	LongJob* hJobs = nullptr;
-	bool cellPoolPinned = 0;
-	uint64_t waveWords = 0;
-	LongJob* dLongJobs = nullptr;
-	LongAln* dLongAlns = nullptr;
-	uint32_t cursorWords = 0;
-	uint64_t workCapacity = 0;       // entries of the rounds' work arrays
-	uint64_t roundTraceBudget = 0;   // words of the rounds' trace pool
-	unsigned long long* dLongCursor = nullptr;
-	LongState* dLongState = nullptr;
-	LongWork* dLongWork = nullptr;
-	LongWorkResult* dLongWorkResults = nullptr;
-	uint32_t* dCandSeed = nullptr;
-	uint32_t* dWorkLen = nullptr;
-	uint32_t* dRetryList = nullptr;
-	uint32_t* dOrder = nullptr;
-	unsigned long long* dRoundTrace = nullptr;
-	uint64_t scratchLanes = 0;
-	hipStream_t ls = nullptr;
-	ExtendConfig lcfg;
-	unsigned long long* dLongScratchOwn = nullptr;   // (this stream's own scratch: only without the one-pass-at-a-time token)
-	uint64_t maxReadLen = 1;
-	// startWholeReadPass()
-	std::thread longThread;
-	double passThreadCpuMs = 0;   // GC_DEBUG_TIMES: CPU time of the pass thread (read after the join)
-	std::exception_ptr longError;
-	double tLongWall0 = 0;
-	double longWallBeginUs = 0.0;   // when the pass first got the device's token (waiting for another batch's pass is not its own time; 0: not yet); written by the pass thread, read after the join
-	double longWallEndUs = 0.0;     // when it last gave the token back
+	// the whole-read pass: on its own host thread between pass.start() and pass.join(); what the two threads may touch meanwhile is written down in batch/gc_long_pass.hpp
+	WholeReadPass pass { sw, G, R, P, clip, st, pool, res, tCall };
 	// fragmentPipeline()
 	double tDev = 0;
 	uint32_t nWork = 0;
@@ -140,14 +87,15 @@ struct BatchRun {
 	const FastChainJob* fastChainJobs = nullptr;   // gc_params::fast_mode, per read: its stitched piece and the chain's (x, y); cells == 0: none
 	// withoutChaining()
 	std::vector<uint32_t> zeroWords; std::vector<unsigned long long> zeroLongs; std::vector<uint4> zeroPerRead;
-	// joinWholeReadPass()
+	// pass.join()
 	double tJoined = 0;
-	const LongCell* longCells = nullptr;   // keep_traces: the merged traces in pinned staging (a pageable destination made this copy 2-3 s per 10 k reads)
 
 	BatchRun(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, const ClipOptions& clip, gc_result* res, double tCall, double cpuCall)
 		: sw(sw), G(G), S(S), H(H), st(st), R(R), P(P), clip(clip), res(res), tCall(tCall), cpuCall(cpuCall), cpuJoined(cpuCall), n(R->offsets.size() - 1), hg(G->host), pool(WorkerPool::batch()), glue(st->glue),
 		  stream(st->stream) {}
-	~BatchRun() { if (longThread.joinable()) longThread.join(); }   // (an exception on the main thread must not leave the pass thread behind with dangling state)
+	// (an exception on the main thread must not leave the pass thread behind with dangling state - and the pass's hook writes the output stage's members, which the .inc files
+	// declare after `pass`: member order alone would destroy them before the pass object joins its thread)
+	~BatchRun() { pass.joinIfRunning(); }
 	BatchRun(const BatchRun&) = delete;
 	BatchRun& operator=(const BatchRun&) = delete;
 
@@ -170,9 +118,9 @@ struct BatchRun {
 			cpuAt = now; poolAt = poolNow;
 		};
 		seeds(); stageDone(0);
-		prepareWholeReadPass(); stageDone(1);
-		startWholeReadPass(); stageDone(2);
-		if (!P->colinear_chaining) { withoutChaining(); joinWholeReadPass(); stageDone(6); encodeOutput(); stageDone(8); assemble(); stageDone(9); st->batchesDone++; return; }
+		pass.prepare(dPassSeeds, nSeedsTotal); stageDone(1);
+		pass.start([this] { encodeOutputStart(); }); stageDone(2);
+		if (!P->colinear_chaining) { withoutChaining(); pass.join(tJoined, cpuJoined); stageDone(6); encodeOutput(); stageDone(8); assemble(); stageDone(9); st->batchesDone++; return; }
 		fragmentPipeline(); stageDone(3);
 		resultsBack(); stageDone(4);
 		// r5: the trace pool and the anchor path pool are sized by what the stream's batches have used, not by every slot's worst case (a 2 000 x 50 kb batch on a 960 Mbp
@@ -181,7 +129,7 @@ struct BatchRun {
 		res->counters[6] = poolReruns;
 		compactAnchors(); stageDone(4);
 		stitchAndChainDistances(); stageDone(5);
-		joinWholeReadPass(); stageDone(6);
+		pass.join(tJoined, cpuJoined); stageDone(6);
 		chainedAlignments(); stageDone(7);
 		encodeOutput(); stageDone(8);
 		assemble(); stageDone(9);
@@ -189,16 +137,15 @@ struct BatchRun {
 		st->batchesDone++;
 		if (cpuStages)
 			fprintf(stderr, "[gc cpu] main thread, ms of its own CPU: seeds %.1f, whole-read set-up %.1f + start %.1f, fragment pipeline %.1f, results back %.1f, stitching + chain distances %.1f, join %.1f, chained alignments %.1f, output %.1f, assembly %.1f; pass thread %.1f\n",
-				cpuStage[0], cpuStage[1], cpuStage[2], cpuStage[3], cpuStage[4], cpuStage[5], cpuStage[6], cpuStage[7], cpuStage[8], cpuStage[9], passThreadCpuMs);
+				cpuStage[0], cpuStage[1], cpuStage[2], cpuStage[3], cpuStage[4], cpuStage[5], cpuStage[6], cpuStage[7], cpuStage[8], cpuStage[9], pass.passCpuMs());
 		if (cpuStages)   // (with one batch in flight: this call's own; the pool's figure includes this thread's share of the jobs, which the line above counts too)
 			fprintf(stderr, "[gc cpu] worker pool jobs, ms of CPU over all threads, by stage: %.1f %.1f %.1f %.1f %.1f %.1f %.1f %.1f %.1f %.1f; the process in all %.1f\n",
 				poolStage[0], poolStage[1], poolStage[2], poolStage[3], poolStage[4], poolStage[5], poolStage[6], poolStage[7], poolStage[8], poolStage[9], processCpuMs() - processAt);
 	}
 
 #include "batch/gc_batch_seeds.inc"   // K1 seed lookup and the glue between it and the extension kernels
-#include "batch/gc_batch_long.inc"   // the whole-read pass: set-up, the round loop, fallback reruns, selection and NW distance, its own host thread
 #include "batch/gc_batch_fragments.inc"   // the fragment pipeline: windows, work items, extension and anchors in lazy rounds, chaining, stitching
-#include "batch/gc_batch_results.inc"   // what comes down: anchors, chains, stitched paths, the chains' NW distances; the pass thread's join
+#include "batch/gc_batch_results.inc"   // what comes down: anchors, chains, stitched paths, the chains' NW distances
 #include "batch/gc_batch_output.inc"   // the chained alignments' traces, the output encoders on the device, the flat result
 };
 

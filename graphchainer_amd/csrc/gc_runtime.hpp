@@ -18,6 +18,7 @@
 #include "host/gc_mxm_build.hpp"
 #include "host/gc_mxm_cache.hpp"
 #include "host/gc_layout.hpp"
+#include "host/gc_long_policy.hpp"
 #include "hip/gc_mxm_core.hpp"
 #include "hip/gc_seedfile_core.hpp"
 #include <hip/hip_runtime.h>
@@ -91,6 +92,8 @@ struct DeviceBuffer {   // growable device allocation owned by a stream object
 		}
 		return (T*)ptr;
 	}
+	// grows to count elements in a new block, the first usedCount elements copied over on `stream` (awaited before the old block goes); the pointer changes
+	template <typename T> T* growKeeping(size_t count, size_t usedCount, hipStream_t stream, bool tight = false);
 	void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
 	// a pool that a rerun sized from an overshooting request count comes back to what its batches use: called once, by the batch after the rerun (hipFree drains the device)
 	void shrinkTo(size_t needBytes, size_t floor)   // (floor: 64 MB; GC_TEST_POOL_SHRINK_FLOOR lets small pools shrink too)
@@ -104,7 +107,7 @@ struct DeviceBuffer {   // growable device allocation owned by a stream object
 // (two batches in flight on two gc_streams) only take turns at a finer grain and both finish late. With the token the second batch's
 // seeding, seed glue and fragment pipeline overlap the first batch's whole-read pass, and its own pass starts the moment the first
 // one ends - a software pipeline over batches (GC_LONG_TOKEN=0 turns it off).
-// r4 / r5: two tokens per device, each with a scratch of its own, for passes that cannot fill the chip (longTokenCount below)
+// r4 / r5: two tokens per device, each with a scratch of its own, for passes that cannot fill the chip (longTokenCount, host/gc_long_policy.hpp)
 using gc::LONG_TOKENS_MAX;
 struct PassTokens {
 	std::mutex m;
@@ -141,20 +144,8 @@ struct TokenHold {
 	void unlock() { if (slot >= 0) { tokens->release(slot); slot = -1; } }
 	~TokenHold() { unlock(); }
 };
-// r5: how many passes may run side by side on a device is decided per batch. A pass whose rounds cannot fill the chip - round 0 holds two work items per read, k_long_extend<1> has
-// 5 120 wave slots (256 CUs x 4 SIMDs x 5 waves) - shares the device with a second one: 2 000 x 50 kb reads on a 192 Mbp graph 4.0-4.2 k -> 5.0-5.3 k reads/s (`gpurun_out/r5_cfg5_tok`);
-// a pass that fills it (10 k x 10 kb: 20 000 items) keeps the device to itself (two side by side measured slower in r4). GC_LONG_TOKENS=1|2 overrides (read per batch: the tests switch
-// inside one process). The second token has a scratch of its own and is only taken when the device has the memory for it.
-inline constexpr uint64_t LONG_WAVE_SLOTS = 5120;
-// r6: ... and only while the fragment pipeline leaves the device room for it, told by the fragment extensions the stream's previous batch ran per read base (a count, not a time:
-// times under five batches in flight are residencies, and a rule on them would feed back on itself). On a 192 Mbp graph that is 0.09 and two passes side by side gave 4.2 -> 5.0 k
-// reads/s (r5); at 960 Mbp, where chance hits of 15-mers make it 0.42, the second pass that r6's freed memory suddenly had room for cost 4.31 -> 3.63 k (`gpurun_out/r6_cfg5_960p` / `_960q`)
-inline int longTokenCount(std::optional<int> tokensOverride, uint64_t nReads, uint64_t streamBatchesDone, double extensionsPerBase)
-{
-	if (tokensOverride) return *tokensOverride;
-	// (a stream's first batch sizes its buffers - pools that rerun and grow: a second scratch taken while the device still looks empty cost config 5 at 960 Mbp its fifth stream)
-	return streamBatchesDone > 0 && 2 * nReads + 128 <= LONG_WAVE_SLOTS && extensionsPerBase < 0.2 ? 2 : 1;
-}
+// (how many passes may run side by side is decided per batch: longTokenCount, host/gc_long_policy.hpp)
+using gc::longTokenCount;
 // The pass's extension scratch (up to 48 GB: one region per resident wave) is only touched while the token is held, so the gc_streams of a device share ONE
 // (r3: 85 -> 37 GB per stream for 10 k x 10 kb batches, which is what lets five batches be in flight on a 288 GB device instead of three). It belongs to the
 // token: reserved (grown) by the pass that holds it, freed when the device's last gc_stream goes.
@@ -243,6 +234,16 @@ inline void syncEvent(hipEvent_t ev)
 			if (spins >= 12 && sleepUs < 4 * pollUs) sleepUs += sleepUs / 4 + 1;
 		}
 	}
+}
+
+template <typename T> T* DeviceBuffer::growKeeping(size_t count, size_t usedCount, hipStream_t stream, bool tight)
+{
+	DeviceBuffer larger;
+	T* dLarger = larger.reserve<T>(count, tight);
+	if (usedCount) HIP_CHECK(hipMemcpyAsync(dLarger, ptr, usedCount * sizeof(T), hipMemcpyDeviceToDevice, stream));
+	syncStream(stream);
+	std::swap(ptr, larger.ptr); std::swap(bytes, larger.bytes);
+	return dLarger;
 }
 
 // Persistent worker pool for the per-read host work between the kernels: bookkeeping, selection, host stitching, result assembly (threads are created once per process).
@@ -723,11 +724,8 @@ struct gc_stream {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev[12] {};
 	hipEvent_t fragEv[16] {};   // r5: a (begin, end) pair around each of the lazy rounds' k_extend launches [0..7] and k_build_anchors launches [8..15]: kernel_us[1] / [2] are sums of exactly those
-	DeviceBuffer tmp, matches, readMatchOff, readMatchCount, cursors, readSeeds, fragFirstSeed, longRetryList, extLists, fragItems, fragRetryList, fragClaims, pendingFrags, fragNext, roundCounts, work, results, scratch, scratchRetry, tracePool, frags, fragSeeds, anchors, fragStatus, fragExtended, readTies, pathPool, jobs, chainOut, chainLen, chainScore, chainStatus, chainScratch, counters;
+	DeviceBuffer tmp, matches, readMatchOff, readMatchCount, cursors, readSeeds, fragFirstSeed, extLists, fragItems, fragRetryList, fragClaims, pendingFrags, fragNext, roundCounts, work, results, scratch, scratchRetry, tracePool, frags, fragSeeds, anchors, fragStatus, fragExtended, readTies, pathPool, jobs, chainOut, chainLen, chainScore, chainStatus, chainScratch, counters;
 	PinnedBuffer hFragDeclined, hReadSeeds, hFragFirstSeed, hFrags, hJobs, hAnchors, hFragStatus, hFragExtended, hReadTies, hChainOut, hChainLen, hChainScore, hChainStatus, hPathPool, hSmall;
-	// whole-read pass: runs on its own stream, concurrently with the fragment kernels
-	hipStream_t longStream = nullptr;
-	hipEvent_t longEv[2] {};
 	DeviceBuffer edPathNodes, edJobs, edLetters, edLettersLen, edPairs, edOut;
 	PinnedBuffer hEdPathNodes, hEdJobs, hEdPairs, hEdOut;
 	DeviceBuffer outJobs, outRecs, outOffsets, outMapSizes, outPathText, outCigarText, outVgBytes, outTotals;   // output encoding on the device (gc_output.hip)
@@ -743,31 +741,37 @@ struct gc_stream {
 	PinnedBuffer hEdPathJobs, hEdPathOps, hEdPathLen;
 	DeviceBuffer fastJobs, fastScore, fastTraceJobs, fastTrace, fastWritten;   // the chained alignment of gc_params::fast_mode (gc_fastchain.hip)
 	PinnedBuffer hFastJobs, hFastScore, hFastTraceJobs, hFastTrace, hFastWritten;
-	// whole-read decision (selection + edit distance of the best alignment)
-	struct LongDecision {
-		PinnedBuffer hJobs, hPairs, hOut;
-		DeviceBuffer jobs, letters, lettersLen, pairs, out;
-		EditDistanceRun run;
-		std::vector<uint32_t> pairRead;
-		uint32_t nPairs = 0;
-	} edLong[2];
-	uint64_t longCellsPerBase = 4;           // merged-trace cells per read base the whole-read pass reserves (10 kb ONT-like reads use 1.1, 50 kb CLR-like reads on a genome with repeats 9-10; grows by what a batch asks for)
+	// The whole-read pass's own: what batch/gc_long_pass.hip (WholeReadPass) works in, kept from batch to batch. While a batch's pass thread runs it is that thread's alone.
+	struct LongPass {
+		hipStream_t longStream = nullptr;        // the pass runs on its own stream, concurrently with the fragment kernels
+		// whole-read decision (selection + edit distance of the best alignment)
+		struct LongDecision {
+			PinnedBuffer hJobs, hPairs, hOut;
+			DeviceBuffer jobs, letters, lettersLen, pairs, out;
+			EditDistanceRun run;
+			std::vector<uint32_t> pairRead;
+			uint32_t nPairs = 0;
+		} edLong;
+		uint64_t longCellsPerBase = 4;           // merged-trace cells per read base the whole-read pass reserves (10 kb ONT-like reads use 1.1, 50 kb CLR-like reads on a genome with repeats 9-10; grows by what a batch asks for)
+		RoundStream ownRounds;                   // the round loop's stream WITHOUT the token (GC_LONG_TOKEN=0; created by the stream's first such pass). With it the rounds run on the token slot's stream
+		                                         // (SharedLongScratch::rounds); longStream carries the pass's uploads, its first select, reruns and decision
+		DeviceBuffer longRetryList, longJobs, longAlns, longResults, longScratch, longCells, longCursor, longJobsFallback, longResultsFallback, longScratchFallback;
+		DeviceBuffer longState, longWork, longWorkResults, longRoundTrace, longCandSeed, longWorkLen, longOrder;
+		PinnedBuffer hLongJobs, hLongAlns, hLongResults, hLongSmall, hLongCells;
+	} longPass;
 	double fragShare = 0;                     // fragment extensions per read base in the stream's last batch (longTokenCount)
 	uint64_t batchesDone = 0;                 // batches this stream has finished (a second whole-read token is only taken from the second batch on: the first sizes the stream's buffers)
 	bool poolsRerun = false;                  // the last batch ran its fragment pipeline again with larger pools: the next one gives back what that overshot
 	double traceCellsPerSlot = 0, pathWordsPerSlot = 0;   // what this stream's batches have used of the fragment pipeline's trace pool / anchor path pool per anchor slot (0: no batch yet)
-	RoundStream ownRounds;                   // the round loop's stream WITHOUT the token (GC_LONG_TOKEN=0; created by the stream's first such pass). With it the rounds run on the token slot's stream
-	                                         // (SharedLongScratch::rounds); longStream carries the pass's uploads, its first select, reruns and decision
-	DeviceBuffer longSeeds, longJobs, longAlns, longResults, longScratch, longCells, longCursor, longJobsFallback, longResultsFallback, longScratchFallback;
+	DeviceBuffer longSeeds;   // the seeds in the whole-read pass's order: written by the seeding stage, read by the pass
 	DeviceBuffer gluePerRead, glueCursors, glueOut, glueSeedCap, glueSeedOff, glueWinCapOff, glueU32[8], glueSort, gluePos, glueWin;   // seed glue on the device (gc_seedglue.hip)
 	PinnedBuffer hGlueOut, hGlueWinCapOff, hGlueSmall;
-	DeviceBuffer longState, longWork, longWorkResults, longRoundTrace, longCandSeed, longWorkLen, longOrder;
-	PinnedBuffer hLongJobs, hLongAlns, hLongResults, hLongSmall, hLongCells;
 	// every device allocation of the stream with its size (GC_DEBUG_TIMES: "[gc mem]" lines; the whole-read decision's and the edit-distance runs' own buffers are listed by their owners)
 	template <typename F> void forEachDeviceBuffer(F f) const
 	{
+		const LongPass& L = longPass;
 		f("tmp", tmp.bytes); f("matches", matches.bytes); f("readMatchOff", readMatchOff.bytes); f("readMatchCount", readMatchCount.bytes); f("cursors", cursors.bytes); f("readSeeds", readSeeds.bytes);
-		f("fragFirstSeed", fragFirstSeed.bytes); f("longRetryList", longRetryList.bytes); f("extLists", extLists.bytes); f("pendingFrags", pendingFrags.bytes); f("fragNext", fragNext.bytes);
+		f("fragFirstSeed", fragFirstSeed.bytes); f("longRetryList", L.longRetryList.bytes); f("extLists", extLists.bytes); f("pendingFrags", pendingFrags.bytes); f("fragNext", fragNext.bytes);
 		f("roundCounts", roundCounts.bytes); f("fragItems", fragItems.bytes); f("fragRetryList", fragRetryList.bytes); f("work", work.bytes); f("results", results.bytes); f("scratch", scratch.bytes); f("scratchRetry", scratchRetry.bytes); f("tracePool", tracePool.bytes);
 		f("frags", frags.bytes); f("fragSeeds", fragSeeds.bytes); f("anchors", anchors.bytes); f("fragStatus", fragStatus.bytes); f("fragExtended", fragExtended.bytes); f("readTies", readTies.bytes);
 		f("pathPool", pathPool.bytes); f("jobs", jobs.bytes); f("chainOut", chainOut.bytes); f("chainLen", chainLen.bytes); f("chainScore", chainScore.bytes); f("chainStatus", chainStatus.bytes);
@@ -779,23 +783,22 @@ struct gc_stream {
 		f("anchorPerRead", anchorPerRead.bytes); f("anchorSlotEnd", anchorSlotEnd.bytes); f("anchorOff", anchorOff.bytes); f("anchorDense", anchorDense.bytes);
 		f("edPathJobs", edPathJobs.bytes); f("edPathOps", edPathOps.bytes); f("edPathLen", edPathLen.bytes); f("edPathScratch", edPathScratch.bytes); f("longSeeds", longSeeds.bytes);
 		f("fastJobs", fastJobs.bytes); f("fastScore", fastScore.bytes); f("fastTraceJobs", fastTraceJobs.bytes); f("fastTrace", fastTrace.bytes); f("fastWritten", fastWritten.bytes);
-		f("longJobs", longJobs.bytes); f("longAlns", longAlns.bytes); f("longResults", longResults.bytes); f("longScratch", longScratch.bytes); f("longCells", longCells.bytes);
-		f("longCursor", longCursor.bytes); f("longJobsFallback", longJobsFallback.bytes); f("longResultsFallback", longResultsFallback.bytes); f("longScratchFallback", longScratchFallback.bytes);
+		f("longJobs", L.longJobs.bytes); f("longAlns", L.longAlns.bytes); f("longResults", L.longResults.bytes); f("longScratch", L.longScratch.bytes); f("longCells", L.longCells.bytes);
+		f("longCursor", L.longCursor.bytes); f("longJobsFallback", L.longJobsFallback.bytes); f("longResultsFallback", L.longResultsFallback.bytes); f("longScratchFallback", L.longScratchFallback.bytes);
 		f("gluePerRead", gluePerRead.bytes); f("glueCursors", glueCursors.bytes); f("glueOut", glueOut.bytes); f("glueSeedCap", glueSeedCap.bytes); f("glueSeedOff", glueSeedOff.bytes);
 		f("glueWinCapOff", glueWinCapOff.bytes); f("glueU32[0]", glueU32[0].bytes); f("glueU32[1]", glueU32[1].bytes); f("glueU32[2]", glueU32[2].bytes); f("glueU32[3]", glueU32[3].bytes);
 		f("glueU32[4]", glueU32[4].bytes); f("glueU32[5]", glueU32[5].bytes); f("glueU32[6]", glueU32[6].bytes); f("glueU32[7]", glueU32[7].bytes); f("glueSort", glueSort.bytes);
-		f("gluePos", gluePos.bytes); f("glueWin", glueWin.bytes); f("longState", longState.bytes); f("longWork", longWork.bytes); f("longWorkResults", longWorkResults.bytes);
-		f("longRoundTrace", longRoundTrace.bytes); f("longCandSeed", longCandSeed.bytes); f("longWorkLen", longWorkLen.bytes); f("longOrder", longOrder.bytes);
-		for (int k = 0; k < 2; k++) { f("edLong.letters", edLong[k].letters.bytes); f("edLong.jobs+pairs+out", edLong[k].jobs.bytes + edLong[k].lettersLen.bytes + edLong[k].pairs.bytes + edLong[k].out.bytes); }
+		f("gluePos", gluePos.bytes); f("glueWin", glueWin.bytes); f("longState", L.longState.bytes); f("longWork", L.longWork.bytes); f("longWorkResults", L.longWorkResults.bytes);
+		f("longRoundTrace", L.longRoundTrace.bytes); f("longCandSeed", L.longCandSeed.bytes); f("longWorkLen", L.longWorkLen.bytes); f("longOrder", L.longOrder.bytes);
+		f("edLong.letters", L.edLong.letters.bytes); f("edLong.jobs+pairs+out", L.edLong.jobs.bytes + L.edLong.lettersLen.bytes + L.edLong.pairs.bytes + L.edLong.out.bytes);
 	}
 	~gc_stream()
 	{
 		for (auto& e : ev) if (e) (void)hipEventDestroy(e);
 		for (auto& e : fragEv) if (e) (void)hipEventDestroy(e);
-		for (auto& e : longEv) if (e) (void)hipEventDestroy(e);
-		ownRounds.release();
+		longPass.ownRounds.release();
 		if (stream) (void)hipStreamDestroy(stream);
-		if (longStream) (void)hipStreamDestroy(longStream);
+		if (longPass.longStream) (void)hipStreamDestroy(longPass.longStream);
 	}
 };
 
@@ -1002,6 +1005,15 @@ inline int64_t capacityOr(std::optional<int64_t> env, int64_t param, int64_t aut
 	if (env) return *env;
 	return param != 0 ? param : automatic;
 }
+
+// gc_params_ext as the batch runs with it: the cut-off the reference would run with (0.66 for an X-drop without one, src/AlignerMain.cpp:443-448) and its error cost in double
+struct ClipOptions {
+	double cutoff = 0;     // preciseClippingIdentityCutoff; 0: clipping off
+	double errorCost = 0;  // XscoreErrorCost = c / (1 - c) + 1 (src/GraphAlignerCommon.h:108)
+	int32_t xDrop = 0;     // Xdropcutoff
+	bool on() const { return cutoff != 0; }
+	void apply(ExtendConfig& cfg) const { if (on()) { cfg.setClipErrorCost(errorCost); cfg.xDrop = xDrop; } }
+};
 
 template <typename F>
 inline int guarded(F&& f)

@@ -24,10 +24,10 @@ CSRC = os.path.join(ROOT, "graphchainer_amd", "csrc")
 def product_thresholds():
     """The capacities the tiers are placed against, read from the sources that define them (never by running the product)."""
     kernels = open(os.path.join(CSRC, "hip", "gc_chain.hip")).read()
-    long_pass = open(os.path.join(CSRC, "batch", "gc_batch_long.inc")).read()
+    long_policy = open(os.path.join(CSRC, "host", "gc_long_policy.hpp")).read()
     lds_anchors = int(re.search(r"#define CHAIN_LDS_ANCHORS (\d+)", kernels).group(1))
     assert "job.nSlots > 2 * LDS_ANCHORS" in kernels and "LDS == 2 ? CHAIN_LDS_ANCHORS / 2 : CHAIN_LDS_ANCHORS" in kernels
-    first_cap = int(re.search(r"firstAlnCap = \(uint32_t\)std::max<uint64_t>\((\d+), maxReadLen / 512\)", long_pass).group(1))
+    first_cap = int(re.search(r"longFirstAlnCap\(uint64_t maxReadLen\) \{ return \(uint32_t\)std::max<uint64_t>\((\d+), maxReadLen / 512\); \}", long_policy).group(1))
     return {"small_class": lds_anchors // 2, "large_class": lds_anchors, "slot_routing_small": lds_anchors, "slot_routing_large": 2 * lds_anchors, "alignments": first_cap, "chain_16bit": 65535}
 
 
