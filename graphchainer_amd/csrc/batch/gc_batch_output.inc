@@ -1,4 +1,5 @@
-// gc_batch.hip, stage by stage (r6: one file of 2 000 lines before): the chained alignments' traces, the output encoders on the device, the flat result.
+// gc_batch.hip, stage by stage (r6: one file of 2 000 lines before): the chained alignments' traces and the flat result. The output encoders on the device, which run
+// between the two, are a class of their own (OutputEncoder, batch/gc_output_encoder.hpp): assemble() hands it the result to fill.
 // Member functions of struct BatchRun - this file is included INSIDE the struct's body (gc_batch.hip), which holds the members, the constructor and run().
 	// ---------------- edlib path + trace of the chained alignments that are wanted (src/Aligner.cpp:845-905)
 	void chainedAlignments()
@@ -150,273 +151,6 @@
 			gl.chainTraceSeqPos.assign(tSeqPos + b, tSeqPos + e); gl.chainTraceSwitch.assign(tSwitch + b, tSwitch + e);
 		});
 		return m;
-	}
-
-	// ---------------- the final alignments encoded where their traces are (params->device_output; gc_output.hip): the GAF path / CIGAR text and the vg::Path bytes of
-	// every alignment the reference would write for the batch (src/Aligner.cpp:901-920,1003-1023), so that no trace cell has to come down for the writers
-	struct OutEntry { uint32_t read, aln; uint8_t source; };   // aln: index into the read's longAlns (source 0); source 1: the read's chained alignment, encoded by the host from its trace
-	std::vector<OutEntry> outEntries;
-	std::vector<uint64_t> readOutOff;
-	const OutRec* hOutRecs = nullptr; const uint64_t* hOutOffsets = nullptr;
-	const char* hOutPath = nullptr; const char* hOutCigar = nullptr; const uint8_t* hOutVg = nullptr;
-	const uint64_t* hCorrOffsets = nullptr; const char* hCorrText = nullptr;   // (device_output & 8) the corrected pieces of the jobs: [nOutJobs + 1], letters
-	uint64_t nOutJobs = 0;
-	std::vector<uint64_t> outJobOfEntry;
-	// Started by the whole-read pass's own thread as soon as the selection is known (the end of afterLongPass): the main thread is still in the fragment pipeline, the stitching and the
-	// chain distances then, so the two passes of the encoder, their two waits and the download of the text overlap that work instead of following it (r4: with the encoder after the
-	// join, every batch's latency grew by the encoder's launches waiting for wave slots among the other batches' kernels, and five streams in flight completed a batch every 255-268 ms
-	// end to end against 160 for the hot path). Every read's selected alignments are encoded; a read whose chained alignment wins in the end (known only after the join) drops its pieces
-	// in encodeOutput - wasted work in proportion to the winners.
-	std::vector<uint64_t> readJobBegin;   // first job of every read (jobs of a read: its selected alignments sorted by alignmentStart); [n] = number of jobs
-	std::vector<uint32_t> jobAln;         // the alignment (index into the read's longAlns) of every job
-	void encodeOutputStart()
-	{
-		if (!P->device_output) return;
-		const double t0 = nowUs();
-		readJobBegin.assign(n + 1, 0);
-		jobAln.clear();
-		for (uint64_t r = 0; r < n; r++) {
-			const ReadGlue& gl = glue[r];
-			readJobBegin[r] = jobAln.size();
-			if (gl.longFailed) continue;
-			struct Item { uint32_t start; uint32_t aln; };
-			std::vector<Item> items;
-			for (uint32_t k : gl.longSelected) items.push_back(Item { gl.longAlns[k].start, k });
-			auto byStart = [](const Item& l, const Item& rr) { return l.start < rr.start; };
-			std::sort(items.begin(), items.end(), byStart);   // src/Aligner.cpp:1003
-			std::sort(items.begin(), items.end(), byStart);   // :1023 (an unstable sort may move ties even in a sorted list)
-			for (const Item& it : items) jobAln.push_back(it.aln);
-		}
-		readJobBegin[n] = jobAln.size();
-		nOutJobs = jobAln.size();
-		if (nOutJobs == 0) return;
-		if (nOutJobs >= 0xffffffffull) throw std::runtime_error("too many alignments in one batch for the output encoder");
-		OutJob* hJobsOut = st->hOutJobs.reserve<OutJob>(nOutJobs);
-		const uint32_t flags = ((P->device_output & 2) ? 1u : 0u) | ((P->device_output & 3) ? 2u : 0u) | ((P->device_output & 4) ? 4u : 0u);
-		for (uint64_t r = 0; r < n; r++)
-			for (uint64_t k = readJobBegin[r]; k < readJobBegin[r + 1]; k++) {
-				const LongAln& al = glue[r].longAlns[jobAln[k]];
-				hJobsOut[k] = OutJob { al.traceOff, R->offsets[r], al.traceLen, (uint32_t)(R->offsets[r + 1] - R->offsets[r]), flags, 0 };
-			}
-		hipStream_t q = st->longPass.longStream;   // (the pass and its decision are done with it)
-		OutJob* dJobsOut = st->outJobs.reserve<OutJob>(nOutJobs);
-		OutRec* dRecs = st->outRecs.reserve<OutRec>(nOutJobs);
-		uint64_t* dOffsets = st->outOffsets.reserve<uint64_t>(3 * (nOutJobs + 1));
-		unsigned long long* dTotals = st->outTotals.reserve<unsigned long long>(4);
-		uint32_t* dMapSizes = (P->device_output & 4) ? st->outMapSizes.reserve<uint32_t>(std::max<uint64_t>(1, pass.cellsAsked()))   /* one word per cell of the pool in use */ : nullptr;
-		unsigned long long* hTotals = st->hOutTotals.reserve<unsigned long long>(4);
-		HIP_CHECK(hipMemcpyAsync(dJobsOut, hJobsOut, nOutJobs * sizeof(OutJob), hipMemcpyHostToDevice, q));
-		hipEvent_t timed[6] = {};   // GC_DEBUG_TIMES: device time of the encoder's and the corrected reads' kernels, each pass between events of its own
-		if (sw.debugTimes) for (auto& e : timed) HIP_CHECK(hipEventCreate(&e));
-		auto mark = [&](int k) { if (timed[k]) HIP_CHECK(hipEventRecord(timed[k], q)); };
-		mark(0);
-		launchOutCount(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), R->devBases, dRecs, dOffsets, dMapSizes, dTotals);
-		mark(1);
-		HIP_CHECK(hipMemcpyAsync(hTotals, dTotals, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
-		// corrected reads (device_output & 8; gc_corrected.hip): their own kernels behind the encoder's on the same stream, their count and text beside the encoder's
-		const bool corrected = (P->device_output & 8) != 0;
-		uint32_t* dCorrLens = nullptr; uint64_t* dCorrOffsets = nullptr; unsigned long long* hCorrTotal = nullptr;
-		if (corrected) {
-			dCorrLens = st->corrLens.reserve<uint32_t>(nOutJobs);
-			dCorrOffsets = st->corrOffsets.reserve<uint64_t>(nOutJobs + 1);
-			unsigned long long* dCorrTotal = st->corrTotal.reserve<unsigned long long>(1);
-			hCorrTotal = st->hCorrTotal.reserve<unsigned long long>(1);
-			launchCorrectedCount(q, G->dev, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), dCorrLens, dCorrOffsets, dCorrTotal);
-			HIP_CHECK(hipMemcpyAsync(hCorrTotal, dCorrTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
-		}
-		mark(2);
-		syncStream(q);
-		const uint64_t pathBytes = hTotals[0], cigarBytes = hTotals[1], vgBytes = hTotals[2];
-		char* dPath = st->outPathText.reserve<char>(pathBytes + 1);
-		char* dCigar = st->outCigarText.reserve<char>(cigarBytes + 1);
-		uint8_t* dVg = st->outVgBytes.reserve<uint8_t>(vgBytes + 1);
-		mark(3);
-		launchOutWrite(q, G->dev, G->devNames, G->devIupac, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), R->devBases, dRecs, dOffsets, dMapSizes, dPath, dCigar, dVg);
-		mark(4);
-		OutRec* recs = st->hOutRecs.reserve<OutRec>(nOutJobs);
-		uint64_t* offs = st->hOutOffsets.reserve<uint64_t>(3 * (nOutJobs + 1));
-		char* pathText = st->hOutPathText.reserve<char>(pathBytes + 1);
-		char* cigarText = st->hOutCigarText.reserve<char>(cigarBytes + 1);
-		uint8_t* vg = st->hOutVgBytes.reserve<uint8_t>(vgBytes + 1);
-		HIP_CHECK(hipMemcpyAsync(recs, dRecs, nOutJobs * sizeof(OutRec), hipMemcpyDeviceToHost, q));
-		HIP_CHECK(hipMemcpyAsync(offs, dOffsets, 3 * (nOutJobs + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, q));
-		if (pathBytes) HIP_CHECK(hipMemcpyAsync(pathText, dPath, pathBytes, hipMemcpyDeviceToHost, q));
-		if (cigarBytes) HIP_CHECK(hipMemcpyAsync(cigarText, dCigar, cigarBytes, hipMemcpyDeviceToHost, q));
-		if (vgBytes) HIP_CHECK(hipMemcpyAsync(vg, dVg, vgBytes, hipMemcpyDeviceToHost, q));
-		uint64_t corrBytes = 0;
-		uint32_t* corrLens = nullptr;
-		if (corrected) {
-			corrBytes = *hCorrTotal;
-			char* dCorrText = st->corrText.reserve<char>(corrBytes + 1);
-			launchCorrectedWrite(q, G->dev, dJobsOut, (uint32_t)nOutJobs, pass.deviceCells(), dCorrLens, dCorrOffsets, dCorrText);
-			mark(5);
-			corrLens = st->hCorrLens.reserve<uint32_t>(nOutJobs);
-			uint64_t* corrOffs = st->hCorrOffsets.reserve<uint64_t>(nOutJobs + 1);
-			char* corrText = st->hCorrText.reserve<char>(corrBytes + 1);
-			HIP_CHECK(hipMemcpyAsync(corrLens, dCorrLens, nOutJobs * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
-			HIP_CHECK(hipMemcpyAsync(corrOffs, dCorrOffsets, (nOutJobs + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, q));
-			if (corrBytes) HIP_CHECK(hipMemcpyAsync(corrText, dCorrText, corrBytes, hipMemcpyDeviceToHost, q));
-			hCorrOffsets = corrOffs; hCorrText = corrText;
-		}
-		syncStream(q);
-		if (corrected) for (uint64_t k = 0; k < nOutJobs; k++) if (corrLens[k] == 0xffffffffu) throw std::runtime_error("internal: the corrected-read kernel's two passes disagree on an alignment's size");
-		for (uint64_t k = 0; k < nOutJobs; k++) if (recs[k].steps == 0xffffffffu) throw std::runtime_error("internal: the output encoder's two passes disagree on an alignment's size");
-		hOutRecs = recs; hOutOffsets = offs; hOutPath = pathText; hOutCigar = cigarText; hOutVg = vg;
-		if (sw.debugTimes) fprintf(stderr, "[gc times] output encoding on the device: %llu alignments, %.1f MB of path text, %.1f MB of CIGAR, %.1f MB of vg::Path bytes, %.1f ms (on the whole-read pass's thread, beside the fragment pipeline)\n",
-			(unsigned long long)nOutJobs, pathBytes / 1e6, cigarBytes / 1e6, vgBytes / 1e6, (nowUs() - t0) / 1e3);
-		if (timed[0]) {
-			auto between = [&](int a, int b) { float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, timed[a], timed[b])); return (double)ms; };
-			const double encodeMs = between(0, 1) + between(3, 4), correctedMs = corrected ? between(1, 2) + between(4, 5) : 0.0;
-			for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
-			fprintf(stderr, "[gc times] output kernels on the device: k_out_encode (both passes, k_out_place) %.3f ms; corrected reads (k_corr_walk both passes, k_corr_place) %.3f ms, %.1f MB of letters down\n",
-				encodeMs, correctedMs, corrBytes / 1e6);
-		}
-	}
-
-	// After the decision: which of the encoded alignments are the batch's output, in the reference's order
-	void encodeOutput()
-	{
-		if (!P->device_output) return;
-		readOutOff.assign(n + 1, 0);
-		outEntries.clear();
-		outJobOfEntry.clear();
-		for (uint64_t r = 0; r < n; r++) {
-			const ReadGlue& gl = glue[r];
-			readOutOff[r] = outEntries.size();
-			if (gl.longFailed) continue;
-			if (gl.chainWins) { outEntries.push_back(OutEntry { (uint32_t)r, 0, 1 }); outJobOfEntry.push_back(~0ull); continue; }
-			for (uint64_t k = readJobBegin[r]; k < readJobBegin[r + 1]; k++) { outEntries.push_back(OutEntry { (uint32_t)r, jobAln[k], 0 }); outJobOfEntry.push_back(k); }
-		}
-		readOutOff[n] = outEntries.size();
-		if (st->coverage) countCoverage();
-	}
-
-	// gc_stream_set_coverage: the batch's output entries - exactly the alignments the writers will print - are counted into the handle (gc_coverage.hip). Here and not beside the
-	// encoder: the encoder runs before the chained-versus-whole-read decision and drops the losers' pieces afterwards, and a count cannot be dropped. Entries of source 0 are
-	// read where they lie, in the cell pool (still resident: nothing reserves it again before the next batch), under a keep byte per encoder job; the chained winners' traces
-	// exist only on the host (chain_trace_*: edlib's path walked, or the fast mode's stitched cells) and go up for the same kernel. The stream is waited for: a finished batch
-	// is a counted batch.
-	void countCoverage()
-	{
-		gc_coverage* cov = st->coverage;
-		const double t0 = nowUs();
-		hipEvent_t timed[2] = {};
-		if (sw.debugTimes) for (auto& e : timed) HIP_CHECK(hipEventCreate(&e));
-		if (timed[0]) HIP_CHECK(hipEventRecord(timed[0], stream));
-		uint64_t nKept = 0, nWinners = 0, winnerCells = 0;
-		if (nOutJobs) {
-			uint8_t* hKeep = st->hCovKeep.reserve<uint8_t>(nOutJobs);
-			memset(hKeep, 0, nOutJobs);
-			for (uint64_t k : outJobOfEntry) if (k != ~0ull) { hKeep[k] = 1; nKept++; }
-			if (nKept) {
-				uint8_t* dKeep = st->covKeep.reserve<uint8_t>(nOutJobs);
-				HIP_CHECK(hipMemcpyAsync(dKeep, hKeep, nOutJobs, hipMemcpyHostToDevice, stream));
-				launchCoverageAdd(stream, cov->dev, cov->links, (const OutJob*)st->outJobs.ptr, (uint32_t)nOutJobs, dKeep, pass.deviceCells(), cov->dBases, cov->dDepth, cov->dBad);
-			}
-		}
-		for (const OutEntry& en : outEntries) if (en.source == 1) { nWinners++; winnerCells += glue[en.read].chainTraceNode.size(); }
-		if (nWinners) {
-			if (nWinners >= 0xffffffffull) throw std::runtime_error("too many chained alignments in one batch for the coverage kernel");
-			LongCell* hCells = st->hCovCells.reserve<LongCell>(winnerCells);
-			OutJob* hJobsCov = st->hCovJobs.reserve<OutJob>(nWinners);
-			uint64_t at = 0, w = 0;
-			for (const OutEntry& en : outEntries) {
-				if (en.source != 1) continue;
-				const ReadGlue& gl = glue[en.read];
-				const size_t cells = gl.chainTraceNode.size();
-				if (cells == 0) throw std::runtime_error("coverage: a chained alignment won and the batch holds no trace for it (chain_traces == 0?)");
-				hJobsCov[w++] = OutJob { at, 0, (uint32_t)cells, 0, 0, 0 };
-				for (size_t i = 0; i < cells; i++) hCells[at++] = LongCell { gl.chainTraceNode[i], gl.chainTraceOffset[i], gl.chainTraceSeqPos[i], gl.chainTraceSwitch[i] };
-			}
-			LongCell* dCells = st->covCells.reserve<LongCell>(winnerCells);
-			OutJob* dJobsCov = st->covJobs.reserve<OutJob>(nWinners);
-			HIP_CHECK(hipMemcpyAsync(dCells, hCells, winnerCells * sizeof(LongCell), hipMemcpyHostToDevice, stream));
-			HIP_CHECK(hipMemcpyAsync(dJobsCov, hJobsCov, nWinners * sizeof(OutJob), hipMemcpyHostToDevice, stream));
-			launchCoverageAdd(stream, cov->dev, cov->links, dJobsCov, (uint32_t)nWinners, nullptr, dCells, cov->dBases, cov->dDepth, cov->dBad);
-		}
-		if (timed[1]) HIP_CHECK(hipEventRecord(timed[1], stream));
-		HIP_CHECK(hipGetLastError());
-		syncStream(stream);
-		if (timed[0]) {
-			float ms = 0;
-			HIP_CHECK(hipEventElapsedTime(&ms, timed[0], timed[1]));
-			for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
-			fprintf(stderr, "[gc times] coverage: k_cov_add over %llu alignments in the cell pool and %llu chained winners (%llu cells up), %.3f ms on the device, %.1f ms in all; per-base depth %s, links %s\n",
-				(unsigned long long)nKept, (unsigned long long)nWinners, (unsigned long long)winnerCells, ms, (nowUs() - t0) / 1e3, cov->dDepth ? "on" : "off", cov->hasLinks ? "on" : "off");
-		}
-	}
-
-	void assembleOutput()   // the pieces into the result (entries of chained winners stay empty: source 1)
-	{
-		res->device_output = P->device_output;
-		if (!P->device_output) return;
-		const uint64_t nOut = outEntries.size();
-		res->read_out_off = resultArray<uint64_t>(n + 1);
-		memcpy(res->read_out_off, readOutOff.data(), (n + 1) * sizeof(uint64_t));
-		res->out_source = resultArray<uint8_t>(nOut);
-		res->out_numbers = resultArray<uint64_t>(12 * nOut);
-		res->out_path_off = resultArray<uint64_t>(nOut + 1); res->out_cigar_off = resultArray<uint64_t>(nOut + 1); res->out_vg_off = resultArray<uint64_t>(nOut + 1);
-		const uint64_t stride = nOutJobs + 1;
-		// where every entry's pieces go: the kept jobs' bytes back to back (all of them, in order, unless chained alignments won)
-		uint64_t pathBytes = 0, cigarBytes = 0, vgBytes = 0;
-		for (uint64_t e = 0; e < nOut; e++) {
-			res->out_path_off[e] = pathBytes; res->out_cigar_off[e] = cigarBytes; res->out_vg_off[e] = vgBytes;
-			const uint64_t k = outJobOfEntry[e];
-			if (k == ~0ull) continue;
-			pathBytes += hOutOffsets[k + 1] - hOutOffsets[k]; cigarBytes += hOutOffsets[stride + k + 1] - hOutOffsets[stride + k]; vgBytes += hOutOffsets[2 * stride + k + 1] - hOutOffsets[2 * stride + k];
-		}
-		res->out_path_off[nOut] = pathBytes; res->out_cigar_off[nOut] = cigarBytes; res->out_vg_off[nOut] = vgBytes;
-		res->out_path_text = resultArray<char>(pathBytes + 1); res->out_cigar_text = resultArray<char>(cigarBytes + 1); res->out_vg_path = resultArray<uint8_t>(vgBytes + 1);
-		bool allKept = nOut == nOutJobs;   // no chained winner: the device's blobs are the result's, job k is entry k
-		for (uint64_t e = 0; e < nOut && allKept; e++) allKept = outJobOfEntry[e] == e;   // (a winner's one entry can stand where a read's one dropped job was: the counts alone do not tell)
-		const size_t parts = 16;
-		if (allKept) pool.run(3 * parts, [&](size_t i, size_t) {
-			const size_t which = i / parts, part = i % parts;
-			const uint64_t total = which == 0 ? pathBytes : which == 1 ? cigarBytes : vgBytes;
-			const char* src = which == 0 ? hOutPath : which == 1 ? hOutCigar : (const char*)hOutVg;
-			char* dst = which == 0 ? res->out_path_text : which == 1 ? res->out_cigar_text : (char*)res->out_vg_path;
-			const uint64_t b = total * part / parts, e = total * (part + 1) / parts;
-			if (e > b) memcpy(dst + b, src + b, e - b);
-		});
-		else pool.run(nOut, [&](size_t e, size_t) {
-			const uint64_t k = outJobOfEntry[e];
-			if (k == ~0ull) return;
-			memcpy(res->out_path_text + res->out_path_off[e], hOutPath + hOutOffsets[k], hOutOffsets[k + 1] - hOutOffsets[k]);
-			memcpy(res->out_cigar_text + res->out_cigar_off[e], hOutCigar + hOutOffsets[stride + k], hOutOffsets[stride + k + 1] - hOutOffsets[stride + k]);
-			memcpy(res->out_vg_path + res->out_vg_off[e], hOutVg + hOutOffsets[2 * stride + k], hOutOffsets[2 * stride + k + 1] - hOutOffsets[2 * stride + k]);
-		});
-		res->out_path_text[pathBytes] = 0; res->out_cigar_text[cigarBytes] = 0;
-		if (P->device_output & 8) {   // the corrected pieces, compacted like the other three (entries of chained winners stay empty: the host spells them from chain_trace_*)
-			res->out_corrected_off = resultArray<uint64_t>(nOut + 1);
-			uint64_t corrBytes = 0;
-			for (uint64_t e = 0; e < nOut; e++) {
-				res->out_corrected_off[e] = corrBytes;
-				const uint64_t k = outJobOfEntry[e];
-				if (k != ~0ull) corrBytes += hCorrOffsets[k + 1] - hCorrOffsets[k];
-			}
-			res->out_corrected_off[nOut] = corrBytes;
-			res->out_corrected_text = resultArray<char>(corrBytes + 1);
-			if (allKept) pool.run(parts, [&](size_t part, size_t) {
-				const uint64_t b = corrBytes * part / parts, e = corrBytes * (part + 1) / parts;
-				if (e > b) memcpy(res->out_corrected_text + b, hCorrText + b, e - b);
-			});
-			else pool.run(nOut, [&](size_t e, size_t) {
-				const uint64_t k = outJobOfEntry[e];
-				if (k != ~0ull) memcpy(res->out_corrected_text + res->out_corrected_off[e], hCorrText + hCorrOffsets[k], hCorrOffsets[k + 1] - hCorrOffsets[k]);
-			});
-			res->out_corrected_text[corrBytes] = 0;
-		}
-		for (uint64_t e = 0; e < nOut; e++) {
-			const OutEntry& en = outEntries[e];
-			res->out_source[e] = en.source;
-			uint64_t* num = res->out_numbers + 12 * e;
-			if (en.source == 0) {
-				const OutRec& rec = hOutRecs[outJobOfEntry[e]];
-				const LongAln& al = glue[en.read].longAlns[en.aln];
-				num[0] = rec.nodePathLen; num[1] = rec.nodePathStart; num[2] = rec.nodePathEnd; num[3] = rec.matches; num[4] = rec.mismatches; num[5] = rec.insertions; num[6] = rec.deletions;
-				num[7] = al.traceLen; num[8] = al.start; num[9] = al.end; num[10] = rec.steps; num[11] = al.score;
-			} else for (int i = 0; i < 12; i++) num[i] = 0;
-		}
 	}
 
 	// ---------------- the flat result: count per read, prefix-sum, fill in parallel
@@ -648,7 +382,7 @@
 				a++;
 			});
 		});
-		assembleOutput();
+		output.assembleInto(res);
 		res->host_us[1] = nowUs() - tAsm;
 		if (sw.debugTimes) {
 			// what the stream holds on the device, largest first, and how much of the pools this batch used

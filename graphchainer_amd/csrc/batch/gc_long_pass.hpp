@@ -4,8 +4,8 @@
 //
 // Who may touch what while the pass thread runs (between start() and join()):
 // - the pass thread writes this object's members, st->longPass, res->counters_long, and of the batch's ReadGlue records the fields longAlns, longSelected,
-//   longEditDistance, longFailed and capacityExceededLong; through the selectionKnown hook it writes BatchRun's output-encoder state, which the main thread leaves alone
-//   until join() has returned;
+//   longEditDistance, longFailed and capacityExceededLong; through the selectionKnown hook it runs OutputEncoder::encodeSelected (batch/gc_output_encoder.hpp), which
+//   writes that object's private members and st->output; the main thread calls nothing of the encoder until join() has returned;
 // - the main thread touches none of those. It reads st->batchesDone, st->fragShare, st->glue's other fields and the seeds (st->longSeeds) like the pass, and writes the first
 //   two only after join().
 //
@@ -14,7 +14,7 @@
 // stream (if the pass still held it) and for longStream - a kernel of this pass may still be writing to the shared scratch, which goes to the next pass with the token.
 //
 // Lifetime: ~WholeReadPass joins a thread that is still running (an exception on the main thread must not leave the pass thread behind with dangling state). The hook's
-// target has to outlive the thread too: BatchRun joins in its own destructor (joinIfRunning), before any of its members goes.
+// target has to outlive the thread too: BatchRun declares its OutputEncoder before its WholeReadPass, so the pass is destroyed - and its thread joined - first.
 #pragma once
 #include "../gc_runtime.hpp"
 

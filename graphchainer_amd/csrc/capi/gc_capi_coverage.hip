@@ -1,5 +1,5 @@
 // C entry points of the coverage accumulators: gc_coverage_create / _create2 / _destroy, gc_stream_set_coverage, gc_coverage_add_traces, gc_coverage_counts, _link_counts,
-// gc_coverage_merge, gc_coverage_format_segments / _bases / _links / _gfa_segments / _gfa_links. The kernels are in hip/gc_coverage.hip, the per-batch counting in batch/gc_batch_output.inc (countCoverage).
+// gc_coverage_merge, gc_coverage_format_segments / _bases / _links / _gfa_segments / _gfa_links. The kernels are in hip/gc_coverage.hip, the per-batch counting in batch/gc_output_encoder.hip (OutputEncoder::choose, countCoverage).
 #include "../gc_runtime.hpp"
 #include "../hip/gc_coverage_links_core.hpp"
 

@@ -1,7 +1,8 @@
 // gc_align_batch: the batch pipeline (BatchRun) - seeding, the whole-read pass on its own thread (WholeReadPass, batch/gc_long_pass.hpp), the fragment pipeline, chaining, stitching,
-// edit distances, the decision, output encoding, result assembly.
+// edit distances, the decision, output encoding (OutputEncoder, batch/gc_output_encoder.hpp: started on the pass's thread, finished here), result assembly.
 #include "gc_runtime.hpp"
 #include "batch/gc_long_pass.hpp"
+#include "batch/gc_output_encoder.hpp"
 
 extern "C" {
 
@@ -33,6 +34,9 @@ struct BatchRun {
 	unsigned long long* dCursors = nullptr;
 	unsigned long long* dCounters = nullptr;
 	const gc::EValueModel evalueModel { clip.on() ? clip.cutoff : 0.7 };   // src/Aligner.cpp:474-482: the clipping cut-off is the model's identity
+	// the device output encoder (batch/gc_output_encoder.hpp). The pass's thread runs its first stage through the selectionKnown hook, so it is declared BEFORE the pass:
+	// ~WholeReadPass joins a thread that is still running, and members go in reverse order - the hook's target outlives the thread
+	OutputEncoder output { sw, G, R, P, st, pool, pass };
 	// the whole-read pass: on its own host thread between pass.start() and pass.join(); what the two threads may touch meanwhile is written down in batch/gc_long_pass.hpp
 	WholeReadPass pass { sw, G, R, P, clip, st, pool, res, tCall };
 	// fragmentPipeline()
@@ -93,9 +97,6 @@ struct BatchRun {
 	BatchRun(const gc::Switches& sw, const gc_graph* G, const gc_seeder* S, const gc_seeds* H, gc_stream* st, const gc_reads* R, const gc_params* P, const ClipOptions& clip, gc_result* res, double tCall, double cpuCall)
 		: sw(sw), G(G), S(S), H(H), st(st), R(R), P(P), clip(clip), res(res), tCall(tCall), cpuCall(cpuCall), cpuJoined(cpuCall), n(R->offsets.size() - 1), hg(G->host), pool(WorkerPool::batch()), glue(st->glue),
 		  stream(st->stream) {}
-	// (an exception on the main thread must not leave the pass thread behind with dangling state - and the pass's hook writes the output stage's members, which the .inc files
-	// declare after `pass`: member order alone would destroy them before the pass object joins its thread)
-	~BatchRun() { pass.joinIfRunning(); }
 	BatchRun(const BatchRun&) = delete;
 	BatchRun& operator=(const BatchRun&) = delete;
 
@@ -119,8 +120,8 @@ struct BatchRun {
 		};
 		seeds(); stageDone(0);
 		pass.prepare(dPassSeeds, nSeedsTotal); stageDone(1);
-		pass.start([this] { encodeOutputStart(); }); stageDone(2);
-		if (!P->colinear_chaining) { withoutChaining(); pass.join(tJoined, cpuJoined); stageDone(6); encodeOutput(); stageDone(8); assemble(); stageDone(9); st->batchesDone++; return; }
+		pass.start([this] { output.encodeSelected(); }); stageDone(2);
+		if (!P->colinear_chaining) { withoutChaining(); pass.join(tJoined, cpuJoined); stageDone(6); output.choose(stream); stageDone(8); assemble(); stageDone(9); st->batchesDone++; return; }
 		fragmentPipeline(); stageDone(3);
 		resultsBack(); stageDone(4);
 		// r5: the trace pool and the anchor path pool are sized by what the stream's batches have used, not by every slot's worst case (a 2 000 x 50 kb batch on a 960 Mbp
@@ -131,7 +132,7 @@ struct BatchRun {
 		stitchAndChainDistances(); stageDone(5);
 		pass.join(tJoined, cpuJoined); stageDone(6);
 		chainedAlignments(); stageDone(7);
-		encodeOutput(); stageDone(8);
+		output.choose(stream); stageDone(8);
 		assemble(); stageDone(9);
 		st->fragShare = (double)res->counters[4] / (double)std::max<uint64_t>(1, R->totalBases);
 		st->batchesDone++;
@@ -146,7 +147,7 @@ struct BatchRun {
 #include "batch/gc_batch_seeds.inc"   // K1 seed lookup and the glue between it and the extension kernels
 #include "batch/gc_batch_fragments.inc"   // the fragment pipeline: windows, work items, extension and anchors in lazy rounds, chaining, stitching
 #include "batch/gc_batch_results.inc"   // what comes down: anchors, chains, stitched paths, the chains' NW distances
-#include "batch/gc_batch_output.inc"   // the chained alignments' traces, the output encoders on the device, the flat result
+#include "batch/gc_batch_output.inc"   // the chained alignments' traces, the flat result
 };
 
 // The extension block's checks (src/AlignerMain.cpp:300-322,443-448; getSlices' assertion, ...Banded.h:504): host only, nothing but the two structs is read

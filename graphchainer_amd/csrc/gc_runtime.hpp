@@ -19,6 +19,7 @@
 #include "host/gc_mxm_cache.hpp"
 #include "host/gc_layout.hpp"
 #include "host/gc_long_policy.hpp"
+#include "host/gc_output_plan.hpp"
 #include "hip/gc_mxm_core.hpp"
 #include "hip/gc_seedfile_core.hpp"
 #include <hip/hip_runtime.h>
@@ -718,9 +719,7 @@ struct gc_coverage {
 struct gc_stream {
 	std::vector<ReadGlue> glue;   // per-read host records of the batch in flight (storage reused)
 	gc_coverage* coverage = nullptr;   // gc_stream_set_coverage: the batches of this stream with device_output != 0 are counted into it
-	DeviceBuffer covKeep, covCells, covJobs;   // a batch's keep bytes over its output jobs; the chained winners' cells and jobs
-	PinnedBuffer hCovKeep, hCovCells, hCovJobs;
-	int device = 0;             // the device the stream was created on; gc_align_batch selects it for the calling thread
+	int device = 0;            // the device the stream was created on; gc_align_batch selects it for the calling thread
 	hipStream_t stream = nullptr;
 	hipEvent_t ev[12] {};
 	hipEvent_t fragEv[16] {};   // r5: a (begin, end) pair around each of the lazy rounds' k_extend launches [0..7] and k_build_anchors launches [8..15]: kernel_us[1] / [2] are sums of exactly those
@@ -728,10 +727,16 @@ struct gc_stream {
 	PinnedBuffer hFragDeclined, hReadSeeds, hFragFirstSeed, hFrags, hJobs, hAnchors, hFragStatus, hFragExtended, hReadTies, hChainOut, hChainLen, hChainScore, hChainStatus, hPathPool, hSmall;
 	DeviceBuffer edPathNodes, edJobs, edLetters, edLettersLen, edPairs, edOut;
 	PinnedBuffer hEdPathNodes, hEdJobs, hEdPairs, hEdOut;
-	DeviceBuffer outJobs, outRecs, outOffsets, outMapSizes, outPathText, outCigarText, outVgBytes, outTotals;   // output encoding on the device (gc_output.hip)
-	DeviceBuffer corrLens, corrOffsets, corrText, corrTotal;   // corrected reads' pieces (gc_corrected.hip; device_output & 8)
-	PinnedBuffer hCorrLens, hCorrOffsets, hCorrText, hCorrTotal;
-	PinnedBuffer hOutJobs, hOutRecs, hOutOffsets, hOutPathText, hOutCigarText, hOutVgBytes, hOutTotals;
+	// The device output encoder's own: what batch/gc_output_encoder.hip (OutputEncoder) works in, kept from batch to batch. Between the whole-read pass's selectionKnown
+	// hook and the pass's join it is the pass thread's alone; after the join the main thread's.
+	struct Output {
+		DeviceBuffer outJobs, outRecs, outOffsets, outMapSizes, outPathText, outCigarText, outVgBytes, outTotals;   // output encoding on the device (gc_output.hip)
+		DeviceBuffer corrLens, corrOffsets, corrText, corrTotal;   // corrected reads' pieces (gc_corrected.hip; device_output & 8)
+		PinnedBuffer hCorrLens, hCorrOffsets, hCorrText, hCorrTotal;
+		PinnedBuffer hOutJobs, hOutRecs, hOutOffsets, hOutPathText, hOutCigarText, hOutVgBytes, hOutTotals;
+		DeviceBuffer covKeep, covCells, covJobs;   // (coverage, gc_coverage.hip) a batch's keep bytes over its output jobs; the chained winners' cells and jobs
+		PinnedBuffer hCovKeep, hCovCells, hCovJobs;
+	} output;
 	DeviceBuffer stitchSlotOf, stitchRegions, stitchNodes, stitchInfo, stitchCursor, stitchSpill;   // chain stitching on the device (gc_stitch.hip)
 	DeviceBuffer anchorPerRead, anchorSlotEnd, anchorOff, anchorDense;   // the result's dense anchor arrays made on the device (gc_results.hip)
 	PinnedBuffer hAnchorPerRead, hAnchorOff, hAnchorDense;
@@ -770,15 +775,17 @@ struct gc_stream {
 	template <typename F> void forEachDeviceBuffer(F f) const
 	{
 		const LongPass& L = longPass;
+		const Output& O = output;
 		f("tmp", tmp.bytes); f("matches", matches.bytes); f("readMatchOff", readMatchOff.bytes); f("readMatchCount", readMatchCount.bytes); f("cursors", cursors.bytes); f("readSeeds", readSeeds.bytes);
 		f("fragFirstSeed", fragFirstSeed.bytes); f("longRetryList", L.longRetryList.bytes); f("extLists", extLists.bytes); f("pendingFrags", pendingFrags.bytes); f("fragNext", fragNext.bytes);
 		f("roundCounts", roundCounts.bytes); f("fragItems", fragItems.bytes); f("fragRetryList", fragRetryList.bytes); f("work", work.bytes); f("results", results.bytes); f("scratch", scratch.bytes); f("scratchRetry", scratchRetry.bytes); f("tracePool", tracePool.bytes);
 		f("frags", frags.bytes); f("fragSeeds", fragSeeds.bytes); f("anchors", anchors.bytes); f("fragStatus", fragStatus.bytes); f("fragExtended", fragExtended.bytes); f("readTies", readTies.bytes);
 		f("pathPool", pathPool.bytes); f("jobs", jobs.bytes); f("chainOut", chainOut.bytes); f("chainLen", chainLen.bytes); f("chainScore", chainScore.bytes); f("chainStatus", chainStatus.bytes);
 		f("chainScratch", chainScratch.bytes); f("counters", counters.bytes); f("edPathNodes", edPathNodes.bytes); f("edJobs", edJobs.bytes); f("edLetters", edLetters.bytes);
-		f("edLettersLen", edLettersLen.bytes); f("edPairs", edPairs.bytes); f("edOut", edOut.bytes); f("outJobs", outJobs.bytes); f("outRecs", outRecs.bytes); f("outOffsets", outOffsets.bytes);
-		f("outMapSizes", outMapSizes.bytes); f("outPathText", outPathText.bytes); f("outCigarText", outCigarText.bytes); f("outVgBytes", outVgBytes.bytes); f("outTotals", outTotals.bytes);
-		f("corrLens", corrLens.bytes); f("corrOffsets", corrOffsets.bytes); f("corrText", corrText.bytes); f("corrTotal", corrTotal.bytes);
+		f("edLettersLen", edLettersLen.bytes); f("edPairs", edPairs.bytes); f("edOut", edOut.bytes); f("outJobs", O.outJobs.bytes); f("outRecs", O.outRecs.bytes); f("outOffsets", O.outOffsets.bytes);
+		f("outMapSizes", O.outMapSizes.bytes); f("outPathText", O.outPathText.bytes); f("outCigarText", O.outCigarText.bytes); f("outVgBytes", O.outVgBytes.bytes); f("outTotals", O.outTotals.bytes);
+		f("corrLens", O.corrLens.bytes); f("corrOffsets", O.corrOffsets.bytes); f("corrText", O.corrText.bytes); f("corrTotal", O.corrTotal.bytes);
+		f("covKeep", O.covKeep.bytes); f("covCells", O.covCells.bytes); f("covJobs", O.covJobs.bytes);
 		f("stitchSlotOf", stitchSlotOf.bytes); f("stitchRegions", stitchRegions.bytes); f("stitchNodes", stitchNodes.bytes); f("stitchInfo", stitchInfo.bytes); f("stitchCursor", stitchCursor.bytes); f("stitchSpill", stitchSpill.bytes);
 		f("anchorPerRead", anchorPerRead.bytes); f("anchorSlotEnd", anchorSlotEnd.bytes); f("anchorOff", anchorOff.bytes); f("anchorDense", anchorDense.bytes);
 		f("edPathJobs", edPathJobs.bytes); f("edPathOps", edPathOps.bytes); f("edPathLen", edPathLen.bytes); f("edPathScratch", edPathScratch.bytes); f("longSeeds", longSeeds.bytes);

@@ -124,7 +124,7 @@ struct LongSeed {    // a seed in goodness order (after OrderSeeds); 16 bytes: 3
 struct LongJob {     // one read
 	uint64_t maskOff;               // word offset of the read's match masks: [strand][base][maskWords]
 	uint32_t maskWords;
-	uint32_t alnCap;                // alignments this read may keep: the slots at alnBegin (a read that needs more ends with status 3 and runs again with more, gc_batch_long.inc)
+	uint32_t alnCap;                // alignments this read may keep: the slots at alnBegin (a read that needs more ends with status 3 and runs again with more, batch/gc_long_pass.hip)
 	uint64_t readOff;               // forward bases at bases[readOff..], reverse complement at bases[rcBase + readOff..]
 	uint32_t readLen;
 	uint32_t seedBegin, seedEnd;    // into the LongSeed array
