@@ -28,12 +28,15 @@ EXPORTED_SYMBOLS = [
     "gc_coverage_create", "gc_coverage_destroy", "gc_stream_set_coverage", "gc_coverage_add_traces", "gc_coverage_counts", "gc_coverage_merge",
     "gc_coverage_format_segments", "gc_coverage_format_bases",
     "gc_coverage_link_counts", "gc_coverage_format_links", "gc_coverage_format_gfa_segments", "gc_coverage_format_gfa_links",
+    "gc_coverage_pileup_counts", "gc_coverage_format_pileup",
     "gc_index_build", "gc_index_save", "gc_index_load", "gc_index_check", "gc_result_cache_trim",
     "gc_reads_parse", "gc_fastx_table_free", "gc_bgzf_inflate", "gc_reads_parse_bgzf", "gc_reads_parse_bam", "gc_reads_parse_bam_bgzf",
     "gc_seed_store_open", "gc_seed_store_from_memory", "gc_seed_store_info", "gc_seed_store_destroy", "gc_seeds_from_store",
 ]
-EXPORTED_SYMBOLS_NUMBERED = ["gc_coverage_create2"]   # declared in the header too; apart because tests/test_library_exports.py reads the header for names of letters and underscores only
-GC_COVERAGE_PER_BASE, GC_COVERAGE_LINKS = 1, 2
+EXPORTED_SYMBOLS_NUMBERED = ["gc_coverage_create2", "gc_coverage_add_traces2"]   # declared in the header too; apart because tests/test_library_exports.py reads the header for names of letters and underscores only
+GC_COVERAGE_PER_BASE, GC_COVERAGE_LINKS, GC_COVERAGE_PILEUP = 1, 2, 4
+PILEUP_CHANNELS = ("mmA", "mmC", "mmG", "mmT", "mmN", "del", "ins_after", "ins_before")   # the columns of Coverage.pileup_counts
+PILEUP_PIECE_BASES = 1 << 20         # Coverage.pileup_pieces: forward bases per call into the library (a line is some 40 bytes)
 GFA_PIECE_BYTES = 64 << 20           # Coverage.gfa_pieces / link_table: about this much text per call into the library
 
 
@@ -385,27 +388,43 @@ class Coverage:
     live on the current device, across batches: Aligner.align_batch(..., coverage=cov) or Aligner.set_coverage(cov) counts a batch's output alignments before the call
     returns, and several aligners may share one handle. per_base: also a 32-bit depth per forward base (4 bytes each on the device; RuntimeError when that does not fit).
     links: also how often every link of the graph is walked (16 bytes per link on the device; the header has the meaning of a link and its canonical form).
+    pileup: also eight 32-bit channels per forward base - mismatches by read letter, deletions, insertions after and before (PILEUP_CHANNELS; the header has the rule);
+    it implies per_base, 36 bytes per forward base in all.
     Integers added with atomics: the same reads give the same counts however they were batched."""
 
-    def __init__(self, graph, per_base=False, links=False):
+    def __init__(self, graph, per_base=False, links=False, pileup=False):
         self.lib = load_library()
-        self.graph, self.per_base, self.links = graph, bool(per_base), bool(links)          # (the graph must outlive the handle)
+        self.graph, self.per_base, self.links, self.pileup = graph, bool(per_base) or bool(pileup), bool(links), bool(pileup)          # (the graph must outlive the handle)
         self.handle = C.c_void_p()
         self.lib.gc_coverage_create2.restype = C.c_int
         self.lib.gc_coverage_create2.argtypes = [C.c_void_p, C.c_uint, _P(C.c_void_p)]
-        _check(self.lib.gc_coverage_create2(graph.handle, (GC_COVERAGE_PER_BASE if self.per_base else 0) | (GC_COVERAGE_LINKS if self.links else 0), C.byref(self.handle)))
+        _check(self.lib.gc_coverage_create2(graph.handle, (GC_COVERAGE_PER_BASE if self.per_base else 0) | (GC_COVERAGE_LINKS if self.links else 0) | (GC_COVERAGE_PILEUP if self.pileup else 0), C.byref(self.handle)))
 
-    def add_traces(self, traces):
-        """Counts a list of traces, each (node, offset) in output coordinates, with the kernel the batches use (gc_coverage_add_traces); every cell is checked against the graph first."""
+    def add_traces(self, traces, seq_pos=None, reads=None):
+        """Counts a list of traces, each (node, offset) in output coordinates, with the kernel the batches use (gc_coverage_add_traces); every cell is checked against the graph first.
+        seq_pos / reads (both or neither; a handle with the pileup needs them): per trace the read position of every cell and the read's letters (bytes) - gc_coverage_add_traces2,
+        which also checks every position against its read."""
         n = len(traces)
         off = np.zeros(n + 1, dtype=np.uint64)
         off[1:] = np.cumsum([len(t[0]) for t in traces], dtype=np.uint64) if n else []
-        cat = lambda k, dtype: np.ascontiguousarray(np.concatenate([np.asarray(t[k], dtype=dtype) for t in traces]) if n else np.zeros(0, dtype=dtype), dtype=dtype)   # noqa: E731
-        node, offset = cat(0, np.int32), cat(1, np.uint32)
+        cat = lambda rows, dtype: np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=dtype) for r in rows]) if n else np.zeros(0, dtype=dtype), dtype=dtype)   # noqa: E731
+        node, offset = cat([t[0] for t in traces], np.int32), cat([t[1] for t in traces], np.uint32)
         assert len(node) == len(offset) == int(off[n])
-        self.lib.gc_coverage_add_traces.restype = C.c_int
-        self.lib.gc_coverage_add_traces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
-        _check(self.lib.gc_coverage_add_traces(self.handle, node.ctypes.data, offset.ctypes.data, off.ctypes.data, n))
+        if seq_pos is None and reads is None:
+            self.lib.gc_coverage_add_traces.restype = C.c_int
+            self.lib.gc_coverage_add_traces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+            _check(self.lib.gc_coverage_add_traces(self.handle, node.ctypes.data, offset.ctypes.data, off.ctypes.data, n))
+            return
+        if seq_pos is None or reads is None or len(seq_pos) != n or len(reads) != n:
+            raise ValueError("add_traces: seq_pos and reads go together, one of each per trace")
+        positions = cat(seq_pos, np.uint32)
+        assert len(positions) == len(node)
+        letters = b"".join(bytes(r) for r in reads)
+        read_off = np.zeros(n + 1, dtype=np.uint64)
+        read_off[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64) if n else []
+        self.lib.gc_coverage_add_traces2.restype = C.c_int
+        self.lib.gc_coverage_add_traces2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p]
+        _check(self.lib.gc_coverage_add_traces2(self.handle, node.ctypes.data, offset.ctypes.data, positions.ctypes.data, off.ctypes.data, n, letters, read_off.ctypes.data))
 
     def counts(self):
         """-> (bases [segments] uint64, depth [forward bases] uint32 or None without per_base): the accumulators as they stand."""
@@ -521,6 +540,45 @@ class Coverage:
         n, step = self._n_links(), max(1, int(piece_bytes) // 48)
         for first in range(0, n, step):
             yield self._rows(self.lib.gc_coverage_format_gfa_links, first, step, supported_only)
+
+    def pileup_counts(self):
+        """-> rows [forward bases, 8] uint32 (needs pileup), columns PILEUP_CHANNELS, bases in the order of counts()'s depth."""
+        rows, n_bases = C.c_void_p(), C.c_uint64()
+        self.lib.gc_coverage_pileup_counts.restype = C.c_int
+        self.lib.gc_coverage_pileup_counts.argtypes = [C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]
+        _check(self.lib.gc_coverage_pileup_counts(self.handle, C.byref(rows), C.byref(n_bases)))
+        try:
+            n = int(n_bases.value)
+            return np.ctypeslib.as_array(C.cast(rows, _P(C.c_uint32)), shape=(n, 8)).copy() if n else np.zeros((0, 8), dtype=np.uint32)
+        finally:
+            self.lib.gc_free(rows)
+
+    def _pileup_rows(self, first, count, min_alt, min_fraction):
+        text, length, line_off, n_lines = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        fn = self.lib.gc_coverage_format_pileup
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, _P(C.c_void_p), _P(C.c_uint64), _P(C.c_void_p), _P(C.c_uint64)]
+        _check(fn(self.handle, int(first), int(count), int(min_alt), float(min_fraction), C.byref(text), C.byref(length), C.byref(line_off), C.byref(n_lines)))
+        try:
+            data = C.string_at(text.value, int(length.value))
+            offsets = np.ctypeslib.as_array(C.cast(line_off, _P(C.c_uint64)), shape=(int(n_lines.value) + 1,)).copy()
+        finally:
+            self.lib.gc_free(text)
+            self.lib.gc_free(line_off)
+        return data, offsets
+
+    def pileup_table(self, first=0, count=None, min_alt=1, min_fraction=0.0, line_offsets=False):
+        """The --pileup-out table (bytes; needs pileup) over forward bases [first, first + count) (count None: to the end), spelled on the device by one call:
+        "#segment\tpos\tref\tdepth\tmatch\tmmA\tmmC\tmmG\tmmT\tmmN\tdel\tins_before\tins_after" (only with first == 0), then a line per base with depth > 0 whose largest
+        channel is >= min_alt and >= min_fraction * depth. line_offsets: -> (bytes, byte offsets of the lines)."""
+        data, offsets = self._pileup_rows(first, (1 << 31) - 2 if count is None else count, min_alt, min_fraction)
+        return (data, offsets) if line_offsets else data
+
+    def pileup_pieces(self, min_alt=1, min_fraction=0.0, piece_bases=PILEUP_PIECE_BASES):
+        """The --pileup-out table as a generator of (bytes, byte offsets of the lines), piece_bases forward bases per piece: the text of a large graph is never whole."""
+        n, step = int(np.sum(self._segment_lengths())), max(1, int(piece_bases))
+        for first in range(0, max(n, 1), step):
+            yield self._pileup_rows(first, step, min_alt, min_fraction)
 
     def close(self):
         if self.handle:

@@ -11,6 +11,8 @@ corrected reads, their pieces spelled on the device, beside -a or without it.
 device while the traces are there (api.Coverage), one handle per device, merged and spelled at the end; beside -a or without it.
 --link-coverage-out / --coverage-gfa-out / --supported-subgraph-out, this build's own too, come from the same handles: how often every link of the graph is walked, as a
 table, as the graph itself with RC tags on segments and links, and as the part of the graph the alignments touch.
+--pileup-out (with --pileup-min-alt / --pileup-min-alt-fraction), from the same handles as well: per base of the graph how the alignments written disagree with it -
+mismatches by read letter, deletions, insertions before and after - written piece by piece.
 
 Accepted and without effect: -t / --threads (checked >= 1), --high-memory, --verbose, --short-verbose (the progress text and the closing statistics are not
 reproduced), and --greedy-E / --greedy-score, which the reference declares and never reads. --try-all-seeds (and --all-alignments, which sets it) does what it does
@@ -49,13 +51,15 @@ OPTIONS = {
     "corrected-out": (None, "string", False), "corrected-clipped-out": (None, "string", False),   # GraphAligner's: the reference keeps their mechanism and dropped the two option lines
     "coverage-out": (None, "string", False), "base-coverage-out": (None, "string", False),
     "link-coverage-out": (None, "string", False), "coverage-gfa-out": (None, "string", False), "supported-subgraph-out": (None, "string", False),
+    "pileup-out": (None, "string", False), "pileup-min-alt": (None, "size", False), "pileup-min-alt-fraction": (None, "double", False),
 }
 MAX_INFLIGHT = 5                   # the most the benchmark keeps in flight on a device (bench.py: BATCH_MS_BY_INFLIGHT ends there)
 MAX_DEVICES = 16                   # the library's per-device slots
 COVERAGE_GZ_PIECE = 1 << 20         # a .gz coverage table is written as gzip members of about this many bytes of whole lines
 COVERAGE_OUTPUTS = (("coverage", "coverage-out"), ("base_coverage", "base-coverage-out"), ("link_coverage", "link-coverage-out"), ("coverage_gfa", "coverage-gfa-out"),
-                    ("supported_subgraph", "supported-subgraph-out"))          # Config.coverage key, option
-FULL_NAME_ONLY = ("coverage-gfa-out",)   # spelled out in full: the abbreviations of --coverage-out that scripts use (--cov, --coverage) were there first and keep their meaning
+                    ("supported_subgraph", "supported-subgraph-out"), ("pileup", "pileup-out"))          # Config.coverage key, option
+# spelled out in full: the abbreviations of --coverage-out that scripts use (--cov, --coverage) were there first and keep their meaning, and so do --p / --pr (--precise-clipping)
+FULL_NAME_ONLY = ("coverage-gfa-out", "pileup-out", "pileup-min-alt", "pileup-min-alt-fraction")
 LINK_OUTPUTS = ("link_coverage", "coverage_gfa", "supported_subgraph")     # these need the handles' link table
 CORRECTED_SUFFIXES = (".fa", ".fasta", ".fa.gz", ".fasta.gz")   # src/AlignerMain.cpp:360,365 (a name shorter than a suffix does not end in it; the reference's substr would throw)
 REFUSED = ("optimal-alignment", "seedless-DP", "DP-restart-stride", "generate-path", "generate-path-seed", "graph-statistics")
@@ -129,6 +133,11 @@ This build's own:
                                         --coverage-out (divide by LN:i for the mean depth), RC:i on a link its traversals. Letters in upper case.
                                         The option's name is not abbreviated (--cov stays --coverage-out)
   --supported-subgraph-out arg          the same GFA without the segments no alignment covers and the links no alignment walks
+  --pileup-out arg                      table "#segment pos ref depth match mmA mmC mmG mmT mmN del ins_before ins_after" (tab-separated; gzipped for a
+                                        .gz name): for every base where the alignments written disagree with the graph, how they do. Holds 36 bytes
+                                        per base of the graph on every device. The three --pileup options are not abbreviated
+  --pileup-min-alt arg (=1)             a base gets a line when its largest count other than match is at least this (0: every covered base)
+  --pileup-min-alt-fraction arg (=0)    ... and at least this fraction of the base's depth (0 to 1)
 
 Accepted and without effect: -t [ --threads ] arg (must be >= 1), --high-memory, --verbose, --short-verbose, --greedy-E, --greedy-score.
 Not supported by this build: --optimal-alignment, --seedless-DP, --DP-restart-stride, --generate-path, --generate-path-seed,
@@ -150,7 +159,9 @@ class Config:
     reads: list = field(default_factory=list)
     outputs: dict = field(default_factory=dict)          # "gaf" / "json" / "gam" -> path (the last one given of each kind, as the reference keeps it)
     corrected: dict = field(default_factory=dict)        # "corrected" / "corrected_clipped" -> path (--corrected-out / --corrected-clipped-out; a .gz name is compressed)
-    coverage: dict = field(default_factory=dict)         # "coverage" / "base_coverage" / "link_coverage" / "coverage_gfa" / "supported_subgraph" -> path (COVERAGE_OUTPUTS; a .gz name is compressed)
+    coverage: dict = field(default_factory=dict)         # "coverage" / "base_coverage" / "link_coverage" / "coverage_gfa" / "supported_subgraph" / "pileup" -> path (COVERAGE_OUTPUTS; a .gz name is compressed)
+    pileup_min_alt: int = 1                              # --pileup-min-alt / --pileup-min-alt-fraction: which bases of --pileup-out get a line
+    pileup_min_fraction: float = 0.0
     aligner: dict = field(default_factory=dict)          # keyword arguments of api.Aligner
     min_cluster_size: int = 1                            # gc_params::min_cluster_size
     seeder: dict = field(default_factory=dict)           # {"kind": "minimizer", "length", "window", "keep_fraction"}, {"kind": "mxm", "mode", "count", "min_len", "cache_prefix"} or {"kind": "file", "paths"}
@@ -342,6 +353,11 @@ def resolve(argv):
     for fmt, path in coverage_outs:
         if path != "":
             cfg.coverage[fmt] = path
+    cfg.pileup_min_alt, cfg.pileup_min_fraction = last("pileup-min-alt", 1), last("pileup-min-alt-fraction", 0.0)
+    if not 0.0 <= cfg.pileup_min_fraction <= 1.0:          # (a NaN fails both comparisons)
+        error("pileup minimum alternative fraction (--pileup-min-alt-fraction) must be between 0 and 1")
+    if "pileup" not in cfg.coverage and ("pileup-min-alt" in vm or "pileup-min-alt-fraction" in vm):
+        error("--pileup-min-alt and --pileup-min-alt-fraction need --pileup-out")
     if cfg.threads < 1:
         error("number of threads must be >= 1")
     if "inflight" in vm and vm["inflight"][-1] < 1:
@@ -527,7 +543,7 @@ def _setup_replicas(cfg, api, replicas):
             elif not minimizer:
                 rep.index = api.MxmIndex(rep.graph, cache_prefix=mxm_prefix)
             if cfg.coverage:               # the accumulators of this device, here so that choose_inflight measures the free memory with them in place
-                rep.coverage = api.Coverage(rep.graph, per_base="base_coverage" in cfg.coverage, links=any(f in cfg.coverage for f in LINK_OUTPUTS))
+                rep.coverage = api.Coverage(rep.graph, per_base="base_coverage" in cfg.coverage, links=any(f in cfg.coverage for f in LINK_OUTPUTS), pileup="pileup" in cfg.coverage)
             rep.setup_seconds = time.time() - started
     finally:
         if tmp:
@@ -661,6 +677,10 @@ def run(cfg, stderr=sys.stderr):
                     if fmt in cfg.coverage:    # piece by piece: the text of a large graph is never whole on either side
                         for text, line_off in pieces():
                             outputs.write(fmt, gzip_lines(api, text, line_off) if cfg.coverage[fmt].endswith(".gz") else text)
+                if "pileup" in cfg.coverage:
+                    for text, line_off in total.pileup_pieces(cfg.pileup_min_alt, cfg.pileup_min_fraction):
+                        if len(text):
+                            outputs.write("pileup", gzip_lines(api, text, line_off) if cfg.coverage["pileup"].endswith(".gz") else text)
         counts["seconds"] = time.time() - started
     finally:
         for rep in replicas:

@@ -119,7 +119,8 @@ void OutputEncoder::choose(hipStream_t fragmentStream)
 // gc_stream_set_coverage: the batch's output entries - exactly the alignments the writers will print - are counted into the handle (gc_coverage.hip). Here and not beside the
 // encoder: the encoder runs before the chained-versus-whole-read decision and drops the losers' pieces afterwards, and a count cannot be dropped. Entries of source 0 are
 // read where they lie, in the cell pool (still resident: nothing reserves it again before the next batch), under a keep byte per encoder job; the chained winners' traces
-// exist only on the host (chain_trace_*: edlib's path walked, or the fast mode's stitched cells) and go up for the same kernel. The stream is waited for: a finished batch
+// exist only on the host (chain_trace_*: edlib's path walked, or the fast mode's stitched cells) and go up for the same kernel, each job with its read's place in the
+// batch's resident bases (the pileup reads the letter under seqPos). The stream is waited for: a finished batch
 // is a counted batch.
 void OutputEncoder::countCoverage(hipStream_t stream)
 {
@@ -136,7 +137,7 @@ void OutputEncoder::countCoverage(hipStream_t stream)
 		if (nKept) {
 			uint8_t* dKeep = st->output.covKeep.reserve<uint8_t>(nOutJobs);
 			HIP_CHECK(hipMemcpyAsync(dKeep, hKeep, nOutJobs, hipMemcpyHostToDevice, stream));
-			launchCoverageAdd(stream, cov->dev, cov->links, (const OutJob*)st->output.outJobs.ptr, (uint32_t)nOutJobs, dKeep, pass.deviceCells(), cov->dBases, cov->dDepth, cov->dBad);
+			launchCoverageAdd(stream, cov->dev, cov->links, (const OutJob*)st->output.outJobs.ptr, (uint32_t)nOutJobs, dKeep, pass.deviceCells(), cov->dBases, cov->dDepth, cov->dBad, cov->pileFor(R->devBases));
 		}
 	}
 	for (const OutEntry& en : outEntries) if (en.source == 1) { nWinners++; winnerCells += glue[en.read].chainTraceNode.size(); }
@@ -150,14 +151,14 @@ void OutputEncoder::countCoverage(hipStream_t stream)
 			const ReadGlue& gl = glue[en.read];
 			const size_t cells = gl.chainTraceNode.size();
 			if (cells == 0) throw std::runtime_error("coverage: a chained alignment won and the batch holds no trace for it (chain_traces == 0?)");
-			hJobsCov[w++] = OutJob { at, 0, (uint32_t)cells, 0, 0, 0 };
+			hJobsCov[w++] = OutJob { at, R->offsets[en.read], (uint32_t)cells, (uint32_t)(R->offsets[en.read + 1] - R->offsets[en.read]), 0, 0 };   // (the read, in the batch's resident bases: the pileup looks under seqPos)
 			for (size_t i = 0; i < cells; i++) hCells[at++] = LongCell { gl.chainTraceNode[i], gl.chainTraceOffset[i], gl.chainTraceSeqPos[i], gl.chainTraceSwitch[i] };
 		}
 		LongCell* dCells = st->output.covCells.reserve<LongCell>(winnerCells);
 		OutJob* dJobsCov = st->output.covJobs.reserve<OutJob>(nWinners);
 		HIP_CHECK(hipMemcpyAsync(dCells, hCells, winnerCells * sizeof(LongCell), hipMemcpyHostToDevice, stream));
 		HIP_CHECK(hipMemcpyAsync(dJobsCov, hJobsCov, nWinners * sizeof(OutJob), hipMemcpyHostToDevice, stream));
-		launchCoverageAdd(stream, cov->dev, cov->links, dJobsCov, (uint32_t)nWinners, nullptr, dCells, cov->dBases, cov->dDepth, cov->dBad);
+		launchCoverageAdd(stream, cov->dev, cov->links, dJobsCov, (uint32_t)nWinners, nullptr, dCells, cov->dBases, cov->dDepth, cov->dBad, cov->pileFor(R->devBases));
 	}
 	if (timed[1]) HIP_CHECK(hipEventRecord(timed[1], stream));
 	HIP_CHECK(hipGetLastError());
@@ -166,8 +167,8 @@ void OutputEncoder::countCoverage(hipStream_t stream)
 		float ms = 0;
 		HIP_CHECK(hipEventElapsedTime(&ms, timed[0], timed[1]));
 		for (hipEvent_t e : timed) HIP_CHECK(hipEventDestroy(e));
-		fprintf(stderr, "[gc times] coverage: k_cov_add over %llu alignments in the cell pool and %llu chained winners (%llu cells up), %.3f ms on the device, %.1f ms in all; per-base depth %s, links %s\n",
-			(unsigned long long)nKept, (unsigned long long)nWinners, (unsigned long long)winnerCells, ms, (nowUs() - t0) / 1e3, cov->dDepth ? "on" : "off", cov->hasLinks ? "on" : "off");
+		fprintf(stderr, "[gc times] coverage: k_cov_add over %llu alignments in the cell pool and %llu chained winners (%llu cells up), %.3f ms on the device, %.1f ms in all; per-base depth %s, links %s, pileup %s\n",
+			(unsigned long long)nKept, (unsigned long long)nWinners, (unsigned long long)winnerCells, ms, (nowUs() - t0) / 1e3, cov->dDepth ? "on" : "off", cov->hasLinks ? "on" : "off", cov->dPile ? "on" : "off");
 	}
 }
 

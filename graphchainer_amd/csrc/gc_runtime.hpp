@@ -706,14 +706,16 @@ struct gc_coverage {
 	const gc_graph* graph = nullptr;
 	unsigned long long* dBases = nullptr;   // [segments]
 	uint32_t* dDepth = nullptr;             // [forward bases], only with per_base
-	uint32_t* dBad = nullptr;               // flag word: 1 a cell outside the graph was met (and not counted), 2 the finish step's runs did not pair up
+	uint32_t* dBad = nullptr;               // flag word: 1 a cell outside the graph was met (and not counted), 2 the finish step's runs did not pair up, 4 a node change that is no link, 8 a GFA line of 2^32 bytes, COV_BAD_SEQPOS a cell's seqPos behind its read
 	void* dSegStart = nullptr;
 	bool hasLinks = false;                  // GC_COVERAGE_LINKS: the graph's links, sorted canonical keys (gc_coverage_links_core.hpp), here and on the device with a 64-bit counter each
 	std::vector<uint64_t> linkKeys;
 	uint64_t* dLinkKeys = nullptr;
 	unsigned long long* dLinkCounts = nullptr;
 	CovLinks links {};                      // (counts == nullptr without links: launchCoverageAdd then takes the kernel without the traversal step)
-	~gc_coverage() { for (void* p : { (void*)dBases, (void*)dDepth, (void*)dBad, dSegStart, (void*)dLinkKeys, (void*)dLinkCounts }) if (p) (void)hipFree(p); }
+	uint32_t* dPile = nullptr;              // GC_COVERAGE_PILEUP: [8 * forward bases] the rows of hip/gc_pileup_core.hpp (null without the pileup: launchCoverageAdd then takes the kernel without that step)
+	CovPile pileFor(const char* reads) const { return CovPile { graph->dev, graph->devIupac, reads, dPile }; }   // the kernel's view, over the resident bases the jobs' readOff point into
+	~gc_coverage() { for (void* p : { (void*)dBases, (void*)dDepth, (void*)dBad, dSegStart, (void*)dLinkKeys, (void*)dLinkCounts, (void*)dPile }) if (p) (void)hipFree(p); }
 };
 
 struct gc_stream {

@@ -8,10 +8,12 @@
 // its predecessor's; one ballot of the covering lanes, one of the lanes that open a run of the same segment; the opening lane adds the run's length to bases[segment];
 // with depth on every covering lane adds 1 to its word (neighbouring lanes, neighbouring words, except across a strand flip where they run the other way).
 // A cell outside the graph is not counted and raises *bad (the batch's own cells never are; a caller's traces are checked on the host before they get here).
-// k_cov_add<true> (a handle with links; gc_coverage_links_core.hpp): the traversal step. A lane whose node differs from its predecessor's - the lane below, the carry for
+// k_cov_add<true, ..> (a handle with links; gc_coverage_links_core.hpp): the traversal step. A lane whose node differs from its predecessor's - the lane below, the carry for
 // lane 0 - forms the canonical key of the pair, finds it among the graph's sorted link keys by binary search and adds 1 to the link's 64-bit counter. A pair that is no link
-// is not counted and raises *bad (4). k_cov_add<false> is the kernel of a handle without links: the step is compiled out, not branched over (DESIGN.md §3.14 has both
+// is not counted and raises *bad (4). k_cov_add<false, ..> is the kernel of a handle without links: the step is compiled out, not branched over (DESIGN.md §3.14 has both
 // resource lines).
+// k_cov_add<.., true> (a handle with the pileup; gc_pileup_core.hpp): the lane also carries its predecessor's seqPos, reads its read letter and - for an aligned pair - the
+// graph's letter set, and adds 1 to one channel of the base's 32-byte row: mismatches by read letter, deletions, insertions. Compiled out of the other two instantiations.
 // Measured alternative for the depth (difference marks at run ends + a segmented scan in the finish step): see DESIGN.md §10.
 //
 // The finish step spells both tables on the device, as the GAF encoder spells its text: per segment / per run a line length, a scan, the lines. The runs of the base table
@@ -19,6 +21,7 @@
 #include "gc_kernels.hpp"
 #include "gc_coverage_core.hpp"
 #include "gc_coverage_links_core.hpp"
+#include "gc_pileup_core.hpp"
 #include "gc_corrected_core.hpp"
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -32,9 +35,20 @@ namespace {
 
 constexpr uint32_t COV_TILE_THREADS = 256, COV_TILE_ITEMS = 8, COV_TILE = COV_TILE_THREADS * COV_TILE_ITEMS;
 
-template <bool LINKS>
+// the set of plain bases of the letter under (bigraph node, offset in the original node), as k_out_encode reads it (gc_output.hip, graphLetterSet): an all-zero column is 'N'
+__device__ __forceinline__ uint32_t covLetterSet(const DGraph& dg, int32_t node, uint32_t offset)
+{
+	const uint32_t split = dg.lookup[dg.lookupOff[node] + (offset >> 6)];
+	const uint32_t at = offset & 63u;
+	if (split < dg.firstAmbiguous) return 1u << ((dg.nodeSeq[2 * (size_t)split + (at >> 5)] >> ((at & 31u) * 2)) & 3u);
+	const uint64_t* p = dg.ambSeq + 4 * (size_t)(split - dg.firstAmbiguous);
+	const uint32_t set = (uint32_t)((p[0] >> at) & 1) | (uint32_t)(((p[1] >> at) & 1) << 1) | (uint32_t)(((p[2] >> at) & 1) << 2) | (uint32_t)(((p[3] >> at) & 1) << 3);
+	return set ? set : 15u;
+}
+
+template <bool LINKS, bool PILEUP>
 __global__ void __launch_bounds__(64) k_cov_add(CovGraph g, CovLinks links, const OutJob* __restrict__ jobs, uint32_t nJobs, const uint8_t* __restrict__ keep, const LongCell* __restrict__ cellPool,
-	unsigned long long* __restrict__ bases, uint32_t* __restrict__ depth, uint32_t* __restrict__ bad)
+	unsigned long long* __restrict__ bases, uint32_t* __restrict__ depth, uint32_t* __restrict__ bad, CovPile pile)
 {
 	const uint32_t j = blockIdx.x, lane = threadIdx.x;
 	if (j >= nJobs || (keep && !keep[j])) return;
@@ -42,6 +56,7 @@ __global__ void __launch_bounds__(64) k_cov_add(CovGraph g, CovLinks links, cons
 	if (n == 0) return;
 	const LongCell* cells = cellPool + jobs[j].cellOff;
 	int32_t carryNode = 0; uint32_t carryOffset = 0;   // the cell before this chunk's first
+	uint32_t carrySeqPos = 0;                          // (PILEUP only)
 	for (uint32_t base = 0; base < n; base += 64) {
 		const uint32_t pos = base + lane;
 		const bool valid = pos < n;
@@ -50,6 +65,31 @@ __global__ void __launch_bounds__(64) k_cov_add(CovGraph g, CovLinks links, cons
 		int32_t pNode = __shfl_up(c.node, 1); uint32_t pOffset = __shfl_up(c.offset, 1);
 		if (lane == 0) { pNode = carryNode; pOffset = carryOffset; }
 		bool covers = valid && covCovers(pos == 0, pNode, pOffset, c.node, c.offset);
+		if (PILEUP) {
+			// the pileup step (gc_pileup_core.hpp), before the depth: an aligned pair, a deletion or an insertion adds 1 to one channel of the row of the base under the
+			// cell. Everything the cell says is checked before it indexes anything: node and offset against the graph, seqPos against the read.
+			uint32_t pSeqPos = __shfl_up(c.seqPos, 1);
+			if (lane == 0) pSeqPos = carrySeqPos;
+			const uint32_t kind = valid ? pileKind(covers, pileMoved(pos == 0, pSeqPos, c.seqPos)) : (uint32_t)PILE_KIND_NOTHING;
+			if (kind != PILE_KIND_NOTHING) {
+				const uint32_t readLen = jobs[j].readLen;
+				if (c.seqPos >= readLen) atomicOr(bad, COV_BAD_SEQPOS);
+				else if (c.node >= 0 && (uint32_t)c.node < g.nIds && c.offset < pile.dg.origSize[c.node]) {   // (a cell outside the graph: the step below says so when it covers; an insertion there has no base to count into)
+					const uint32_t s = covSegment(c.node);
+					const uint64_t s0 = g.segStart[s], len = g.segStart[s + 1] - s0;
+					if (c.offset < len) {
+						const uint8_t letter = (uint8_t)pile.reads[jobs[j].readOff + c.seqPos];
+						const uint32_t graphSet = kind == PILE_KIND_PAIR ? covLetterSet(pile.dg, c.node, c.offset) : 0u;
+						const uint32_t channel = pileCellChannel(kind, (c.node & 1) != 0, letter, pile.iupac[letter], graphSet);
+						if (channel != PILE_NONE) {
+							uint32_t* word = pile.rows + (s0 + covForward(c.node, c.offset, (uint32_t)len)) * PILE_CHANNELS + channel;
+							if (atomicAdd(word, 1u) == 0xffffffffu) atomicExch(word, 0xffffffffu);   // (stays full, like the depth word below)
+						}
+					}
+				} else if (!covers) atomicOr(bad, 1u);
+			}
+			carrySeqPos = __shfl(c.seqPos, (int)nValid - 1);
+		}
 		uint32_t seg = 0; uint64_t at = 0;
 		if (covers) {
 			// bounds before anything is indexed with what the cell says
@@ -174,6 +214,28 @@ __global__ void __launch_bounds__(256) k_cov_gfa_letters(CovGraph g, DGraph dg, 
 	text[off[s - first] + covGfaSegmentLettersAt(nameLen, s) + (i - s0)] = corrLetter(covForwardSet(dg, g.nIds, s, (uint32_t)(i - s0), (uint32_t)(g.segStart[s + 1] - s0)));
 }
 
+// ---- the pileup table: a thread per forward base of [first, first + count); a base that does not pass (pilePasses) has length 0
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_cov_pileup(CovGraph g, DGraph dg, OutNames names, const uint32_t* __restrict__ depth, const uint32_t* __restrict__ rows, uint64_t first, uint64_t count, uint64_t minAlt, double minFraction,
+	uint32_t* __restrict__ lens, const uint64_t* __restrict__ off, char* __restrict__ text)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r > count) return;
+	if (r == count) { if (!WRITE) lens[r] = 0; return; }   // (the scan's last entry is the total)
+	const uint64_t i = first + r;
+	const uint32_t d = depth[i];
+	uint32_t row[PILE_CHANNELS];
+	const uint4 lo = *(const uint4*)(rows + i * PILE_CHANNELS), hi = *(const uint4*)(rows + i * PILE_CHANNELS + 4);   // (a row is 32 bytes, aligned as such)
+	row[0] = lo.x; row[1] = lo.y; row[2] = lo.z; row[3] = lo.w; row[4] = hi.x; row[5] = hi.y; row[6] = hi.z; row[7] = hi.w;
+	if (!pilePasses(d, row, minAlt, minFraction)) { if (!WRITE) lens[r] = 0; return; }
+	const uint64_t s = covSegmentOfBase(g.segStart, g.nSegments, i);
+	const uint64_t s0 = g.segStart[s];
+	const uint32_t id = (uint32_t)(2 * s);
+	const uint32_t nameLen = names.nameOff[id + 1] - names.nameOff[id];
+	if (!WRITE) lens[r] = pileLineLen(nameLen, s, i - s0, d, row);
+	else pileLine(text + off[r], names.nameBytes + names.nameOff[id], nameLen, s, i - s0, corrLetter(covForwardSet(dg, g.nIds, s, (uint32_t)(i - s0), (uint32_t)(g.segStart[s + 1] - s0))), d, row);
+}
+
 // ---- the base table: runs per tile
 // One thread, COV_TILE_ITEMS consecutive bases: visit(i, starts, ends)
 template <typename F>
@@ -271,11 +333,16 @@ hipError_t bringDown(hipStream_t q, const char* head, const char* dText, uint64_
 
 } // namespace
 
-void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const CovLinks& links, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad)
+void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const CovLinks& links, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad,
+	const CovPile& pile)
 {
 	if (!nJobs) return;
-	if (links.counts) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_add<true>), dim3(nJobs), dim3(64), 0, stream, g, links, jobs, nJobs, keep, cellPool, bases, depth, bad);
-	else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_add<false>), dim3(nJobs), dim3(64), 0, stream, g, links, jobs, nJobs, keep, cellPool, bases, depth, bad);
+	const bool l = links.counts != nullptr, p = pile.rows != nullptr;
+	auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nJobs), dim3(64), 0, stream, g, links, jobs, nJobs, keep, cellPool, bases, depth, bad, pile); };
+	if (l && p) launch(k_cov_add<true, true>);
+	else if (p) launch(k_cov_add<false, true>);
+	else if (l) launch(k_cov_add<true, false>);
+	else launch(k_cov_add<false, false>);
 }
 
 void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth,
@@ -410,6 +477,27 @@ hipError_t coverageFormatGfaSegments(hipStream_t q, const CovGraph& g, const DGr
 	COV_TRY(hipGetLastError());
 	COV_TRY(bringDown(q, nullptr, (const char*)out.p, total, (const uint64_t*)off.p, count, text, len, lineOff, nLines));
 	if (supportedOnly) dropEmptyLines(*lineOff, nLines);
+	return hipSuccess;
+}
+
+hipError_t coverageFormatPileup(hipStream_t q, const CovGraph& g, const DGraph& dg, const OutNames& names, const uint32_t* depth, const uint32_t* rows, uint64_t first, uint64_t count, uint64_t minAlt, double minFraction,
+	char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines)
+{
+	if (first > g.nBases || count > g.nBases - first || count + 1 >= 0x7fffffffull) return hipErrorInvalidValue;
+	Scratch lens, off, out;
+	COV_TRY(lens.get((count + 1) * sizeof(uint32_t)));
+	COV_TRY(off.get((count + 1) * sizeof(uint64_t)));
+	const dim3 grid((uint32_t)((count + 1 + 255) / 256));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_pileup<false>), grid, dim3(256), 0, q, g, dg, names, depth, rows, first, count, minAlt, minFraction, (uint32_t*)lens.p, (const uint64_t*)nullptr, (char*)nullptr);
+	COV_TRY(scanCounts(q, (const uint32_t*)lens.p, (uint64_t*)off.p, count + 1));
+	uint64_t total = 0;
+	COV_TRY(hipMemcpyAsync(&total, (uint64_t*)off.p + count, sizeof total, hipMemcpyDeviceToHost, q));
+	COV_TRY(hipStreamSynchronize(q));
+	COV_TRY(out.get(total));
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_pileup<true>), grid, dim3(256), 0, q, g, dg, names, depth, rows, first, count, minAlt, minFraction, (uint32_t*)nullptr, (const uint64_t*)off.p, (char*)out.p);
+	COV_TRY(hipGetLastError());
+	COV_TRY(bringDown(q, first == 0 ? "#segment\tpos\tref\tdepth\tmatch\tmmA\tmmC\tmmG\tmmT\tmmN\tdel\tins_before\tins_after\n" : nullptr, (const char*)out.p, total, (const uint64_t*)off.p, count, text, len, lineOff, nLines));
+	dropEmptyLines(*lineOff, nLines);
 	return hipSuccess;
 }
 

@@ -344,7 +344,13 @@ struct CovGraph { const uint64_t* segStart; uint64_t nSegments, nBases; uint32_t
 // links (gc_coverage_links_core.hpp): keys[n] the graph's sorted canonical link keys, counts[n] += 1 per traversal; counts == nullptr: a handle without links, and the kernel
 // without the traversal step (its own instantiation). *bad |= 4 where a node change is no link of the graph (it is not counted)
 struct CovLinks { const uint64_t* keys; unsigned long long* counts; uint64_t n; };
-void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const CovLinks& links, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad);
+// pile (gc_pileup_core.hpp; GC_COVERAGE_PILEUP): rows[8 * nBases] += 1 in the channel of every cell that is a mismatch, a deletion or an insertion, read through the job's
+// readOff / readLen into `reads` and through dg / iupac like the GAF encoder; rows == nullptr: a handle without the pileup, and the kernel without that step (its own
+// instantiation). *bad |= COV_BAD_SEQPOS where a cell's seqPos lies behind its read (it is not counted in any channel)
+struct CovPile { DGraph dg; const uint8_t* iupac; const char* reads; uint32_t* rows; };
+enum : uint32_t { COV_BAD_SEQPOS = 1u << 8 };
+void launchCoverageAdd(hipStream_t stream, const CovGraph& g, const CovLinks& links, const OutJob* jobs, uint32_t nJobs, const uint8_t* keep, const LongCell* cellPool, unsigned long long* bases, uint32_t* depth, uint32_t* bad,
+	const CovPile& pile = CovPile {});
 // dst += src (depth saturating at 2^32 - 1); both on the stream's device, nothing else adding into them meanwhile
 void launchCoverageMerge(hipStream_t stream, unsigned long long* dstBases, const unsigned long long* srcBases, uint64_t nSegments, uint32_t* dstDepth, const uint32_t* srcDepth, uint64_t nDepth,
 	unsigned long long* dstLinks = nullptr, const unsigned long long* srcLinks = nullptr, uint64_t nLinks = 0);
@@ -359,6 +365,9 @@ hipError_t coverageFormatBases(hipStream_t stream, const CovGraph& g, const OutN
 hipError_t coverageFormatLinks(hipStream_t stream, const OutNames& names, const CovLinks& links, uint64_t first, uint64_t count, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
 hipError_t coverageFormatGfaLinks(hipStream_t stream, const OutNames& names, const CovLinks& links, uint64_t first, uint64_t count, bool supportedOnly, char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
 hipError_t coverageFormatGfaSegments(hipStream_t stream, const CovGraph& g, const DGraph& dg, const OutNames& names, const unsigned long long* bases, uint32_t* bad, uint64_t first, uint64_t count, bool supportedOnly,
+	char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
+// The pileup table, forward bases [first, first + count): the head line with first == 0, then a line per base that passes pilePasses (gc_pileup_core.hpp); rows: [8 * nBases]
+hipError_t coverageFormatPileup(hipStream_t stream, const CovGraph& g, const DGraph& dg, const OutNames& names, const uint32_t* depth, const uint32_t* rows, uint64_t first, uint64_t count, uint64_t minAlt, double minFraction,
 	char** text, uint64_t* len, uint64_t** lineOff, uint64_t* nLines);
 // ---- DEFLATE of independent byte streams (gc_deflate.hip): one dynamic-Huffman block of literals per stream (stored blocks where that is smaller or the code
 // would be deeper than 15 bits). plan[s] = { deflate bytes, mode }, lens[260 * s + symbol]; the caller places stream s at a 4-byte aligned outOff[s] with room for plan[s].x rounded up to 4

@@ -717,6 +717,39 @@ int gc_coverage_format_links(gc_coverage* cov, uint64_t first, uint64_t count, c
 int gc_coverage_format_gfa_segments(gc_coverage* cov, uint64_t first, uint64_t count, int supported_only, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
 int gc_coverage_format_gfa_links(gc_coverage* cov, uint64_t first, uint64_t count, int supported_only, char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
 
+/* Pileup: at which bases the counted alignments disagree with the graph, and how (--pileup-out). This library's own as well; the alignments counted are exactly those the
+ * coverage counts, the entries of gc_result::out_*. For cell i of a trace, with `covers` as above (i == 0 or (node, offset) differs from cell i-1's) and `moved` = (i == 0 or
+ * seqPos differs from cell i-1's):
+ *   covers and moved   an aligned pair: read letter read[seqPos], graph letter under the cell. A match iff their IUPAC sets intersect (the test the GAF's CIGAR makes; a read
+ *                      byte that is no nucleotide code has the empty set), otherwise a mismatch, counted in the channel of the read letter on the forward strand
+ *   covers only        a deletion: a graph base that no read base stands on
+ *   moved only         an insertion: a read base standing on the base of the cell before
+ *   neither            nothing
+ * The base is the one the coverage reports: segment node / 2, forward coordinate. On an odd node id the read letter is complemented before it picks its channel. The
+ * single-letter sets A, C, G, T/U (either case) go to mmA, mmC, mmG, mmT, every other read letter to mmN. An insertion on an even id counts into ins_after of its base (it lies
+ * behind that base on the forward strand), one on an odd id into ins_before.
+ * A row is eight 32-bit channels per forward base in the order mmA mmC mmG mmT mmN del ins_after ins_before; each holds 2^32 - 1 and stays there once it is reached, in a
+ * batch's additions and in gc_coverage_merge, like the depth word. depth[b] = matches + mmA + mmC + mmG + mmT + mmN + del, so the table prints match = depth - those six and
+ * GC_COVERAGE_PILEUP implies GC_COVERAGE_PER_BASE: 4 + 32 = 36 bytes per forward base on the handle's device (GC_ERR_DEVICE with the bytes asked for when the rows do not fit).
+ * A cell whose seqPos is not below its read's length is counted in no channel and raises bit 8 (0x100) of the handle's flag word: the next call that reads the handle fails.
+ * A batch's own cells never do; a caller's are refused on the host before anything is launched. */
+#define GC_COVERAGE_PILEUP 4u
+/* gc_coverage_add_traces with the reads: cell i has read position seq_pos[i] in the read of its alignment a, bases[read_off[a] .. read_off[a+1]) (read_off[0] == 0, ascending).
+ * Every cell is checked on the host first, seq_pos < the read's length included (GC_ERR_INVALID, nothing counted). Any handle takes it; a handle with the pileup takes only
+ * this one: the call without reads answers GC_ERR_INVALID there. */
+int gc_coverage_add_traces2(gc_coverage* cov, const int32_t* node, const uint32_t* offset, const uint32_t* seq_pos, const uint64_t* trace_off, uint64_t n_aln,
+                            const char* bases, const uint64_t* read_off);
+/* The rows as they stand: *rows malloc'd [8 * *n_bases], base after base in the order of gc_coverage_counts' depth. Free with gc_free. */
+int gc_coverage_pileup_counts(gc_coverage* cov, uint32_t** rows, uint64_t* n_bases);
+/* The table, spelled on the device, over forward bases [first_base, first_base + count) in the order of depth (count is cut at the end; first_base behind it:
+ * GC_ERR_INVALID; fewer than 2^31 bases per call): "segment\tpos\tref\tdepth\tmatch\tmmA\tmmC\tmmG\tmmT\tmmN\tdel\tins_before\tins_after\n" for every base with depth > 0,
+ * alt >= min_alt and (double)alt >= min_fraction * (double)depth, where alt is the largest of the eight channels (min_alt 0 and min_fraction 0: every covered base;
+ * min_fraction outside [0, 1]: GC_ERR_INVALID). pos is 0-based forward, ref the graph's letter in upper case as the GFA segments spell it. The call with first_base == 0 puts
+ * the same line with a leading '#' in front as the head line (counted in n_lines). text, len, line_off and n_lines as above.
+ * gc_coverage_merge adds the rows too; handles of which only one has the pileup: GC_ERR_INVALID. */
+int gc_coverage_format_pileup(gc_coverage* cov, uint64_t first_base, uint64_t count, uint64_t min_alt, double min_fraction,
+                              char** text, uint64_t* len, uint64_t** line_off, uint64_t* n_lines);
+
 /* gc_format_gam with the zlib level of the gzip members chosen by the caller (-1 = Z_DEFAULT_COMPRESSION, what the reference's GzipOutputStream uses and gc_format_gam
  * gives; 0..9). The inflated stream is the same at every level; deflate at the default level costs ~1 ms of CPU per 10 kb read - more than the whole alignment costs the
  * GPU - so a host that writes GAM at the hot path's rate wants level 1 (or its own compressor on the bytes of level 0), or GC_GAM_DEVICE_HUFFMAN: the members are then
